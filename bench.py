@@ -8,11 +8,16 @@ backward + Adam step on the conv weights, with identity per-point poses and anch
 enabled (what the shipped model runs).  Inputs are resident in HBM before the timed region.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--points P] [--fwd-only]
+                  [--dump-outputs DIR] [--full]
 For N > 1 launch through torch.distributed.run (one rank per GPU, RCCL): every rank processes
 its own B clouds (weak scaling, no data-path collective), then one pose-hypothesis all-gather
 and one bucketed gradient all-reduce per step.
 
-Rank 0 prints ONE JSON line with the metric, a `roofline` object for the dominant HIP KERNEL (launch
+A plain run sets up, runs W warm-up steps and K timed steps, writes the last timed step's outputs
+with --dump-outputs DIR (dump_outputs), and rank 0 prints ONE JSON line: metric, value, unit,
+ms_per_step (one timed step), higher_is_better, dtype, the run's shape.
+
+With --full, rank 0's line also carries a `roofline` object for the dominant HIP KERNEL (launch
 times are attributed to the kernel, template arguments included, that each C-ABI entry reports through
 eap_last_kernel() -- the same names rocprofv3 prints; achieved = algorithmic flops / measured launch
 time from HIP events recorded on the launch stream inside the timed region), `kernel_rooflines` for the
@@ -747,6 +752,52 @@ def emit(full):
     print(json.dumps(compact_line(detail), allow_nan=False), flush=True)
 
 
+DUMP_BUDGET = 64 * 2 ** 20             # bytes of one --dump-outputs directory
+FEATS_SAMPLE_BUDGET = 16 * 2 ** 20     # of which the sampled output features
+
+
+def feats_sample_points(points, bytes_per_point, budget=FEATS_SAMPLE_BUDGET):
+    """The fixed, seeded sample of point indices whose output features --dump-outputs stores: at most 16 points, no more than fit
+    `budget` bytes at `bytes_per_point` -> sorted int64 array (the same for every run with the same --points / --batch)."""
+    n = max(1, min(16, points, budget // max(bytes_per_point, 1)))
+    return np.sort(np.random.default_rng(2913).choice(points, n, replace=False))
+
+
+def dump_outputs(out_dir, last, model=None):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as DIR/<name>.npy in float32:
+      feats_sample        the output features [B, C, n, A] at the n <= 16 points of feats_sample_points
+      feats_pooled        the output features averaged over ALL points [B, C, A]
+      pose_R, pose_T      the gathered pose hypotheses [B * N, SLOTS, A, 3, 3] and [B * N, SLOTS, A, 3]
+      loss                the stand-in loss [1]                                                      (training step only)
+      param.<name>, grad.<name>, buffer.<name>   the parameters after the Adam step, their gradients and the norms'
+                          running statistics                                      (training step only: `model` is given)
+    -> {name: bytes}.  Refuses to write more than DUMP_BUDGET bytes."""
+    feats = last['feats']
+    b, c, p, a = feats.shape
+    idx = torch.from_numpy(feats_sample_points(p, b * c * a * feats.element_size())).to(feats.device)
+    arrays = {'feats_sample': feats.index_select(2, idx),
+              'feats_pooled': last['pooled'] if 'pooled' in last else feats.mean(2),
+              'pose_R': last['pose_R'], 'pose_T': last['pose_T']}
+    if 'loss' in last:
+        arrays['loss'] = last['loss'].reshape(1)
+    if model is not None:
+        for name, prm in model.named_parameters():
+            arrays['param.' + name] = prm
+            if prm.grad is not None:
+                arrays['grad.' + name] = prm.grad
+        for name, buf in model.named_buffers():
+            if 'running' in name and buf.is_floating_point():
+                arrays['buffer.' + name] = buf
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f'bench.py: --dump-outputs would write {total} bytes, more than {DUMP_BUDGET}')
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), v)
+    return {k: v.nbytes for k, v in arrays.items()}
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -851,7 +902,10 @@ def main(argv=None):
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--plan-points', type=int, default=None, help='radii / sigmas of the backbone built for this input size (default: --points)')
     ap.add_argument('--no-other-configs', action='store_true', help='skip the short runs of the other BASELINE configurations (config 3 composite included)')
-    ap.add_argument('--plain', action='store_true', help='warm-up + timed steps only (no attribution loop, no A/B leg, no extras): what the counter passes of tools/gpu/profile_round.sh run')
+    ap.add_argument('--plain', action='store_true', help='warm-up + timed steps only, even with --full (the default run already is: kept for the scripts that pass it)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also the attribution loop, the A/B legs, config 3, the other configurations, '
+                                                       'the native zpconv roofline and the CPU baseline; the complete record goes to bench_detail.json')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB: see dump_outputs)')
     ap.add_argument('--cpu-baseline-probe', type=int, default=0, help=argparse.SUPPRESS)      # child of cpu_baseline(): one thread count, no GPU
     ap.add_argument('--probe-skip-search', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--probe-slab', type=int, default=32, help=argparse.SUPPRESS)
@@ -895,12 +949,15 @@ def main(argv=None):
     xyz = torch.from_numpy(xyz_np).to(dev)
     pose = torch.from_numpy(pose_np).to(dev)
 
-    def step():
+    def step(keep=None):
+        """One step; `keep` (a dict, or None) receives the tensors the step hands its caller."""
         if args.fwd_only:
             with torch.no_grad():
                 feats = model(xyz, pose)
                 R, T = model.hypotheses(feats)
-                sharding.all_gather_pose_hypotheses(R, T, n_items=n_items)
+                allR, allT = sharding.all_gather_pose_hypotheses(R, T, n_items=n_items)
+            if keep is not None:
+                keep.update(feats=feats, pose_R=allR, pose_T=allT)
             return
         opt.zero_grad(set_to_none=True)
         feats = model(xyz, pose)
@@ -912,18 +969,20 @@ def main(argv=None):
         loss.backward()
         reducer.finish()
         opt.step()
+        if keep is not None:
+            keep.update(feats=feats.detach(), pooled=pooled, pose_R=allR, pose_T=allT, loss=loss.detach())
 
     def barrier():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(n):
-        """n steps between two barrier + synchronize pairs -> seconds, MAX over ranks."""
+    def timed(n, keep=None):
+        """n steps between two barrier + synchronize pairs -> seconds, MAX over ranks; the last step's outputs into `keep`."""
         barrier()
         t0 = time.perf_counter()
-        for _ in range(n):
-            step()
+        for i in range(n):
+            step(keep if i == n - 1 else None)
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -932,21 +991,43 @@ def main(argv=None):
             dt = t.item()
         return dt
 
-    ranks_report = distributed_report(world, backend, dev)          # (collective: every rank)
+    full = args.full and not args.plain
+    ranks_report = distributed_report(world, backend, dev) if full else None          # (collective: every rank)
     for _ in range(args.warmup):
         step()
     # the headline loop: EXACTLY --steps steps, no per-launch events
-    dt = timed(args.steps)
-    # kernel attribution in a second, short loop: every C-ABI launch bracketed by two HIP events on the launch stream
-    if args.plain:
+    last = {} if args.dump_outputs else None
+    dt = timed(args.steps, last)
+    headline = {
+        'metric': 'point-clouds/sec (4096 pts, 60 anchors) ' + ('fwd' if args.fwd_only else 'fwd+bwd'),
+        'value': args.batch * world * args.steps / dt, 'unit': 'point-clouds/sec', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+        'rccl_ranks': world if backend == 'nccl' and world > 1 else 0,
+        'config': {'workload': f'{args.batch} x {args.points}-pt synthetic ' + ('partial (depth-buffer visible) ' if args.partial else '') + 'laptop clouds per GPU, 3-block '
+                               + ('separable (inter+intra+skip) glb_backbone' if args.separable else 'inter backbone')
+                               + f' 1->64->128->512 (NN=64,K=24,A=60), '
+                               + ('forward' if args.fwd_only else 'forward+backward+Adam'),
+                   'clouds_per_gpu': args.batch, 'points': args.points, 'anchors': NA,
+                   'sharding': f'clouds x{world}, pose all-gather + gradient all-reduce overlapped with the backward' if world > 1 else 'single GPU'},
+    }
+    if world > 1:
+        headline['backend'] = backend + (' (RCCL)' if backend == 'nccl' else '')
+        if backend != 'nccl':
+            headline['functional_check_only'] = (f'{world} ranks over {backend} on {n_dev} device(s): the N > 1 code path runs, '
+                                                 f'this is NOT a scaling measurement')
+    if last is not None:
         if rank == 0:
-            print(json.dumps({'metric': 'point-clouds/sec (4096 pts, 60 anchors) ' + ('fwd' if args.fwd_only else 'fwd+bwd'), 'value': args.batch * world * args.steps / dt,
-                              'unit': 'point-clouds/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
-                              'plain': True}))
+            dump_outputs(args.dump_outputs, last, None if args.fwd_only else model)
+        del last
+    if not full:
+        if rank == 0:
+            print(json.dumps(_clean(headline), allow_nan=False), flush=True)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
         return
+    # --full: kernel attribution in a second, short loop: every C-ABI launch bracketed by two HIP events on the launch stream
     attr_steps = min(args.steps, 3)
     _hip.KERNEL_TIMES = []
     dt_attr = timed(attr_steps)
@@ -980,25 +1061,14 @@ def main(argv=None):
         roof['flops_definition'] = ('algorithmic: 2*M*N*K*batch for GEMMs; 2*channels*K(24)*P*NN*A*B for the grouping kernels '
                                     '(the MFMA tiles pad K 24->32 and the anchors 60->64, not counted)')
         step_flops = sum(k['flops'] for k in by_kernel.values()) / attr_steps
-        clouds = args.batch * world * args.steps
         line = {
-            'metric': 'point-clouds/sec (4096 pts, 60 anchors) ' + ('fwd' if args.fwd_only else 'fwd+bwd'),
-            'value': clouds / dt, 'unit': 'point-clouds/sec', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'rccl_ranks': world if backend == 'nccl' and world > 1 else 0,
+            **headline,
             'dtype_note': 'fp32 tensors, fp32 accumulation everywhere.  The dense product of the deep layers (csrc/so3_dense.hip, BOTH directions), the '
                           'contractions and the small GEMMs around them form their fp32 products on the fp16 matrix cores from two-plane splits '
                           'x = h + l of the stored operand after a power-of-two scale per row (three partial products h h + h l + l h, fp32 accumulate; '
                           '|err| <= 2^-21 sum|a||b|); tests/test_gpu_split_planes.py, tests/test_gpu_dense.py against float64.  Same-run A/B legs: '
                           'bf16x3_contraction (three bf16 planes, six products) and fp32_mfma_contraction (vgtk._hip.SPLIT_PLANES = 3 / '
                           'SPLIT_BF16_CONTRACTION = False)',
-            'config': {'workload': f'{args.batch} x {args.points}-pt synthetic ' + ('partial (depth-buffer visible) ' if args.partial else '') + 'laptop clouds per GPU, 3-block '
-                                   + ('separable (inter+intra+skip) glb_backbone' if args.separable else 'inter backbone')
-                                   + f' 1->64->128->512 (NN=64,K=24,A=60), '
-                                   + ('forward' if args.fwd_only else 'forward+backward+Adam'),
-                       'clouds_per_gpu': args.batch, 'points': args.points, 'anchors': NA,
-                       'sharding': f'clouds x{world}, pose all-gather + gradient all-reduce overlapped with the backward' if world > 1 else 'single GPU'},
             'timing': {'headline_loop': 'no per-launch events', 'ms_per_step_with_launch_events': dt_attr / attr_steps * 1e3,
                        'attribution_steps': attr_steps,
                        'note': 'roofline / kernels / whole_step come from the second loop (two HIP events per C-ABI launch on the launch stream)'},
@@ -1027,11 +1097,7 @@ def main(argv=None):
             line['bf16x3_contraction'] = ab3
         if world > 1:
             line['ranks'] = ranks_report
-            line['backend'] = backend + (' (RCCL)' if backend == 'nccl' else '')
             line['expected_scaling'] = expected_scaling(world, line['ms_per_step'], sum(p.numel() for p in conv_params))
-        if world > 1 and backend != 'nccl':
-            line['functional_check_only'] = (f'{world} ranks over {backend} on {n_dev} device(s): the N > 1 code path runs, '
-                                             f'this is NOT a scaling measurement')
         if world == 1 and default_cfg and not args.no_other_configs:
             del model, opt, xyz, pose
             torch.cuda.empty_cache()

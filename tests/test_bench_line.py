@@ -7,6 +7,7 @@ import math
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -79,3 +80,50 @@ def test_emit_writes_the_detail_file_and_prints_one_line(tmp_path, monkeypatch, 
     for d in (tmp_path, tmp_path / 'gpurun_out'):
         detail = _strict(open(d / 'bench_detail.json').read())
         assert 'kernels' in detail and 'launch_shapes' in detail
+
+
+def test_dump_outputs_writes_float32_arrays_of_a_fixed_sample(tmp_path):
+    """`--dump-outputs DIR` (bench.dump_outputs) on CPU tensors shaped as the step's: float32 .npy files, the features at the
+    seeded point sample, the trained model's parameters, gradients and running statistics, within the budget."""
+    import torch
+    torch.manual_seed(0)
+    feats = torch.randn(2, 8, 40, 60, dtype=torch.float64)
+    model = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.BatchNorm1d(4))
+    model(torch.randn(5, 3)).sum().backward()
+    last = {'feats': feats, 'pooled': feats.mean(2), 'pose_R': torch.randn(2, 2, 60, 3, 3), 'pose_T': torch.randn(2, 2, 60, 3),
+            'loss': torch.tensor(1.5)}
+    sizes = bench.dump_outputs(str(tmp_path / 'out'), last, model)
+    files = sorted(p.name for p in (tmp_path / 'out').iterdir())
+    assert files == sorted(k + '.npy' for k in sizes)
+    for k in ('feats_sample', 'feats_pooled', 'pose_R', 'pose_T', 'loss', 'param.0.weight', 'grad.0.weight', 'buffer.1.running_mean'):
+        assert k in sizes, k
+    arrays = {k: np.load(tmp_path / 'out' / (k + '.npy')) for k in sizes}
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    pts = bench.feats_sample_points(40, 2 * 8 * 60 * 8)
+    assert np.array_equal(pts, bench.feats_sample_points(40, 2 * 8 * 60 * 8)) and len(pts) == 16 and len(set(pts.tolist())) == 16
+    np.testing.assert_array_equal(arrays['feats_sample'], feats[:, :, torch.from_numpy(pts)].float().numpy())
+    np.testing.assert_array_equal(arrays['grad.0.weight'], model[0].weight.grad.numpy())
+    assert sum(sizes.values()) <= bench.DUMP_BUDGET
+    # a larger output is sampled down to the budget, never written whole
+    assert len(bench.feats_sample_points(4096, bench.FEATS_SAMPLE_BUDGET // 3)) == 3
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_line_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) on a small shape: one JSON line with the contract's keys and exactly --steps timed steps,
+    and --dump-outputs writes the last step's outputs as finite float32 arrays."""
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--batch', '1', '--points', '512',
+                          '--dump-outputs', str(tmp_path / 'dump')], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = _strict(out.stdout.strip().splitlines()[-1])
+    for k in CONTRACT:
+        assert k in line, k
+    assert line['steps'] == 3 and line['dtype'] == 'f32' and line['higher_is_better'] is True and 'roofline' not in line
+    assert line['value'] == pytest.approx(1e3 / line['ms_per_step'], rel=1e-4)
+    arrays = {p.stem: np.load(p) for p in (tmp_path / 'dump').glob('*.npy')}
+    assert arrays['feats_sample'].shape == (1, 512, 16, 60) and arrays['feats_pooled'].shape == (1, 512, 60)
+    assert arrays['pose_R'].shape == (1, 2, 60, 3, 3) and 'loss' in arrays and 'grad.convs.2.basic_conv.W' in arrays
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    assert not (tmp_path / 'bench_detail.json').exists()

@@ -16,7 +16,7 @@ import pytest
 
 REF = '/root/reference'
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'vgtk', 'vgtk', 'app')), reason='needs /root/reference (build container only)')
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'vgtk', 'vgtk', 'app')), reason='needs the reference checkout at REF (build container only)')
 
 
 def _overlay(tmp_path):
@@ -72,6 +72,7 @@ def _run(script, tmp_path, token):
     return out.stdout
 
 
+@needs_reference
 def test_root_exports_with_the_reference_runtime_overlaid(tmp_path):
     pkg = _overlay(tmp_path)
     script = _prelude(pkg, ('SPConvNets.models.common_utils', 'SPConvNets.utils.loss_util', 'model_util')) + textwrap.dedent('''
@@ -90,6 +91,7 @@ def test_root_exports_with_the_reference_runtime_overlaid(tmp_path):
     _run(script, tmp_path, 'OVERLAY-OK')
 
 
+@needs_reference
 def test_reference_model_builder_yields_the_product_operators_with_the_reference_state_dict(tmp_path):
     """SPConvNets/models/unsup_seg_so3_pose_conv_pn_38_multi_stage.py:L2067-2325 `build_model_from(opt)` -- the call the trainer
     makes (trainer_unsup_arti_align.py:L333-334) -- on product + overlay, with the reference's own option parser

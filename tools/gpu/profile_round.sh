@@ -15,10 +15,10 @@ if [ -z "$QUICK" ]; then
   ( time timeout 2400 python -m pytest tests -m gpu -x -q --durations=8 ) > $O/pytest.log 2>&1
   echo "pytest rc $?" >> $O/pytest.log
   python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-  timeout 1500 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; cp $R/gpurun_out/bench_detail.json $O/bench_detail.json
+  timeout 1500 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; cp $R/bench_detail.json $O/bench_detail.json
 fi
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o bench --output-format csv -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs > $O/bench_under_rocprof.json 2> $O/prof.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o bench --output-format csv -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs > $O/bench_under_rocprof.json 2> $O/prof.err
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVES"; do
   tag=$(echo $c | tr ' ' '_')
   timeout 600 rocprofv3 --kernel-trace --pmc $c -d $O/pmc_$tag -o pmc --output-format csv -- python $R/bench.py --plain --steps 1 --warmup 1 > $O/pmc_$tag.log 2>&1
