@@ -57,7 +57,8 @@ typedef unsigned long long u64;
 typedef const __attribute__((address_space(4))) unsigned long long *cu64p;      // constant address space: uniform loads go through the scalar cache
 
 constexpr int KC_BK = 32;                 // contraction elements per k-step (two MFMA k-blocks of 16)
-constexpr int KC_LIST_BYTES = 2048;       // LDS behind the operand ring for a column block's k-step list: at most 512 k-steps with a list
+constexpr int KC_LIST_BYTES = 4096;       // LDS behind the operand ring for a column block's k-step list: at most 1024 k-steps with a list
+                                          // (the forward's contraction axis at ks = 24, rp = 1024 has 768); ring + list = 140 KB (MI = 8) / 76 KB (MI = 4)
 
 // The DENSE INDEX d of a (kernel point k, row slot r) pair: d = (r / 16) 16 ks + 16 k + r % 16 -- groups of 16 row slots outermost,
 // then the kernel point, then the 16 slots.  Rows are sorted longest list first and every cloud has its own count R <= rp, so a
@@ -123,17 +124,22 @@ __global__ __launch_bounds__(256) void dense_slots_kernel(int n_sup, int rp, int
     if ((unsigned)r < (unsigned)n_sup) slot_of[(size_t)b * n_sup + r] = j;
 }
 
-// memb[b][p][w] (w < MEMB_WORDS = 16 words per point, whatever rp) bit i = row slot 32 w + i is named by p's list; flags[b] |= 1 when a list names a row twice (the ball
+// memb[b][p][w] (w < W words per point, whatever rp) bit i = row slot 32 w + i is named by p's list; flags[b] |= 1 when a list names a row twice (the ball
 // query pads short lists with their first hit, grouping_cuda_kernel.cu:L98-107: such clouds stay on the list kernels),
 // |= 2 when a list names a row without a slot (more referenced rows than `rp`)
+// W (template, here and in the mask and key kernels): MEMB_WORDS = 16 words per point (rp <= 512, 32 groups of 16 rows, a 32-bit group
+// key) or MEMB_WORDS_WIDE = 32 (rp <= 1024, 64 groups, a 64-bit key).  Clouds of at most 512 referenced rows stay on the 16-word tables
+// all the way -- the point order that the sort by key gives, and with it the summation order of the backward, is the 32-bit key's.
 constexpr int MEMB_WORDS = 16;           // rp <= 512
+constexpr int MEMB_WORDS_WIDE = 32;      // rp <= 1024: the LDS tile of the member kernel is 256 x 33 words = 33 KB
+constexpr int DENSE_MAX_ROWS = 32 * MEMB_WORDS_WIDE;
+template <int W>
 __global__ __launch_bounds__(256) void dense_member_kernel(int p, int n_sup, int nn, int rp, const int32_t *__restrict__ idx,
                                                            const int32_t *__restrict__ slot_of, unsigned *__restrict__ memb,
                                                            int32_t *__restrict__ flags) {
-    __shared__ unsigned sw[256][MEMB_WORDS + 1];
+    __shared__ unsigned sw[256][W + 1];
     const int b = blockIdx.y, pt = blockIdx.x * 256 + threadIdx.x;
     if (pt >= p) return;
-    constexpr int W = MEMB_WORDS;
     unsigned *w = sw[threadIdx.x];
     for (int k = 0; k < W; ++k) w[k] = 0u;
     const int32_t *list = idx + ((size_t)b * p + pt) * nn;
@@ -155,9 +161,9 @@ __global__ __launch_bounds__(256) void dense_member_kernel(int p, int n_sup, int
 // bits[b][wave tile wt][step][lane]: bit 16 t + 8 j + e of the lane's dword  <->  column n = 64 wt + 32 j + (lane & 31), contraction index
 // kk = 32 step + 16 t + 8 (lane >> 5) + e -- the 32 weights the lane generates in a k-step of the product kernel
 //   dir 0 (backward): kk = point, n = dense index of (k, r), n < ks rp        dir 1 (forward): kk = dense index of (k, r), n = point
+template <int W>
 __global__ __launch_bounds__(256) void dense_mask_kernel(int p, int ks, int rp, int dir, int wtiles, int steps,
                                                          const unsigned *__restrict__ memb, unsigned *__restrict__ bits) {
-    constexpr int W = MEMB_WORDS;
     const int b = blockIdx.y, lane = threadIdx.x & 63, li = lane & 31, kg = lane >> 5;
     const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (wv >= (long long)wtiles * steps) return;
@@ -212,27 +218,31 @@ __global__ __launch_bounds__(256) void dense_mask_kernel(int p, int ks, int rp, 
     bits[(((size_t)b * wtiles + wt) * steps + step) * 64 + lane] = word;
 }
 
-// keys[b][p]: bit g = point p's list names a row of the 16-row group g (row slots 16 g .. 16 g + 15; rp <= 512: 32 groups).  Sorting a
+// keys[b][p]: bit g = point p's list names a row of the 16-row group g (row slots 16 g .. 16 g + 15; W = 16, rp <= 512: 32 groups, an int32
+// key; W = 32, rp <= 1024: 64 groups, an int64 key).  Sorting a
 // cloud's points by this key (any total order: equal keys become neighbours, and keys that share their high groups stay close) makes
 // the 0/1 mask of the dense product BLOCK-sparse: the first-nsample-by-index ball query (grouping_cuda_kernel.cu:L68-113) gives
 // every point 64 of the R referenced rows, i.e. rows of only 0.45-0.7 of the 16-row groups, and points with the same groups meet
 // in the same 32-point k-steps (backward) / 256-point column blocks (forward) -- dense_steps_kernel lists the non-empty ones.
-__global__ __launch_bounds__(256) void dense_keys_kernel(long long total, const unsigned *__restrict__ memb, int32_t *__restrict__ keys) {
+template <int W>
+__global__ __launch_bounds__(256) void dense_keys_kernel(long long total, const unsigned *__restrict__ memb,
+                                                         std::conditional_t<W == MEMB_WORDS, int32_t, int64_t> *__restrict__ keys) {
+    using UK = std::conditional_t<W == MEMB_WORDS, unsigned, u64>;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;            // (b, p)
     if (i >= total) return;
-    const u32x4 *w = reinterpret_cast<const u32x4 *>(memb + i * MEMB_WORDS);
-    unsigned key = 0;
+    const u32x4 *w = reinterpret_cast<const u32x4 *>(memb + i * W);
+    UK key = 0;
 #pragma unroll
-    for (int q = 0; q < MEMB_WORDS / 4; ++q) {
+    for (int q = 0; q < W / 4; ++q) {
         const u32x4 v = w[q];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int g = 2 * (4 * q + e);
-            key |= ((v[e] & 0xffffu) ? 1u : 0u) << g;
-            key |= ((v[e] >> 16) ? 1u : 0u) << (g + 1);
+            key |= (UK)((v[e] & 0xffffu) ? 1u : 0u) << g;
+            key |= (UK)((v[e] >> 16) ? 1u : 0u) << (g + 1);
         }
     }
-    keys[i] = (int32_t)key;
+    keys[i] = (std::conditional_t<W == MEMB_WORDS, int32_t, int64_t>)key;
 }
 
 // steps[(b blocks_n + bn) (KS + 1)]: [0] = count >= 1, [1 ..] = the k-steps (ascending) of column block bn of cloud b in which at least
@@ -1105,10 +1115,18 @@ extern "C" int eap_so3_dense_form(int form) {
     return old;
 }
 
-extern "C" int eap_so3_dense_supported(int p, int na, int ks, int rp, int o) {
-    return p > 0 && (p % 32) == 0 && na > 0 && (na % 4) == 0 && na <= 64 && ks > 0 && (ks % 2) == 0 && rp > 0 && (rp % 16) == 0 && rp <= 32 * MEMB_WORDS &&
+namespace {
+// the shapes the product takes at `words` membership words per point (rp <= 32 words)
+inline bool dense_shape_ok(int p, int na, int ks, int rp, int o, int words) {
+    return p > 0 && (p % 32) == 0 && na > 0 && (na % 4) == 0 && na <= 64 && ks > 0 && (ks % 2) == 0 && rp > 0 && (rp % 16) == 0 && rp <= 32 * words &&
            (o % 128) == 0;
 }
+}  // namespace
+
+extern "C" int eap_so3_dense_supported(int p, int na, int ks, int rp, int o) { return dense_shape_ok(p, na, ks, rp, o, MEMB_WORDS_WIDE); }
+
+// the largest rp the product takes (the wide tables: memb [b,p,32], int64 keys); up to 512 the 16-word entries serve
+extern "C" int eap_so3_dense_max_rows(void) { return DENSE_MAX_ROWS; }
 
 extern "C" int64_t eap_so3_dense_mask_words(int b, int p, int ks, int rp, int dir) {
     const int n = dir ? p : ks * rp, kd = dir ? ceil_to(ks * rp, KC_BK) : p;
@@ -1116,26 +1134,52 @@ extern "C" int64_t eap_so3_dense_mask_words(int b, int p, int ks, int rp, int di
     return ((int64_t)b * wtiles * steps * 64 + 1) / 2;               // (in 64-bit words: the table holds 32-bit words)
 }
 
-extern "C" int eap_so3_dense_member(int b, int p, int n_sup, int nn, int rp, int rows_ld, const int32_t *idx, const int32_t *rows,
-                                    const int32_t *n_rows, int32_t *slot_of, uint32_t *memb, int32_t *flags, eap_stream_t stream) {
+namespace {
+template <int W>
+int dense_member(int b, int p, int n_sup, int nn, int rp, int rows_ld, const int32_t *idx, const int32_t *rows, const int32_t *n_rows, int32_t *slot_of,
+                 uint32_t *memb, int32_t *flags, eap_stream_t stream) {
     if (b <= 0 || p <= 0) return 0;
-    if (rp <= 0 || rp > 32 * MEMB_WORDS || b > 65535) return eap::bad_arg("so3_dense_member: 0 < rp <= 512, b <= 65535");
+    if (rp <= 0 || rp > 32 * W || b > 65535)
+        return eap::bad_arg(W == MEMB_WORDS ? "so3_dense_member: 0 < rp <= 512, b <= 65535" : "so3_dense_member_wide: 0 < rp <= 1024, b <= 65535");
     hipStream_t s = eap::S(stream);
     if (int e = eap::hip_fail(hipMemsetAsync(slot_of, 0xff, sizeof(int32_t) * (size_t)b * n_sup, s), "so3_dense_member memset")) return e;
     if (int e = eap::hip_fail(hipMemsetAsync(flags, 0, sizeof(int32_t) * (size_t)b, s), "so3_dense_member memset")) return e;
     hipLaunchKernelGGL(dense_slots_kernel, dim3(eap::cdiv(rp, 256), b), dim3(256), 0, s, n_sup, rp, rows_ld, rows, n_rows, slot_of);
-    hipLaunchKernelGGL(dense_member_kernel, dim3(eap::cdiv(p, 256), b), dim3(256), 0, s, p, n_sup, nn, rp, idx, slot_of, memb, flags);
+    hipLaunchKernelGGL(dense_member_kernel<W>, dim3(eap::cdiv(p, 256), b), dim3(256), 0, s, p, n_sup, nn, rp, idx, slot_of, memb, flags);
     return eap::check_launch("so3_dense_member");
 }
 
-extern "C" int eap_so3_dense_masks(int b, int p, int ks, int rp, int dir, const uint32_t *memb, uint64_t *mask, eap_stream_t stream) {
+template <int W>
+int dense_masks(int b, int p, int ks, int rp, int dir, const uint32_t *memb, uint64_t *mask, eap_stream_t stream) {
     if (b <= 0) return 0;
-    if (!eap_so3_dense_supported(p, 4, ks, rp, 256) || b > 65535) return eap::bad_arg("so3_dense_masks: shape not taken");
+    if (!dense_shape_ok(p, 4, ks, rp, 256, W) || b > 65535) return eap::bad_arg("so3_dense_masks: shape not taken");
     const int n = dir ? p : ks * rp, kd = dir ? ceil_to(ks * rp, KC_BK) : p;
     const int wtiles = 4 * ((n + 255) / 256), steps = kd / KC_BK;
-    hipLaunchKernelGGL(dense_mask_kernel, dim3(eap::cdiv((long long)wtiles * steps, 4), b), dim3(256), 0, eap::S(stream), p, ks, rp, dir, wtiles, steps, memb,
+    if (((long long)wtiles * steps + 3) / 4 > 0x7fffffffLL) return eap::bad_arg("so3_dense_masks: too many workgroups");
+    hipLaunchKernelGGL(dense_mask_kernel<W>, dim3((unsigned)eap::cdiv((long long)wtiles * steps, 4), b), dim3(256), 0, eap::S(stream), p, ks, rp, dir, wtiles, steps, memb,
                        reinterpret_cast<unsigned *>(mask));
     return eap::check_launch("so3_dense_masks");
+}
+}  // namespace
+
+extern "C" int eap_so3_dense_member(int b, int p, int n_sup, int nn, int rp, int rows_ld, const int32_t *idx, const int32_t *rows,
+                                    const int32_t *n_rows, int32_t *slot_of, uint32_t *memb, int32_t *flags, eap_stream_t stream) {
+    return dense_member<MEMB_WORDS>(b, p, n_sup, nn, rp, rows_ld, idx, rows, n_rows, slot_of, memb, flags, stream);
+}
+
+// memb uint32 [b,p,32], rp <= 1024
+extern "C" int eap_so3_dense_member_wide(int b, int p, int n_sup, int nn, int rp, int rows_ld, const int32_t *idx, const int32_t *rows,
+                                         const int32_t *n_rows, int32_t *slot_of, uint32_t *memb, int32_t *flags, eap_stream_t stream) {
+    return dense_member<MEMB_WORDS_WIDE>(b, p, n_sup, nn, rp, rows_ld, idx, rows, n_rows, slot_of, memb, flags, stream);
+}
+
+extern "C" int eap_so3_dense_masks(int b, int p, int ks, int rp, int dir, const uint32_t *memb, uint64_t *mask, eap_stream_t stream) {
+    return dense_masks<MEMB_WORDS>(b, p, ks, rp, dir, memb, mask, stream);
+}
+
+// memb uint32 [b,p,32], rp <= 1024; the table has the layout and the size (eap_so3_dense_mask_words) of eap_so3_dense_masks'
+extern "C" int eap_so3_dense_masks_wide(int b, int p, int ks, int rp, int dir, const uint32_t *memb, uint64_t *mask, eap_stream_t stream) {
+    return dense_masks<MEMB_WORDS_WIDE>(b, p, ks, rp, dir, memb, mask, stream);
 }
 
 extern "C" int eap_so3_dense_tables_f32(int b, int p, int n_sup, int na, int ks, int rp, int rows_ld, float sigma, const float *q_xyz,
@@ -1286,7 +1330,7 @@ extern "C" int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int
         g.cB = (long long)na * o * p; g.cA = (long long)o * p; g.ldm = p; g.rp = p; g.kstride = 0;
     }
     g.mask = reinterpret_cast<const unsigned *>(mask);
-    g.steps = (steps != nullptr && g.KS <= KC_LIST_BYTES / 4) ? steps : nullptr;      // (longer contraction axes run every k-step)
+    g.steps = (steps != nullptr && g.KS <= KC_LIST_BYTES / 4) ? steps : nullptr;      // (contraction axes of more than 1024 k-steps run every k-step)
     g.C = out;
     g.neg_inv_sigma = -1.0f / sigma;
     g.n_rows = n_rows; g.ks = ks; g.trim = dir ? 2 : 1;       // (columns / k axis are dense indices either way; without n_rows every slot counts)
@@ -1324,8 +1368,18 @@ extern "C" int eap_so3_dense_product_f32(int dir, int b, int o, int p, int na, i
 extern "C" int eap_so3_dense_point_keys(int b, int p, const uint32_t *memb, int32_t *keys, eap_stream_t stream) {
     if (b <= 0 || p <= 0) return 0;
     const long long total = (long long)b * p;
-    hipLaunchKernelGGL(dense_keys_kernel, dim3((unsigned)eap::cdiv(total, 256)), dim3(256), 0, eap::S(stream), total, memb, keys);
+    if ((total + 255) / 256 > 0x7fffffffLL) return eap::bad_arg("so3_dense_point_keys: too many workgroups");
+    hipLaunchKernelGGL(dense_keys_kernel<MEMB_WORDS>, dim3((unsigned)eap::cdiv(total, 256)), dim3(256), 0, eap::S(stream), total, memb, keys);
     return eap::check_launch("so3_dense_point_keys");
+}
+
+// memb uint32 [b,p,32] -> keys int64 [b,p], bit g = a row of group g < 64 (rp <= 1024)
+extern "C" int eap_so3_dense_point_keys_wide(int b, int p, const uint32_t *memb, int64_t *keys, eap_stream_t stream) {
+    if (b <= 0 || p <= 0) return 0;
+    const long long total = (long long)b * p;
+    if ((total + 255) / 256 > 0x7fffffffLL) return eap::bad_arg("so3_dense_point_keys_wide: too many workgroups");
+    hipLaunchKernelGGL(dense_keys_kernel<MEMB_WORDS_WIDE>, dim3((unsigned)eap::cdiv(total, 256)), dim3(256), 0, eap::S(stream), total, memb, keys);
+    return eap::check_launch("so3_dense_point_keys_wide");
 }
 
 // int32 words of the k-step lists of one direction: [b][column blocks of 256][k-steps + 1]
@@ -1335,16 +1389,28 @@ extern "C" int64_t eap_so3_dense_steps_words(int b, int p, int ks, int rp, int d
 }
 
 // the k-step lists of one direction from its mask table (eap_so3_dense_masks, same b, p, ks, rp, dir); skip = 0: every k-step is listed
-extern "C" int eap_so3_dense_steps(int b, int p, int ks, int rp, int dir, int skip, const int32_t *n_rows, const uint64_t *mask, int32_t *steps,
-                                   eap_stream_t stream) {
+namespace {
+int dense_steps(int words, int b, int p, int ks, int rp, int dir, int skip, const int32_t *n_rows, const uint64_t *mask, int32_t *steps, eap_stream_t stream) {
     if (b <= 0) return 0;
-    if (!eap_so3_dense_supported(p, 4, ks, rp, 256) || b > 65535) return eap::bad_arg("so3_dense_steps: shape not taken");
+    if (!dense_shape_ok(p, 4, ks, rp, 256, words) || b > 65535) return eap::bad_arg("so3_dense_steps: shape not taken");
     const int n = dir ? p : ks * rp, kd = dir ? ceil_to(ks * rp, KC_BK) : p;
     const int blocks_n = (n + 255) / 256, KS = kd / KC_BK;
     if ((size_t)KS * sizeof(int) > 48 * 1024) return eap::bad_arg("so3_dense_steps: more than 12288 k-steps");
     hipLaunchKernelGGL(dense_steps_kernel, dim3(blocks_n, b), dim3(256), sizeof(int) * (size_t)KS, eap::S(stream), KS, blocks_n, 4 * blocks_n, dir, ks, rp, skip,
                        n_rows, reinterpret_cast<const unsigned *>(mask), steps);
     return eap::check_launch("so3_dense_steps");
+}
+}  // namespace
+
+extern "C" int eap_so3_dense_steps(int b, int p, int ks, int rp, int dir, int skip, const int32_t *n_rows, const uint64_t *mask, int32_t *steps,
+                                   eap_stream_t stream) {
+    return dense_steps(MEMB_WORDS, b, p, ks, rp, dir, skip, n_rows, mask, steps, stream);
+}
+
+// ... from a mask table of eap_so3_dense_masks_wide: rp <= 1024
+extern "C" int eap_so3_dense_steps_wide(int b, int p, int ks, int rp, int dir, int skip, const int32_t *n_rows, const uint64_t *mask, int32_t *steps,
+                                        eap_stream_t stream) {
+    return dense_steps(MEMB_WORDS_WIDE, b, p, ks, rp, dir, skip, n_rows, mask, steps, stream);
 }
 
 // psum, psq (may be null): float [o][b * ceil(p / 64)] partial sums of (y - y[0,o,0,0]) and of its square per 64-point chunk

@@ -498,21 +498,39 @@ def so3_dense_supported(p, na, ks, rp, o):
     return bool(lib.eap_so3_dense_supported(int(p), int(na), int(ks), int(rp), int(o)))
 
 
-DENSE_MAX_ROWS = 512        # csrc/so3_dense.hip MEMB_WORDS * 32
+DENSE_MAX_ROWS = int(lib.eap_so3_dense_max_rows())        # 1024: the wide tables (32 membership words per point, int64 keys)
+DENSE_NARROW_ROWS = 512                                   # up to here the 16-word tables and the int32 key (include/eap_hip.h)
+
+
+def _dense_wide(memb):
+    """the membership table is the 32-word form (the *_wide entries of include/eap_hip.h)"""
+    return memb.shape[2] == 32
 
 
 def so3_dense_member(idx, rows, n_rows, n):
-    """Which of a cloud's referenced rows (rows [b, >= 512], n_rows [b]; eap_inv_lists_rows) every neighbour list names:
-    -> memb int32 [b,p,16] (bit masks), flags int32 [b] (non-zero: the cloud cannot take the dense product -- a list names a row
-    twice, or more than 512 rows are referenced).  No host value is needed: runs before the row count is known."""
+    """Which of a cloud's referenced rows (rows [b, n], n_rows [b]; eap_inv_lists_rows) every neighbour list names:
+    -> memb int32 [b,p,16] (bit masks; [b,p,32] when the support has more than 512 rows, so that up to 1024 referenced rows fit),
+    flags int32 [b] (non-zero: the cloud cannot take the dense product -- a list names a row twice, or more than min(n, 1024) rows are
+    referenced).  No host value is needed: runs before the row count is known, which is why the width follows the SUPPORT size;
+    the list head narrows the table once it knows that at most 512 rows are referenced (so3_dense_narrow; DenseGeometry does the same
+    for a caller that hands it a wide probe)."""
     b, p, nn = idx.shape
     dev = idx.device
-    memb = torch.empty(b, p, 16, dtype=torch.int32, device=dev)
+    wide = n > DENSE_NARROW_ROWS
+    memb = torch.empty(b, p, 32 if wide else 16, dtype=torch.int32, device=dev)
     flags = torch.empty(b, dtype=torch.int32, device=dev)
     slot_of = torch.empty(b, n, dtype=torch.int32, device=dev)
-    call('eap_so3_dense_member', idx, b, p, n, nn, min(DENSE_MAX_ROWS, n), rows.stride(0), _ptr(idx), _ptr(rows), _ptr(n_rows), _ptr(slot_of),
-         _ptr(memb), _ptr(flags))
+    call('eap_so3_dense_member_wide' if wide else 'eap_so3_dense_member', idx, b, p, n, nn, min(DENSE_MAX_ROWS if wide else DENSE_NARROW_ROWS, n),
+         rows.stride(0), _ptr(idx), _ptr(rows), _ptr(n_rows), _ptr(slot_of), _ptr(memb), _ptr(flags))
     return memb, flags
+
+
+def so3_dense_narrow(memb, rp):
+    """The table the product's geometry is built from at rp row slots: up to 512 the 16-word form -- the first 16 words of a wide probe,
+    whose words 16-31 are zero then -- so that keys, point order, masks and step lists are those of the 16-word tables."""
+    if _dense_wide(memb) and rp <= DENSE_NARROW_ROWS:
+        return memb[:, :, :16].contiguous()
+    return memb
 
 
 # Occupancy-sorted query points (round 6): a cloud's query points are handed to the dense product sorted by WHICH 16-row groups of the
@@ -538,10 +556,17 @@ class DenseGeometry:
         n = s_xyz.shape[2]
         na, ks, _ = rk.shape
         dev = memb.device
+        # up to 512 row slots the 16-word tables and the int32 key, whatever width the probe had: the point order the sort below gives -- and
+        # with it the backward's summation order -- is then the same for every support size
+        memb = so3_dense_narrow(memb, rp)
+        if memb.dtype != torch.int32 or not memb.is_contiguous() or memb.shape[2] not in (16, 32) or int(rp) > 32 * memb.shape[2]:
+            raise RuntimeError('DenseGeometry: memb must be a contiguous int32 [b,p,16] (rp <= 512) or [b,p,32] (rp <= 1024)')
+        self.wide = _dense_wide(memb)
         self.order = self.pivot_pos = None
         if SORT_DENSE_POINTS if sort is None else sort:
-            keys = torch.empty(b, p, dtype=torch.int32, device=dev)
-            call('eap_so3_dense_point_keys', memb, b, p, _ptr(memb), _ptr(keys))
+            # (32-word tables: one bit per group g < 64, an int64 key)
+            keys = torch.empty(b, p, dtype=torch.int64 if _dense_wide(memb) else torch.int32, device=dev)
+            call('eap_so3_dense_point_keys_wide' if _dense_wide(memb) else 'eap_so3_dense_point_keys', memb, b, p, _ptr(memb), _ptr(keys))
             order = torch.sort(keys, dim=1, stable=True).indices                               # int64 [b,p]: column j of the product is point order[b, j]
             q_xyz = q_xyz.gather(2, order[:, None, :].expand(b, 3, p)).contiguous()
             memb = memb.gather(1, order[:, :, None].expand(b, p, memb.shape[2])).contiguous()
@@ -564,7 +589,7 @@ class DenseGeometry:
         if m is None:
             words = int(lib.eap_so3_dense_mask_words(self.b, self.p, self.ks, self.rp, int(direction)))
             m = torch.empty(words, dtype=torch.int64, device=self.memb.device)
-            call('eap_so3_dense_masks', m, self.b, self.p, self.ks, self.rp, int(direction), _ptr(self.memb), _ptr(m))
+            call('eap_so3_dense_masks_wide' if self.wide else 'eap_so3_dense_masks', m, self.b, self.p, self.ks, self.rp, int(direction), _ptr(self.memb), _ptr(m))
             self._masks[direction] = m
         return m
 
@@ -580,7 +605,8 @@ class DenseGeometry:
             words = int(lib.eap_so3_dense_steps_words(self.b, self.p, self.ks, self.rp, int(direction)))
             assert words == self.b * blocks_n * (k_steps + 1)
             st = torch.empty(self.b, blocks_n, k_steps + 1, dtype=torch.int32, device=self.memb.device)
-            call('eap_so3_dense_steps', st, self.b, self.p, self.ks, self.rp, int(direction), 1, _ptr(self.n_rows), _ptr(self.mask(direction)), _ptr(st))
+            call('eap_so3_dense_steps_wide' if self.wide else 'eap_so3_dense_steps', st, self.b, self.p, self.ks, self.rp, int(direction), 1, _ptr(self.n_rows),
+                 _ptr(self.mask(direction)), _ptr(st))
             self._steps[direction] = st
         return self._steps[direction]
 
@@ -629,7 +655,7 @@ def _dense_executed_flops(geo, o, p, direction):
     rows = geo.rp * geo.b
     if KERNEL_TIMES is not None:
         st = geo.steps(direction)
-        if st is not None and st.shape[2] - 1 <= 512:
+        if st is not None and st.shape[2] - 1 <= 1024:      # (csrc/so3_dense.hip KC_LIST_BYTES / 4: longer lists are ignored)
             return 6.0 * o * geo.na * 256 * 32 * float(st[:, :, 0].sum().item())
         if geo.n_rows is not None:
             rows = sum(min((int(r) + 15) & ~15, geo.rp) for r in geo.n_rows.tolist())

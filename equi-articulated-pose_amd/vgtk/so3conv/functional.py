@@ -441,8 +441,9 @@ class _ListHead:
         are small latency-bound kernels (0.3 + 0.45 ms per layer) that nothing in the forward waits for, and the grouping and
         contraction kernels that follow on the main stream leave them room; the backward waits for `event`.
         dense_probe = (rotation blocks or None, ...): also the membership bits of the dense product (csrc/so3_dense.hip) and
-        whether every cloud can take it (no list names a row twice, at most 512 referenced rows, every given pose rotation
-        EXACTLY the identity -- the dense operand has no rotation in it)."""
+        whether every cloud can take it (no list names a row twice, at most min(n_sup, 1024) referenced rows, every given pose rotation
+        EXACTLY the identity -- the dense operand has no rotation in it).  The row count is not known on the host yet, so a support of
+        more than 512 rows is probed with the 32-word table (vgtk._hip.so3_dense_member); decide() narrows it once the count is known."""
         dev = idx.device
         main = torch.cuda.current_stream(dev)
         side = _side_stream(dev) if LISTS_ON_SIDE_STREAM else main
@@ -503,20 +504,28 @@ class _ListHead:
         """the current stream waits for the lists (device side; no host stall)"""
         torch.cuda.current_stream(self.rows.device).wait_event(self.event)
 
+    def _settle(self):
+        """Wait for the host copy.  A probe at the wide width whose clouds reference at most 512 rows is narrowed here, once: `memb` becomes
+        its first 16 words per point (words 16-31 are zero then), and everything downstream -- keys, point order, masks, step lists -- is what
+        a support of at most 512 rows gets.  (The lists have run by now: the copy needs no wait on the side stream.)"""
+        self.event.synchronize()
+        if self.memb is not None and int(self.host[0]) <= _hip.DENSE_NARROW_ROWS:
+            self.memb = _hip.so3_dense_narrow(self.memb, _hip.DENSE_NARROW_ROWS)
+
     def decide(self):
         """-> (rcap, any_nonident) as Python values."""
-        self.event.synchronize()
+        self._settle()
         rcap, flag, _, _ = self.host.tolist()
         return int(rcap), bool(flag)
 
     def groups_touched(self):
         """mean number of 16-row groups a point's list touches (the largest per-cloud mean); blocks on the host like decide()"""
-        self.event.synchronize()
+        self._settle()
         return int(self.host[3]) / 16.0
 
     def dense_possible(self):
         """every cloud can take the dense product (see __init__); blocks on the host like decide()"""
-        self.event.synchronize()
+        self._settle()
         return self.memb is not None and int(self.host[2]) == 0
 
 
@@ -658,10 +667,14 @@ FORWARD_LOG = None       # the same for the forward: {'channels', 'dense': the d
 # whenever the shapes are taken: tests).
 DENSE_MODE = os.environ.get('EAP_DENSE', 'auto')
 DENSE_ROW_FACTOR = 5.0
-# ... and beyond that row count (up to the 512 row slots the membership words hold) while a point's list touches few enough 16-row groups: with
+# ... and beyond that row count (up to the 1024 row slots the wide membership words hold) while a point's list touches few enough 16-row groups: with
 # the listed k-steps the product executes ~ groups_touched x 16 / nsample times the algorithmic flops (x 3 on the fp16 pipe at ~1.3 PFLOP/s)
 # against the list kernels' 0.46 of the fp32 peak -- it wins below ~24 groups; 16 leaves margin for the per-block overheads
 DENSE_MAX_GROUPS = float(os.environ.get('EAP_DENSE_MAX_GROUPS', '16'))
+# the same bound for clouds of more than 512 referenced rows (the 32-word tables); a knob of its own so that it can be raised for them alone.
+# Measured at 24 (the 64 -> 128 layer of 8 x 4096-point clouds with the 512-point radii, ~21 groups touched): the 128-row product costs what
+# the list kernels cost and the leg does not gain (profiles/dense_wide_rows.txt) -- 16 stays
+DENSE_MAX_GROUPS_WIDE = float(os.environ.get('EAP_DENSE_MAX_GROUPS_WIDE', '16'))
 # the forward at widths that fill 128-row blocks only (the 64 -> 128 layer): with every k-step it tied with grouping + contraction
 # (round 5: 9.0 against 9.1 ms); with the empty k-steps skipped (round 6) the product wins: 4.2 + 1.3 + 0.9 ms against 5.7 + 3.3, same run
 # 129.2 against 128.0 clouds/s before the operand kernel, more after it
@@ -686,7 +699,8 @@ def _dense_wanted(head, o, p, na, ks, nn, n):
         return 0, False
     if DENSE_MODE == 'force':
         return rp, True
-    if rp > DENSE_ROW_FACTOR * nn and not (rp <= _hip.DENSE_MAX_ROWS and head.groups_touched() <= DENSE_MAX_GROUPS):
+    if rp > DENSE_ROW_FACTOR * nn and not (rp <= _hip.DENSE_MAX_ROWS and
+                                           head.groups_touched() <= (DENSE_MAX_GROUPS if rp <= _hip.DENSE_NARROW_ROWS else DENSE_MAX_GROUPS_WIDE)):
         return 0, False
     return rp, (o % 256 == 0) or DENSE_FWD_NARROW
 

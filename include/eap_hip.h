@@ -333,7 +333,10 @@ int eap_rows_scatter_f32(int b, int c, int n, int na, int rcap, int rows_ld, con
  * prefix of it, and with n_rows given the products stop there (dir 0 zeroes the slots past ceil16(n_rows[b]) in Z).
  *   eap_so3_dense_form        how the weights are evaluated: 1 (default) from the squared distance, 0 from the expanded square
  *                             (fewer instructions, ~3 x the rounding error); tables and product under the same setting; -> old setting
- *   eap_so3_dense_supported   p % 32 == 0, na % 4 == 0, na <= 64, ks % 2 == 0, rp % 16 == 0, rp <= 512, o % 128 == 0 (256-row blocks when o % 256 == 0)
+ *   eap_so3_dense_supported   p % 32 == 0, na % 4 == 0, na <= 64, ks % 2 == 0, rp % 16 == 0, rp <= 1024 (eap_so3_dense_max_rows), o % 128 == 0 (256-row
+ *                             blocks when o % 256 == 0).  The product, table, split and operand entries take every such rp; the entries that take
+ *                             `memb` come in two widths: the plain ones below (memb [b,p,16], int32 keys, rp <= 512) and the *_wide ones further down
+ *                             (memb [b,p,32], int64 keys, rp <= 1024).  Up to 512 rows both give the same tables from the same membership bits.
  *   eap_so3_dense_member      slot_of int32 [b,n] (scratch), memb uint32 [b,p,16] (bit r of point p = m[p,r]; rp <= 512),
  *                             flags int32 [b]: 1 = a list names a row twice (padded short lists, grouping_cuda_kernel.cu:L98-107:
  *                             not representable by a 0/1 mask), 2 = a list names a row outside rows[:, :rp] -- such clouds
@@ -368,7 +371,7 @@ int eap_rows_scatter_f32(int b, int c, int n, int na, int rcap, int rows_ld, con
  *                             count (>= 1) and the ascending k-steps in which the block generates a weight that is not masked out
  *                             (skip = 0: every k-step; dir 1 with n_rows: of the cloud's prefix)
  *   eap_so3_dense_product_steps_f32   eap_so3_dense_product_f32 whose column blocks run their listed k-steps only (steps may be null; lists
- *                             longer than 512 k-steps are ignored: every k-step runs).  Skipped k-steps would have added exact zeros:
+ *                             longer than 1024 k-steps are ignored: every k-step runs).  Skipped k-steps would have added exact zeros:
  *                             bit-equal to running them all in the same point order.  so3conv/functional.py:L1221-1261 */
 int eap_so3_dense_supported(int p, int na, int ks, int rp, int o);
 int eap_so3_dense_form(int form);
@@ -414,6 +417,21 @@ int eap_so3_dense_steps(int b, int p, int ks, int rp, int dir, int skip, const i
 int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int na, int ks, int rp, int64_t ldz, float sigma, const int32_t *n_rows,
                                     const void *planes, const float *scale, const float *pt, const float *kr, const uint64_t *mask,
                                     const int32_t *steps, float *out, eap_stream_t stream);
+/* Clouds that reference up to 1024 support rows: 64 groups of 16 rows, 32 membership words per point, a 64-bit group key.
+ *   eap_so3_dense_max_rows          the largest rp any entry takes (1024)
+ *   eap_so3_dense_member_wide       eap_so3_dense_member with memb uint32 [b,p,32] (bit i of word w of point p = m[p, 32 w + i]); rp <= 1024;
+ *                                   flag 2 = more than rp referenced rows
+ *   eap_so3_dense_point_keys_wide   memb uint32 [b,p,32] -> keys int64 [b,p], bit g < 64 = the list of p names a row slot of 16 g .. 16 g + 15
+ *   eap_so3_dense_masks_wide        memb uint32 [b,p,32], rp <= 1024 -> the mask table of eap_so3_dense_masks (same layout, eap_so3_dense_mask_words)
+ *   eap_so3_dense_steps_wide        eap_so3_dense_steps for rp <= 1024 (same layout, eap_so3_dense_steps_words)
+ * Everything else (tables, split, operand, product, re-ordering) is the same entry at either width. */
+int eap_so3_dense_max_rows(void);
+int eap_so3_dense_member_wide(int b, int p, int n, int nn, int rp, int rows_ld, const int32_t *idx, const int32_t *rows,
+                              const int32_t *n_rows, int32_t *slot_of, uint32_t *memb, int32_t *flags, eap_stream_t stream);
+int eap_so3_dense_point_keys_wide(int b, int p, const uint32_t *memb, int64_t *keys, eap_stream_t stream);
+int eap_so3_dense_masks_wide(int b, int p, int ks, int rp, int dir, const uint32_t *memb, uint64_t *mask, eap_stream_t stream);
+int eap_so3_dense_steps_wide(int b, int p, int ks, int rp, int dir, int skip, const int32_t *n_rows, const uint64_t *mask, int32_t *steps,
+                             eap_stream_t stream);
 
 /* ---- SO(3) intra convolution -------------------------------------------------------------- */
 
