@@ -11,6 +11,7 @@ import, and non-device tensors are rejected.
 """
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -184,30 +185,34 @@ def _planes2(transB, M, N, K, A, lda, batch, B, ldb, strideB, b_bound):
     return None if abs_b is None else (abs_a, abs_b, 1 if transB else 4, 1.0)
 
 
+def _gemm_split(transB, M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, batch, b_bound, tag, epilogue=None):
+    """C_z = A B_z on the split-operand kernels (csrc/gemm_bf16x3.hip: A shared by the batch, 'nt' or 'nn'), two fp16 planes where _planes2
+    has the magnitudes, else three bf16 planes; epilogue = (scale, shift, slope, residual) of gemm_epilogue.  -> False when the operands do
+    not qualify (nothing launched)."""
+    tb = int(bool(transB))
+    split = 'eap_gemm_bf16x3_f32' if tb else 'eap_gemm_bf16x3_nn_f32'
+    if not getattr(lib, split + '_supported')(M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB)):
+        return False
+    ops = (M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C), _I64(ldc), _I64(strideC), batch)
+    ep = (None, None, _F32(0.0), None, _I64(0)) if epilogue is None else \
+        (_ptr(epilogue[0]), _ptr(epilogue[1]), _F32(epilogue[2]), _ptr(epilogue[3]), _I64(strideC))
+    two = _planes2(tb, M, N, K, A, lda, batch, B, ldb, strideB, b_bound)
+    if two is not None:
+        call('eap_gemm_f16x2_f32', C, tb, *ops, _ptr(two[0]), _ptr(two[1]), two[2], _F32(two[3]), *ep, tag=tag)
+    elif epilogue is None:
+        call(split, C, *ops, tag=tag)
+    else:
+        call('eap_gemm_bf16x3_ep_f32', C, tb, *ops, *ep, tag=tag)
+    return True
+
+
 def gemm(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch, b_blocked=False, b_bound=None):
     """b_blocked: B is stored blocked by 4 (include/eap_hip.h); `ldb` is then ignored.  b_bound = (words int32 [batch, N // grp] holding
     non-negative float bit patterns, grp = consecutive columns per word, factor): words * factor bounds the magnitudes of B's columns,
     see _planes2 (saves the two-plane kernel its pass over B)."""
     tag = {'flops': 2.0 * M * N * K * batch, 'shape': ('gemm', int(transA), int(transB), M, N, K, batch)}
-    if SPLIT_BF16_CONTRACTION and not b_blocked and not transA and transB and (strideA == 0 or batch == 1) and \
-            lib.eap_gemm_bf16x3_f32_supported(M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB)):
-        two = _planes2(1, M, N, K, A, lda, batch, B, ldb, strideB, b_bound)
-        if two is not None:
-            call('eap_gemm_f16x2_f32', C, 1, M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C), _I64(ldc), _I64(strideC),
-                 batch, _ptr(two[0]), _ptr(two[1]), two[2], _F32(two[3]), None, None, _F32(0.0), None, _I64(0), tag=tag)
-            return
-        call('eap_gemm_bf16x3_f32', C, M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C), _I64(ldc), _I64(strideC),
-             batch, tag=tag)
-        return
-    if SPLIT_BF16_CONTRACTION and not b_blocked and not transA and not transB and (strideA == 0 or batch == 1) and \
-            lib.eap_gemm_bf16x3_nn_f32_supported(M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB)):
-        two = _planes2(0, M, N, K, A, lda, batch, B, ldb, strideB, b_bound)
-        if two is not None:
-            call('eap_gemm_f16x2_f32', C, 0, M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C), _I64(ldc), _I64(strideC),
-                 batch, _ptr(two[0]), _ptr(two[1]), two[2], _F32(two[3]), None, None, _F32(0.0), None, _I64(0), tag=tag)
-            return
-        call('eap_gemm_bf16x3_nn_f32', C, M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C), _I64(ldc), _I64(strideC),
-             batch, tag=tag)
+    if SPLIT_BF16_CONTRACTION and not b_blocked and not transA and (strideA == 0 or batch == 1) and \
+            _gemm_split(transB, M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, batch, b_bound, tag):
         return
     if not b_blocked and _dma_ok(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB):
         call('eap_gemm_dma_f32', C, int(transA), int(transB), M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb),
@@ -221,22 +226,9 @@ def gemm_epilogue(transB, M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, bat
     """C_z = leaky_relu(scale[row] * (A B_z) + shift[row], slope) (+ residual_z, laid out like C) on the split kernel
     (eap_gemm_bf16x3_ep_f32): an inference-mode BatchNorm + activation folded into the contraction.  -> False when the
     operands do not qualify for that kernel (nothing launched: the caller runs product and epilogue separately)."""
-    if not SPLIT_BF16_CONTRACTION:
-        return False
-    ok = (lib.eap_gemm_bf16x3_f32_supported if transB else lib.eap_gemm_bf16x3_nn_f32_supported)(
-        M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB))
-    if not ok:
-        return False
     tag = {'flops': 2.0 * M * N * K * batch, 'shape': ('gemm_epilogue', 0, int(transB), M, N, K, batch)}
-    two = _planes2(int(transB), M, N, K, A, lda, batch, B, ldb, strideB, b_bound)
-    if two is not None:
-        call('eap_gemm_f16x2_f32', C, int(transB), M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C), _I64(ldc),
-             _I64(strideC), batch, _ptr(two[0]), _ptr(two[1]), two[2], _F32(two[3]), _ptr(scale), _ptr(shift), _F32(slope), _ptr(residual),
-             _I64(strideC), tag=tag)
-        return True
-    call('eap_gemm_bf16x3_ep_f32', C, int(transB), M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C), _I64(ldc),
-         _I64(strideC), batch, _ptr(scale), _ptr(shift), _F32(slope), _ptr(residual), _I64(strideC), tag=tag)
-    return True
+    return bool(SPLIT_BF16_CONTRACTION and _gemm_split(transB, M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, batch, b_bound, tag,
+                                                       (scale, shift, slope, residual)))
 
 
 def gemm_nn_takes_split(M, N, K, A, lda, B, ldb):
@@ -252,28 +244,22 @@ def gemm_reduce_takes_split(M, N, K, A, lda, strideA, B, ldb, strideB, ldc):
 
 def gemm_reduce(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, batch, b_blocked=False):
     tag = {'flops': 2.0 * M * N * K * batch, 'shape': ('gemm_reduce', int(transA), int(transB), M, N, K, batch)}
-    if SPLIT_BF16_CONTRACTION and not b_blocked and not transA and transB and \
-            lib.eap_gemm_bf16x3_reduce_f32_supported(M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb), _I64(strideB), _I64(ldc)):
-        ws = torch.empty(int(lib.eap_gemm_bf16x3_reduce_workspace(M, N, K, batch)), dtype=torch.float32, device=C.device)
-        call('eap_gemm_bf16x3_reduce_f32', C, M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C),
-             _I64(ldc), batch, _ptr(ws), tag=tag)
-        return
-    if not b_blocked and not transA and transB and lib.eap_gemm_skinny_reduce_f32_supported(M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B),
-                                                                                         _I64(ldb), _I64(strideB)):
+    ops = (M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb), _I64(strideB))
+    nt = not b_blocked and not transA and transB
+    lead = (int(transA), int(transB))
+    if SPLIT_BF16_CONTRACTION and nt and lib.eap_gemm_bf16x3_reduce_f32_supported(*ops, _I64(ldc)):
+        name, ws_words, lead = 'eap_gemm_bf16x3_reduce_f32', lib.eap_gemm_bf16x3_reduce_workspace, ()      # ('nt' only: no transposition flags)
+    elif nt and lib.eap_gemm_skinny_reduce_f32_supported(*ops):
         # a small output over a long contraction (the first layer's weight gradient): streaming reduction, csrc/gemm_skinny.hip
-        ws = torch.empty(max(int(lib.eap_gemm_skinny_reduce_workspace(M, N, K, batch)), 1), dtype=torch.float32, device=C.device)
-        call('eap_gemm_skinny_reduce_f32', C, M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C), _I64(ldc),
-             batch, _ptr(ws), tag=tag)
-        return
-    if not b_blocked and _dma_ok(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB):
-        ws = torch.empty(max(int(lib.eap_gemm_dma_f32_reduce_workspace(M, N, K, batch)), 1), dtype=torch.float32, device=C.device)
-        call('eap_gemm_dma_f32_reduce', C, int(transA), int(transB), M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb),
-             _I64(strideB), _ptr(C), _I64(ldc), batch, _ptr(ws), tag=tag)
-        return
-    n_ws = lib.eap_gemm_f32_reduce_workspace(M, N, K, batch)
-    ws = torch.empty(max(int(n_ws), 1), dtype=torch.float32, device=C.device)
-    call('eap_gemm_f32_reduce_xb' if b_blocked else 'eap_gemm_f32_reduce', C, int(transA), int(transB), M, N, K, _ptr(A), _I64(lda), _I64(strideA),
-         _ptr(B), _I64((N if transB else K) if b_blocked else ldb), _I64(strideB), _ptr(C), _I64(ldc), batch, _ptr(ws), tag=tag)
+        name, ws_words, lead = 'eap_gemm_skinny_reduce_f32', lib.eap_gemm_skinny_reduce_workspace, ()
+    elif not b_blocked and _dma_ok(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB):
+        name, ws_words = 'eap_gemm_dma_f32_reduce', lib.eap_gemm_dma_f32_reduce_workspace
+    else:
+        name, ws_words = 'eap_gemm_f32_reduce_xb' if b_blocked else 'eap_gemm_f32_reduce', lib.eap_gemm_f32_reduce_workspace
+        if b_blocked:
+            ops = ops[:7] + (_I64(N if transB else K),) + ops[8:]
+    ws = torch.empty(max(int(ws_words(M, N, K, batch)), 1), dtype=torch.float32, device=C.device)
+    call(name, C, *lead, *ops, _ptr(C), _I64(ldc), batch, _ptr(ws), tag=tag)
 
 
 def so3_prep(q_xyz, s_xyz, idx, q_pose, s_pose, anchors, identity_anchor):
@@ -338,6 +324,7 @@ def so3_inter_group_fwd(feats, idx, gx, rk, mult, sigma, nonident=None, blocked=
     p, nn = idx.shape[1], idx.shape[2]
     ks = rk.shape[1]
     out = torch.empty(b, c, ks, p, na, dtype=torch.float32, device=feats.device)
+    tag = lambda kind: {'flops': 2.0 * b * c * ks * p * nn * na, 'shape': (kind, b, c, p, nn, na, ks)}
     if (coset is not None and int(blocked) == 2 and mult is not None and nonident is not None and nn > 0
             and so3_group_perm_lists2_takes(c, na, ks, n)):
         # clouds with anchor permutations on the two-tile kernel (csrc/so3_inter_lists2.hip, PERM): their features with a coset-major
@@ -347,17 +334,17 @@ def so3_inter_group_fwd(feats, idx, gx, rk, mult, sigma, nonident=None, blocked=
         ent_pc, ent_gx2 = so3_perm_entries(idx.view(b, p * nn), gx.view(b, p * nn, 4), coset[1], None, 0, na, n, nonident)
         call('eap_so3_inter_group_fwd_perm2_t_f32', out, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(feats), _ptr(feats_c), _ptr(idx), _ptr(gx),
              _ptr(ent_pc), _ptr(ent_gx2), _ptr(rk), _ptr(coset[0]), _ptr(nonident), int(bool(store_order)), _ptr(out),
-             tag={'flops': 2.0 * b * c * ks * p * nn * na, 'shape': ('group_fwd_perm2', b, c, p, nn, na, ks)})
+             tag=tag('group_fwd_perm2'))
         return out
     if store_order:
         if mult is not None or int(blocked) != 2:
             raise RuntimeError('store-order columns: transposed layout, clouds without permutation (or the coset tables for the flagged ones)')
         call('eap_so3_inter_group_fwd_tp_f32', out, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(feats), _ptr(idx), _ptr(gx), _ptr(rk), _ptr(out),
-             tag={'flops': 2.0 * b * c * ks * p * nn * na, 'shape': ('group_fwd_tp', b, c, p, nn, na, ks)})
+             tag=tag('group_fwd_tp'))
         return out
     call({0: 'eap_so3_inter_group_fwd_f32', 1: 'eap_so3_inter_group_fwd_xb_f32', 2: 'eap_so3_inter_group_fwd_t_f32'}[int(blocked)], out, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(feats), _ptr(idx),
          _ptr(gx), _ptr(rk), _ptr(mult), _ptr(nonident), _ptr(out),
-         tag={'flops': 2.0 * b * c * ks * p * nn * na, 'shape': ('group_fwd', b, c, p, nn, na, ks)})
+         tag=tag('group_fwd'))
     return out
 
 
@@ -662,6 +649,16 @@ def _dense_executed_flops(geo, o, p, direction):
     return 6.0 * o * p * geo.na * geo.ks * rows
 
 
+def _dense_product(direction, geo, b, o, p, ld, scale, planes, out, flops):
+    """One launch of the product kernel over p columns with the stored operand (scale, planes): direction 0 -> Z [b,o,ks,ld] (the backward;
+    row pitch ld), 1 -> Yt [b,na,o,p] (the forward; ld 0).  flops: what the launch stands for algorithmically (bench.py).  -> out"""
+    call('eap_so3_dense_product_steps_f32', out, direction, b, o, p, geo.na, geo.ks, geo.rp, _I64(ld), _F32(geo.sigma), _ptr(geo.n_rows), _ptr(planes),
+         _ptr(scale), _ptr(geo.pt), _ptr(geo.kr), _ptr(geo.mask(direction)), _ptr(geo.steps(direction)), _ptr(out),
+         tag={'flops': flops, 'executed_f16_flops': _dense_executed_flops(geo, o, p, direction),
+              'shape': ('so3_dense', direction, b, o, p, geo.na, geo.ks, geo.rp)})
+    return out
+
+
 def so3_dense_bwd(gy, geo, ldz=None, colmap=None, rowmax=False):
     """gy [b,o,p,na] -> Z [b,o,ks,ldz] whose rows hold [na,rp] (the inverse-list kernel's Z with the anchor axis in front of the row
     axis); ldz >= na*rp (default: equal) pads the rows for the GEMMs that follow -- the padding is NOT written.
@@ -674,11 +671,7 @@ def so3_dense_bwd(gy, geo, ldz=None, colmap=None, rowmax=False):
     if colmap is not None:
         p = colmap.shape[1]
     z = torch.empty(b, o, geo.ks, ldz, dtype=torch.float32, device=gy.device)
-    call('eap_so3_dense_product_steps_f32', gy, 0, b, o, p, na, geo.ks, geo.rp, _I64(ldz), _F32(geo.sigma), _ptr(geo.n_rows), _ptr(planes), _ptr(scale), _ptr(geo.pt),
-         _ptr(geo.kr), _ptr(geo.mask(0)), _ptr(geo.steps(0)), _ptr(z),
-         tag={'flops': 2.0 * b * o * p * na * geo.ks * geo.nn, 'executed_f16_flops': _dense_executed_flops(geo, o, p, 0),
-              'shape': ('so3_dense', 0, b, o, p, na, geo.ks, geo.rp)})
-    return z
+    return _dense_product(0, geo, b, o, p, ldz, scale, planes, z, 2.0 * b * o * p * na * geo.ks * geo.nn)
 
 
 def so3_dense_gplanes(fc4, W3, geo):
@@ -713,22 +706,21 @@ def so3_dense_fwd(g, geo, p, c=0, ldg=None, out=None, col_map=None, operand=None
     out [b,o,p_dst,na] with col_map int32 [b,p]: the p columns are the points col_map[b, :] of `out` (negative: padding) -- the launch
     of one rigid part of posed clouds; returns out."""
     yt = _dense_fwd_yt(g, geo, p, c, ldg, operand, o)
-    g = yt
     b, na, o = yt.shape[0], geo.na, yt.shape[2]
     if col_map is not None:
         if out is None or col_map.dtype != torch.int32 or tuple(col_map.shape) != (b, p) or not col_map.is_contiguous() or not out.is_contiguous():
             raise RuntimeError('so3_dense_fwd: col_map must be a contiguous int32 [b,p] and come with a contiguous out')
-        call('eap_so3_dense_untranspose_map_f32', g, b, o, p, na, out.shape[2], _ptr(geo.columns(col_map)), _ptr(yt), _ptr(out))
+        call('eap_so3_dense_untranspose_map_f32', yt, b, o, p, na, out.shape[2], _ptr(geo.columns(col_map)), _ptr(yt), _ptr(out))
         return out
-    y = torch.empty(b, o, p, na, dtype=torch.float32, device=g.device)
+    y = torch.empty(b, o, p, na, dtype=torch.float32, device=yt.device)
     # the re-ordering pass also leaves the channel moments a BatchNorm right behind this layer starts with (its own pass otherwise)
     chunks = (p + 63) // 64
-    ps = torch.empty(o, b * chunks, dtype=torch.float32, device=g.device)
+    ps = torch.empty(o, b * chunks, dtype=torch.float32, device=yt.device)
     pq = torch.empty_like(ps)
     if geo.order is not None:                                     # columns in the geometry's point order: written through it
-        call('eap_so3_dense_untranspose_map_stats_f32', g, b, o, p, na, p, _ptr(geo.order), _ptr(geo.pivot_pos), _ptr(yt), _ptr(y), _ptr(ps), _ptr(pq))
+        call('eap_so3_dense_untranspose_map_stats_f32', yt, b, o, p, na, p, _ptr(geo.order), _ptr(geo.pivot_pos), _ptr(yt), _ptr(y), _ptr(ps), _ptr(pq))
     else:
-        call('eap_so3_dense_untranspose_f32', g, b, o, p, na, _ptr(yt), _ptr(y), _ptr(ps), _ptr(pq))
+        call('eap_so3_dense_untranspose_f32', yt, b, o, p, na, _ptr(yt), _ptr(y), _ptr(ps), _ptr(pq))
     leave_stats_hint(y, (ps, pq))
     return y
 
@@ -744,11 +736,7 @@ def _dense_fwd_yt(g, geo, p, c, ldg, operand, o):
         scale, planes = operand
         b = geo.b
     yt = torch.empty(b, na, o, p, dtype=torch.float32, device=planes.device)
-    call('eap_so3_dense_product_steps_f32', yt, 1, b, o, p, na, geo.ks, geo.rp, _I64(0), _F32(geo.sigma), _ptr(geo.n_rows), _ptr(planes), _ptr(scale), _ptr(geo.pt),
-         _ptr(geo.kr), _ptr(geo.mask(1)), _ptr(geo.steps(1)), _ptr(yt),
-         tag={'flops': 2.0 * b * c * geo.ks * na * (p * geo.nn + o * p - o * geo.rp), 'executed_f16_flops': _dense_executed_flops(geo, o, p, 1),
-              'shape': ('so3_dense', 1, b, o, p, na, geo.ks, geo.rp)})
-    return yt
+    return _dense_product(1, geo, b, o, p, 0, scale, planes, yt, 2.0 * b * c * geo.ks * na * (p * geo.nn + o * p - o * geo.rp))
 
 
 def so3_dense_fwd_bnact(g, geo, p, c, ldg, norm_moments, operand=None, o=None, affine=None):
@@ -797,11 +785,7 @@ def so3_dense_bwd_bn(gy, yact, geo, ldz, coef, rowbound, slope):
     call('eap_so3_dense_split_bn_f32', gy, b, o, l, p, na, _ptr(rowbound.view(torch.int32)), _ptr(colmap), _ptr(gy), _ptr(yact), _ptr(coef), _F32(slope), _ptr(scale),
          _ptr(planes))
     z = torch.empty(b, o, geo.ks, ldz, dtype=torch.float32, device=gy.device)
-    call('eap_so3_dense_product_steps_f32', gy, 0, b, o, l, na, geo.ks, geo.rp, _I64(ldz), _F32(geo.sigma), _ptr(geo.n_rows), _ptr(planes), _ptr(scale), _ptr(geo.pt),
-         _ptr(geo.kr), _ptr(geo.mask(0)), _ptr(geo.steps(0)), _ptr(z),
-         tag={'flops': 2.0 * b * o * l * na * geo.ks * geo.nn, 'executed_f16_flops': _dense_executed_flops(geo, o, l, 0),
-              'shape': ('so3_dense', 0, b, o, l, na, geo.ks, geo.rp)})
-    return z
+    return _dense_product(0, geo, b, o, l, ldz, scale, planes, z, 2.0 * b * o * l * na * geo.ks * geo.nn)
 
 
 def _partials(x, b, c, n):
@@ -816,18 +800,27 @@ _STATS_HINT = [None]
 STATS_HINTS_TAKEN = 0
 
 
+def _leave_hint(slot, t, payload):
+    slot[0] = (weakref.ref(t), t._version, tuple(t.shape), payload)
+
+
+def _take_hint(slot, t):
+    """the slot's payload if it was left for exactly this tensor (object, version, shape), else None; the slot is empty afterwards"""
+    h, slot[0] = slot[0], None
+    if not USE_ROWMAX_HINT or h is None or h[0]() is not t or h[1] != t._version or h[2] != tuple(t.shape):
+        return None
+    return h[3]
+
+
 def leave_stats_hint(t, partials):
-    import weakref
-    _STATS_HINT[0] = (weakref.ref(t), t._version, tuple(t.shape), partials)
+    _leave_hint(_STATS_HINT, t, partials)
 
 
 def take_stats_hint(t):
     global STATS_HINTS_TAKEN
-    h, _STATS_HINT[0] = _STATS_HINT[0], None
-    if not USE_ROWMAX_HINT or h is None or h[0]() is not t or h[1] != t._version or h[2] != tuple(t.shape):
-        return None
-    STATS_HINTS_TAKEN += 1
-    return h[3]
+    partials = _take_hint(_STATS_HINT, t)
+    STATS_HINTS_TAKEN += partials is not None
+    return partials
 
 
 def bn_stats(x, b, c, n):
@@ -866,17 +859,14 @@ ROWMAX_HINTS_TAKEN = 0        # how often a hint was accepted (tests)
 
 
 def leave_rowmax_hint(t, rowmax):
-    import weakref
-    _ROWMAX_HINT[0] = (weakref.ref(t), t._version, tuple(t.shape), rowmax)
+    _leave_hint(_ROWMAX_HINT, t, rowmax)
 
 
 def take_rowmax_hint(t):
     global ROWMAX_HINTS_TAKEN
-    h, _ROWMAX_HINT[0] = _ROWMAX_HINT[0], None
-    if not USE_ROWMAX_HINT or h is None or h[0]() is not t or h[1] != t._version or h[2] != tuple(t.shape):
-        return None
-    ROWMAX_HINTS_TAKEN += 1
-    return h[3]
+    rowmax = _take_hint(_ROWMAX_HINT, t)
+    ROWMAX_HINTS_TAKEN += rowmax is not None
+    return rowmax
 
 
 def bn_act_bwd_apply(gy, x, b, c, n, scale, shift, mean, invstd, k2, k3, slope):

@@ -37,6 +37,21 @@ def batch_moments(s1, s2, pivot, count, sync=False):
     return mean, var, total
 
 
+def affine_from_moments(mean, var, weight, bias, eps):
+    """BatchNorm as one per-channel map y = scale x + shift, formed in float64 from the (float64) mean and biased variance:
+    -> (scale float32, shift float32, invstd float64)."""
+    invstd = torch.rsqrt(var + eps)
+    scale64 = weight.double() * invstd
+    return scale64.float(), (bias.double() - mean * scale64).float(), invstd
+
+
+def update_running_stats(running_mean, running_var, mean, var, count, momentum):
+    """nn.BatchNorm2d's running statistics after a training batch of `count` elements per channel (unbiased variance)."""
+    with torch.no_grad():
+        running_mean.mul_(1.0 - momentum).add_(mean.to(running_mean.dtype), alpha=momentum)
+        running_var.mul_(1.0 - momentum).add_((var * (count / (count - 1))).to(running_var.dtype), alpha=momentum)
+
+
 def all_reduce_sums(*tensors, sync=False):
     """Sum float64 per-channel reductions over the ranks (one all-reduce); identity without sync."""
     if not _syncing(sync):
@@ -73,18 +88,12 @@ class _BNAct(torch.autograd.Function):
             s1, s2 = _hip.bn_stats(x, b, c, n)
             mean, var, count = batch_moments(s1, s2, pivot, count, sync)    # biased variance, as BatchNorm normalises with
             if running_mean is not None:
-                with torch.no_grad():
-                    full = mean if pre_bias is None else mean + pre_bias.double()
-                    running_mean.mul_(1.0 - momentum).add_(full.to(running_mean.dtype), alpha=momentum)
-                    running_var.mul_(1.0 - momentum).add_((var * (count / (count - 1))).to(running_var.dtype), alpha=momentum)
+                update_running_stats(running_mean, running_var, mean if pre_bias is None else mean + pre_bias.double(), var, count, momentum)
         else:
             mean, var = running_mean.double(), running_var.double()
             if pre_bias is not None:
                 mean = mean - pre_bias.double()
-        invstd = torch.rsqrt(var + eps)
-        scale64 = weight.double() * invstd
-        scale = scale64.float()
-        shift = (bias.double() - mean * scale64).float()
+        scale, shift, invstd = affine_from_moments(mean, var, weight, bias, eps)
         y = _hip.bn_act_fwd(x, b, c, n, scale, shift, slope, residual)
         ctx.has_res = residual is not None
         ctx.has_pre_bias = pre_bias is not None
@@ -142,9 +151,9 @@ class BatchNormLeakyReLU(nn.BatchNorm2d):
         from .functional import FoldedEpilogue
         if self.training:
             raise RuntimeError('BatchNormLeakyReLU.folded: training-mode statistics depend on the data; call .eval() first')
-        scale64 = self.weight.detach().double() * torch.rsqrt(self.running_var.double() + self.eps)
         mean = self.running_mean.double() if pre_bias is None else self.running_mean.double() - pre_bias.detach().double()
-        return FoldedEpilogue(scale64.float(), (self.bias.detach().double() - mean * scale64).float(), self.negative_slope, residual)
+        scale, shift, _ = affine_from_moments(mean, self.running_var.double(), self.weight.detach(), self.bias.detach(), self.eps)
+        return FoldedEpilogue(scale, shift, self.negative_slope, residual)
 
 
 def conv_norm_act(conv, norm, x, **conv_kwargs):
@@ -182,13 +191,10 @@ def pointwise_norm_act(conv1x1, norm, x, residual=None):
     from .functional import so3_contract
     b, c, n, a = x.shape
     W = conv1x1.weight.view(conv1x1.out_channels, c)
-    if not norm.training and not torch.is_grad_enabled():
-        ep = norm.folded(pre_bias=conv1x1.bias, residual=residual)
-        y = so3_contract(W, x.reshape(b, c, n * a), ep).view(b, conv1x1.out_channels, n, a)
-        if ep.applied:
-            return y
-        return norm(y, residual=residual, pre_bias=conv1x1.bias)
-    y = so3_contract(W, x.reshape(b, c, n * a)).view(b, conv1x1.out_channels, n, a)
+    ep = norm.folded(pre_bias=conv1x1.bias, residual=residual) if (not norm.training and not torch.is_grad_enabled()) else None
+    y = so3_contract(W, x.reshape(b, c, n * a), ep).view(b, conv1x1.out_channels, n, a)
+    if ep is not None and ep.applied:
+        return y
     return norm(y, residual=residual, pre_bias=conv1x1.bias)
 
 

@@ -608,19 +608,13 @@ class TrainEpilogue:
     def moments(self, s1, s2, pivot, count):
         """pivoted sums of the conv output per channel -> (scale, shift, slope) of the fused pass; updates the running statistics exactly as
         vgtk.so3conv.blocks._BNAct.forward does; leaves what the backward needs in self.saved"""
-        from .blocks import batch_moments
+        from .blocks import affine_from_moments, batch_moments, update_running_stats
         norm = self.norm
         mean, var, total = batch_moments(s1, s2, pivot, count, norm.sync)
         if norm.running_mean is not None:
-            with torch.no_grad():
-                m = norm.momentum
-                norm.running_mean.mul_(1.0 - m).add_(mean.to(norm.running_mean.dtype), alpha=m)
-                norm.running_var.mul_(1.0 - m).add_((var * (total / (total - 1))).to(norm.running_var.dtype), alpha=m)
-        invstd = torch.rsqrt(var + norm.eps)
+            update_running_stats(norm.running_mean, norm.running_var, mean, var, total, norm.momentum)
         gamma = norm.weight.detach().double()
-        scale64 = gamma * invstd
-        scale = scale64.float()
-        shift = (norm.bias.detach().double() - mean * scale64).float()
+        scale, shift, _ = affine_from_moments(mean, var, gamma, norm.bias.detach(), norm.eps)
         inv_gamma = torch.where(gamma == 0, torch.zeros_like(gamma), 1.0 / gamma).float()
         # (copies, not views of the parameters: the backward must see the values this forward normalised with)
         self.saved = (scale, norm.bias.detach().float().clone(), inv_gamma.contiguous(), total)
@@ -857,6 +851,11 @@ def _dense_g(fc4, W, geo):
     return g.view(b, o, ks, ld), (None if ld == ra else ld), None
 
 
+def _dense_operand(feats, W, rows, geo):
+    """the dense forward's stored operand from the support features: _dense_g over the referenced rows"""
+    return _dense_g(_hip.rows_gather(feats, rows, geo.rp), W, geo)
+
+
 def _dense_forward_parts(feats, W, rows, pd, p):
     """the dense forward of posed clouds, one launch per part slot (see _PartsDense) -> y [b,o,p,a]"""
     b, c, n, na = feats.shape
@@ -873,327 +872,394 @@ def _dense_forward_parts(feats, W, rows, pd, p):
 
 def _dense_forward(feats, W, rows, geo, p):
     """y [b,o,p,a] = sum_(k,r) G[o,(k,r),a] Wd[p,(k,r),a] with G = W F over the referenced rows (csrc/so3_dense.hip)."""
-    g, ldg, operand = _dense_g(_hip.rows_gather(feats, rows, geo.rp), W, geo)
+    g, ldg, operand = _dense_operand(feats, W, rows, geo)
     return _hip.so3_dense_fwd(g, geo, p, feats.shape[1], ldg=ldg, operand=operand, o=W.shape[0])
+
+
+class _InterConvArgs:
+    """The inputs of _InterConv that carry no gradient, as one record, made where the conv is called."""
+
+    def __init__(self, idx, gx, rk, mult, sigma, ident, nonident=None, anchors=None, epilogue=None, geometry=None):
+        self.idx, self.gx, self.rk, self.mult, self.sigma, self.ident, self.nonident = idx, gx, rk, mult, float(sigma), ident, nonident
+        self.anchors = anchors.detach().contiguous() if (anchors is not None and mult is not None) else None   # the rotations `mult` was built from
+        # epilogue: a FoldedEpilogue or a TrainEpilogue;
+        # geometry = (q_xyz, xyz, q_rot, rot): what the dense product over the referenced rows is built from (csrc/so3_dense.hip)
+        self.epilogue, self.geometry = epilogue, geometry
+        # torch.is_grad_enabled() AT THE CALL (inside forward() autograd always has it off; and under torch.no_grad()
+        # needs_input_grad still reports the parameters although nothing will be differentiated)
+        self.grad_mode = torch.is_grad_enabled()
+
+
+class _DensePlan:
+    """Whether an inter conv takes the dense product over its referenced rows, decided once in the forward: rp = row slots per cloud (0: not
+    taken), forward = the forward runs it too (else the backward alone), parts = the _PoseParts when it runs once per rigid part, probed = the
+    batch was probed for it; head = the _ListHead of the neighbour lists (None when neither the probe nor a backward needs one)."""
+
+    def __init__(self, args, n, o, lists_ok, needs_grad, keep, folded):
+        # (folded: the FoldedEpilogue of an inference call or None)
+        # whether the batch can take the product is known on the host once the lists' first half has run -- one host wait per layer,
+        # only for layers whose width fills the dense kernel's blocks
+        idx, geometry = args.idx, args.geometry
+        p, nn = idx.shape[1], idx.shape[2]
+        na, ks = args.rk.shape[0], args.rk.shape[1]
+        self.args, self.parts, self._geo = args, None, None
+        probe = None
+        # (a folded inference epilogue does not stop it: the dense forward's re-ordering pass applies it; posed parts leave
+        # `epilogue.applied` False and the caller runs the norm as a pass of its own)
+        # (without gradients only the forward can use the product, and 'auto' takes it at o % 256 == 0 only: no probe -- and no host wait --
+        # for an inference call it could not change)
+        if (DENSE_MODE != 'off' and geometry is not None and lists_ok and (folded is None or o % 256 == 0 or DENSE_FWD_NARROW)
+                and (needs_grad or o % 256 == 0 or DENSE_FWD_NARROW or DENSE_MODE == 'force')
+                and _hip.so3_dense_supported(p, na, ks, 16, o)):
+            probe = (geometry[2], geometry[3])
+            if (DENSE_PARTS and geometry[3] is not None and geometry[0] is geometry[1] and geometry[2] is geometry[3] and p == n):
+                self.parts = _pose_parts(geometry[3])      # (one host read per pose tensor)
+                if self.parts is not None:
+                    probe = ()                             # the rotations are accounted for per part: no "exactly the identity" requirement
+                    if self.parts.single:
+                        # one rotation per cloud: every relative rotation R R^T is the identity -- the plain product -- PROVIDED the
+                        # block is orthonormal (checked on the device with the other conditions)
+                        probe = (('orthonormal', self.parts.reps[:, 0].contiguous()),)
+                        self.parts = None
+        # inverse neighbour lists (device only; the host-side numbers arrive asynchronously), started before the grouping so that
+        # they run beside it; the entries too when the previous backward of this layer took the lists
+        self.head = None
+        if (lists_ok and needs_grad) or probe is not None:
+            self.head = _ListHead(idx, n, args.nonident, args.gx, prefill=(not keep) and probe is None, dense_probe=probe)
+        self.probed = probe is not None
+        self.rp, self.forward = _dense_wanted(self.head, o, p, na, ks, nn, n) if self.probed else (0, False)
+
+    def geo(self):
+        """the product's DenseGeometry (_PartsDense when it runs per part), built by whoever needs it first: the forward if it runs the
+        product, else the backward"""
+        if self._geo is None:
+            args, head = self.args, self.head
+            head.wait()
+            rest = (head.memb, head.rows, self.rp, args.rk, args.sigma, args.idx.shape[2], head.n_rows)
+            if self.parts is None:
+                self._geo = _hip.DenseGeometry(args.geometry[0], args.geometry[1], *rest)
+            else:
+                self._geo = _PartsDense(self.parts, args.geometry[1], *rest, args.mult, args.anchors)
+        return self._geo
+
+
+# ---- the forward regimes of _InterConv -----------------------------------------------------------------------------------------------
+
+def _forward_dense(feats, W, plan, p, train_ep, folded):
+    """The forward as the dense product: plain, with the training-mode norm in the node (train_ep), with a folded inference norm, or once per
+    rigid part -> (y [b,o,p,a], bn): bn = what the node's BatchNorm backward needs, None unless train_ep joined the node."""
+    geo, rows = plan.geo(), plan.head.rows
+    if plan.parts is not None:
+        return _dense_forward_parts(feats, W, rows, geo, p), None
+    moments = affine = None
+    if train_ep is not None:
+        ep, moments = train_ep, train_ep.moments
+    elif folded is not None and folded.residual is None:
+        # an inference-mode norm folded into one per-channel map: applied by the re-ordering pass too
+        ep, affine = folded, (folded.scale, folded.shift, folded.slope)
+    else:
+        return _dense_forward(feats, W, rows, geo, p), None
+    g, ldg, operand = _dense_operand(feats, W, rows, geo)
+    y = _hip.so3_dense_fwd_bnact(g, geo, p, feats.shape[1], ldg, moments, operand=operand, o=W.shape[0], affine=affine)
+    ep.applied = True
+    return y, (None if train_ep is None else train_ep.saved + (float(train_ep.norm.negative_slope), bool(train_ep.norm.sync)))
+
+
+def _forward_lists(feats, W, args, layout, keep, folded, head, fill):
+    """The forward on the list kernels: grouping into the intermediate X (layout 0 / 1 / 2: reference / blocked / transposed, see X_LAYOUT),
+    then the contraction -> (y [b,o,p,a], x): x = the intermediate when it is kept for a textbook backward (keep), else None -- X is then
+    scratch, X_CHUNK_CLOUDS clouds at a time.  fill: the second half of head's lists is still to be made."""
+    idx, gx, rk, mult, sigma, nonident = args.idx, args.gx, args.rk, args.mult, args.sigma, args.nonident
+    b, c, n, na = feats.shape
+    p, ks, o = idx.shape[1], rk.shape[1], W.shape[0]
+    if fill:
+        head.fill(idx, gx, n)                          # (the probe postponed it; a dense backward does not need the entries)
+    y = torch.empty(b, o, p, na, dtype=torch.float32, device=feats.device)
+    coset = _coset_tables(mult, args.ident) if (mult is not None and nonident is not None and layout == 2 and COSET_OPERAND) else None
+    x_bound = _grouped_bound(feats, idx) if layout == 2 else None          # [b, p] words
+    step = max(1, b if keep else X_CHUNK_CLOUDS)          # (a kept X is one slab of all clouds)
+    # where X is scratch between the grouping and the contraction its columns may be in the order the grouping kernel's
+    # lanes hold them (1 KB store runs, csrc/so3_inter_lists2.hip LAYOUT 4) with W's columns permuted to match
+    tp = (not keep and STORE_ORDER_COLUMNS and layout == 2 and _hip.so3_group_fwd_tp_takes(c, na, ks)
+          and (mult is None or (coset is not None and _hip.so3_group_perm_lists2_takes(c, na, ks, n))))
+    Wc = W.index_select(1, _hip.so3_group_fwd_tp_columns(c, ks, W.device)) if tp else W
+    x = None
+    for b0 in range(0, b, step):
+        b1 = min(b, b0 + step)
+        x = _hip.so3_inter_group_fwd(feats[b0:b1], idx[b0:b1], gx[b0:b1], rk, mult, sigma,
+                                     None if nonident is None else nonident[b0:b1], blocked=layout, coset=coset, store_order=tp)   # [b,c,k,p,a] (nominal shape)
+        _contract_into(Wc, x, y[b0:b1].view(b1 - b0, o, p * na), layout, folded, b0,
+                       x_bound=None if x_bound is None else (x_bound[b0:b1], na, 1.0))
+        x = x if keep else None
+    return y, x
+
+
+# ---- the gradient tail: dF and dW from Z --------------------------------------------------------------------------------------------
+# Z [b, o*ks, ldz] holds per row the (referenced row, anchor) pairs of a cloud: rp * na columns, (row, anchor) order from the list kernels,
+# (anchor, row) order (`anchor_major`) from the dense product; ldz >= rp * na is the row pitch.  The two halves are launched in the order
+# the regime wants (the per-part backward gathers the feature rows once, in front, and scatters the summed row gradient once, at the end).
+
+def _weight_operand(W, c, ks, pad_c=None):
+    """W [o, (c,k)] as the feature-gradient GEMM's shared operand W2 [c, (o,k)], zero-extended to pad_c rows"""
+    o = W.shape[0]
+    W2 = W.view(o, c, ks).permute(1, 0, 2).reshape(c, o * ks).contiguous()
+    if pad_c is not None and pad_c != c:
+        W2 = torch.cat([W2, torch.zeros(pad_c - c, o * ks, dtype=torch.float32, device=W.device)])
+    return W2
+
+
+def _rows_grad_from_z(z, W2, c, rp, na, ldz, anchor_major, z_bound=None, reorder=None):
+    """dF over the referenced rows: W2 . Z -> [b,c,rp,na] (a view where the layout allows).  z_bound: a bound on Z's columns (see _hip.gemm
+    b_bound); reorder: the anchor axis of Z is coset-major, `reorder` = the position of every anchor in it."""
+    b, (pad_c, oks) = z.shape[0], W2.shape
+    gFc = torch.empty(b, pad_c, ldz, dtype=torch.float32, device=z.device)
+    _hip.gemm(0, 0, pad_c, ldz, oks, W2, oks, 0, z, ldz, oks * ldz, gFc, ldz, pad_c * ldz, b, b_bound=z_bound)
+    if anchor_major:
+        return gFc[:, :c, :rp * na].reshape(b, c, na, rp).transpose(2, 3)
+    gFc = gFc.view(b, c, rp, na)
+    return gFc if reorder is None else _hip.anchor_reorder(gFc, reorder)
+
+
+def _weight_grad_rows(z, fc4, o, ks, ldz, anchor_major, reorder=None):
+    """dW from Z and the referenced feature rows fc4 [b,c,rp,na] (reorder: Z's coset-major anchor order, see _coset_tables)"""
+    b, c, rp, na = fc4.shape
+    if reorder is not None:
+        fc4 = _hip.anchor_reorder(fc4, reorder)
+    fc = fc4.transpose(2, 3).contiguous() if anchor_major else fc4
+    return _weight_grad_from_z(z, fc.view(b, c, rp * na), b, c, o, ks, rp * na, ldz)
+
+
+# ---- the backward regimes of _InterConv ----------------------------------------------------------------------------------------------
+# Strategy: when few support rows are referenced (the reference's first-nsample-in-index-
+# order ball query with large radii), BOTH gradients follow from
+#     Z[o,k,q,a'] = sum_{(p,n)->q} dY[o,p,a] w(p,a,k,n)          (csrc/so3_inter_inv.hip; csrc/so3_dense.hip as a dense product)
+#     dF[c,q,a'] = sum_{o,k} W[o,(c,k)] Z[o,k,q,a']       dW[o,(c,k)] = sum_{q,a'} Z[o,k,q,a'] F[c,q,a']
+# two small GEMMs over the referenced rows only -- no dX = W^T dY, no scatter, and the
+# [O x P*A] x [P*A x C*K] weight-gradient GEMM shrinks by P / (referenced rows).
+
+def _backward_dense(gy, W, feats, head, geo, bn, yact, need_f, need_w):
+    """Z by the dense product (bn: through the node's BatchNorm + leaky_relu first, yact = the node's output) -> (gF, gW, g_bn_w, g_bn_b)"""
+    b, c, n, na = feats.shape
+    o, ks, p, rp = W.shape[0], geo.ks, gy.shape[2], geo.rp
+    if BACKWARD_LOG is not None:
+        BACKWARD_LOG.append({'channels': (c, o), 'support_rows': n, 'referenced_rows_max': int(rp), 'regime': 'dense rows',
+                             **({'norm': 'in the node'} if bn is not None else {})})
+    ra = na * rp
+    # Z's rows padded to whole 128-column tiles where that puts the feature-gradient GEMM on the split-operand kernels
+    # (the padding is never written: garbage columns of gFc nobody reads; the weight gradient contracts over ra columns)
+    # (c = 64: W2 padded to 128 zero-extended rows for the same reason -- the 64-row product ran on the fp32 pipe: 0.92 ms)
+    pad_c = 128 if (c == 64 and bn is not None) else c
+    ldz = _hip.dense_pitch(ra) if (pad_c % 128 == 0 and (o * ks) % 16 == 0 and need_f) else ra
+    gF = gW = g_bn_w = g_bn_b = z_bound = None
+    if bn is not None:
+        # the BatchNorm + leaky_relu backward of the node (csrc/bn_act.hip header): one reduction pass over (dL/dy', y'), then gx is
+        # formed inside the split of the product's stored operand
+        k1, beta, inv_gamma, count, slope, sync = bn
+        from .blocks import all_reduce_sums
+        sg, sgx, gmax, xmax = _hip.bn_act_bwd_reduce_fromy(gy, yact, beta, inv_gamma, slope)
+        g_bn_w, g_bn_b = sgx.float(), sg.float()
+        tg, tgx = all_reduce_sums(sg, sgx, sync=sync)                        # whole-batch means (SyncBatchNorm backward)
+        k2 = (k1.double() * tg / count).float()
+        k3 = (k1.double() * tgx / count).float()
+        coef = torch.stack([k1, k2, k3, beta, inv_gamma]).contiguous()      # [5, o]
+        bound = (k1.abs()[None, :, None] * gmax + k2.abs()[None, :, None] + k3.abs()[None, :, None] * xmax).contiguous()
+        z = _hip.so3_dense_bwd_bn(gy, yact, geo, ldz, coef, bound, slope)
+        if ldz % 4 == 0 and rp % 4 == 0:
+            # a bound on Z's columns for the feature-gradient GEMM below (it then runs with two fp16 planes per operand instead of
+            # three bf16 planes, without a pass over Z): |Z[o,k,(a,r)]| = |sum_p gx[o,p,a] w| <= max_o bound[o,a] x (points listing row r)
+            live = torch.arange(rp, device=gy.device)[None, :] < head.n_rows[:, None]                      # (slots past a cloud's rows: zero columns)
+            cntf = torch.where(live, head.cnt[:, :rp], torch.zeros_like(head.cnt[:, :rp])).clamp(min=0, max=p).to(torch.float32)
+            cols = bound.amax(1)[:, :, None] * cntf[:, None, :]                                           # [b,na,rp]
+            words = torch.zeros(b, ldz // 4, dtype=torch.float32, device=gy.device)
+            words[:, :ra // 4] = cols.view(b, na, rp // 4, 4).amax(3).view(b, ra // 4)
+            z_bound = (words.view(torch.int32), 4, 1.0)
+    else:
+        z = _hip.so3_dense_bwd(gy, geo, ldz)                                 # [b,o,ks,ldz] rows = [na,rp]: the lists' Z, anchor axis in front
+    if need_f:
+        gFr = _rows_grad_from_z(z, _weight_operand(W, c, ks, pad_c), c, rp, na, ldz, True, z_bound)
+        gF = _hip.rows_scatter(gFr.contiguous(), head.rows, n)
+    if need_w:
+        gW = _weight_grad_rows(z, _hip.rows_gather(feats, head.rows, rp), o, ks, ldz, True)
+    return gF, gW, g_bn_w, g_bn_b
+
+
+def _backward_dense_parts(gy, W, feats, head, pd, need_f, need_w):
+    """the dense backward of posed clouds, one product per part slot (_PartsDense): Z_i over the part's query points, the two small
+    GEMMs per part, the rows' anchor axis permuted back before the sum over the parts -> (gF, gW)"""
+    b, c, n, na = feats.shape
+    o, ks, rp = W.shape[0], pd.ks, pd.rp
+    ra = na * rp
+    if BACKWARD_LOG is not None:
+        BACKWARD_LOG.append({'channels': (c, o), 'support_rows': n, 'referenced_rows_max': int(rp), 'regime': 'dense rows', 'parts': pd.parts.n})
+    ldz = _hip.dense_pitch(ra) if (c % 128 == 0 and (o * ks) % 16 == 0 and need_f) else ra
+    W2 = _weight_operand(W, c, ks) if need_f else None
+    fc0 = _hip.rows_gather(feats, head.rows, rp) if need_w else None                        # [b,c,rp,na]
+    gFr = gW = None
+    # (the row maxima the BatchNorm backward left are those of ALL points: an upper bound for every part's columns)
+    rowmax = _hip.take_rowmax_hint(gy)
+    for i, geo in enumerate(pd.geo):
+        perm = pd.perm[i]
+        z = _hip.so3_dense_bwd(gy, geo, ldz, colmap=pd.parts.col_map[i], rowmax=rowmax)      # [b,o,ks,ldz] rows = [na,rp]
+        pe = None if perm is None else perm[:, None].expand(b, c, rp, na)
+        if need_f:
+            t = _rows_grad_from_z(z, W2, c, rp, na, ldz, True)                                # gradient of F_i[.., r, a] = F[.., r, perm[r, a]]
+            if gFr is None:
+                gFr = torch.zeros(b, c, rp, na, dtype=torch.float32, device=gy.device)
+            if pe is None:
+                gFr += t
+            else:
+                gFr.scatter_add_(3, pe, t.contiguous())
+        if need_w:
+            gw = _weight_grad_rows(z, fc0 if pe is None else fc0.gather(3, pe), o, ks, ldz, True)
+            gW = gw if gW is None else gW + gw
+        del z
+    gF = _hip.rows_scatter(gFr, head.rows, n) if need_f else None
+    return gF, gW
+
+
+def _backward_lists(gy, W, feats, idx, gx, rk, mult, args, head, rcap, any_nonident, need_f, need_w):
+    """Z by the inverse-list kernels (csrc/so3_inter_inv.hip, csrc/so3_inter_lists2.hip) over the first rcap referenced rows -> (gF, gW)"""
+    b, c, n, na = feats.shape
+    p, ks, o = idx.shape[1], rk.shape[1], W.shape[0]
+    gF = gW = None
+    # slots past a cloud's last referenced row are empty (rows = -1): a multiple of 4 rows makes K = rcap * na of the
+    # gradient GEMMs a multiple of 16.  (A multiple of 32 would put the dF GEMM on the split kernel -- measured: the 18 %
+    # more rows at 136 referenced rows cost what the faster kernel gains.)
+    rcap = min((rcap + 3) & ~3, n)
+    head.wait()
+    rows = head.rows[:, :rcap].contiguous()
+    off, cnt = head.off[:, :rcap].contiguous(), head.cnt[:, :rcap].contiguous()
+    ent_p, ent_gx = head.entries if head.entries is not None else _hip.inv_lists_fill(idx, gx, head.rows, head.off, rcap)
+    multinv = _group_tables_inverse(mult) if (mult is not None and any_nonident) else None
+    coset = _coset_tables(multinv, args.ident) if (multinv is not None and COSET_OPERAND) else None
+    z_order = z_pos = None
+    if coset is not None and _hip.so3_group_perm_lists2_takes(o, na, ks, p):
+        # permuted clouds on the two-tile kernel (csrc/so3_inter_lists2.hip, PERM): gy and Z with a coset-major anchor
+        # axis, the per-entry words prepared once; the small tensors around the two GEMMs change their anchor order
+        z_order, z_pos = coset[0], coset[2]
+        ent_pc, ent_gx2 = _hip.so3_perm_entries(ent_p, ent_gx, coset[1], args.anchors, args.ident, na, p)
+        z = _hip.so3_inter_group_inv_perm2(_hip.anchor_reorder(gy, z_order), rows, off, cnt, ent_pc, ent_gx2, rk, z_order,
+                                           args.sigma, idx.shape[2])
+    else:
+        z = _hip.so3_inter_group_inv(gy, rows, off, cnt, ent_p, ent_gx, rk, multinv, args.sigma, idx.shape[2],
+                                     args.ident, args.anchors, coset)              # [b,o,ks,rcap,na]
+    if need_f:
+        gFr = _rows_grad_from_z(z, _weight_operand(W, c, ks), c, rcap, na, rcap * na, False, reorder=z_pos)
+        gF = _hip.rows_scatter(gFr, rows, n)                                    # unreferenced rows: zero gradient
+    if need_w:
+        # (rows_gather: [b,c,rcap,na]; unused slots: zeros)
+        gW = _weight_grad_rows(z, _hip.rows_gather(feats, rows, rcap), o, ks, rcap * na, False, reorder=z_order)
+    return gF, gW
+
+
+def _backward_textbook(gy, W, feats, x, idx, gx, rk, mult, nonident, args, layout, need_f, need_w):
+    """dW = dY X^T, dX = W^T dY followed by the transposed grouping; x = the forward's intermediate or None (not kept) -> (gF, gW)"""
+    b, c, n, na = feats.shape
+    p, ks = idx.shape[1], rk.shape[1]
+    o, ck, pa = W.shape[0], c * ks, p * na
+    gF = gW = None
+    if x is None:                                     # wrong guess (or the first step): one more run of the grouping kernel
+        x = _hip.so3_inter_group_fwd(feats, idx, gx, rk, mult, args.sigma, nonident, blocked=layout,
+                                     coset=_coset_tables(mult, args.ident) if (mult is not None and layout == 2 and COSET_OPERAND) else None)
+    if need_w:
+        gW = torch.empty_like(W)          # sum_b gy_b x_b^T
+        # (measured and dropped: every cloud's dY_b X^T_b on the split-operand 'nn' kernel instead of the batch-reducing fp32 kernel --
+        # 512 x 3072 outputs over K = 30720 are 48 workgroups without a split of K: 15.5 -> 48 ms at 16 x 512 points)
+        if layout == 2:     # X^T [pa, ck]: dW = dY X^T is a plain row-major product
+            _hip.gemm_reduce(0, 0, o, ck, pa, gy, pa, o * pa, x, ck, ck * pa, gW, ck, b)
+        else:
+            _hip.gemm_reduce(0, 1, o, ck, pa, gy, pa, o * pa, x, pa, ck * pa, gW, ck, b, b_blocked=layout == 1)
+    if need_f:
+        gx_ = torch.empty_like(x.view(b, ck, pa))      # W^T gy
+        # (W^T written out -- a few MB: the product is then 'nn' with a shared A operand, which the split-operand kernels take;
+        # with the transposition left to the GEMM it ran on the fp32 matrix pipe: 15.6 of the 61.6 ms step at 16 x 512 points)
+        Wt = W.t().contiguous()
+        _hip.gemm(0, 0, ck, pa, o, Wt, o, 0, gy.view(b, o, pa), pa, o * pa, gx_, pa, ck * pa, b)
+        gF = _hip.so3_inter_group_bwd(gx_.view(b, c, ks, p, na), idx, gx, rk, mult, args.sigma, n, args.ident)
+    return gF, gW
 
 
 class _InterConv(torch.autograd.Function):
     """Fused inter conv  y = W . group(feats)  (functional.py:L1221-1261 + modules.py:L48-55)
-    with the re-associated feature gradient (csrc/so3_inter_inv.hip)."""
+    with the re-associated feature gradient (csrc/so3_inter_inv.hip).  forward and backward decide the regime and dispatch to the
+    _forward_* / _backward_* functions above."""
+
+    DIFFERENTIABLE = 4      # feats, W, bn_weight, bn_bias come first: needs_input_grad is indexed by these positions only
 
     @staticmethod
-    def forward(ctx, feats, W_param, idx, gx, rk, mult, sigma, ident, nonident=None, anchors=None, epilogue=None, grad_mode=True, geometry=None,
-                bn_weight=None, bn_bias=None):
-        # (bn_weight, bn_bias: the parameters of a TrainEpilogue's norm -- inputs of the node so that it can hand back their gradients)
+    def forward(ctx, feats, W_param, bn_weight, bn_bias, args):
+        # (bn_weight, bn_bias: the parameters of a TrainEpilogue's norm -- inputs of the node so that it can hand back their gradients;
+        # args: an _InterConvArgs)
         feats = feats.contiguous()
         W = W_param.contiguous()
-        ctx.anchors = anchors.detach().contiguous() if anchors is not None else None   # the rotations `mult` was built from
+        idx, rk, mult, nonident = args.idx, args.rk, args.mult, args.nonident
         # X is internal to this Function: where the kernels allow it, it is kept blocked by anchor
         # quads ([b,p,a/4,c,k,4]) -- coalesced row-end stores in the grouping kernel -- and the GEMMs
         # read it as a blocked B operand (include/eap_hip.h, "blocked intermediate")
         can = BLOCKED_X and X_LAYOUT != 'reference' and _hip.so3_inter_group_fwd_can_block(
             feats.shape[1], feats.shape[2], feats.shape[3], rk.shape[1], mult is not None, nonident is not None)
         layout = 0 if not can else (2 if X_LAYOUT == 'transposed' else 1)
-        b, c, n, na = feats.shape
+        _, c, n, na = feats.shape
         p, ks, o = idx.shape[1], rk.shape[1], W.shape[0]
-        # grad_mode = torch.is_grad_enabled() AT THE CALL (inside forward() autograd always has it off; and under torch.no_grad()
-        # needs_input_grad still reports the parameters although nothing will be differentiated)
-        needs_grad = (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and grad_mode
-        train_ep = epilogue if isinstance(epilogue, TrainEpilogue) else None
-        if train_ep is not None:
-            epilogue = None                                # (the list kernels know nothing of it: `applied` stays False there)
-        ctx.bn = None
-        if epilogue is not None and (needs_grad or not epilogue.inference):
+        needs_grad = (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and args.grad_mode
+        train_ep = args.epilogue if isinstance(args.epilogue, TrainEpilogue) else None
+        folded = None if train_ep is not None else args.epilogue      # (the list kernels know nothing of a TrainEpilogue: `applied` stays False there)
+        if folded is not None and (needs_grad or not folded.inference):
             raise RuntimeError('a folded epilogue is an inference-time fusion: build and use it under torch.no_grad()')
         lists_ok = BACKWARD_MODE != 'dx' and _inv_lists_supported(idx, n, na, ks)
         keep = needs_grad and (not lists_ok or _keep_x_hint(W_param))
-        # inverse neighbour lists (device only; the host-side numbers arrive asynchronously), started before the grouping so that
-        # they run beside it; the entries too when the previous backward of this layer took the lists
-        # geometry = (q_xyz, xyz, q_rot, rot): what the dense product over the referenced rows is built from (csrc/so3_dense.hip);
-        # whether the batch can take it is known on the host once the lists' first half has run -- one host wait per layer,
-        # only for layers whose width fills the dense kernel's blocks
-        probe = parts = None
-        # (a folded inference epilogue does not stop it: the dense forward's re-ordering pass applies it; posed parts leave
-        # `epilogue.applied` False and the caller runs the norm as a pass of its own)
-        # (without gradients only the forward can use the product, and 'auto' takes it at o % 256 == 0 only: no probe -- and no host wait --
-        # for an inference call it could not change)
-        if (DENSE_MODE != 'off' and geometry is not None and lists_ok and (epilogue is None or o % 256 == 0 or DENSE_FWD_NARROW)
-                and (needs_grad or o % 256 == 0 or DENSE_FWD_NARROW or DENSE_MODE == 'force')
-                and _hip.so3_dense_supported(p, na, ks, 16, o)):
-            probe = (geometry[2], geometry[3])
-            if (DENSE_PARTS and geometry[3] is not None and geometry[0] is geometry[1] and geometry[2] is geometry[3] and p == n):
-                parts = _pose_parts(geometry[3])           # (one host read per pose tensor)
-                if parts is not None:
-                    probe = ()                             # the rotations are accounted for per part: no "exactly the identity" requirement
-                    if parts.single:
-                        # one rotation per cloud: every relative rotation R R^T is the identity -- the plain product -- PROVIDED the
-                        # block is orthonormal (checked on the device with the other conditions)
-                        probe = (('orthonormal', parts.reps[:, 0].contiguous()),)
-                        parts = None
-        head = None
-        if (lists_ok and needs_grad) or probe is not None:
-            head = _ListHead(idx, n, nonident, gx, prefill=(not keep) and probe is None, dense_probe=probe)
-        rp, dense_fwd = _dense_wanted(head, o, p, na, ks, idx.shape[2], n) if probe is not None else (0, False)
-        ctx.dense = None
-        ctx.parts = parts if rp > 0 else None
-        if rp > 0 and needs_grad:                         # (built by whoever needs it first: the forward below, or the backward)
-            ctx.dense = [None, (geometry[0], geometry[1], head.memb, head.rows, rp, rk, sigma, idx.shape[2], head.n_rows)]
+        plan = _DensePlan(args, n, o, lists_ok, needs_grad, keep, folded)
+        head = plan.head if needs_grad else None
         if FORWARD_LOG is not None:
-            FORWARD_LOG.append({'channels': (c, o), 'dense': bool(rp > 0 and dense_fwd), 'parts': None if parts is None else parts.n})
-        if rp > 0 and dense_fwd:
-            head.wait()
-            if parts is None:
-                geo = _hip.DenseGeometry(geometry[0], geometry[1], head.memb, head.rows, rp, rk, sigma, idx.shape[2], head.n_rows)
-                # (a frozen conv under a trainable norm -- gradients wanted for the norm's parameters only -- keeps the separate module:
-                # the node's backward is the conv's dense backward)
-                bn_only = grad_mode and not needs_grad and len(ctx.needs_input_grad) > 14 and (ctx.needs_input_grad[13] or ctx.needs_input_grad[14])
-                if train_ep is not None and FUSE_CONV_NORM and not bn_only:
-                    g_, ldg, operand = _dense_g(_hip.rows_gather(feats, head.rows, geo.rp), W, geo)
-                    y = _hip.so3_dense_fwd_bnact(g_, geo, p, c, ldg, train_ep.moments, operand=operand, o=o)
-                    del g_, operand
-                    train_ep.applied = True
-                    ctx.bn = train_ep.saved + (float(train_ep.norm.negative_slope), bool(train_ep.norm.sync))
-                elif epilogue is not None and epilogue.residual is None:
-                    # an inference-mode norm folded into one per-channel map: applied by the re-ordering pass too
-                    g_, ldg, operand = _dense_g(_hip.rows_gather(feats, head.rows, geo.rp), W, geo)
-                    y = _hip.so3_dense_fwd_bnact(g_, geo, p, c, ldg, None, operand=operand, o=o, affine=(epilogue.scale, epilogue.shift, epilogue.slope))
-                    del g_, operand
-                    epilogue.applied = True
-                else:
-                    y = _dense_forward(feats, W, head.rows, geo, p)
-            else:
-                geo = _PartsDense(parts, geometry[1], head.memb, head.rows, rp, rk, sigma, idx.shape[2], head.n_rows, mult, ctx.anchors)
-                y = _dense_forward_parts(feats, W, head.rows, geo, p)
-            ctx.head = head if needs_grad else None
-            if needs_grad:
-                ctx.dense[0] = geo
-            ctx.layout, ctx.kept_x = 0, False
-            ctx.W_param = weakref.ref(W_param)
-            ctx.save_for_backward(W, torch.empty(0), idx, gx, rk, mult if mult is not None else torch.empty(0),
-                                  nonident if nonident is not None else torch.empty(0), feats, *((y,) if (ctx.bn is not None and needs_grad) else ()))
-            ctx.has_mult = mult is not None
-            ctx.has_flag = nonident is not None
-            ctx.sigma, ctx.ident, ctx.n = sigma, ident, feats.shape[2]
-            return y
-        if head is not None and not (lists_ok and needs_grad):
-            head = None
-        elif head is not None and probe is not None and not keep and rp == 0:
-            head.fill(idx, gx, n)                          # (the probe postponed it; a dense backward does not need the entries)
-        ctx.head = head
-        y = torch.empty(b, o, p, na, dtype=torch.float32, device=feats.device)
-        coset = _coset_tables(mult, ident) if (mult is not None and nonident is not None and layout == 2 and COSET_OPERAND) else None
-        x_bound = _grouped_bound(feats, idx) if layout == 2 else None          # [b, p] words
-        if keep:
-            x = _hip.so3_inter_group_fwd(feats, idx, gx, rk, mult, sigma, nonident, blocked=layout, coset=coset)   # [b,c,k,p,a] (nominal shape)
-            _contract_into(W, x, y.view(b, o, p * na), layout, x_bound=None if x_bound is None else (x_bound, na, 1.0))
+            FORWARD_LOG.append({'channels': (c, o), 'dense': bool(plan.forward), 'parts': None if plan.parts is None else plan.parts.n})
+        if plan.forward:
+            # (a frozen conv under a trainable norm -- gradients wanted for the norm's parameters only -- keeps the separate module:
+            # the node's backward is the conv's dense backward)
+            bn_only = args.grad_mode and not needs_grad and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+            y, ctx.bn = _forward_dense(feats, W, plan, p, train_ep if (FUSE_CONV_NORM and not bn_only) else None, folded)
+            x, layout = None, 0
         else:
-            x = None
-            step = max(1, X_CHUNK_CLOUDS)
-            # X is scratch between the grouping and the contraction here: its columns may be in the order the grouping kernel's
-            # lanes hold them (1 KB store runs, csrc/so3_inter_lists2.hip LAYOUT 4) with W's columns permuted to match
-            tp = (STORE_ORDER_COLUMNS and layout == 2 and _hip.so3_group_fwd_tp_takes(c, na, ks)
-                  and (mult is None or (coset is not None and _hip.so3_group_perm_lists2_takes(c, na, ks, n))))
-            Wc = W.index_select(1, _hip.so3_group_fwd_tp_columns(c, ks, W.device)) if tp else W
-            for b0 in range(0, b, step):
-                b1 = min(b, b0 + step)
-                xs = _hip.so3_inter_group_fwd(feats[b0:b1], idx[b0:b1], gx[b0:b1], rk, mult, sigma,
-                                              None if nonident is None else nonident[b0:b1], blocked=layout, coset=coset, store_order=tp)
-                _contract_into(Wc, xs, y[b0:b1].view(b1 - b0, o, p * na), layout, epilogue, b0,
-                               x_bound=None if x_bound is None else (x_bound[b0:b1], na, 1.0))
-                del xs
-        ctx.layout = layout
-        ctx.kept_x = x is not None
+            fill = head is not None and plan.probed and not keep and plan.rp == 0
+            y, x = _forward_lists(feats, W, args, layout, keep, folded, head, fill)
+            ctx.bn = None
+        ctx.conv_args, ctx.head, ctx.layout = args, head, layout
+        ctx.plan = plan if (plan.rp > 0 and needs_grad) else None
         ctx.W_param = weakref.ref(W_param)
         # feats: needed by the re-associated weight gradient (saved, not copied: autograd's version check
-        # then catches an in-place update of the previous block's output)
-        ctx.save_for_backward(W, x if x is not None else torch.empty(0), idx, gx, rk, mult if mult is not None else torch.empty(0),
-                              nonident if nonident is not None else torch.empty(0), feats)
-        ctx.has_mult = mult is not None
-        ctx.has_flag = nonident is not None
-        ctx.sigma, ctx.ident, ctx.n = sigma, ident, feats.shape[2]
+        # then catches an in-place update of the previous block's output); y: the node's output when it holds the norm (TrainEpilogue)
+        ctx.save_for_backward(W, x, idx, args.gx, rk, mult, nonident, feats, y if (ctx.bn is not None and needs_grad) else None)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        W, x, idx, gx, rk, mult, nonident, feats = ctx.saved_tensors[:8]
-        yact = ctx.saved_tensors[8] if ctx.bn is not None else None
-        mult = mult if ctx.has_mult else None
-        nonident = nonident if ctx.has_flag else None
+        W, x, idx, gx, rk, mult, nonident, feats, yact = ctx.saved_tensors       # (x, mult, nonident, yact: None where the forward had none)
+        args, head, plan = ctx.conv_args, ctx.head, ctx.plan
         gy = gy.contiguous()
-        b, c, n, na = feats.shape
-        p, ks = idx.shape[1], rk.shape[1]
-        o, ck, pa = W.shape[0], c * ks, p * na
-        gW = gF = None
-        # Strategy: when few support rows are referenced (the reference's first-nsample-in-index-
-        # order ball query with large radii), BOTH gradients follow from
-        #     Z[o,k,q,a'] = sum_{(p,n)->q} dY[o,p,a] w(p,a,k,n)          (csrc/so3_inter_inv.hip)
-        #     dF[c,q,a'] = sum_{o,k} W[o,(c,k)] Z[o,k,q,a']       dW[o,(c,k)] = sum_{q,a'} Z[o,k,q,a'] F[c,q,a']
-        # two small GEMMs over the referenced rows only -- no dX = W^T dY, no scatter, and the
-        # [O x P*A] x [P*A x C*K] weight-gradient GEMM shrinks by P / (referenced rows).
-        head, rcap, any_nonident = ctx.head, 0, True
-        if ctx.dense is not None:
-            if ctx.dense[0] is None:                       # list-kernel forward, dense backward
-                head.wait()
-                if ctx.parts is None:
-                    ctx.dense[0] = _hip.DenseGeometry(*ctx.dense[1])
-                else:
-                    a_ = ctx.dense[1]
-                    ctx.dense[0] = _PartsDense(ctx.parts, a_[1], a_[2], a_[3], a_[4], a_[5], a_[6], a_[7], a_[8], mult, ctx.anchors)
-            if ctx.parts is not None:
-                return _InterConv._backward_parts(ctx, gy, W, feats, head, ctx.dense[0]) + (None,) * 13
-            geo = ctx.dense[0]
-            if BACKWARD_LOG is not None:
-                BACKWARD_LOG.append({'channels': (c, o), 'support_rows': n, 'referenced_rows_max': int(geo.rp), 'regime': 'dense rows',
-                                     **({'norm': 'in the node'} if ctx.bn is not None else {})})
-            rp = geo.rp
-            ra = na * rp
-            # Z's rows padded to whole 128-column tiles where that puts the feature-gradient GEMM on the split-operand kernels
-            # (the padding is never written: garbage columns of gFc nobody reads; the weight gradient contracts over ra columns)
-            # (c = 64: W2 padded to 128 zero-extended rows for the same reason -- the 64-row product ran on the fp32 pipe: 0.92 ms)
-            pad_c = 128 if (c == 64 and ctx.bn is not None) else c
-            ldz = _hip.dense_pitch(ra) if (pad_c % 128 == 0 and (o * ks) % 16 == 0 and ctx.needs_input_grad[0]) else ra
-            g_bn_w = g_bn_b = None
-            z_bound = None
-            if ctx.bn is not None:
-                # the BatchNorm + leaky_relu backward of the node (csrc/bn_act.hip header): one reduction pass over (dL/dy', y'), then gx is
-                # formed inside the split of the product's stored operand
-                k1, beta, inv_gamma, count, slope, sync = ctx.bn
-                from .blocks import all_reduce_sums
-                sg, sgx, gmax, xmax = _hip.bn_act_bwd_reduce_fromy(gy, yact, beta, inv_gamma, slope)
-                g_bn_w, g_bn_b = sgx.float(), sg.float()
-                tg, tgx = all_reduce_sums(sg, sgx, sync=sync)                        # whole-batch means (SyncBatchNorm backward)
-                k2 = (k1.double() * tg / count).float()
-                k3 = (k1.double() * tgx / count).float()
-                coef = torch.stack([k1, k2, k3, beta, inv_gamma]).contiguous()      # [5, o]
-                bound = (k1.abs()[None, :, None] * gmax + k2.abs()[None, :, None] + k3.abs()[None, :, None] * xmax).contiguous()
-                z = _hip.so3_dense_bwd_bn(gy, yact, geo, ldz, coef, bound, slope)
-                if ldz % 4 == 0 and rp % 4 == 0:
-                    # a bound on Z's columns for the feature-gradient GEMM below (it then runs with two fp16 planes per operand instead of
-                    # three bf16 planes, without a pass over Z): |Z[o,k,(a,r)]| = |sum_p gx[o,p,a] w| <= max_o bound[o,a] x (points listing row r)
-                    live = torch.arange(rp, device=gy.device)[None, :] < head.n_rows[:, None]                      # (slots past a cloud's rows: zero columns)
-                    cntf = torch.where(live, head.cnt[:, :rp], torch.zeros_like(head.cnt[:, :rp])).clamp(min=0, max=p).to(torch.float32)
-                    cols = bound.amax(1)[:, :, None] * cntf[:, None, :]                                           # [b,na,rp]
-                    words = torch.zeros(b, ldz // 4, dtype=torch.float32, device=gy.device)
-                    words[:, :ra // 4] = cols.view(b, na, rp // 4, 4).amax(3).view(b, ra // 4)
-                    z_bound = (words.view(torch.int32), 4, 1.0)
-            else:
-                z = _hip.so3_dense_bwd(gy, geo, ldz)                                 # [b,o,ks,ldz] rows = [na,rp]: the lists' Z, anchor axis in front
-            if ctx.needs_input_grad[0]:
-                W2 = W.view(o, c, ks).permute(1, 0, 2).reshape(c, o * ks).contiguous()
-                if pad_c != c:
-                    W2 = torch.cat([W2, torch.zeros(pad_c - c, o * ks, dtype=torch.float32, device=gy.device)])
-                gFc = torch.empty(b, pad_c, ldz, dtype=torch.float32, device=gy.device)
-                _hip.gemm(0, 0, pad_c, ldz, o * ks, W2, o * ks, 0, z, ldz, o * ks * ldz, gFc, ldz, pad_c * ldz, b, b_bound=z_bound)
-                gF = _hip.rows_scatter(gFc[:, :c, :ra].reshape(b, c, na, rp).transpose(2, 3).contiguous(), head.rows, n)
-            if ctx.needs_input_grad[1]:
-                fc = _hip.rows_gather(feats, head.rows, rp).transpose(2, 3).contiguous().view(b, c, ra)      # [b,c,(a,r)]
-                gW = _weight_grad_from_z(z, fc, b, c, o, ks, ra, ldz)
-            return gF, gW, None, None, None, None, None, None, None, None, None, None, None, g_bn_w, g_bn_b
-        if head is not None:
-            rcap, any_nonident = head.decide()
-            if BACKWARD_MODE == 'auto' and rcap * INV_ROW_FRACTION > n:
-                head.entries = None                        # (prefilled on last step's hint, not needed after all: 20 bytes per entry)
-                head = None
-        if BACKWARD_LOG is not None:      # diagnostics for bench.py / tests: which regime each layer's backward took
-            BACKWARD_LOG.append({'channels': (c, o), 'support_rows': n, 'referenced_rows_max': int(rcap),
-                                 'regime': 'inverse lists' if head is not None else 'textbook dX'})
-        Wp = ctx.W_param()
-        if Wp is not None:
-            _set_keep_x_hint(Wp, head is None)            # the next forward of this layer keeps X iff this backward needed it
-        if head is None and not ctx.kept_x:               # wrong guess (or the first step): one more run of the grouping kernel
-            x = _hip.so3_inter_group_fwd(feats, idx, gx, rk, mult, ctx.sigma, nonident, blocked=ctx.layout,
-                                         coset=_coset_tables(mult, ctx.ident) if (mult is not None and ctx.layout == 2 and COSET_OPERAND) else None)
-        if head is not None:
-            # slots past a cloud's last referenced row are empty (rows = -1): a multiple of 4 rows makes K = rcap * na of the
-            # gradient GEMMs a multiple of 16.  (A multiple of 32 would put the dF GEMM on the split kernel -- measured: the 18 %
-            # more rows at 136 referenced rows cost what the faster kernel gains.)
-            rcap = min((rcap + 3) & ~3, n)
-            head.wait()
-            rows = head.rows[:, :rcap].contiguous()
-            off, cnt = head.off[:, :rcap].contiguous(), head.cnt[:, :rcap].contiguous()
-            ent_p, ent_gx = head.entries if head.entries is not None else _hip.inv_lists_fill(idx, gx, head.rows, head.off, rcap)
-            multinv = _group_tables_inverse(mult) if (mult is not None and any_nonident) else None
-            coset = _coset_tables(multinv, ctx.ident) if (multinv is not None and COSET_OPERAND) else None
-            z_order = None
-            if coset is not None and _hip.so3_group_perm_lists2_takes(o, na, ks, p):
-                # permuted clouds on the two-tile kernel (csrc/so3_inter_lists2.hip, PERM): gy and Z with a coset-major anchor
-                # axis, the per-entry words prepared once; the small tensors around the two GEMMs change their anchor order
-                z_order, z_pos = coset[0], coset[2]
-                ent_pc, ent_gx2 = _hip.so3_perm_entries(ent_p, ent_gx, coset[1], ctx.anchors, ctx.ident, na, p)
-                z = _hip.so3_inter_group_inv_perm2(_hip.anchor_reorder(gy, z_order), rows, off, cnt, ent_pc, ent_gx2, rk, z_order,
-                                                   ctx.sigma, idx.shape[2])
-            else:
-                z = _hip.so3_inter_group_inv(gy, rows, off, cnt, ent_p, ent_gx, rk, multinv, ctx.sigma, idx.shape[2],
-                                             ctx.ident, ctx.anchors, coset)              # [b,o,ks,rcap,na]
-            ra = rcap * na
-            if ctx.needs_input_grad[0]:
-                W2 = W.view(o, c, ks).permute(1, 0, 2).reshape(c, o * ks).contiguous()
-                gFc = torch.empty(b, c, ra, dtype=torch.float32, device=gy.device)
-                _hip.gemm(0, 0, c, ra, o * ks, W2, o * ks, 0, z, ra, o * ks * ra, gFc, ra, c * ra, b)
-                if z_order is not None:
-                    gFc = _hip.anchor_reorder(gFc.view(b, c, rcap, na), z_pos)
-                gF = _hip.rows_scatter(gFc.view(b, c, rcap, na), rows, n)           # unreferenced rows: zero gradient
-            if ctx.needs_input_grad[1]:
-                fc = _hip.rows_gather(feats, rows, rcap)                             # [b,c,rcap,na]; unused slots: zeros
-                if z_order is not None:
-                    fc = _hip.anchor_reorder(fc, z_order)
-                gW = _weight_grad_from_z(z, fc.view(b, c, ra), b, c, o, ks, ra)
-        else:
-            if ctx.needs_input_grad[1]:
-                gW = torch.empty_like(W)          # sum_b gy_b x_b^T
-                # (measured and dropped: every cloud's dY_b X^T_b on the split-operand 'nn' kernel instead of the batch-reducing fp32 kernel --
-                # 512 x 3072 outputs over K = 30720 are 48 workgroups without a split of K: 15.5 -> 48 ms at 16 x 512 points)
-                if ctx.layout == 2:     # X^T [pa, ck]: dW = dY X^T is a plain row-major product
-                    _hip.gemm_reduce(0, 0, o, ck, pa, gy, pa, o * pa, x, ck, ck * pa, gW, ck, b)
-                else:
-                    _hip.gemm_reduce(0, 1, o, ck, pa, gy, pa, o * pa, x, pa, ck * pa, gW, ck, b, b_blocked=ctx.layout == 1)
-            if ctx.needs_input_grad[0]:
-                gx_ = torch.empty_like(x.view(b, ck, pa))      # W^T gy
-                # (W^T written out -- a few MB: the product is then 'nn' with a shared A operand, which the split-operand kernels take;
-                # with the transposition left to the GEMM it ran on the fp32 matrix pipe: 15.6 of the 61.6 ms step at 16 x 512 points)
-                Wt = W.t().contiguous()
-                _hip.gemm(0, 0, ck, pa, o, Wt, o, 0, gy.view(b, o, pa), pa, o * pa, gx_, pa, ck * pa, b)
-                gF = _hip.so3_inter_group_bwd(gx_.view(b, c, ks, p, na), idx, gx, rk, mult, ctx.sigma, n, ctx.ident)
-        return gF, gW, None, None, None, None, None, None, None, None, None, None, None, None, None
-
-
-    @staticmethod
-    def _backward_parts(ctx, gy, W, feats, head, pd):
-        """the dense backward of posed clouds, one product per part slot (_PartsDense): Z_i over the part's query points, the two small
-        GEMMs per part, the rows' anchor axis permuted back before the sum over the parts -> (gF, gW)"""
-        b, c, n, na = feats.shape
-        o, ks, rp = W.shape[0], pd.ks, pd.rp
-        ra = na * rp
-        if BACKWARD_LOG is not None:
-            BACKWARD_LOG.append({'channels': (c, o), 'support_rows': n, 'referenced_rows_max': int(rp), 'regime': 'dense rows', 'parts': pd.parts.n})
+        n = feats.shape[2]
         need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        ldz = _hip.dense_pitch(ra) if (c % 128 == 0 and (o * ks) % 16 == 0 and need_f) else ra
-        W2 = W.view(o, c, ks).permute(1, 0, 2).reshape(c, o * ks).contiguous() if need_f else None
-        fc0 = _hip.rows_gather(feats, head.rows, rp) if need_w else None                        # [b,c,rp,na]
-        gFr = gW = None
-        # (the row maxima the BatchNorm backward left are those of ALL points: an upper bound for every part's columns)
-        rowmax = _hip.take_rowmax_hint(gy)
-        for i, geo in enumerate(pd.geo):
-            perm = pd.perm[i]
-            z = _hip.so3_dense_bwd(gy, geo, ldz, colmap=pd.parts.col_map[i], rowmax=rowmax)      # [b,o,ks,ldz] rows = [na,rp]
-            pe = None if perm is None else perm[:, None].expand(b, c, rp, na)
-            if need_f:
-                gFc = torch.empty(b, c, ldz, dtype=torch.float32, device=gy.device)
-                _hip.gemm(0, 0, c, ldz, o * ks, W2, o * ks, 0, z, ldz, o * ks * ldz, gFc, ldz, c * ldz, b)
-                t = gFc[:, :, :ra].reshape(b, c, na, rp).transpose(2, 3)                          # [b,c,rp,na]: gradient of F_i[.., r, a] = F[.., r, perm[r, a]]
-                if gFr is None:
-                    gFr = torch.zeros(b, c, rp, na, dtype=torch.float32, device=gy.device)
-                if pe is None:
-                    gFr += t
-                else:
-                    gFr.scatter_add_(3, pe, t.contiguous())
-            if need_w:
-                fci = fc0 if pe is None else fc0.gather(3, pe)
-                gw = _weight_grad_from_z(z, fci.transpose(2, 3).contiguous().view(b, c, ra), b, c, o, ks, ra, ldz)
-                gW = gw if gW is None else gW + gw
-            del z
-        gF = _hip.rows_scatter(gFr, head.rows, n) if need_f else None
-        return gF, gW
+        g_bn_w = g_bn_b = None
+        if plan is not None and plan.parts is not None:
+            gF, gW = _backward_dense_parts(gy, W, feats, head, plan.geo(), need_f, need_w)
+        elif plan is not None:
+            gF, gW, g_bn_w, g_bn_b = _backward_dense(gy, W, feats, head, plan.geo(), ctx.bn, yact, need_f, need_w)
+        else:
+            rcap, any_nonident = 0, True
+            if head is not None:
+                rcap, any_nonident = head.decide()
+                if BACKWARD_MODE == 'auto' and rcap * INV_ROW_FRACTION > n:
+                    head.entries = None                        # (prefilled on last step's hint, not needed after all: 20 bytes per entry)
+                    head = None
+            if BACKWARD_LOG is not None:      # diagnostics for bench.py / tests: which regime each layer's backward took
+                BACKWARD_LOG.append({'channels': (feats.shape[1], W.shape[0]), 'support_rows': n, 'referenced_rows_max': int(rcap),
+                                     'regime': 'inverse lists' if head is not None else 'textbook dX'})
+            Wp = ctx.W_param()
+            if Wp is not None:
+                _set_keep_x_hint(Wp, head is None)            # the next forward of this layer keeps X iff this backward needed it
+            if head is not None:
+                gF, gW = _backward_lists(gy, W, feats, idx, gx, rk, mult, args, head, rcap, any_nonident, need_f, need_w)
+            else:
+                gF, gW = _backward_textbook(gy, W, feats, x, idx, gx, rk, mult, nonident, args, ctx.layout, need_f, need_w)
+        return (gF, gW, g_bn_w, g_bn_b) + (None,) * (len(ctx.needs_input_grad) - _InterConv.DIFFERENTIABLE)
 
 
 INTRA_DW_SLICE = 64      # channels whose 12-tap gather is materialised at a time for the intra weight gradient
@@ -1313,16 +1379,30 @@ def _strided_centres(xyz, pose, stride, lazy_sample):
     return sample_idx, sample_xyz.contiguous(), sampled_pose
 
 
-def _inter_group(xyz, pose, feats, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz=None, q_pose=None):
-    if feats.dtype != torch.float32 or xyz.dtype != torch.float32:
+def _check_inputs(xyz, feats, W=None, on_device=True):
+    if feats.dtype != torch.float32 or xyz.dtype != torch.float32 or (W is not None and W.dtype != torch.float32):
         raise RuntimeError('so3conv: float32 only')
     _hip.check_input(xyz)
-    if not feats.is_cuda:
-        raise RuntimeError('so3conv: feats must be a device tensor')
+    if on_device and not (feats.is_cuda and (W is None or W.is_cuda)):
+        raise RuntimeError('so3conv: feats must be a device tensor' if W is None else 'so3conv: feats and W must be device tensors')
+
+
+def _permutation_tables(anchors):
+    """(mult, ident) of _group_tables for a conv that permutes the anchor axis by the relative rotations"""
+    mult, ident = _group_tables(anchors)
+    if mult is None:
+        raise NotImplementedError(
+            'anchor permutation with per-point poses needs a closed anchor set (kanchor 60 or 1)')
+    return mult, ident
+
+
+def _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose, epilogue=None):
+    """The shared front of the inter convs: ball query around the centres q_xyz (default: every point), rotated kernels, pose checks, the
+    anchor group's tables when the poses permute the anchor axis, offsets + relative-rotation anchors (so3_prep) -> _InterConvArgs."""
     q_xyz = xyz if q_xyz is None else q_xyz
     ball_idx = cuda_nn.ball_query(q_xyz, xyz, radius, n_neighbor)
     rk = rotated_kernels(anchors, kernels)
-    mult = ident = None
+    mult, ident = None, 0
     rot = q_rot = None
     if pose is not None:
         rot = pose.contiguous()
@@ -1330,14 +1410,17 @@ def _inter_group(xyz, pose, feats, n_neighbor, anchors, kernels, radius, sigma, 
         if rot.shape[-2:] != (4, 4) or rot.dtype != torch.float32:
             raise RuntimeError('so3conv: pose must be float32 [b,p,4,4]')
         if permute:
-            mult, ident = _group_tables(anchors)
-            if mult is None:
-                raise NotImplementedError(
-                    'anchor permutation with per-point poses needs a closed anchor set (kanchor 60 or 1)')
-    gx, nonident = _hip.so3_prep(q_xyz, xyz, ball_idx, q_rot, rot, anchors.contiguous(), 0 if ident is None else ident)
-    new_feats = _InterGroup.apply(feats, ball_idx, gx, rk, mult, float(sigma), 0 if ident is None else ident, nonident)
-    inter_w = InterWeights(gx, rk, sigma)
-    return ball_idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), new_feats
+            mult, ident = _permutation_tables(anchors)
+    gx, nonident = _hip.so3_prep(q_xyz, xyz, ball_idx, q_rot, rot, anchors.contiguous(), ident)
+    return _InterConvArgs(ball_idx, gx, rk, mult, sigma, ident, nonident, anchors, epilogue, (q_xyz.contiguous(), xyz.contiguous(), q_rot, rot))
+
+
+def _inter_group(xyz, pose, feats, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz=None, q_pose=None):
+    _check_inputs(xyz, feats)
+    a = _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose)
+    new_feats = _InterGroup.apply(feats, a.idx, a.gx, a.rk, a.mult, a.sigma, a.ident, a.nonident)
+    inter_w = InterWeights(a.gx, a.rk, sigma)
+    return a.idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), new_feats
 
 
 def inter_so3conv_fused(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz=None, q_pose=None,
@@ -1345,34 +1428,14 @@ def inter_so3conv_fused(xyz, pose, feats, W, n_neighbor, anchors, kernels, radiu
     """ball query + prep + fused (grouping . contraction) -> (ball_idx, InterWeights, y [b,o,p,a]).
     What InterSO3PoseConv / InterSO3Conv.forward run; q_xyz / q_pose = the sampled centres of a strided conv
     (default: every point is a centre).  epilogue: a FoldedEpilogue the contraction may apply (inference only)."""
-    if feats.dtype != torch.float32 or xyz.dtype != torch.float32 or W.dtype != torch.float32:
-        raise RuntimeError('so3conv: float32 only')
-    _hip.check_input(xyz)
-    if not feats.is_cuda or not W.is_cuda:
-        raise RuntimeError('so3conv: feats and W must be device tensors')
-    q_xyz = xyz if q_xyz is None else q_xyz
-    ball_idx = cuda_nn.ball_query(q_xyz, xyz, radius, n_neighbor)
-    rk = rotated_kernels(anchors, kernels)
-    mult = ident = rot = q_rot = None
-    if pose is not None:
-        rot = pose.contiguous()
-        q_rot = rot if q_pose is None else q_pose.contiguous()
-        if rot.shape[-2:] != (4, 4) or rot.dtype != torch.float32:
-            raise RuntimeError('so3conv: pose must be float32 [b,p,4,4]')
-        if permute:
-            mult, ident = _group_tables(anchors)
-            if mult is None:
-                raise NotImplementedError(
-                    'anchor permutation with per-point poses needs a closed anchor set (kanchor 60 or 1)')
-    gx, nonident = _hip.so3_prep(q_xyz, xyz, ball_idx, q_rot, rot, anchors.contiguous(), 0 if ident is None else ident)
+    _check_inputs(xyz, feats, W)
+    a = _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose, epilogue)
     bn_w = bn_b = None
     if isinstance(epilogue, TrainEpilogue):
         bn_w, bn_b = epilogue.norm.weight, epilogue.norm.bias
-    y = _InterConv.apply(feats, W, ball_idx, gx, rk, mult, float(sigma), 0 if ident is None else ident, nonident,
-                         anchors if mult is not None else None, epilogue, torch.is_grad_enabled(),
-                         (q_xyz.contiguous(), xyz.contiguous(), q_rot, rot), bn_w, bn_b)
-    inter_w = InterWeights(gx, rk, sigma)
-    return ball_idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), y
+    y = _InterConv.apply(feats, W, bn_w, bn_b, a)
+    inter_w = InterWeights(a.gx, a.rk, sigma)
+    return a.idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), y
 
 
 def inter_so3conv_fused_art_mode(xyz, pose, feats, W, seg_labels, n_neighbor, anchors, kernels, radius, sigma, permute):
@@ -1386,9 +1449,7 @@ def inter_so3conv_fused_art_mode(xyz, pose, feats, W, seg_labels, n_neighbor, an
         raise RuntimeError('use_art_mode: xyz must be [b, n_states, 3, p]')
     if seg_labels is None:
         raise RuntimeError('use_art_mode: the per-point state labels `seg` are required')
-    if feats.dtype != torch.float32 or xyz.dtype != torch.float32 or W.dtype != torch.float32:
-        raise RuntimeError('so3conv: float32 only')
-    _hip.check_input(xyz)
+    _check_inputs(xyz, feats, W, on_device=False)
     b, ns, _, p = xyz.shape
     flat = xyz.reshape(b * ns, 3, p).contiguous()
     idx_all = cuda_nn.ball_query(flat, flat, radius, n_neighbor)                                     # [b*ns, p, nn]
@@ -1402,15 +1463,13 @@ def inter_so3conv_fused_art_mode(xyz, pose, feats, W, seg_labels, n_neighbor, an
     ident = 0
     if pose is not None and permute:
         rot = pose.contiguous()
-        mult, ident = _group_tables(anchors)
-        if mult is None:
-            raise NotImplementedError('anchor permutation with per-point poses needs a closed anchor set (kanchor 60 or 1)')
+        mult, ident = _permutation_tables(anchors)
         # the nearest anchor of every pair's relative rotation (4th word of gx) and the per-cloud "not all identity" flag; the
         # rotated offsets this call also produces are not used in this mode
         first = xyz[:, 0].contiguous()
         g_rot, nonident = _hip.so3_prep(first, first, ball_idx, rot, rot, anchors.contiguous(), ident)
         gx = torch.cat([gx[..., :3], g_rot[..., 3:]], dim=-1).contiguous()
-    y = _InterConv.apply(feats, W, ball_idx, gx, rk, mult, float(sigma), ident, nonident, anchors if mult is not None else None, None, torch.is_grad_enabled())
+    y = _InterConv.apply(feats, W, None, None, _InterConvArgs(ball_idx, gx, rk, mult, sigma, ident, nonident, anchors))
     inter_w = InterWeights(gx, rk, sigma)
     return (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), y
 
@@ -1457,11 +1516,7 @@ def _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, p
     only, with the weights of rotation A_a RES_z: FOUR ordinary convolutions on the fused kernels, one per residual rotation,
     over the anchor sets {A_a RES_z}_a (the poses still rotate the offsets).  Otherwise the reference's expression in device
     tensor ops, a slab of SLOW_2D_CHUNK query points at a time (correct, not accelerated: the permuted 2-D case has no kernel)."""
-    if feats.dtype != torch.float32 or xyz.dtype != torch.float32:
-        raise RuntimeError('so3conv: float32 only')
-    _hip.check_input(xyz)
-    if not feats.is_cuda:
-        raise RuntimeError('so3conv: feats must be a device tensor')
+    _check_inputs(xyz, feats)
     b, c, p, na4 = feats.shape
     na = anchors.shape[0]
     if na4 != 4 * na:
