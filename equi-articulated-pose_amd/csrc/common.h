@@ -1,4 +1,5 @@
-// csrc/common.h -- shared helpers for the gfx950 kernels behind include/eap_hip.h.
+// csrc/common.h -- host-side helpers shared by the launchers behind include/eap_hip.h, in three parts: error / launch
+// helpers, the side-stream helpers, the cross-file launcher prototypes.  (Device-side primitives: csrc/device_prims.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,6 +9,7 @@
 
 namespace eap {
 
+// ---- 1. error / launch helpers --------------------------------------------------------------------------------------
 void set_error(const char *msg);
 // name (with template arguments, as rocprofv3 prints it) of the dominant kernel the calling thread launched last -- set by
 // the launchers of the hot kernels, read by bench.py through eap_last_kernel() to attribute time per KERNEL, not per entry
@@ -41,21 +43,33 @@ static inline hipStream_t S(eap_stream_t s) { return (hipStream_t)s; }
 
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
-}  // namespace eap
-
-#ifdef __HIPCC__
-// Consecutive points must land on the SAME XCD: each (channel, k) output row of a point is only
-// 4*na bytes, so neighbouring points share cache lines; with the default round-robin dispatch
-// (block b -> XCD b % 8) they would sit half-written in eight different L2s and reach HBM as
-// partial lines (measured: X written at ~1 TB/s).  Remap so that XCD x gets a contiguous range
-// of points (bijective for any P).
-__device__ __forceinline__ int xcd_point(int bx, int p) {
-    const int q = p >> 3, r = p & 7, xcd = bx & 7, j = bx >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+// lets `kernel` be launched with `bytes` of dynamic LDS (more than the 64 KB a kernel may use without asking); called before
+// every such launch
+template <typename K>
+static inline int allow_dynamic_lds(K *kernel, size_t bytes, const char *what) {
+    return hip_fail(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), what);
 }
 
+// ---- 2. side-stream helpers -----------------------------------------------------------------------------------------
+// csrc/abi.hip: a side stream per device (fork: it waits for `s` so far; join: `s` waits for it)
+int side_fork(hipStream_t s, hipStream_t *side);
+int side_join(hipStream_t s);
+// Joins on EVERY exit path after a fork: an early error return must not leave the side stream reading buffers the caller frees
+// once the entry has failed.  (One side stream and one fork / join event pair per device, shared by every caller: entries that
+// fork are meant to be called from ONE host thread per device -- the autograd thread of a process that owns the GPU, as the
+// reference's extensions are; two host threads forking on the same device would share the events.)
+struct SideJoin {
+    hipStream_t s;
+    bool armed = true;
+    explicit SideJoin(hipStream_t stream) : s(stream) {}
+    ~SideJoin() { if (armed) side_join(s); }
+    int join() { armed = false; return side_join(s); }
+};
+
+// ---- 3. cross-file launcher prototypes ------------------------------------------------------------------------------
+// csrc/gemm_f32.hip: C[M,N] (leading dimension ldc, mn = M * N) = the sum of `slabs` contiguous partial slabs of `ws`, in slab order
+int reduce_slabs(const float *ws, float *C, long long mn, int N, int slabs, long long ldc, hipStream_t s, const char *what);
 // csrc/so3_inter_lists.hip: the two-workgroups-per-CU grouping kernel (no anchor permutation)
-namespace eap {
 bool group_lists_supported(int na, int ks);
 int group_lists_fwd(int b, int c, int p, int n, int nn, int na, int ks, float sigma, const float *feats,
                     const int32_t *idx, const float *gx, const float *rk, const int32_t *nonident, int blocked, float *out,
@@ -113,20 +127,7 @@ int zpconv_index_check(int b, int np, int per_point, int nn, const int32_t *idx,
 // idx0[b,p,:] = the first (a,k) row of every point's 5-D index (1 MB per cloud): what the matrix kernels walk while the full
 // comparison above still streams on the side stream
 int zpconv_first_rows(int b, int np, int per_point, int nn, const int32_t *idx, int32_t *idx0, hipStream_t s);
-// csrc/abi.hip: a side stream per device (fork: it waits for `s` so far; join: `s` waits for it)
-int side_fork(hipStream_t s, hipStream_t *side);
-int side_join(hipStream_t s);
-// Joins on EVERY exit path after a fork: an early error return must not leave the side stream reading buffers the caller frees
-// once the entry has failed.  (One side stream and one fork / join event pair per device, shared by every caller: entries that
-// fork are meant to be called from ONE host thread per device -- the autograd thread of a process that owns the GPU, as the
-// reference's extensions are; two host threads forking on the same device would share the events.)
-struct SideJoin {
-    hipStream_t s;
-    bool armed = true;
-    explicit SideJoin(hipStream_t stream) : s(stream) {}
-    ~SideJoin() { if (armed) side_join(s); }
-    int join() { armed = false; return side_join(s); }
-};
+// csrc/zpconv.hip: the flag-gated scatter backward
 int inter_zpconv_bwd_flagged(int b, int np, int nq, int na, int ks, int ann, int c, const int32_t *idx, const float *w,
                              const float *grad, float *gfeats, const int32_t *only_flagged, hipStream_t s);
 // csrc/so3_inter_mfma.hip with the clouds already served by group_lists_fwd skipped
@@ -136,5 +137,5 @@ int group_fwd_perm_lists(int b, int c, int p, int n, int nn, int na, int ks, flo
 int group_fwd_mfma(int b, int c, int p, int n, int nn, int na, int ks, float sigma, const float *feats,
                    const int32_t *idx, const float *gx, const float *rk, const uint8_t *mult,
                    const int32_t *nonident, int skip_plain, int blocked, float *out, hipStream_t s);
-}
-#endif
+
+}  // namespace eap

@@ -34,17 +34,12 @@
 //   2  implicit intra-SO(3) gather: B[(c, t), (p, a)] = F_z[c, p, idx[a, t]] (so3conv/functional.py:L2553-2602), the 60 x 12
 //      table in LDS; a piece = the four taps t0..t0+3 of one channel, four dword loads inside the point's 240-byte row
 #include "common.h"
+#include "device_prims.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK = 16, BN = 256;
 constexpr unsigned PLANE_BYTES = 256 * BK * 2;                 // one plane of one operand tile: 8 KB
@@ -97,22 +92,11 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned &h, unsi
 // the remainder is usually well below its bound) as long as l stays a normal fp16 number, i.e. |x| >= 2^-2; below that
 // l is a subnormal and |e| <= 2^-25 absolute.  The scales put each tensor's largest magnitude in [2^14, 2^15) (or a
 // bound on it at 2^15), so elements down to 2^-17 of the largest keep the relative bound and nothing overflows.
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split_pair_h(float x0, float x1, unsigned &h, unsigned &l) {
     const f16x2 hh = __builtin_convertvector((f32x2){x0, x1}, f16x2);               // v_cvt_pk_f16_f32
     const f16x2 ll = __builtin_convertvector((f32x2){x0 - (float)hh.x, x1 - (float)hh.y}, f16x2);
     h = __builtin_bit_cast(unsigned, hh);
     l = __builtin_bit_cast(unsigned, ll);
-}
-// the scale 2^(14 - e) of a tensor whose largest magnitude (or a bound on it) is v in [2^e, 2^(e+1)); 1 for 0, inf, nan
-__device__ __forceinline__ float pow2_scale(float v) {
-    const unsigned b = __float_as_uint(v) & 0x7fffffffu;
-    const int e = (int)(b >> 23) - 127;
-    if (b == 0u || e == 128) return 1.0f;
-    const int se = max(-120, min(120, 14 - max(e, -126)));
-    return __uint_as_float((unsigned)(se + 127) << 23);
 }
 
 __device__ __forceinline__ void split_quad(const f32x4 &a, const f32x4 &b, u32x4 &h, u32x4 &m, u32x4 &l) {   // 8 k's
@@ -607,7 +591,7 @@ int launch_split(Args &g, int batch, hipStream_t stream, const char *who) {
     g.tiles_n = (g.N + BN - 1) / BN;
     const size_t shmem = shmem_bytes(PL) + (BMODE == 2 ? TBL_BYTES : 0);
     auto launch = [&](auto kern) {
-        int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem), who);
+        int e = eap::allow_dynamic_lds(kern, shmem, who);
         if (e) return e;
         hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, batch), dim3(128 * WAVES_N), shmem, stream, g);
         return 0;

@@ -35,14 +35,13 @@
 //     half-wave (conflict-free ds_read_b32).  Both images use the same k <-> (step, half-wave) assignment.
 // Block tile 256 x 256 (wave tile 128 x 128), or 128 x 256 / 256 x 128 for small M / N; 96 KB of LDS.
 #include "common.h"
+#include "device_prims.h"
 
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 16, STAGES = 3, NT = 256;
 
@@ -56,7 +55,6 @@ struct DmaArgs {
 };
 
 // the k-tile in flight: eight named 16-byte quads (an indexed array of vectors is not promoted to registers)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 struct Staging {
     f32x4 v0, v1, v2, v3, v4, v5, v6, v7, v8, v9;
     template <int U>
@@ -316,16 +314,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_dma_f32_kernel(DmaArgs g) {
         }
 }
 
-// sum `slabs` partial [M,N] slabs (contiguous, pitch M*N) into C (leading dimension ldc), in slab order
-__global__ void dma_reduce_slabs_kernel(long long mn, int N, int slabs, const float *__restrict__ ws,
-                                        float *__restrict__ C, long long ldc) {
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= mn) return;
-    float s = 0.f;
-    for (int z = 0; z < slabs; ++z) s += ws[(long long)z * mn + e];
-    C[(e / N) * ldc + (e % N)] = s;
-}
-
 template <int WM, int WN, int MI, int NI, bool AKM, bool BKN>
 int launch_one(DmaArgs g, int zcount, hipStream_t s) {
     constexpr int BM = 32 * MI * WM, BN = 32 * NI * WN;
@@ -333,8 +321,7 @@ int launch_one(DmaArgs g, int zcount, hipStream_t s) {
     g.tiles_n = (g.N + BN - 1) / BN;
     const size_t shmem = (size_t)STAGES * (BM + BN) * BK * 4;
     auto kern = gemm_dma_f32_kernel<WM, WN, MI, NI, AKM, BKN>;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                          "gemm_dma_f32 shared memory");
+    int e = eap::allow_dynamic_lds(kern, shmem, "gemm_dma_f32 shared memory");
     if (e) return e;
     hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, zcount), dim3(NT), shmem, s, g);
     {
@@ -351,7 +338,7 @@ int launch_debug(DmaArgs g, int zcount, hipStream_t s) {
     g.tiles_n = (g.N + 255) / 256;
     const size_t shmem = (size_t)STAGES * 512 * BK * 4;
     auto kern = gemm_dma_f32_kernel<2, 2, 4, 4, false, false, DBG>;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem), "gemm_dma_f32 debug");
+    int e = eap::allow_dynamic_lds(kern, shmem, "gemm_dma_f32 debug");
     if (e) return e;
     hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, zcount), dim3(NT), shmem, s, g);
     return eap::check_launch("gemm_dma_f32 (debug variant)");
@@ -445,8 +432,5 @@ extern "C" int eap_gemm_dma_f32_reduce(int transA, int transB, int M, int N, int
     DmaArgs g{M, N, K, A, lda, strideA, B, ldb, strideB, workspace, N, (long long)M * N, 0, 0, splits, kchunk};
     int e = launch(transA != 0, transB == 0, g, batch * splits, s);
     if (e) return e;
-    const long long mn = (long long)M * N;
-    hipLaunchKernelGGL(dma_reduce_slabs_kernel, dim3(eap::cdiv(mn, 256)), dim3(256), 0, s, mn, N, batch * splits, workspace, C,
-                       (long long)ldc);
-    return eap::check_launch("gemm_dma_f32_reduce");
+    return eap::reduce_slabs(workspace, C, (long long)M * N, N, batch * splits, ldc, s, "gemm_dma_f32_reduce");
 }

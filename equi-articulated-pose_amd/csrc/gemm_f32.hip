@@ -15,12 +15,11 @@
 // panel of the streamed operand are adjacent in dispatch order on the SAME XCD (blockIdx % 8),
 // so the panel is fetched from HBM once and re-read from that XCD's L2.
 #include "common.h"
+#include "device_prims.h"
 
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 16, PAD = 4;
 
@@ -247,7 +246,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN >= 16 ? 4 : 2)) void gem
     }
 }
 
-// sum `slabs` partial [M,N] slabs (contiguous, pitch M*N) into C (leading dimension ldc)
+// sum `slabs` partial [M,N] slabs (contiguous, pitch M*N) into C (leading dimension ldc), in slab order (eap::reduce_slabs)
 __global__ void reduce_slabs_kernel(long long mn, int N, int slabs, const float *__restrict__ ws,
                                     float *__restrict__ C, long long ldc) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -319,7 +318,24 @@ int pick_splits(int M, int N, int K, int batch) {
     return splits;
 }
 
+// the tail of both split-K entries: pick the splits, run them into `workspace` slabs, sum the slabs into C
+// (bblk: GemmArgs::bblk, 0 for a plain B)
+int run_reduce(int transA, int transB, int M, int N, int K, const float *A, int64_t lda, int64_t strideA, const float *B,
+               int64_t ldb, int64_t strideB, float *C, int64_t ldc, int batch, float *workspace, int64_t bblk, hipStream_t s) {
+    const int splits = pick_splits(M, N, K, batch);
+    int kchunk = ((K + splits - 1) / splits + BK - 1) / BK * BK;
+    GemmArgs g{M, N, K, A, lda, strideA, B, ldb, strideB, workspace, N, (long long)M * N, splits, kchunk, 0, 0, nullptr, 0, 0, bblk};
+    int e = run(transA != 0, transB != 0, g, batch * splits, s);
+    if (e) return e;
+    return eap::reduce_slabs(workspace, C, (long long)M * N, N, batch * splits, ldc, s, "gemm_f32_reduce");
+}
+
 }  // namespace
+
+int eap::reduce_slabs(const float *ws, float *C, long long mn, int N, int slabs, long long ldc, hipStream_t s, const char *what) {
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(eap::cdiv(mn, 256)), dim3(256), 0, s, mn, N, slabs, ws, C, ldc);
+    return eap::check_launch(what);
+}
 
 extern "C" int eap_gemm_f32(int transA, int transB, int M, int N, int K, const float *A, int64_t lda,
                             int64_t strideA, const float *B, int64_t ldb, int64_t strideB, float *C,
@@ -364,16 +380,7 @@ extern "C" int eap_gemm_f32_reduce_xb(int transA, int transB, int M, int N, int 
     if (batch <= 0 || K <= 0) return eap_gemm_f32_reduce(transA, transB, M, N, K, A, lda, strideA, B, 4, strideB, C, ldc, batch, workspace, stream);
     if (((transB ? K : N) & 3) != 0 || b_block_rows != (transB ? N : K))
         return eap::bad_arg("gemm_f32_reduce_xb: blocked dimension must be a multiple of 4 and b_block_rows the other one");
-    hipStream_t s = eap::S(stream);
-    const int splits = pick_splits(M, N, K, batch);
-    int kchunk = ((K + splits - 1) / splits + BK - 1) / BK * BK;
-    GemmArgs g{M, N, K, A, lda, strideA, B, 4, strideB, workspace, N, (long long)M * N, splits, kchunk, 0, 0, nullptr, 0, 0, b_block_rows};
-    int e = run(transA != 0, transB != 0, g, batch * splits, s);
-    if (e) return e;
-    const long long mn = (long long)M * N;
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(eap::cdiv(mn, 256)), dim3(256), 0, s, mn, N,
-                       batch * splits, workspace, C, (long long)ldc);
-    return eap::check_launch("gemm_f32_reduce");
+    return run_reduce(transA, transB, M, N, K, A, lda, strideA, B, 4, strideB, C, ldc, batch, workspace, b_block_rows, eap::S(stream));
 }
 
 extern "C" int64_t eap_gemm_f32_reduce_workspace(int M, int N, int K, int batch) {
@@ -393,13 +400,5 @@ extern "C" int eap_gemm_f32_reduce(int transA, int transB, int M, int N, int K, 
         }
         return 0;
     }
-    const int splits = pick_splits(M, N, K, batch);
-    int kchunk = ((K + splits - 1) / splits + BK - 1) / BK * BK;
-    GemmArgs g{M, N, K, A, lda, strideA, B, ldb, strideB, workspace, N, (long long)M * N, splits, kchunk, 0, 0, nullptr, 0, 0, 0};
-    int e = run(transA != 0, transB != 0, g, batch * splits, s);
-    if (e) return e;
-    const long long mn = (long long)M * N;
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(eap::cdiv(mn, 256)), dim3(256), 0, s, mn, N,
-                       batch * splits, workspace, C, (long long)ldc);
-    return eap::check_launch("gemm_f32_reduce");
+    return run_reduce(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, batch, workspace, 0, s);
 }

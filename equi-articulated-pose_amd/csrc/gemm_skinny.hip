@@ -10,10 +10,9 @@
 // float4 A[i][k + 4 h .. + 3]; component c of the two halves is the pair (k + c, k + 4 + c) -- some pair of contraction
 // indices, the same one on the B side, which is all a sum needs.
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int NT = 256;          // 4 waves
 constexpr int KSTEP = 32;        // contraction indices per wave and iteration (4 float4 per lane and tile)

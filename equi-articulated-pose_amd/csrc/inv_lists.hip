@@ -197,8 +197,7 @@ extern "C" int eap_inv_lists_rows(int b, int p, int n, int nn, const int32_t *id
     int n2 = RT;
     while (n2 < n) n2 <<= 1;
     const size_t shmem = sizeof(unsigned long long) * n2;
-    e = eap::hip_fail(hipFuncSetAttribute((const void *)inv_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                      "inv_lists_rows shared memory");
+    e = eap::allow_dynamic_lds(inv_rows_kernel, shmem, "inv_lists_rows shared memory");
     if (e) return e;
     hipLaunchKernelGGL(inv_rows_kernel, dim3(b), dim3(RT), shmem, s, n, n2, counts, rows, off, cnt, n_rows);
     return eap::check_launch("inv_lists_rows (sort)");

@@ -10,6 +10,7 @@
 //   dW           : lanes hold the gradient of their 4 columns and accumulate per-channel partial sums over a column slab;
 //                  partials [slab][cloud][o][c] are summed in a fixed order by the caller (deterministic, no atomics)
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace {
@@ -17,8 +18,6 @@ namespace {
 constexpr int TB = 256;
 constexpr int MAXC = 2048;          // W rows staged in LDS: 4 * 2048 floats = 32 KB
 constexpr int CS = 16;              // channels per accumulator group of the dW kernel
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int O>
 __global__ __launch_bounds__(TB) void narrow_fwd_kernel(int c, long n, const float *__restrict__ W, const float *__restrict__ x,

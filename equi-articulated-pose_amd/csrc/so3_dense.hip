@@ -42,17 +42,12 @@
 // matrix instruction, issued in their shadow.
 #include <atomic>
 #include "common.h"
+#include "device_prims.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned long long u64;
 typedef const __attribute__((address_space(4))) unsigned long long *cu64p;      // constant address space: uniform loads go through the scalar cache
 
@@ -71,30 +66,8 @@ __host__ __device__ __forceinline__ void dense_kr(int d, int ks, int &k, int &r)
     r = 16 * g + (rem & 15);
 }
 
-__device__ inline unsigned lds_addr(const void *ptr) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ptr;
-}
-// wave-wide global -> LDS DMA (16 / 4 bytes per lane, destination = lds_dst + 16 / 4 * lane), invisible to hipcc's waitcnt
-// bookkeeping on purpose: the k-loop waits with its own counted s_waitcnt before the step's barrier
-__device__ inline void glds16s(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds4s(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
-// the scale 2^(14 - e) of a row whose largest magnitude is v in [2^e, 2^(e+1)); 1 for 0, inf, nan (as csrc/gemm_bf16x3.hip)
-__device__ __forceinline__ float pow2_scale(float v) {
-    const unsigned b = __float_as_uint(v) & 0x7fffffffu;
-    const int e = (int)(b >> 23) - 127;
-    if (b == 0u || e == 128) return 1.0f;
-    const int se = max(-120, min(120, 14 - max(e, -126)));
-    return __uint_as_float((unsigned)(se + 127) << 23);
-}
+// The operand ring is filled with glds16s / glds4s (device_prims.h); the k-loop owns the wait: a counted s_waitcnt of its own
+// before each step's barrier.
 
 // x (scaled) = h + l + e, h = fp16(x), l = fp16(x - h), both to nearest even; two values -> the packed h word and l word.
 // v_fma_mix{lo,hi}_f16 form fp16(-1 * h + x) in one instruction each, reading h's half straight from the packed word.
@@ -1081,8 +1054,7 @@ int kc_launch(const KcArgs &g, hipStream_t s) {
     if (int e = eap::hip_fail(hipGetDevice(&dev), "so3_dense: hipGetDevice")) return e;
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(set_on.load(std::memory_order_acquire) & bit)) {
-        if (int e = eap::hip_fail(hipFuncSetAttribute(reinterpret_cast<const void *>(kc_gemm_kernel<MI, FORM, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      (int)shmem), "so3_dense: shared memory attribute"))
+        if (int e = eap::allow_dynamic_lds(kc_gemm_kernel<MI, FORM, DBG>, shmem, "so3_dense: shared memory attribute"))
             return e;
         set_on.fetch_or(bit, std::memory_order_release);
     }
@@ -1291,8 +1263,7 @@ extern "C" int eap_so3_dense_gplanes_f32(int b, int o, int c, int na, int ks, in
     const size_t shmem = (size_t)rch * (2 * c + 16) * 2;
     hipStream_t s = eap::S(stream);
     auto launch = [&](auto kern) -> int {
-        if (int e = eap::hip_fail(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                                  "so3_dense_gplanes: shared memory attribute"))
+        if (int e = eap::allow_dynamic_lds(kern, shmem, "so3_dense_gplanes: shared memory attribute"))
             return e;
         hipLaunchKernelGGL(kern, dim3(eap::cdiv(o / 32, 4), b * na), dim3(256), shmem, s, o, na, ks, rp, rch, kb_total, W3, Ft, n_rows, bound, scale,
                            reinterpret_cast<u32x4 *>(planes));

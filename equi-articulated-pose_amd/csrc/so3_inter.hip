@@ -21,6 +21,7 @@
 //   * so3_inter_weights / so3_anchor_perm materialise w / perm only when a caller asks for them
 //     (the module API returns inter_w; parity tests compare them with the oracle).
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
 

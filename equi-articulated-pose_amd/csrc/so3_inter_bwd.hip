@@ -21,6 +21,7 @@
 //   * slab loads bypass L1 (agent-scope relaxed load) so a wave always sees its own earlier
 //     stores; slabs are summed over the point ranges by a second, deterministic kernel.
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -31,8 +32,6 @@ constexpr int KS = 24;      // kernel points held in registers
 constexpr int NB = 8;       // neighbours per weight chunk (= NW: one per wave in phase 1)
 constexpr int RP = KS * 3 + 1;  // LDS pitch of one anchor's rotated kernel points (odd: conflict-free)
 constexpr int T_ = 64 * NW;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float4 ld_l2(const float4 *p) {
     // one 16-byte non-temporal load: bypasses L1 (served by L2), so a wave always sees its own
@@ -230,9 +229,7 @@ extern "C" int eap_so3_inter_group_bwd_slab_f32(int b, int c, int p, int n, int 
     int e = eap::hip_fail(hipMemsetAsync(workspace, 0, sizeof(float) * ws_floats, s), "so3_inter_group_bwd_slab memset");
     if (e) return e;
     const size_t shmem = sizeof(float) * (2 * NB * KS * 64 + NW * CW * 64 + 64 * RP + 4) + 20 * (size_t)nn + 4 * ((size_t)nn / NB + 1) + (mult ? (size_t)na * na : 0);
-    e = eap::hip_fail(hipFuncSetAttribute((const void *)so3_inter_group_bwd_slab_kernel,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                      "so3_inter_group_bwd_slab shared memory");
+    e = eap::allow_dynamic_lds(so3_inter_group_bwd_slab_kernel, shmem, "so3_inter_group_bwd_slab shared memory");
     if (e) return e;
     hipLaunchKernelGGL(so3_inter_group_bwd_slab_kernel, dim3(ps, nch, b), dim3(T_), shmem, s, c, p, n, nn, na, ks,
                        1.0f / sigma, nch, ps, ppb, identity_anchor, gout, idx, reinterpret_cast<const float4 *>(gx), rk, mult, workspace);

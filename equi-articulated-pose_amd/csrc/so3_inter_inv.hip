@@ -20,6 +20,7 @@
 // VGPRs, 8 waves (2 per SIMD).  With an anchor permutation the weight's anchor changes per entry,
 // so the rotated kernel points come from an LDS table instead of registers.
 #include "common.h"
+#include "device_prims.h"
 #include <algorithm>
 
 #ifdef EAP_INV_TRACE
@@ -31,9 +32,6 @@ __device__ unsigned long long eap_inv_trace[8 * 16];
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int CB = 32;        // dY channels per block (one MFMA M tile)
 constexpr int NBK = 8;        // entries per LDS stage (4 MFMA k-steps)
 constexpr int FPMAX = 68;     // LDS pitch of one staged row: 60 floats for <= 60 anchors, 68 for 61..64 (16-byte
@@ -41,23 +39,6 @@ constexpr int FPMAX = 68;     // LDS pitch of one staged row: 60 floats for <= 6
 constexpr int APW = 8;        // max anchors per wave
 constexpr int NWV = 8;
 constexpr int TM = 64 * NWV;
-
-// LDS byte address of a __shared__ object (what M0 takes for the LDS-DMA loads)
-__device__ inline unsigned lds_addr(const void *ptr) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ptr;
-}
-
-// One wave-wide 16-byte-per-lane global -> LDS DMA: lane l's 16 bytes land at lds_dst + 16*l.
-// Inline asm on purpose: hipcc tracks the builtin as an LDS store and drains vmcnt before every
-// later ds_read, which would serialise the next chunk's rows behind this chunk's operand reads;
-// an asm load is invisible to its bookkeeping and the kernel waits for it explicitly (dma_wait)
-// before the chunk barrier.  M0 is saved and restored in the same statement.
-__device__ inline void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // DMA = true: dY rows go global -> LDS directly (row pitch = na, no padding possible), issued
 // between the MFMA steps of the previous chunk; DMA = false: register-staged rows with a padded
@@ -583,7 +564,7 @@ int eap::group_fwd_perm_lists(int b, int c, int p, int n, int nn, int na, int ks
     const size_t shmem = stage_b + 16 * 3 * NBK + 16 * NBK + 16 * 3 * (size_t)na + (size_t)na * na;
     if (shmem > 160 * 1024) return -1;
     auto kern = so3_inter_group_inv_kernel<true, true, true>;
-    if (int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem), "so3_inter_group_fwd (permuted) shared memory")) return e;
+    if (int e = eap::allow_dynamic_lds(kern, shmem, "so3_inter_group_fwd (permuted) shared memory")) return e;
     hipLaunchKernelGGL(kern, dim3(p, (c + CB - 1) / CB, b), dim3(TM), shmem, s, c, n, nn, na, ks, p, 1.0f / sigma, -1, feats,
                        (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, idx, reinterpret_cast<const float4 *>(gx), rk,
                        mult, (const float *)nullptr, out, blocked, nonident, (const uint8_t *)nullptr);
@@ -713,7 +694,7 @@ static int group_inv(int b, int o, int p, int nn, int na, int ks, int rcap, floa
     dim3 grid(rcap, (o + CB - 1) / CB, b);
     const float4 *g4 = reinterpret_cast<const float4 *>(ent_gx);
     auto launch = [&](auto kern) {
-        int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem), "so3_inter_group_inv shared memory");
+        int e = eap::allow_dynamic_lds(kern, shmem, "so3_inter_group_inv shared memory");
         if (e) return e;
         hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, o, p, nn, na, ks, rcap, 1.0f / sigma, identity_anchor, gy, rows, off, cnt, ent_p, g4, rk, multinv, anchors, z,
                            0, (const int32_t *)nullptr, (const uint8_t *)nullptr);
@@ -723,7 +704,7 @@ static int group_inv(int b, int o, int p, int nn, int na, int ks, int rcap, floa
     if (multinv && coset_order) {
         // (the code table travels in the `multinv` argument slot; with the DMA loader gy's anchor axis is ALREADY coset-major)
         auto go = [&](auto kern) {
-            int e2 = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem), "so3_inter_group_inv shared memory");
+            int e2 = eap::allow_dynamic_lds(kern, shmem, "so3_inter_group_inv shared memory");
             if (e2) return e2;
             hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, o, p, nn, na, ks, rcap, 1.0f / sigma, identity_anchor, gy, rows, off, cnt, ent_p, g4, rk, coset_code,
                                anchors, z, 0, (const int32_t *)nullptr, coset_order);

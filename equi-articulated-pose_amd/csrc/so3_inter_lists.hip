@@ -35,12 +35,10 @@
 //   * Row end: accumulators straight to global (16-byte stores, no LDS transposition, no barrier);
 //     in the forward a workgroup streams through 8 consecutive rows without draining its pipeline.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CB = 32;        // channels per block (one MFMA M tile)
 constexpr int NBK = 8;        // entries per LDS stage (4 MFMA k-steps)
@@ -50,29 +48,6 @@ constexpr int TM = 64 * NWV;
 constexpr int NSTD = 4;       // DMA instructions per thread and chunk: NBK*CB*8 pieces / TM
 constexpr int PITCH = 32;     // floats per LDS row = 8 pieces, whatever the group's anchor count (see the DMA mapping)
 constexpr unsigned BUF_BYTES = NBK * CB * PITCH * 4;
-
-__device__ inline unsigned lds_addr(const void *ptr) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ptr;
-}
-// wave-wide 16-byte-per-lane global -> LDS DMA, invisible to hipcc's waitcnt bookkeeping on
-// purpose (see csrc/so3_inter_inv.hip); the kernel waits with dma_wait() before the chunk barrier
-__device__ inline void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// the same with a wave-uniform 64-bit base in SGPRs and a 32-bit byte offset per lane: no 64-bit VALU add per request
-__device__ inline void glds16s(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds4(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // LISTS = true : rows / off / cnt describe variable-length entry lists (backward);
 // LISTS = false: row r of cloud b owns entries [ (b*R + r)*nn, +nn ) (forward: its neighbours).
@@ -426,7 +401,7 @@ int launch(int blocked, int b, int C, int PF, int na, int fpitch, int ks, int R,
     if (((long long)ks * R * na * 4 + 32ll * R * na + 64) * 4 >= (1ll << 31)) return eap::bad_arg("so3_group_lists: output rows too far apart for 32-bit store offsets");
     auto kern = blocked == 2 ? so3_group_lists_kernel<LISTS, LISTS ? 0 : 2> : blocked == 1 ? so3_group_lists_kernel<LISTS, LISTS ? 0 : 1>
                                                                                           : so3_group_lists_kernel<LISTS, 0>;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.shmem), what);
+    int e = eap::allow_dynamic_lds(kern, g.shmem, what);
     if (e) return e;
     // forward: a workgroup streams through a run of consecutive rows (the next row's entries and
     // first chunk are in flight during the current row's last chunk)

@@ -21,13 +21,10 @@
 // MI355X_MICROARCH.md section LDS) then touch 16 different 16-byte slots of the 256-byte bank row -- conflict-free at a
 // 64-byte row pitch, and still one contiguous 1 KB destination per global->LDS DMA instruction.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CT = 2;         // channel tiles (MFMA M tiles) per wave
 constexpr int CB = 32 * CT;   // channels per block
@@ -41,28 +38,6 @@ constexpr int PITCH = 4 * SL; // floats per LDS row
 constexpr int NSTD = NBK * CB * SL / TM;   // DMA instructions per thread and chunk (8): instruction u carries entry u
 constexpr unsigned BUF_BYTES = NBK * CB * PITCH * 4;
 static_assert(CB * SL == TM, "one DMA instruction per entry: thread t <-> (row t >> 2, slot t & 3)");
-
-__device__ inline unsigned lds_addr(const void *ptr) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ptr;
-}
-// wave-wide 16-byte-per-lane global -> LDS DMA, invisible to hipcc's waitcnt bookkeeping on purpose (the kernel waits
-// with dma_wait() before the chunk barrier); same idiom as csrc/so3_inter_lists.hip
-__device__ inline void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds16s(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds4(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // Timing ablations (WRONG RESULTS), compiled only with `make ABLATION=1` and selected by EAP_LISTS2_DEBUG (bit mask):
 // 1 no feature DMA after the prologue, 2 constant weights (no weight evaluation), 4 no row-end stores, 8 no chunk barrier
@@ -505,7 +480,7 @@ int launch2(int layout, int b, int C, int PF, int na, int fpitch, int ks, int R,
     auto kern = perm ? (lane_order ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 4, true> : wide ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 3, true> : layout == 2 ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 2, true> : so3_group_lists2_kernel<LISTS, 0, true>)
                      : (lane_order ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 4> : wide ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 3> : layout == 2 ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 2> : so3_group_lists2_kernel<LISTS, 0>);
     const size_t shmem = perm ? SHMEM_PERM : SHMEM;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem), what);
+    int e = eap::allow_dynamic_lds(kern, shmem, what);
     if (e) return e;
     const int AG = (na + GSZ - 1) / GSZ;
     const int RPB = LISTS ? 1 : ((nn % NBK) == 0 ? 8 : 1);

@@ -21,11 +21,9 @@
 // fp32 MFMA issue: 2*32*32*NN*A flops per (point, 32 channels) = 4/3 of the useful flops (K padded
 // 24 -> 32).
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CB = 32;        // channels per block (one MFMA M tile)
 constexpr int NBK = 8;        // neighbours per LDS stage (4 MFMA k-steps; the pipeline below is written for 4)
@@ -330,8 +328,7 @@ int eap::group_fwd_mfma(int b, int c, int p, int n, int nn, int na, int ks, floa
 #define EAP_MFMA_LAUNCH(APW_, EXACT_, MULT_)                                                                  \
     do {                                                                                                      \
         auto kern = so3_inter_group_fwd_mfma_kernel<APW_, EXACT_, MULT_>;                                     \
-        e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                              (int)shmem), "so3_inter_group_fwd_mfma shared memory");         \
+        e = eap::allow_dynamic_lds(kern, shmem, "so3_inter_group_fwd_mfma shared memory");                    \
         if (e) return e;                                                                                      \
         hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, c, p, n, nn, na, ks, inv_sigma, feats, idx, g4,    \
                            rk, mult, nonident, skip_plain, blocked, out);                                     \

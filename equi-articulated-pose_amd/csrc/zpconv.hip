@@ -21,6 +21,7 @@
 // csrc/zpconv_rows.hip (30-34 %); this file serves f64, the backward and tiny channel counts.  The backward kernels keep scatter semantics (fp atomics on the
 // gradient of feats), lanes along `a` as well.
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -115,8 +116,7 @@ int launch_inter(int b, int np, int nq, int na, int ks, int ann, int c, const in
     const size_t shmem = (sizeof(T) + sizeof(int32_t)) * (size_t)na * (KC * ann + 1);
     if (shmem > 160 * 1024) return eap::bad_arg("inter_zpconv: neighbourhood too large for LDS staging");
     auto kern = inter_zpconv_kernel<T, 8, BWD>;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                          "inter_zpconv shared memory");
+    int e = eap::allow_dynamic_lds(kern, shmem, "inter_zpconv shared memory");
     if (e) return e;
     dim3 grid(np, 1, b);
     hipLaunchKernelGGL(kern, grid, dim3(ZP_THREADS), shmem, s, np, nq, na, ks, ann, c, idx, w, src, dst, only_flagged);

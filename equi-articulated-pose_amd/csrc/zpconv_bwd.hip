@@ -23,29 +23,15 @@
 // T costs 4*P*NN*C*A bytes per cloud (4 GB at 4096 points, C = 64): the caller provides it (workspace) and may
 // split the batch.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 #include <utility>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int NWV = 8, TM = 64 * NWV;
 constexpr int KS2 = 12;                    // MFMA k-steps: up to 24 kernel points
 constexpr int TP = 68;                     // LDS tile pitch (floats): 16-byte aligned rows, 4 banks apart
-
-// uniform 64-bit base + 32-bit byte offset per lane: hipcc then uses the SGPR-base addressing form and no 64-bit
-// vector arithmetic (the first version spent 260 v_lshl_add_u64 per unit and, under the register pressure they
-// caused, waited for every single load)
-template <typename V>
-__device__ __forceinline__ V ld_off(const float *ubase, unsigned voff) {
-    return *reinterpret_cast<const V *>(reinterpret_cast<const char *>(ubase) + voff);
-}
-template <typename V>
-__device__ __forceinline__ void st_off(float *ubase, unsigned voff, V v) {
-    *reinterpret_cast<V *>(reinterpret_cast<char *>(ubase) + voff) = v;
-}
 
 // FULL: ks == 24, nn == 64, channel slice complete -- no clamps, no masks
 template <bool FULL>
@@ -261,11 +247,9 @@ extern "C" int eap_inter_zpconv_bwd_ws_f32(int b, int np, int nq, int na, int ks
     // T, 64 channels per pass
     {
         const size_t shmem = sizeof(float) * NWV * 64 * TP;
-        e = eap::hip_fail(hipFuncSetAttribute((const void *)zpconv_bwd_t_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                          "inter_zpconv_backward shared memory");
+        e = eap::allow_dynamic_lds(zpconv_bwd_t_kernel<true>, shmem, "inter_zpconv_backward shared memory");
         if (e) return e;
-        e = eap::hip_fail(hipFuncSetAttribute((const void *)zpconv_bwd_t_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                          "inter_zpconv_backward shared memory");
+        e = eap::allow_dynamic_lds(zpconv_bwd_t_kernel<false>, shmem, "inter_zpconv_backward shared memory");
         if (e) return e;
         const long long total = (long long)b * np * (na >> 2);
         const int upw = 4;

@@ -34,13 +34,10 @@
 // A cloud whose referenced rows do not fit, whose lists repeat a row, or whose 5-D index is not one list per point is
 // reported in `status` and left to csrc/zpconv_bwd.hip.
 #include "common.h"
+#include "device_prims.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int AQ = 4;                         // anchors per workgroup = waves
 constexpr int CH = 32;                        // channels per workgroup = MFMA N
@@ -61,11 +58,6 @@ constexpr int RCAP = (LDS_BYTES - STAGE_G - STAGE_S) / ROWB - 1;      // referen
 #else
 #define ABL(bit) false
 #endif
-
-template <typename V>
-__device__ __forceinline__ V ld_off(const float *ubase, unsigned voff) {
-    return *reinterpret_cast<const V *>(reinterpret_cast<const char *>(ubase) + voff);
-}
 
 // One workgroup per cloud: the cloud's referenced support rows from its per-point lists idx0[b, p, :] -- a bit per row in LDS
 // (read before the atomic: after the first few hundred entries every bit is set), then ranks by a scan over the words:
@@ -414,8 +406,7 @@ extern "C" int eap_inter_zpconv_bwd_hot_f32(int b, int np, int nq, int na, int k
     // rows nobody references receive no gradient (clouds left to the other path are zeroed again there)
     e = eap::hip_fail(hipMemsetAsync(gfeats, 0, sizeof(float) * (size_t)b * c * nq * na, s), "inter_zpconv_backward (on-chip rows) memset");
     if (e) return e;
-    e = eap::hip_fail(hipFuncSetAttribute((const void *)zp_hot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES),
-                      "inter_zpconv_backward (on-chip rows) shared memory");
+    e = eap::allow_dynamic_lds(zp_hot_kernel, LDS_BYTES, "inter_zpconv_backward (on-chip rows) shared memory");
     if (e) return e;
     // The comparison of every other (a,k) row with the first -- the op's 12 GB index read -- streams on the side stream BESIDE
     // the matrix kernel (forked here: behind the short kernels above, which its 32768 workgroups would starve of wave slots;

@@ -22,14 +22,12 @@
 // Flagged clouds (an arbitrary 5-D index) are served by csrc/zpconv_rows.hip, which skips the others: no host
 // round trip decides anything.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 #include <utility>
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CT = 256;
 
@@ -84,23 +82,6 @@ constexpr int NSTD = 8;       // DMA instructions per thread and stage: NBK * CB
 constexpr int PITCH = 32;     // floats per LDS row (8 pieces)
 constexpr int RPB = 8;        // consecutive points per workgroup
 constexpr unsigned BUF_BYTES = NBK * CB * PITCH * 4;      // 64 KB
-
-__device__ inline unsigned lds_addr(const void *ptr) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ptr;
-}
-// wave-wide 16-byte-per-lane global -> LDS DMA (wave-uniform 64-bit base in SGPRs + a 32-bit byte offset per
-// lane), invisible to hipcc's waitcnt bookkeeping on purpose: the stage's vmcnt(0) before its barrier covers it
-__device__ inline void glds16s(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds4(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 struct WSet { f32x4 a0l, a0h, a1l, a1h, a2l, a2h, a3l, a3h; };    // [anchor][half of the lane's 8 neighbours]
 template <int AI, int H>
@@ -397,8 +378,7 @@ int inter_zpconv_mfma_fwd(int b, int np, int nq, int na, int ks, int nn, int c, 
                           const float *feats, const int32_t *skip, float *out, hipStream_t s) {
     const int AG = na > 32 ? 2 : 1, gsz = AG == 1 ? na : ((na / 2 + 3) & ~3);
     const size_t shmem = 2 * (size_t)BUF_BYTES + 4 * 3 * SBK;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)zpconv_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                          "inter_zpconv_forward (matrix path) shared memory");
+    int e = eap::allow_dynamic_lds(zpconv_mfma_kernel, shmem, "inter_zpconv_forward (matrix path) shared memory");
     if (e) return e;
     const int ny = (c + CB - 1) / CB;
     const long long units = (long long)((np + RPB - 1) / RPB) * AG * b, blocks = 8 * ((units + 7) / 8) * ny;

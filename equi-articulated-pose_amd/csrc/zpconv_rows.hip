@@ -34,6 +34,7 @@
 // workgroups per CU or with dedicated loader waves (row re-reads double: MALL-bound), and
 // half-neighbour tiles with 4 loader + 8 compute waves persistent over 4 points (same speed).
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -229,8 +230,7 @@ int inter_zpconv_rows_fwd(int b, int np, int nq, int na, int ks, int nn, int c, 
                           const float *feats, float *out, const int32_t *only_flagged, hipStream_t s) {
     const int nkt = (ks + KT - 1) / KT;
     const size_t shmem = sizeof(float) * KT * (size_t)nn * w_pitch(na) + 4 * (size_t)nn;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)inter_zpconv_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                          "inter_zpconv_forward shared memory");
+    int e = eap::allow_dynamic_lds(inter_zpconv_rows_kernel, shmem, "inter_zpconv_forward shared memory");
     if (e) return e;
     dim3 grid(np * nkt, (c + NWV * CT - 1) / (NWV * CT), b);
     hipLaunchKernelGGL(inter_zpconv_rows_kernel, grid, dim3(TM), shmem, s, np, nq, na, ks, nn, c, nkt, idx, w, feats, only_flagged, out);

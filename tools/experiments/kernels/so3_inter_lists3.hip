@@ -23,14 +23,10 @@
 // a stage: [16 entries][64 channel rows][4 slots of 16 bytes] (64 KB, two stages), the slot of piece w of row r is
 // (w + (r >> 2)) & 3 as in so3_inter_lists2.hip; a wave reads its two anchors as 8 bytes.  One workgroup per CU.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int CT = 2;         // channel tiles (MFMA M tiles) per wave
 constexpr int CB = 32 * CT;   // channels per block
@@ -44,26 +40,6 @@ constexpr int PITCH = 4 * SL; // floats per LDS row
 constexpr int NSTD = NBK * CB * SL / TM;   // DMA instructions per thread and stage (8): instruction u carries entries 2u, 2u+1
 constexpr unsigned BUF_BYTES = NBK * CB * PITCH * 4;      // 64 KB
 static_assert(2 * CB * SL == TM, "one DMA instruction per entry pair: thread t <-> (entry parity t >> 8, row (t >> 2) & 63, slot t & 3)");
-
-__device__ inline unsigned lds_addr(const void *ptr) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ptr;
-}
-__device__ inline void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds16s(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds4(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 __device__ __forceinline__ unsigned pk_bf16(float a, float b) {          // [15:0] = bf16(a), [31:16] = bf16(b), round to nearest even
     unsigned r;
@@ -352,7 +328,7 @@ int launch3(int layout, int b, int C, int PF, int na, int fpitch, int ks, int R,
     if (((long long)ks * R * na * 4 + 64ll * R * na + 64) * 4 >= (1ll << 31) || (long long)CB * ks * 4 >= (1ll << 31))
         return eap::bad_arg("so3_group_lists3: output rows too far apart for 32-bit store offsets");
     auto kern = layout == 2 ? so3_group_lists3_kernel<LISTS, LISTS ? 0 : 2> : so3_group_lists3_kernel<LISTS, 0>;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SHMEM), what);
+    int e = eap::allow_dynamic_lds(kern, SHMEM, what);
     if (e) return e;
     const int AG = (na + GSZ - 1) / GSZ;
     const int RPB = LISTS ? 1 : ((nn % NBK) == 0 ? 8 : 1);

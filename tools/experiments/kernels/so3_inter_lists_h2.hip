@@ -13,15 +13,10 @@
 // splits): workgroup = 8 waves = (row run, 64 channels, 16 anchors); wave = 2 anchors x 2 channel tiles; K = 16 entries per
 // MFMA; LDS image of a stage [16 entries][64 channel rows][4 slots of 16 bytes] (64 KB, two stages); one workgroup per CU.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CT = 2;         // channel tiles (MFMA M tiles) per wave
 constexpr int CB = 32 * CT;   // channels per block
@@ -36,39 +31,11 @@ constexpr int NSTD = NBK * CB * SL / TM;   // DMA instructions per thread and st
 constexpr unsigned BUF_BYTES = NBK * CB * PITCH * 4;      // 64 KB
 static_assert(2 * CB * SL == TM, "one DMA instruction per entry pair: thread t <-> (entry parity t >> 8, row (t >> 2) & 63, slot t & 3)");
 
-__device__ inline unsigned lds_addr(const void *ptr) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ptr;
-}
-__device__ inline void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds16s(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds4(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 __device__ __forceinline__ void split_pair_h(float x0, float x1, unsigned &h, unsigned &l) {      // round to nearest, both planes
     const f16x2 hh = __builtin_convertvector((f32x2){x0, x1}, f16x2);
     const f16x2 ll = __builtin_convertvector((f32x2){x0 - (float)hh.x, x1 - (float)hh.y}, f16x2);
     h = __builtin_bit_cast(unsigned, hh);
     l = __builtin_bit_cast(unsigned, ll);
-}
-// 2^(14 - e) for v in [2^e, 2^(e+1)); 1 for 0, inf, nan (as csrc/gemm_bf16x3.hip)
-__device__ __forceinline__ float pow2_scale(float v) {
-    const unsigned b = __float_as_uint(v) & 0x7fffffffu;
-    const int e = (int)(b >> 23) - 127;
-    if (b == 0u || e == 128) return 1.0f;
-    const int se = max(-120, min(120, 14 - max(e, -126)));
-    return __uint_as_float((unsigned)(se + 127) << 23);
 }
 constexpr float W_SCALE = 8192.0f;        // weights in [0, 1] -> [0, 2^13]
 struct Planes { u32x4 h, l; };            // 8 values along K as two planes of 8 fp16
@@ -349,7 +316,7 @@ int launch_h(int layout, int b, int C, int PF, int na, int fpitch, int ks, int R
     if (((long long)ks * R * na * 4 + 64ll * R * na + 64) * 4 >= (1ll << 31) || (long long)CB * ks * 4 >= (1ll << 31))
         return eap::bad_arg("so3_group_lists_h2: output rows too far apart for 32-bit store offsets");
     auto kern = layout == 2 ? so3_group_listsh_kernel<LISTS, LISTS ? 0 : 2> : so3_group_listsh_kernel<LISTS, 0>;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SHMEM), what);
+    int e = eap::allow_dynamic_lds(kern, SHMEM, what);
     if (e) return e;
     // the operand's largest magnitude per channel row (stream-ordered scratch, released after the launch)
     void *row_abs = nullptr;

@@ -35,12 +35,11 @@
 // A cloud that references more rows than fit is left to csrc/zpconv_mfma.hip (decided on the device: `mat_skip`), one whose
 // 5-D index is not one list per point is recomputed by csrc/zpconv_rows.hip as before.
 #include "common.h"
+#include "device_prims.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int AQ = 4;                         // anchors per workgroup
@@ -59,11 +58,6 @@ constexpr int RCAP = LDS_BYTES / ROWB;        // referenced rows a cloud may hav
 #else
 #define ABL(bit) false
 #endif
-
-template <typename V>
-__device__ __forceinline__ V ld_off(const void *ubase, unsigned voff) {
-    return *reinterpret_cast<const V *>(reinterpret_cast<const char *>(ubase) + voff);
-}
 
 // marks[b, q] = 1 when a list of the cloud names support row q (out-of-range indices clamped as csrc/zpconv_mfma.hip clamps them)
 __global__ __launch_bounds__(256) void zpf_mark_kernel(long long n, int per_cloud, int nq, const int32_t *__restrict__ idx0,
@@ -390,8 +384,7 @@ extern "C" int eap_inter_zpconv_fwd_hot_f32(int b, int np, int nq, int na, int k
     const int dbg = 0;
 #endif
     auto launch = [&](auto kernel) -> int {
-        int er = eap::hip_fail(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES),
-                               "inter_zpconv_forward (on-chip rows) shared memory");
+        int er = eap::allow_dynamic_lds(kernel, LDS_BYTES, "inter_zpconv_forward (on-chip rows) shared memory");
         if (er) return er;
         hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(TM), LDS_BYTES, s, b, L.S, np, nq, na, ks, c, src, w, slot16, rows, n_rows,
                            hot_skip, dst, dbg);

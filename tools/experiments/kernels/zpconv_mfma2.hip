@@ -24,14 +24,12 @@
 // workgroups of 16 anchors, TWO per CU so that one's row end overlaps the other's matrix work -- was bit-identical and
 // slower still (11.1 ms, 36.4 GB fetched + 15.7 GB written in 64-byte pieces, matrix pipe 0.32): not kept.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 #include <utility>
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CB = 64;        // channels per workgroup: two MFMA M tiles sharing one stream of weights
 constexpr int NBK = 8;        // entries per LDS stage (4 MFMA k-steps)
@@ -44,21 +42,6 @@ constexpr int NSTD = 8;       // DMA instructions per thread and stage: NBK * CB
 constexpr int PITCH = 32;     // floats per LDS row (8 pieces)
 constexpr int RPB = 8;        // consecutive points per workgroup
 constexpr unsigned BUF_BYTES = NBK * CB * PITCH * 4;      // 64 KB
-
-__device__ inline unsigned lds_addr(const void *ptr) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)ptr;
-}
-__device__ inline void glds16s(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ inline void glds4(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ inline void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // one weight block of a wave: [anchor of the pair][quarter of the lane's 16 neighbours]
 struct WSet { f32x4 a0q0, a0q1, a0q2, a0q3, a1q0, a1q1, a1q2, a1q3; };
@@ -341,11 +324,9 @@ int inter_zpconv_mfma2_fwd(int b, int np, int nq, int na, int ks, int nn, int c,
                            const float *feats, const int32_t *skip, float *out, hipStream_t s) {
     const int AG = na > 32 ? 2 : 1, gsz = AG == 1 ? na : ((na / 2 + 3) & ~3);
     const size_t shmem = 2 * (size_t)BUF_BYTES + 4 * 2 * NNMAX;
-    int e = eap::hip_fail(hipFuncSetAttribute((const void *)zpconv_mfma2_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                          "inter_zpconv_forward (matrix path 2) shared memory");
+    int e = eap::allow_dynamic_lds(zpconv_mfma2_kernel<2>, shmem, "inter_zpconv_forward (matrix path 2) shared memory");
     if (e) return e;
-    e = eap::hip_fail(hipFuncSetAttribute((const void *)zpconv_mfma2_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem),
-                      "inter_zpconv_forward (matrix path 2) shared memory");
+    e = eap::allow_dynamic_lds(zpconv_mfma2_kernel<4>, shmem, "inter_zpconv_forward (matrix path 2) shared memory");
     if (e) return e;
     const int ny = (c + CB - 1) / CB;
     const long long units = (long long)((np + RPB - 1) / RPB) * AG * b, blocks = 8 * ((units + 7) / 8) * ny;
