@@ -289,6 +289,53 @@ def so3_anchor_perm(gx, mult):
     return perm
 
 
+lib.eap_so3_inter_group_bwd_map_workspace.restype = ctypes.c_int64
+
+
+def so3_anchor_map(idx, q_pose, s_pose, anchors):
+    """The per-entry anchor index of an anchor set that is not a group (csrc/so3_anchor_map.hip; so3conv/functional.py:L1199-1204):
+    idx int32 [b,p,nn], q_pose [b,p,4,4], s_pose [b,n,4,4], anchors [na,3,3] -> (amap uint8 [b,p,nn,na], nontrivial int32 [b])."""
+    check_input(idx, q_pose, s_pose, anchors)
+    b, p, nn = idx.shape
+    na = anchors.shape[0]
+    if tuple(q_pose.shape) != (b, p, 4, 4) or s_pose.shape[0] != b or tuple(s_pose.shape[2:]) != (4, 4):
+        raise RuntimeError('so3_anchor_map: poses must be [b,p,4,4] (query) and [b,n,4,4] (support)')
+    amap = torch.empty(b, p, nn, na, dtype=torch.uint8, device=idx.device)
+    nontrivial = torch.empty(b, dtype=torch.int32, device=idx.device)
+    call('eap_so3_anchor_map_f32', amap, b, p, s_pose.shape[1], nn, na, _ptr(idx), _ptr(q_pose), _ptr(s_pose), _ptr(anchors), _ptr(amap),
+         _ptr(nontrivial))
+    return amap, nontrivial
+
+
+def _check_map(amap, idx, na):
+    if amap.dtype != torch.uint8 or tuple(amap.shape) != tuple(idx.shape) + (na,) or not amap.is_contiguous():
+        raise RuntimeError('anchor map: contiguous uint8 [b,p,nn,na] expected')
+
+
+def so3_inter_group_fwd_map(feats, idx, gx, rk, amap, sigma):
+    """-> X [b,c,ks,p,na] (reference layout), the gather through the per-entry anchor map (csrc/so3_inter_map.hip)"""
+    b, c, n, na = feats.shape
+    p, nn = idx.shape[1], idx.shape[2]
+    ks = rk.shape[1]
+    _check_map(amap, idx, na)
+    out = torch.empty(b, c, ks, p, na, dtype=torch.float32, device=feats.device)
+    call('eap_so3_inter_group_fwd_map_f32', out, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(feats), _ptr(idx), _ptr(gx), _ptr(rk), _ptr(amap),
+         _ptr(out), tag={'flops': 2.0 * b * c * ks * p * nn * na, 'shape': ('group_fwd_map', b, c, p, nn, na, ks)})
+    return out
+
+
+def so3_inter_group_bwd_map(gout, idx, gx, rk, amap, sigma, n):
+    """gout [b,c,ks,p,na] -> gfeats [b,c,n,na] through the per-entry anchor map; no float atomics (csrc/so3_inter_map.hip)"""
+    b, c, ks, p, na = gout.shape
+    nn = idx.shape[2]
+    _check_map(amap, idx, na)
+    gfeats = torch.empty(b, c, n, na, dtype=torch.float32, device=gout.device)
+    ws = torch.empty(max(1, int(lib.eap_so3_inter_group_bwd_map_workspace(b, c, p, n, na))), dtype=torch.float32, device=gout.device)
+    call('eap_so3_inter_group_bwd_map_f32', gfeats, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(gout), _ptr(idx), _ptr(gx), _ptr(rk), _ptr(amap),
+         _ptr(gfeats), _ptr(ws))
+    return gfeats
+
+
 def so3_inter_group_fwd_can_block(c, n, na, ks, has_mult, has_flag):
     return bool(lib.eap_so3_inter_group_fwd_can_block(c, n, na, ks, int(has_mult), int(has_flag)))
 

@@ -330,21 +330,27 @@ class _InterGroup(torch.autograd.Function):
     """new_feats[b,c,k,p,a] = sum_n feats[b,c,idx_n,perm_n(a)] w(p,a,k,n)  (functional.py:L1221-1261)."""
 
     @staticmethod
-    def forward(ctx, feats, idx, gx, rk, mult, sigma, ident=0, nonident=None):
+    def forward(ctx, feats, idx, gx, rk, mult, sigma, ident=0, nonident=None, amap=None):
+        # (amap: the per-entry anchor map of a set that is not a group, see _anchor_map -- perm_n(a) = amap[b,p,n,a], no table)
         feats = feats.contiguous()
         ctx.ident = ident
-        ctx.save_for_backward(idx, gx, rk, mult if mult is not None else torch.empty(0))
+        ctx.save_for_backward(idx, gx, rk, mult if mult is not None else torch.empty(0), amap)
         ctx.has_mult = mult is not None
         ctx.sigma = sigma
         ctx.n = feats.shape[2]
+        if amap is not None:
+            return _hip.so3_inter_group_fwd_map(feats, idx, gx, rk, amap, sigma)
         return _hip.so3_inter_group_fwd(feats, idx, gx, rk, mult, sigma, nonident)
 
     @staticmethod
     def backward(ctx, gout):
-        idx, gx, rk, mult = ctx.saved_tensors
-        g = _hip.so3_inter_group_bwd(gout.contiguous(), idx, gx, rk, mult if ctx.has_mult else None,
-                                     ctx.sigma, ctx.n, ctx.ident)
-        return g, None, None, None, None, None, None, None
+        idx, gx, rk, mult, amap = ctx.saved_tensors
+        if amap is not None:
+            g = _hip.so3_inter_group_bwd_map(gout.contiguous(), idx, gx, rk, amap, ctx.sigma, ctx.n)
+        else:
+            g = _hip.so3_inter_group_bwd(gout.contiguous(), idx, gx, rk, mult if ctx.has_mult else None,
+                                         ctx.sigma, ctx.n, ctx.ident)
+        return g, None, None, None, None, None, None, None, None
 
 
 class _IntraGroup(torch.autograd.Function):
@@ -879,8 +885,10 @@ def _dense_forward(feats, W, rows, geo, p):
 class _InterConvArgs:
     """The inputs of _InterConv that carry no gradient, as one record, made where the conv is called."""
 
-    def __init__(self, idx, gx, rk, mult, sigma, ident, nonident=None, anchors=None, epilogue=None, geometry=None):
+    def __init__(self, idx, gx, rk, mult, sigma, ident, nonident=None, anchors=None, epilogue=None, geometry=None, amap=None):
         self.idx, self.gx, self.rk, self.mult, self.sigma, self.ident, self.nonident = idx, gx, rk, mult, float(sigma), ident, nonident
+        # amap uint8 [b,p,nn,na]: the per-entry anchor map of an anchor set that is not a group (_anchor_map) -- the 'anchor map' regime
+        self.amap = amap
         self.anchors = anchors.detach().contiguous() if (anchors is not None and mult is not None) else None   # the rotations `mult` was built from
         # epilogue: a FoldedEpilogue or a TrainEpilogue;
         # geometry = (q_xyz, xyz, q_rot, rot): what the dense product over the referenced rows is built from (csrc/so3_dense.hip)
@@ -990,6 +998,24 @@ def _forward_lists(feats, W, args, layout, keep, folded, head, fill):
                                      None if nonident is None else nonident[b0:b1], blocked=layout, coset=coset, store_order=tp)   # [b,c,k,p,a] (nominal shape)
         _contract_into(Wc, x, y[b0:b1].view(b1 - b0, o, p * na), layout, folded, b0,
                        x_bound=None if x_bound is None else (x_bound[b0:b1], na, 1.0))
+        x = x if keep else None
+    return y, x
+
+
+def _forward_map(feats, W, args, keep, folded):
+    """The forward of the 'anchor map' regime (anchor sets that are not a group, really permuted): grouping through the per-entry map
+    (csrc/so3_inter_map.hip) into the reference layout, then the contraction -> (y [b,o,p,a], x): x = the intermediate when it is kept for
+    the backward's dW = dY X^T (keep), else None -- X_CHUNK_CLOUDS clouds at a time then."""
+    idx, gx, rk, amap = args.idx, args.gx, args.rk, args.amap
+    b, na = feats.shape[0], feats.shape[3]
+    p, o = idx.shape[1], W.shape[0]
+    y = torch.empty(b, o, p, na, dtype=torch.float32, device=feats.device)
+    step = max(1, b if keep else X_CHUNK_CLOUDS)
+    x = None
+    for b0 in range(0, b, step):
+        b1 = min(b, b0 + step)
+        x = _hip.so3_inter_group_fwd_map(feats[b0:b1], idx[b0:b1], gx[b0:b1], rk, amap[b0:b1], args.sigma)      # [b,c,k,p,a]
+        _contract_into(W, x, y[b0:b1].view(b1 - b0, o, p * na), 0, folded, b0)
         x = x if keep else None
     return y, x
 
@@ -1179,6 +1205,28 @@ def _backward_textbook(gy, W, feats, x, idx, gx, rk, mult, nonident, args, layou
     return gF, gW
 
 
+def _backward_map(gy, W, feats, x, args, need_f, need_w):
+    """The backward of the 'anchor map' regime: the textbook dW = dY X^T and dX = W^T dY on the GEMMs of _backward_textbook, then the
+    transposed grouping through the map (csrc/so3_inter_map.hip: many-to-one in the support row AND the anchor, accumulated without
+    float atomics) -> (gF, gW)"""
+    b, c, n, na = feats.shape
+    idx, gx, rk, amap = args.idx, args.gx, args.rk, args.amap
+    p, ks = idx.shape[1], rk.shape[1]
+    o, ck, pa = W.shape[0], c * ks, p * na
+    gF = gW = None
+    if need_w:
+        if x is None:
+            x = _hip.so3_inter_group_fwd_map(feats, idx, gx, rk, amap, args.sigma)
+        gW = torch.empty_like(W)          # sum_b gy_b x_b^T
+        _hip.gemm_reduce(0, 1, o, ck, pa, gy, pa, o * pa, x, pa, ck * pa, gW, ck, b)
+    if need_f:
+        gx_ = torch.empty(b, ck, pa, dtype=torch.float32, device=gy.device)      # W^T gy
+        Wt = W.t().contiguous()
+        _hip.gemm(0, 0, ck, pa, o, Wt, o, 0, gy.view(b, o, pa), pa, o * pa, gx_, pa, ck * pa, b)
+        gF = _hip.so3_inter_group_bwd_map(gx_.view(b, c, ks, p, na), idx, gx, rk, amap, args.sigma, n)
+    return gF, gW
+
+
 class _InterConv(torch.autograd.Function):
     """Fused inter conv  y = W . group(feats)  (functional.py:L1221-1261 + modules.py:L48-55)
     with the re-associated feature gradient (csrc/so3_inter_inv.hip).  forward and backward decide the regime and dispatch to the
@@ -1206,6 +1254,15 @@ class _InterConv(torch.autograd.Function):
         folded = None if train_ep is not None else args.epilogue      # (the list kernels know nothing of a TrainEpilogue: `applied` stays False there)
         if folded is not None and (needs_grad or not folded.inference):
             raise RuntimeError('a folded epilogue is an inference-time fusion: build and use it under torch.no_grad()')
+        if args.amap is not None:
+            # an anchor set that is not a group, really permuted: the per-entry map has no inverse-list or dense form
+            if FORWARD_LOG is not None:
+                FORWARD_LOG.append({'channels': (c, o), 'dense': False, 'parts': None, 'regime': 'anchor map'})
+            y, x = _forward_map(feats, W, args, needs_grad and ctx.needs_input_grad[1], folded)
+            ctx.bn, ctx.conv_args, ctx.head, ctx.layout, ctx.plan = None, args, None, 0, None
+            ctx.W_param = weakref.ref(W_param)
+            ctx.save_for_backward(W, x, idx, args.gx, rk, None, nonident, feats, None)
+            return y
         lists_ok = BACKWARD_MODE != 'dx' and _inv_lists_supported(idx, n, na, ks)
         keep = needs_grad and (not lists_ok or _keep_x_hint(W_param))
         plan = _DensePlan(args, n, o, lists_ok, needs_grad, keep, folded)
@@ -1238,7 +1295,11 @@ class _InterConv(torch.autograd.Function):
         n = feats.shape[2]
         need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         g_bn_w = g_bn_b = None
-        if plan is not None and plan.parts is not None:
+        if args.amap is not None:
+            if BACKWARD_LOG is not None:
+                BACKWARD_LOG.append({'channels': (feats.shape[1], W.shape[0]), 'support_rows': n, 'referenced_rows_max': 0, 'regime': 'anchor map'})
+            gF, gW = _backward_map(gy, W, feats, x, args, need_f, need_w)
+        elif plan is not None and plan.parts is not None:
             gF, gW = _backward_dense_parts(gy, W, feats, head, plan.geo(), need_f, need_w)
         elif plan is not None:
             gF, gW, g_bn_w, g_bn_b = _backward_dense(gy, W, feats, head, plan.geo(), ctx.bn, yact, need_f, need_w)
@@ -1387,13 +1448,26 @@ def _check_inputs(xyz, feats, W=None, on_device=True):
         raise RuntimeError('so3conv: feats must be a device tensor' if W is None else 'so3conv: feats and W must be device tensors')
 
 
-def _permutation_tables(anchors):
-    """(mult, ident) of _group_tables for a conv that permutes the anchor axis by the relative rotations"""
+def _anchor_map(idx, q_rot, rot, anchors):
+    """The anchor index of a conv that permutes by poses over an anchor set that is NOT a group (kanchor 20 / 40: subsets of the
+    icosahedral rotations, L2641-2649).  There the reference's argmax_j tr(R_rel^T A_a A_j^T) (L1199-1204) depends on the actual R_rel --
+    no [na,na] table stands for it -- and it is no permutation, so it is searched per entry (csrc/so3_anchor_map.hip).
+    -> amap uint8 [b,p,nn,na], or None when every entry of the batch maps every anchor onto itself (identity poses, one rotation per
+    cloud): the conv then runs exactly as without permutation.  One host read."""
+    na = anchors.shape[0]
+    if na % 4 != 0 or na > 64:
+        raise NotImplementedError('anchor permutation with per-point poses over an anchor set that is not a group: a multiple of 4 anchors, at most 64')
+    amap, nontrivial = _hip.so3_anchor_map(idx, q_rot, rot, anchors.contiguous())
+    return amap if int(nontrivial.max()) != 0 else None
+
+
+def _permutation_tables(anchors, idx, q_rot, rot):
+    """What a conv that permutes the anchor axis by the relative rotations of (q_rot, rot) over the lists idx needs: (mult, ident, None)
+    of _group_tables for a closed anchor set, (None, 0, amap) of _anchor_map otherwise"""
     mult, ident = _group_tables(anchors)
     if mult is None:
-        raise NotImplementedError(
-            'anchor permutation with per-point poses needs a closed anchor set (kanchor 60 or 1)')
-    return mult, ident
+        return None, 0, _anchor_map(idx, q_rot, rot, anchors)
+    return mult, ident, None
 
 
 def _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose, epilogue=None):
@@ -1402,7 +1476,7 @@ def _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permu
     q_xyz = xyz if q_xyz is None else q_xyz
     ball_idx = cuda_nn.ball_query(q_xyz, xyz, radius, n_neighbor)
     rk = rotated_kernels(anchors, kernels)
-    mult, ident = None, 0
+    mult, ident, amap = None, 0, None
     rot = q_rot = None
     if pose is not None:
         rot = pose.contiguous()
@@ -1410,15 +1484,16 @@ def _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permu
         if rot.shape[-2:] != (4, 4) or rot.dtype != torch.float32:
             raise RuntimeError('so3conv: pose must be float32 [b,p,4,4]')
         if permute:
-            mult, ident = _permutation_tables(anchors)
+            mult, ident, amap = _permutation_tables(anchors, ball_idx, q_rot, rot)
     gx, nonident = _hip.so3_prep(q_xyz, xyz, ball_idx, q_rot, rot, anchors.contiguous(), ident)
-    return _InterConvArgs(ball_idx, gx, rk, mult, sigma, ident, nonident, anchors, epilogue, (q_xyz.contiguous(), xyz.contiguous(), q_rot, rot))
+    return _InterConvArgs(ball_idx, gx, rk, mult, sigma, ident, nonident, anchors, epilogue, (q_xyz.contiguous(), xyz.contiguous(), q_rot, rot),
+                          amap=amap)
 
 
 def _inter_group(xyz, pose, feats, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz=None, q_pose=None):
     _check_inputs(xyz, feats)
     a = _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose)
-    new_feats = _InterGroup.apply(feats, a.idx, a.gx, a.rk, a.mult, a.sigma, a.ident, a.nonident)
+    new_feats = _InterGroup.apply(feats, a.idx, a.gx, a.rk, a.mult, a.sigma, a.ident, a.nonident, a.amap)
     inter_w = InterWeights(a.gx, a.rk, sigma)
     return a.idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), new_feats
 
@@ -1459,17 +1534,19 @@ def inter_so3conv_fused_art_mode(xyz, pose, feats, W, seg_labels, n_neighbor, an
     ball_idx = idx_all.view(b, ns, p, nn).gather(1, pick.expand(b, 1, p, nn)).squeeze(1).contiguous()
     gx = gx_all.view(b, ns, p, nn, 4).gather(1, pick.unsqueeze(-1).expand(b, 1, p, nn, 4)).squeeze(1).contiguous()
     rk = rotated_kernels(anchors, kernels)
-    mult = nonident = None
+    mult = nonident = amap = None
     ident = 0
     if pose is not None and permute:
         rot = pose.contiguous()
-        mult, ident = _permutation_tables(anchors)
+        if rot.shape[-2:] != (4, 4) or rot.dtype != torch.float32:
+            raise RuntimeError('so3conv: pose must be float32 [b,p,4,4]')
+        mult, ident, amap = _permutation_tables(anchors, ball_idx, rot, rot)
         # the nearest anchor of every pair's relative rotation (4th word of gx) and the per-cloud "not all identity" flag; the
         # rotated offsets this call also produces are not used in this mode
         first = xyz[:, 0].contiguous()
         g_rot, nonident = _hip.so3_prep(first, first, ball_idx, rot, rot, anchors.contiguous(), ident)
         gx = torch.cat([gx[..., :3], g_rot[..., 3:]], dim=-1).contiguous()
-    y = _InterConv.apply(feats, W, None, None, _InterConvArgs(ball_idx, gx, rk, mult, sigma, ident, nonident, anchors))
+    y = _InterConv.apply(feats, W, None, None, _InterConvArgs(ball_idx, gx, rk, mult, sigma, ident, nonident, anchors, amap=amap))
     inter_w = InterWeights(gx, rk, sigma)
     return (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), y
 
@@ -1662,5 +1739,7 @@ def anchor_permutation_index(xyz, pose, n_neighbor, anchors, radius):
     """The reference's rotated_anchor_idx int64 [b,p,nn,na] (functional.py:L1199-1204); test hook."""
     ball_idx = cuda_nn.ball_query(xyz, xyz, radius, n_neighbor)
     mult, ident = _group_tables(anchors)
+    if mult is None:          # not a group: the per-entry search (csrc/so3_anchor_map.hip)
+        return _hip.so3_anchor_map(ball_idx, pose.contiguous(), pose.contiguous(), anchors.contiguous())[0].long()
     gx, _ = _hip.so3_prep(xyz, xyz, ball_idx, pose.contiguous(), pose.contiguous(), anchors.contiguous(), ident)
     return _hip.so3_anchor_perm(gx, mult)

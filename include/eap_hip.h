@@ -201,6 +201,35 @@ int eap_so3_inter_group_bwd_slab_f32(int b, int c, int p, int n, int nn, int na,
                                      const float *rk, const uint8_t *mult, int identity_anchor,
                                      float *gfeats, float *workspace, eap_stream_t stream);
 
+/* ---- anchor sets that are not a group (the 20- / 40-anchor subsets, so3conv/functional.py:L2641-2649) ---- */
+
+/* so3_anchor_map: the anchor index of so3conv/functional.py:L1199-1204 searched per entry -- on a subset of the group the
+ * arg-max depends on the actual R_rel and is no permutation, so no [na,na] table can stand for it.
+ * idx int32 [b,p,nn], q_pose [b,p,4,4], s_pose [b,n,4,4] (the same tensor unless the conv is strided), anchors [na,3,3],
+ * na % 4 == 0, na <= 64
+ *  -> amap uint8 [b,p,nn,na] = argmax_j <R_rel^T A_a, A_j>_F with R_rel = R_p R_idx^T (the lowest j wins a tie);
+ *     nontrivial int32 [b] = 1 for clouds where some entry's map is not the identity map (zeroed by the call). */
+int eap_so3_anchor_map_f32(int b, int p, int n, int nn, int na, const int32_t *idx, const float *q_pose,
+                           const float *s_pose, const float *anchors, uint8_t *amap, int32_t *nontrivial,
+                           eap_stream_t stream);
+
+/* so3_inter_group_fwd_map: so3conv/functional.py:L1221-1261 with the gather through the map,
+ * out[b,c,k,p,a] = sum_n w(p,a,k,n) feats[b,c,idx_n,amap[b,p,n,a]]  (reference layout [b,c,ks,p,na]; weights from gx and
+ * rk as eap_so3_inter_group_fwd_f32; na % 4 == 0, na <= 64, ks <= 32). */
+int eap_so3_inter_group_fwd_map_f32(int b, int c, int p, int n, int nn, int na, int ks, float sigma,
+                                    const float *feats, const int32_t *idx, const float *gx, const float *rk,
+                                    const uint8_t *amap, float *out, eap_stream_t stream);
+
+/* so3_inter_group_bwd_map: the transpose of the above w.r.t. feats (autograd of so3conv/functional.py:L1221-1261),
+ * gfeats[b,c,q,a'] = sum_{(p,n): idx = q} sum_{a: amap(a) = a'} sum_k w(p,a,k,n) gout[b,c,k,p,a].
+ * The map is many-to-one in q and in a: private slabs in `workspace` (eap_so3_inter_group_bwd_map_workspace floats,
+ * zeroed by the call) accumulated in a fixed order and reduced by a second kernel -- no float atomics, bit-identical
+ * run to run, lists that name a row twice included. */
+int64_t eap_so3_inter_group_bwd_map_workspace(int b, int c, int p, int n, int na);
+int eap_so3_inter_group_bwd_map_f32(int b, int c, int p, int n, int nn, int na, int ks, float sigma,
+                                    const float *gout, const int32_t *idx, const float *gx, const float *rk,
+                                    const uint8_t *amap, float *gfeats, float *workspace, eap_stream_t stream);
+
 /* Which entry-list grouping kernel serves eap_so3_inter_group_fwd*_f32 / eap_so3_inter_group_inv*_f32 when no anchor
  * permutation is in play: 2 (default) = the fp32-MFMA kernel with two channel tiles per wave where the channel count fills
  * 64-channel blocks (csrc/so3_inter_lists2.hip), 1 = always the one-tile fp32-MFMA kernel (csrc/so3_inter_lists.hip);
