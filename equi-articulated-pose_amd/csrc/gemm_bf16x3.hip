@@ -35,7 +35,6 @@
 //      table in LDS; a piece = the four taps t0..t0+3 of one channel, four dword loads inside the point's 240-byte row
 #include "common.h"
 #include "device_prims.h"
-#include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
 
@@ -110,15 +109,13 @@ __device__ __forceinline__ void split_quad(const f32x4 &a, const f32x4 &b, u32x4
     l = (u32x4){l0, l1, l2, l3};
 }
 
-// DBG (timing ablations, `make ABLATION=1` + EAP_GEMM_SPLIT_DEBUG, WRONG results): 1 = no global loads inside the k-loop,
-// 2 = no split / park, 4 = no fragment reads, 8 = no barrier
 // WN = waves along N: 2 -> 4 waves (one per SIMD), wave tile 128 x 128, 256 accumulators; 4 -> 8 waves (two per SIMD),
 // wave tile 128 x 64, 128 accumulators -- the second wave of a SIMD issues matrix instructions while the first waits for
 // its LDS fragments or its staged loads
 // MI = row tiles per wave: 4 -> block tile 256 x 256; 2 -> 128 x 256 (wave tile 64 x 64) for row counts that would leave
 // half of a 256-row tile empty (the second layer's contraction: 128 output channels)
 // PL = planes per operand (3: bf16, 2: fp16 after the tensor scales -- see split_pair_h)
-template <int MI, int WN, int DBG, int BMODE, bool APRE, int PL>
+template <int MI, int WN, int BMODE, bool APRE, int PL>
 __device__ __forceinline__ void split_gemm_body(const Args &g) {
     constexpr unsigned OPER_BYTES = oper_bytes(PL), STAGE_BYTES = stage_bytes(PL);
     constexpr int NT = 128 * WN, NI = 8 / WN, WM = 8 / WN, BM = 32 * MI * WM, RG = NT / 4;   // threads, column tiles per wave, waves along M, rows per block, rows per staging group
@@ -294,11 +291,6 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
     const unsigned rdB = OPER_BYTES + (unsigned)(32 * NI * wn + li) * 32u + rd_half;
     auto frag = [&](const unsigned char *st, unsigned base, int p, auto &f) __attribute__((always_inline)) {
         constexpr int NF = sizeof(f) / sizeof(u32x4);
-        if constexpr (DBG & 4) {
-#pragma unroll
-            for (int i = 0; i < NF; ++i) f[i] = (u32x4){0x3f803f80u + (unsigned)p, 0x3f803f80u, 0x3f803f80u + base, 0x3f803f80u};
-            return;
-        }
 #pragma unroll
         for (int i = 0; i < NF; ++i) f[i] = *reinterpret_cast<const u32x4 *>(st + base + p * PLANE_BYTES + i * 32 * 32);
     };
@@ -338,21 +330,21 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
             frag(st, rdB, 0, bh);
             SB();
             if constexpr (decltype(first)::value) product0(ah, bl); else product(ah, bl);
-            if constexpr (!(DBG & 2)) park_a(s2, sa, wr_off);
+            park_a(s2, sa, wr_off);
             SB();
             frag(st, rdA, 1, al);
             SB();
             product(ah, bh);
-            if constexpr (!(DBG & 2)) park_half(s2 + OPER_BYTES, sb, 0, NPO, wr_offB, sclB[0]);
+            park_half(s2 + OPER_BYTES, sb, 0, NPO, wr_offB, sclB[0]);
             SB();
             frag(s1, rdA, 0, ah);                // the next tile's pair (its stage was certified a tile ago)
             frag(s1, rdB, 1, bl);
             SB();
             product(al, bh);
-            if constexpr (!(DBG & 2)) park_half(s2 + OPER_BYTES, sb, 1, NPO, wr_offB, sclB[1]);
-            if constexpr (!(DBG & 1)) load_tile(min(kt + 4, nk - 1), sa, sb);
+            park_half(s2 + OPER_BYTES, sb, 1, NPO, wr_offB, sclB[1]);
+            load_tile(min(kt + 4, nk - 1), sa, sb);
             SB();
-            if constexpr (!(DBG & 8)) __syncthreads();
+            __syncthreads();
             return;
         }
         u32x4 bm[NI], am[MI], bh[NI], al[MI];
@@ -362,22 +354,22 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
         frag(st, rdB, 1, bm);
         SB();
         if constexpr (decltype(first)::value) product0(ah, bl); else product(ah, bl);
-        if constexpr (!(DBG & 2)) park_half_a(s2, sa, 0, wr_off);
+        park_half_a(s2, sa, 0, wr_off);
         SB();
         frag(st, rdA, 1, am);
         SB();
         product(ah, bm);
-        if constexpr (!(DBG & 2)) park_half_a(s2, sa, 1, wr_off);
+        park_half_a(s2, sa, 1, wr_off);
         SB();
         frag(st, rdB, 0, bh);
         SB();
         product(am, bm);
-        if constexpr (!(DBG & 2)) park_half(s2 + OPER_BYTES, sb, 0, NPO, wr_offB, sclB[0]);
+        park_half(s2 + OPER_BYTES, sb, 0, NPO, wr_offB, sclB[0]);
         SB();
         frag(st, rdA, 2, al);
         SB();
         product(am, bh);
-        if constexpr (!(DBG & 2)) park_half(s2 + OPER_BYTES, sb, 1, NPO, wr_offB, sclB[1]);
+        park_half(s2 + OPER_BYTES, sb, 1, NPO, wr_offB, sclB[1]);
         SB();
         // branch-free on purpose (accumulators that cross a control-flow join get copied): past the last tiles the
         // staged registers are re-split into a stage nobody reads, the loads repeat the last tile, the fragment reads hit
@@ -386,7 +378,7 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
         frag(s1, rdA, 0, ah2);               // the next tile's first two planes (its stage was certified a tile ago)
         SB();
         product(al, bh);
-        if constexpr (!(DBG & 1)) load_tile(min(kt + 4, nk - 1), sa, sb);
+        load_tile(min(kt + 4, nk - 1), sa, sb);
         SB();
         frag(s1, rdB, 2, bl);
         SB();
@@ -395,7 +387,7 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
 #undef SB
 #pragma unroll
         for (int i = 0; i < MI; ++i) ah[i] = ah2[i];
-        if constexpr (!(DBG & 8)) __syncthreads();
+        __syncthreads();
     };
 
     // ---- prologue --------------------------------------------------------------------------------------------------
@@ -451,12 +443,12 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
         }
 }
 
-template <int MI, int WN, int DBG, int BMODE, bool APRE>
-__global__ __launch_bounds__(128 * WN, WN / 2) void gemm_bf16x3_kernel(Args g) { split_gemm_body<MI, WN, DBG, BMODE, APRE, 3>(g); }
+template <int MI, int WN, int BMODE, bool APRE>
+__global__ __launch_bounds__(128 * WN, WN / 2) void gemm_bf16x3_kernel(Args g) { split_gemm_body<MI, WN, BMODE, APRE, 3>(g); }
 
 // two fp16 planes per operand, three products per k-tile (see split_pair_h for what that costs in accuracy)
-template <int MI, int WN, int DBG, int BMODE, bool APRE>
-__global__ __launch_bounds__(128 * WN, WN / 2) void gemm_f16x2_kernel(Args g) { split_gemm_body<MI, WN, DBG, BMODE, APRE, 2>(g); }
+template <int MI, int WN, int BMODE, bool APRE>
+__global__ __launch_bounds__(128 * WN, WN / 2) void gemm_f16x2_kernel(Args g) { split_gemm_body<MI, WN, BMODE, APRE, 2>(g); }
 
 }  // namespace
 
@@ -596,35 +588,14 @@ int launch_split(Args &g, int batch, hipStream_t stream, const char *who) {
         hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, batch), dim3(128 * WAVES_N), shmem, stream, g);
         return 0;
     };
-    auto run = [&](auto dbg_c) {
-        constexpr int D = decltype(dbg_c)::value;
-        if constexpr (PL == 2) {
-            if (pre) return tall ? launch(gemm_f16x2_kernel<4, WAVES_N, D, BMODE, true>) : launch(gemm_f16x2_kernel<2, WAVES_N, D, BMODE, true>);
-            return tall ? launch(gemm_f16x2_kernel<4, WAVES_N, D, BMODE, false>) : launch(gemm_f16x2_kernel<2, WAVES_N, D, BMODE, false>);
-        } else {
-            if (pre) return tall ? launch(gemm_bf16x3_kernel<4, WAVES_N, D, BMODE, true>) : launch(gemm_bf16x3_kernel<2, WAVES_N, D, BMODE, true>);
-            return tall ? launch(gemm_bf16x3_kernel<4, WAVES_N, D, BMODE, false>) : launch(gemm_bf16x3_kernel<2, WAVES_N, D, BMODE, false>);
-        }
-    };
     int e;
-#ifdef EAP_ABLATION
-    const int dbg = getenv("EAP_GEMM_SPLIT_DEBUG") ? atoi(getenv("EAP_GEMM_SPLIT_DEBUG")) : 0;
-    if constexpr (BMODE == 0) {
-        switch (dbg) {
-            case 1: e = run(std::integral_constant<int, 1>{}); break;
-            case 2: e = run(std::integral_constant<int, 2>{}); break;
-            case 3: e = run(std::integral_constant<int, 3>{}); break;
-            case 4: e = run(std::integral_constant<int, 4>{}); break;
-            case 7: e = run(std::integral_constant<int, 7>{}); break;
-            case 15: e = run(std::integral_constant<int, 15>{}); break;
-            default: e = run(std::integral_constant<int, 0>{});
-        }
+    if constexpr (PL == 2) {
+        if (pre) e = tall ? launch(gemm_f16x2_kernel<4, WAVES_N, BMODE, true>) : launch(gemm_f16x2_kernel<2, WAVES_N, BMODE, true>);
+        else e = tall ? launch(gemm_f16x2_kernel<4, WAVES_N, BMODE, false>) : launch(gemm_f16x2_kernel<2, WAVES_N, BMODE, false>);
     } else {
-        e = run(std::integral_constant<int, 0>{});
+        if (pre) e = tall ? launch(gemm_bf16x3_kernel<4, WAVES_N, BMODE, true>) : launch(gemm_bf16x3_kernel<2, WAVES_N, BMODE, true>);
+        else e = tall ? launch(gemm_bf16x3_kernel<4, WAVES_N, BMODE, false>) : launch(gemm_bf16x3_kernel<2, WAVES_N, BMODE, false>);
     }
-#else
-    e = run(std::integral_constant<int, 0>{});
-#endif
     if (e) return e;
     static const char *names[3][2] = {{"gemm_bf16x3_kernel<2, 4>", "gemm_bf16x3_kernel<4, 4>"},
                                       {"gemm_bf16x3_kernel<2, 4, nn>", "gemm_bf16x3_kernel<4, 4, nn>"},

@@ -37,7 +37,6 @@
 #include "common.h"
 #include "device_prims.h"
 
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
@@ -78,9 +77,7 @@ struct Frag { float4 q[NI_]; float s[4][NI_]; };
 
 // WM x WN = 4 waves, wave tile (32 MI) x (32 NI).  AKM: A stored [K, M] (m contiguous) instead of [M, K];
 // BKN: B stored [K, N] (n contiguous) instead of [N, K]
-// DBG (timing experiments only, results are wrong for DBG > 0; profiles/r02_gemm_ablation.txt): 1 = no staging
-// traffic inside the k-loop, 2 = also no fragment reads (the bare MFMA stream: 152.6 TFLOP/s)
-template <int WM, int WN, int MI, int NI, bool AKM, bool BKN, int DBG = 0>
+template <int WM, int WN, int MI, int NI, bool AKM, bool BKN>
 __global__ __launch_bounds__(NT, 1) void gemm_dma_f32_kernel(DmaArgs g) {
     static_assert(WM * WN == 4, "four waves: one per SIMD");
     constexpr int BM = 32 * MI * WM, BN = 32 * NI * WN;
@@ -270,16 +267,14 @@ __global__ __launch_bounds__(NT, 1) void gemm_dma_f32_kernel(DmaArgs g) {
                     // piece, its reload) they cost 8 gaps.
                     if (i == 0 && jn == NI - 1) {
                         __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (DBG < 2) {
 #pragma unroll
-                            for (int r = 0; r < NREADS; ++r)
-                                if (r * 4 / NREADS == s && do_reads) frag_read(nbase, np, r, na_, nb_);
-                        }
-                        if constexpr (u < NP && DBG == 0) {
+                        for (int r = 0; r < NREADS; ++r)
+                            if (r * 4 / NREADS == s && do_reads) frag_read(nbase, np, r, na_, nb_);
+                        if constexpr (u < NP) {
                             park_piece(std::integral_constant<int, u>{}, pstage);     // (a stage nobody reads once it + 2 >= nt)
                             load_piece(std::integral_constant<int, u>{}, adv);
                         }
-                        if constexpr (u + 8 < NP && DBG == 0) {
+                        if constexpr (u + 8 < NP) {
                             park_piece(std::integral_constant<int, u + 8>{}, pstage);
                             load_piece(std::integral_constant<int, u + 8>{}, adv);
                         }
@@ -332,18 +327,6 @@ int launch_one(DmaArgs g, int zcount, hipStream_t s) {
     return eap::check_launch("gemm_dma_f32");
 }
 
-template <int DBG>
-int launch_debug(DmaArgs g, int zcount, hipStream_t s) {
-    g.tiles_m = (g.M + 255) / 256;
-    g.tiles_n = (g.N + 255) / 256;
-    const size_t shmem = (size_t)STAGES * 512 * BK * 4;
-    auto kern = gemm_dma_f32_kernel<2, 2, 4, 4, false, false, DBG>;
-    int e = eap::allow_dynamic_lds(kern, shmem, "gemm_dma_f32 debug");
-    if (e) return e;
-    hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, zcount), dim3(NT), shmem, s, g);
-    return eap::check_launch("gemm_dma_f32 (debug variant)");
-}
-
 template <bool AKM, bool BKN>
 int launch_shape(const DmaArgs &g, int zcount, hipStream_t s) {
     // block tile 256 x 256 (wave tile 128 x 128); for M <= 128: 128 x 512 (the same wave tile) when that still leaves
@@ -359,15 +342,6 @@ int launch_shape(const DmaArgs &g, int zcount, hipStream_t s) {
 
 int launch(bool akm, bool bkn, const DmaArgs &g, int zcount, hipStream_t s) {
     if (zcount > 65535) return eap::bad_arg("gemm_dma_f32: batch * splits exceeds 65535");
-#ifdef EAP_ABLATION
-    // Timing ablations (WRONG RESULTS), only in a library built with `make ABLATION=1`: EAP_GEMM_DEBUG=1,2
-    // (tools/gemm_only.py, profiles/r02_gemm_ablation.txt).  A production build never reads the variable.
-    if (!akm && !bkn && g.M > 128 && g.N > 128) {
-        static const int dbg = getenv("EAP_GEMM_DEBUG") ? atoi(getenv("EAP_GEMM_DEBUG")) : 0;
-        if (dbg == 1) return launch_debug<1>(g, zcount, s);
-        if (dbg == 2) return launch_debug<2>(g, zcount, s);
-    }
-#endif
     if (akm) return bkn ? launch_shape<true, true>(g, zcount, s) : launch_shape<true, false>(g, zcount, s);
     return bkn ? launch_shape<false, true>(g, zcount, s) : launch_shape<false, false>(g, zcount, s);
 }

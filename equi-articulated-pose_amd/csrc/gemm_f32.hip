@@ -17,8 +17,6 @@
 #include "common.h"
 #include "device_prims.h"
 
-#include <stdlib.h>
-
 namespace {
 
 constexpr int BK = 16, PAD = 4;
@@ -279,31 +277,14 @@ int launch(bool ta, bool tb, const GemmArgs &g, int zcount, hipStream_t s) {
     return eap::check_launch("gemm_f32");
 }
 
-int tile_config() {   // 0 (128x128) | 1 (256x128, default: +2% on the L2-layer shape) | 2 (128x256) | 3 (256x256)
-#ifdef EAP_ABLATION      // only in a library built with `make ABLATION=1`; a production build never reads the variable
-    static int cfg = -1;
-    if (cfg < 0) { const char *e = getenv("EAP_GEMM_TILE"); cfg = e ? atoi(e) : 1; }
-    return cfg;
-#else
-    return 1;
-#endif
-}
-
 int run(bool ta, bool tb, GemmArgs g, int zcount, hipStream_t s) {
     if (zcount > 65535) return eap::bad_arg("gemm_f32: batch*splits exceeds 65535");
-    int bm, bn;
-    const int cfg = tile_config();
-    if (g.M <= 64) { bm = 64; bn = 128; }
-    else if (cfg == 1 && g.M >= 256) { bm = 256; bn = 128; }
-    else if (cfg == 2 && g.N >= 256) { bm = 128; bn = 256; }
-    else if (cfg == 3 && g.M >= 256 && g.N >= 256) { bm = 256; bn = 256; }
-    else { bm = 128; bn = 128; }
+    // block tile 64x128 for M <= 64, 256x128 from M = 256 (+2% on the L2-layer shape over 128x128), else 128x128
+    const int bm = g.M <= 64 ? 64 : g.M >= 256 ? 256 : 128;
     g.tiles_m = (g.M + bm - 1) / bm;
-    g.tiles_n = (g.N + bn - 1) / bn;
+    g.tiles_n = (g.N + 127) / 128;
     if (bm == 64) return launch<2, 2, 32>(ta, tb, g, zcount, s);
-    if (bm == 256 && bn == 256) return launch<4, 4, 64>(ta, tb, g, zcount, s);
     if (bm == 256) return launch<4, 2, 64>(ta, tb, g, zcount, s);
-    if (bn == 256) return launch<2, 4, 64>(ta, tb, g, zcount, s);
     return launch<2, 2, 64>(ta, tb, g, zcount, s);
 }
 

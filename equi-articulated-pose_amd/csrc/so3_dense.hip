@@ -43,7 +43,6 @@
 #include <atomic>
 #include "common.h"
 #include "device_prims.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -72,18 +71,11 @@ __host__ __device__ __forceinline__ void dense_kr(int d, int ks, int &k, int &r)
 // x (scaled) = h + l + e, h = fp16(x), l = fp16(x - h), both to nearest even; two values -> the packed h word and l word.
 // v_fma_mix{lo,hi}_f16 form fp16(-1 * h + x) in one instruction each, reading h's half straight from the packed word.
 __device__ __forceinline__ void split2(float x0, float x1, unsigned &h, unsigned &l) {
-#ifdef EAP_DENSE_PLAIN_SPLIT
-    const f16x2 hh = __builtin_convertvector((f32x2){x0, x1}, f16x2);
-    const f16x2 ll = __builtin_convertvector((f32x2){x0 - (float)hh.x, x1 - (float)hh.y}, f16x2);
-    h = __builtin_bit_cast(unsigned, hh);
-    l = __builtin_bit_cast(unsigned, ll);
-#else
     // (one statement: hipcc pads every asm statement whose result the next instruction reads with a wait state)
     asm("v_cvt_pk_f16_f32 %0, %2, %3\n\t"
         "v_fma_mixlo_f16 %1, %0, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
         "v_fma_mixhi_f16 %1, %0, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
         : "=&v"(h), "=&v"(l) : "v"(x0), "v"(x1));
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -746,10 +738,7 @@ struct KcArgs {
     const int32_t *steps;                 // (may be null) [b][blocks_n][KS + 1]: count, then the k-steps this column block runs (dense_steps_kernel)
 };
 
-// DBG (timing ablations, `make ABLATION=1` + EAP_DENSE_DEBUG, WRONG results): 1 = no mask (all lanes kept), 2 = no k-side table
-// reads (constants), 4 = no weight evaluation at all (the B fragments of the prologue for every k-block), 8 = no DMA inside the k-loop,
-// 16 = no fragment reads of the stored operand inside the k-loop
-template <int MI, int FORM, int DBG = 0>
+template <int MI, int FORM>
 __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g) {
     static_assert(MI == 8 || MI == 4, "the DMA piece schedule below: 8 or 4 KB of the stored operand per wave and k-step");
     constexpr unsigned WB = MI * 1024u;                    // bytes of the stored operand a wave moves per k-step
@@ -873,21 +862,14 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
 #pragma unroll
         for (int i = 0; i < MI; ++i) f[i] = *reinterpret_cast<const u32x4 *>(st + (unsigned)sub * SUB_A + (unsigned)(2 * i + plane) * 1024u + (unsigned)lane * 16u);
     };
-    auto frag_loop = [&](const unsigned char *st, int sub, int plane, u32x4 (&f)[MI]) __attribute__((always_inline)) {
-        if constexpr (DBG & 16) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i) f[i] = (u32x4){0x3c003c00u + (unsigned)sub, 0x3c003c00u, 0x3c003c00u + (unsigned)plane, 0x3c003c00u};
-        } else frag_a(st, sub, plane, f);
-    };
     // weights of tile j, elements e0, e0 + 1 of a k-block (k-side entries sv[e]; mask bits 16 tb + 8 j + e of mb) -> word e0 / 2 of h, l.
     // The mask is the fma's addend: 1.0 for a list member, 0.0 otherwise -- the clamp then returns 0 (the product term is <= 0).
-    auto gen2 = [&](const SV (&sv)[8], unsigned mb, int tb, int j, int e0, BFrag &f, bool prologue = false) __attribute__((always_inline)) {
-        if ((DBG & 4) && !prologue) return;
+    auto gen2 = [&](const SV (&sv)[8], unsigned mb, int tb, int j, int e0, BFrag &f) __attribute__((always_inline)) {
         float v[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const SV s = sv[e0 + e];
-            const int keep = (DBG & 1) ? -1 : ((int)(mb << (31 - (16 * tb + 8 * j + e0 + e))) >> 31);
+            const int keep = (int)(mb << (31 - (16 * tb + 8 * j + e0 + e))) >> 31;
             const float one = __int_as_float(keep & 0x3f800000);
             if constexpr (FORM == 1) {
                 const float tx = cc[j].x - s.x, ty = cc[j].y - s.y, tz = cc[j].z - s.z;
@@ -905,10 +887,7 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
     };
     auto load_sv = [&](const f32x4 *str, SV (&sv)[8]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            if constexpr (DBG & 2) sv[e] = SV{0.01f * (float)e, 0.02f, 0.03f * (float)kg};
-            else sv[e] = *reinterpret_cast<const SV *>(str + 8 * kg + e);
-        }
+        for (int e = 0; e < 8; ++e) sv[e] = *reinterpret_cast<const SV *>(str + 8 * kg + e);
     };
     auto mm = [&](const u32x4 &fa, const u32x4 &fb, f32x16 &c) __attribute__((always_inline)) {
         c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa), __builtin_bit_cast(f16x8, fb), c, 0, 0, 0);
@@ -934,7 +913,7 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
         // the kernel is bound by the weight evaluation there) and LDS reads behind the first / second MI matrix instructions
         constexpr int NV1 = (MI == 8 ? 3 : 6) + (FORM ? 1 : 0), NV3 = (MI == 8 ? 2 : 4) + (FORM ? 1 : 0);
         SB();
-        frag_loop(st, sub, 1, al);
+        frag_a(st, sub, 1, al);
         if constexpr (!LEAN) load_sv(nnstr, nsv);
         dma(0);
 #pragma unroll
@@ -948,7 +927,7 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
         gen2(sv, mb, tb, 0, 6, Bn); gen2(sv, mb, tb, 1, 0, Bn); gen2(sv, mb, tb, 1, 2, Bn);
         PIPE(NV1, 0, 0)
         SB();
-        frag_loop(nst, nsub, 0, ah);
+        frag_a(nst, nsub, 0, ah);
         dma(2);
 #pragma unroll
         for (int i = 0; i < MI; ++i) { mm(al[i], Bc.h[0], acc[i][0]); mm(al[i], Bc.h[1], acc[i][1]); }
@@ -975,8 +954,7 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
     {
         load_sv(reinterpret_cast<const f32x4 *>(smem + STR_OFF), sv);
 #pragma unroll
-        for (int e = 0; e < 8; e += 2) { gen2(sv, mbc, 0, 0, e, B0, true); gen2(sv, mbc, 0, 1, e, B0, true); }
-        if constexpr (DBG & 4) B1 = B0;
+        for (int e = 0; e < 8; e += 2) { gen2(sv, mbc, 0, 0, e, B0); gen2(sv, mbc, 0, 1, e, B0); }
         frag_a(smem, 0, 0, ah);
         load_sv(reinterpret_cast<const f32x4 *>(smem + STR_OFF) + 16, sv);                       // k-block 1
     }
@@ -1002,12 +980,12 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
         // k-block 2s: generates k-block 2s + 1 (sv = its k-side entries, mask bits 16..31 of this step's dword); reads the entries of
         // k-block 2s + 2 (first slice of the next stage) for the next call
         kblock(smem + s0, 0, smem + s0, 1, str1, mbc, 1, B0, B1, ah, sv, LEAN ? sv : sw, [&](int slot) __attribute__((always_inline)) {
-            if constexpr (!(DBG & 8)) dma_slot(ssn, dst, slot);
+            dma_slot(ssn, dst, slot);
         });
         // k-block 2s + 1: generates k-block 2s + 2 (mask bits 0..15 of the NEXT step's dword); reads the entries of k-block 2s + 3
         // (past the end: stale data nobody uses)
         kblock(smem + s0, 1, smem + s1, 0, str1 + 16, mbn, 0, B1, B0, ah, LEAN ? sv : sw, sv, [&](int slot) __attribute__((always_inline)) {
-            if constexpr (!(DBG & 8)) dma_slot(ssn, dst, 3 + slot);
+            dma_slot(ssn, dst, 3 + slot);
         });
         mbc = mbn;
         { const unsigned r = s0; s0 = s1; s1 = s2; s2 = s3; s3 = r; }
@@ -1044,7 +1022,7 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
     }
 }
 
-template <int MI, int FORM, int DBG = 0>
+template <int MI, int FORM>
 int kc_launch(const KcArgs &g, hipStream_t s) {
     constexpr size_t shmem = 4 * (2 * (size_t)MI * 2048u + 2048u) + KC_LIST_BYTES;      // the ring + the k-step list
     // per DEVICE (a process may drive several GPUs: the attribute belongs to the function object of the current device) and
@@ -1054,13 +1032,13 @@ int kc_launch(const KcArgs &g, hipStream_t s) {
     if (int e = eap::hip_fail(hipGetDevice(&dev), "so3_dense: hipGetDevice")) return e;
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(set_on.load(std::memory_order_acquire) & bit)) {
-        if (int e = eap::allow_dynamic_lds(kc_gemm_kernel<MI, FORM, DBG>, shmem, "so3_dense: shared memory attribute"))
+        if (int e = eap::allow_dynamic_lds(kc_gemm_kernel<MI, FORM>, shmem, "so3_dense: shared memory attribute"))
             return e;
         set_on.fetch_or(bit, std::memory_order_release);
     }
     const long long blocks = (long long)g.zcount * g.tiles_m * g.blocks_n;
     if (blocks > 0x7fffffffLL) return eap::bad_arg("so3_dense: too many workgroups");
-    hipLaunchKernelGGL((kc_gemm_kernel<MI, FORM, DBG>), dim3((unsigned)blocks), dim3(256), shmem, s, g);
+    hipLaunchKernelGGL((kc_gemm_kernel<MI, FORM>), dim3((unsigned)blocks), dim3(256), shmem, s, g);
     eap::set_kernel(MI == 8 ? (FORM ? "kc_gemm_kernel<8, 1>" : "kc_gemm_kernel<8, 0>") : (FORM ? "kc_gemm_kernel<4, 1>" : "kc_gemm_kernel<4, 0>"));
     return eap::check_launch("so3_dense product");
 }
@@ -1310,21 +1288,6 @@ extern "C" int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int
         hipLaunchKernelGGL(dense_zero_tail_kernel, dim3(o * ks, b), dim3(256), 0, eap::S(stream), o * ks, na, rp, (long long)ldz, n_rows, out);
         if (int e = eap::check_launch("so3_dense zero tail")) return e;
     }
-#ifdef EAP_ABLATION
-    if (const char *d = wide ? getenv("EAP_DENSE_DEBUG") : nullptr) {
-        switch (atoi(d)) {
-            case 1: return kc_launch<8, 1, 1>(g, eap::S(stream));
-            case 2: return kc_launch<8, 1, 2>(g, eap::S(stream));
-            case 3: return kc_launch<8, 1, 3>(g, eap::S(stream));
-            case 4: return kc_launch<8, 1, 4>(g, eap::S(stream));
-            case 8: return kc_launch<8, 1, 8>(g, eap::S(stream));
-            case 16: return kc_launch<8, 1, 16>(g, eap::S(stream));
-            case 20: return kc_launch<8, 1, 20>(g, eap::S(stream));
-            case 28: return kc_launch<8, 1, 28>(g, eap::S(stream));
-            default: break;
-        }
-    }
-#endif
     if (!wide) return g_dense_form ? kc_launch<4, 1>(g, eap::S(stream)) : kc_launch<4, 0>(g, eap::S(stream));
     return g_dense_form ? kc_launch<8, 1>(g, eap::S(stream)) : kc_launch<8, 0>(g, eap::S(stream));
 }

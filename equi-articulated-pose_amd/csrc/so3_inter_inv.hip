@@ -544,18 +544,9 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
 // forward grouping of the clouds WITH per-neighbour anchor permutations on the kernel above (FWD = true); identity clouds
 // (nonident[b] == 0) are skipped.  feats [b,c,n,na], idx [b,p,nn], gx [b,p,nn,4]; out: X [b,c,ks,p,na] (blocked = 0) or
 // transposed (blocked = 2).  -1: this shape is not taken (the caller falls back to csrc/so3_inter_mfma.hip).
-static int g_perm_fwd_lists = 1;      // eap_so3_group_perm_fwd(0): the round-1 register-staged kernel (csrc/so3_inter_mfma.hip), for A/B runs
-
-extern "C" int eap_so3_group_perm_fwd(int on) {
-    const int was = g_perm_fwd_lists;
-    if (on == 0 || on == 1) g_perm_fwd_lists = on;
-    return was;
-}
-
 int eap::group_fwd_perm_lists(int b, int c, int p, int n, int nn, int na, int ks, float sigma, const float *feats, const int32_t *idx,
                               const float *gx, const float *rk, const uint8_t *mult, const int32_t *nonident, int blocked, float *out,
                               hipStream_t s) {
-    if (!g_perm_fwd_lists) return -1;
     if (!mult || !nonident || (blocked != 0 && blocked != 2) || (na & 7) != 4 || na > 64 || ks > 32) return -1;
     if (blocked == 2 && ((ks & 3) != 0 || (c & 7) != 0)) return -1;
     if ((long long)c * n * na >= (1ll << 31)) return -1;
@@ -580,12 +571,6 @@ extern "C" int eap_so3_inter_group_inv_pitch_f32(int b, int o, int p, int nn, in
                                                  float *z, eap_stream_t stream) {
     if (b <= 0 || o <= 0 || rcap <= 0 || na <= 0 || ks <= 0) return 0;
     if (!eap::group_lists_supported(na, ks)) return eap::bad_arg("so3_inter_group_inv_pitch: unsupported anchor / kernel-point count");
-#ifdef EAP_EXPERIMENTS
-    if (eap::group_listsh_preferred(o, na, ks, 0))
-        return eap::group_listsh_inv(b, o, p, nn, na, gy_pitch, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, eap::S(stream));
-    if (eap::group_lists3_preferred(o, na, ks, 0))
-        return eap::group_lists3_inv(b, o, p, nn, na, gy_pitch, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, eap::S(stream));
-#endif
     if (eap::group_lists2_preferred(o, na, ks, 0))
         return eap::group_lists2_inv(b, o, p, nn, na, gy_pitch, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, eap::S(stream));
     return eap::group_lists_inv(b, o, p, nn, na, gy_pitch, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, eap::S(stream));
@@ -672,12 +657,6 @@ static int group_inv(int b, int o, int p, int nn, int na, int ks, int rcap, floa
     hipStream_t s = eap::S(stream);
     // no anchor permutation: the two-workgroups-per-CU kernel of csrc/so3_inter_lists.hip
     if (!multinv && eap::group_lists_supported(na, ks)) {
-#ifdef EAP_EXPERIMENTS
-        if (eap::group_listsh_preferred(o, na, ks, 0))
-            return eap::group_listsh_inv(b, o, p, nn, na, na, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, s);
-        if (eap::group_lists3_preferred(o, na, ks, 0))
-            return eap::group_lists3_inv(b, o, p, nn, na, na, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, s);
-#endif
         if (eap::group_lists2_preferred(o, na, ks, 0))
             return eap::group_lists2_inv(b, o, p, nn, na, na, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, s);
         return eap::group_lists_inv(b, o, p, nn, na, na, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, s);

@@ -39,18 +39,6 @@ constexpr int NSTD = NBK * CB * SL / TM;   // DMA instructions per thread and ch
 constexpr unsigned BUF_BYTES = NBK * CB * PITCH * 4;
 static_assert(CB * SL == TM, "one DMA instruction per entry: thread t <-> (row t >> 2, slot t & 3)");
 
-// Timing ablations (WRONG RESULTS), compiled only with `make ABLATION=1` and selected by EAP_LISTS2_DEBUG (bit mask):
-// 1 no feature DMA after the prologue, 2 constant weights (no weight evaluation), 4 no row-end stores, 8 no chunk barrier
-// (only together with 1), 16 no per-k-step LDS operand reads; PERM: 32 no block move (DMA pieces from the thread's own
-// block), 64 no in-block XOR (selects); 512 the feature DMA always fetches rows 0..7 (all requests hit in cache: the issue cost
-// without the misses), 1024 the forward's row-end stores with the lanes in address order (the same bytes in 1 KB runs, wrong
-// places: what a transposed row end would issue).  tools/lists2_ablation.py, tools/lists2_perm_ablation.py
-#ifdef EAP_ABLATION
-#define ABL(bit) ((dbg & (bit)) != 0)
-#else
-#define ABL(bit) false
-#endif
-
 // LISTS = true : rows / off / cnt describe variable-length entry lists (backward);
 // LISTS = false: row r of cloud b owns entries [ (b*R + r)*nn, +nn ) (forward: its neighbours).
 // LAYOUT of the output: 0 = [b,c,k,row,a] (reference), 2 = transposed [row*na+a][c*ks+k], 3 = the same transposed matrix
@@ -85,7 +73,7 @@ static_assert(CB * SL == TM, "one DMA instruction per entry: thread t <-> (row t
 // tensors that follow); the forward's transposed output has one row per anchor and comes back in memory order.
 template <bool LISTS, int LAYOUT, bool PERM = false>
 __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
-    int C, int PF, int na, int fpitch, int ks, int R, int nn, int ent_stride, int AG, int RPB, int ag_major, int dbg, float inv_sigma,
+    int C, int PF, int na, int fpitch, int ks, int R, int nn, int ent_stride, int AG, int RPB, int ag_major, float inv_sigma,
     const float *__restrict__ F, const int32_t *__restrict__ rows, const int32_t *__restrict__ off,
     const int32_t *__restrict__ cnt, const int32_t *__restrict__ ent_p, const float4 *__restrict__ ent_gx,
     const float *__restrict__ rk, const int32_t *__restrict__ nonident, float *__restrict__ out,
@@ -189,7 +177,7 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
     const int d_row = t >> 2, d_piece = ((t & 3) - (d_row >> 2)) & 3;
     const bool d_valid = d_piece < npg;
     const unsigned dma_off = ((unsigned)(min(c0 + d_row, C - 1) - c0) * (unsigned)PF * (unsigned)fpitch + (PERM ? 0u : (unsigned)(a0 + 4 * min(d_piece, npg - 1)))) * 4u;
-    const int d_pc = min(d_piece, npg - 1), blk_t = (a0 >> 2) + d_pc;   // PERM: the block this thread's DMA piece belongs to
+    const int d_pc = min(d_piece, npg - 1);   // PERM: the piece of its block this thread's DMA instruction fetches
     const unsigned lds_g = lds_addr(s_g), lds_p = lds_addr(s_p);
     auto issue_idx = [&](int j0, int slot) {
         if (wave_u == 0 && lane < NBK) {
@@ -204,17 +192,16 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
 #pragma unroll
         for (int u = 0; u < NSTD; ++u) {
             if (PERM) {                // byte offset of the piece inside the cloud's channel row: point row + its SOURCE block
-                src_off[u] = dma_off + (ABL(32) ? (unsigned)s_p[(slot * NBK + u) * 4] + 16u * (unsigned)blk_t : (unsigned)s_p[(slot * NBK + u) * 4 + d_pc]);
+                src_off[u] = dma_off + (unsigned)s_p[(slot * NBK + u) * 4 + d_pc];
                 continue;
             }
             int pe = s_p[slot * NBK + u];
-            if (ABL(512)) pe = u;                                      // every chunk fetches the same eight rows: cache hits only
             if (!LISTS) pe = (unsigned)pe < (unsigned)PF ? pe : 0;     // shadow row: any valid row, weight 0
             src_off[u] = dma_off + __umul24((unsigned)pe, row_bytes);
         }
     };
     auto issue = [&](int u, int buf) {
-        if (d_valid && !ABL(1))
+        if (d_valid)
             glds16s(fb, src_off[u], __builtin_amdgcn_readfirstlane(lds_f + (unsigned)buf * BUF_BYTES + (unsigned)(u * TM + wave_u * 64) * 16u));
     };
 
@@ -245,15 +232,11 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
         v = make_float4(x1 ? a2_ : a0_, x1 ? a3_ : a1_, x1 ? a0_ : a2_, x1 ? a1_ : a3_);
     };
     auto gather = [&](const float4 *fab, int gslot, int bases, int s, float4 &fa, float4 &fb1, float4 &g, float &bk) {
-        if (ABL(16)) {
-            fa = make_float4(1.f, 2.f, 3.f, 4.f); fb1 = fa; g = make_float4(0.01f * (float)s, 0.02f, 0.03f, 0.f); bk = 0.5f;
-            return;
-        }
         fa = fab[s * STEP_F4];
         fb1 = fab[s * STEP_F4 + TILE_F4];
         g = s_g[gslot * NBK + 2 * s + lh];
         bk = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (2 * s + lh), bases));
-        if (PERM && !ABL(64)) {
+        if (PERM) {
             const int x = __float_as_int(g.w) >> (2 * blk_w);        // the entry's x bits, 2 per block
             unxor(fa, x);
             unxor(fb1, x);
@@ -267,16 +250,11 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
         const float fa1[APW] = {fv1.x, fv1.y, fv1.z, fv1.w};
         f32x2 wv[APW / 2];
         const float bkc = bk + kcl;
-        if (ABL(2)) {
-            wv[0] = kxp[0];
-            wv[1] = kxp[1];
-        } else {
 #pragma unroll
-            for (int j = 0; j < APW / 2; ++j) {
-                f32x2 x = __builtin_elementwise_fma((f32x2){g.x, g.x}, kxp[j], decltype(kcu)::value ? (f32x2){bkc, bkc} : kcp[j] + (f32x2){bk, bk});
-                x = __builtin_elementwise_fma((f32x2){g.y, g.y}, kyp[j], x);
-                asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp\n\ts_nop 1" : "=v"(wv[j]) : "v"((f32x2){g.z, g.w}), "v"(kzp[j]), "v"(x));
-            }
+        for (int j = 0; j < APW / 2; ++j) {
+            f32x2 x = __builtin_elementwise_fma((f32x2){g.x, g.x}, kxp[j], decltype(kcu)::value ? (f32x2){bkc, bkc} : kcp[j] + (f32x2){bk, bk});
+            x = __builtin_elementwise_fma((f32x2){g.y, g.y}, kyp[j], x);
+            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp\n\ts_nop 1" : "=v"(wv[j]) : "v"((f32x2){g.z, g.w}), "v"(kzp[j]), "v"(x));
         }
         __builtin_amdgcn_s_setprio(3);
         if (first) {
@@ -320,10 +298,10 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
             // D[i = kernel point][j = channel]: lane column = channel lk of the tile, accumulator quad q holds kernel points
             // 8 q + 4 lh .. + 3 -- 16 contiguous bytes of out[b][row*na + a][c*ks + k].
             // (Every instruction is 64 separate 16-byte requests, 96 bytes apart; the same bytes written in address order take
-            // 11.6 instead of 12.6 ms (ABL 1024).  Bringing them into address order through a wave-private LDS scratch -- 24
+            // 11.6 instead of 12.6 ms.  Bringing them into address order through a wave-private LDS scratch -- 24
             // ds_write_b128 + 24 ds_read_b128 per row end, pipelined over the (tile, anchor) pairs -- measured 12.8 ms: the wave
             // waits out the LDS round trips instead of issuing matrix instructions.  profiles/r04_row_order_experiment.txt)
-            if (active && !ABL(4)) {
+            if (active) {
                 const size_t CK = (size_t)C * ks;
                 float *rb = obb + ((size_t)row * na + (PERM ? 0 : a0 + al_beg)) * CK + (size_t)c0 * ks;      // uniform
                 const unsigned lo_b = (unsigned)(lk * ks + 4 * lh) * 4u;
@@ -338,7 +316,7 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
 #pragma unroll
                             for (int ai = 0; ai < APW; ++ai) {
                                 const f32x4 v = {acc[ct][ai][4 * q], acc[ct][ai][4 * q + 1], acc[ct][ai][4 * q + 2], acc[ct][ai][4 * q + 3]};
-                                if (LAYOUT == 4 || ABL(1024))     // lanes in address order: 1 KB runs (LAYOUT 3 under ABL 1024: wrong places)
+                                if (LAYOUT == 4)     // lanes in address order: 1 KB runs
                                     asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"((unsigned)lane * 16u), "v"(v),
                                                  "s"(rb + (size_t)(PERM ? am[ai] : ai) * CK + (size_t)(32 * ct) * ks + 256 * q) : "memory");
                                 else
@@ -351,7 +329,7 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
             }
             return;
         }
-        if (active && lk < ks && !ABL(4)) {
+        if (active && lk < ks) {
             if (LAYOUT == 2) {
                 // transposed output out[b][row*na + a][c*ks + k] (the plain [P*A, C*K] matrix the contraction GEMM reads)
                 const size_t CK = (size_t)C * ks;
@@ -431,7 +409,7 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
                 ch_row = 0;                                                                                           \
                 ++row;                                                                                                \
             }                                                                                                         \
-            if (!ABL(8)) __syncthreads();                                                                             \
+            __syncthreads();                                                                                          \
             const int gt = g0; g0 = g1; g1 = g2; g2 = gt;                                                             \
         }                                                                                                             \
         if (nchunk == 0) {                                                                                            \
@@ -485,12 +463,7 @@ int launch2(int layout, int b, int C, int PF, int na, int fpitch, int ks, int R,
     const int AG = (na + GSZ - 1) / GSZ;
     const int RPB = LISTS ? 1 : ((nn % NBK) == 0 ? 8 : 1);
     dim3 grid((R + RPB - 1) / RPB * AG, (C + CB - 1) / CB, b);
-#ifdef EAP_ABLATION
-    const int dbg = getenv("EAP_LISTS2_DEBUG") ? atoi(getenv("EAP_LISTS2_DEBUG")) : 0;
-#else
-    const int dbg = 0;
-#endif
-    hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, C, PF, na, fpitch, ks, R, nn, ent_stride, AG, RPB, (LISTS ? g_xcd_map_inv : g_xcd_map_fwd) == 2, dbg, 1.0f / sigma, F,
+    hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, C, PF, na, fpitch, ks, R, nn, ent_stride, AG, RPB, (LISTS ? g_xcd_map_inv : g_xcd_map_fwd) == 2, 1.0f / sigma, F,
                        rows, off, cnt, ent_p, reinterpret_cast<const float4 *>(ent_gx), rk, nonident, out, order);
     if (lane_order) eap::set_kernel(perm ? "so3_group_lists2_kernel<false, 4, true>" : "so3_group_lists2_kernel<false, 4>");
     else
@@ -503,15 +476,10 @@ int launch2(int layout, int b, int C, int PF, int na, int fpitch, int ks, int R,
 
 static int g_tiles = 2;       // eap_so3_group_lists_tiles
 
-// A/B and test switch: 1 = always the one-tile kernel of csrc/so3_inter_lists.hip, 2 = two tiles where they pay (default),
-// (3 = the 3 x bf16 split kernel of tools/experiments/kernels/so3_inter_lists3.hip, in `make EXPERIMENTS=1` builds only: measured
-// slower on real neighbour lists, the grouping is bound by the L2 -> LDS gather, not by the matrix pipe); 0 = query.  Returns the value in force.  Process-wide, not thread-safe (set it before launching).
+// A/B and test switch: 1 = always the one-tile kernel of csrc/so3_inter_lists.hip, 2 = two tiles where they pay (default);
+// any other value only queries.  Returns the value in force.  Process-wide, not thread-safe (set it before launching).
 extern "C" int eap_so3_group_lists_tiles(int tiles) {
-#ifdef EAP_EXPERIMENTS
-    if (tiles >= 1 && tiles <= 4) g_tiles = tiles;
-#else
     if (tiles >= 1 && tiles <= 2) g_tiles = tiles;
-#endif
     return g_tiles;
 }
 
@@ -549,14 +517,6 @@ bool group_lists2_preferred(int c, int na, int ks, int layout) {
     const int rem = c % CB;
     return c >= CB && (rem == 0 || rem > 32);
 }
-
-#ifdef EAP_EXPERIMENTS
-// mode 3 (eap_so3_group_lists_tiles, `make EXPERIMENTS=1` builds only): the 3 x bf16 split kernel of
-// tools/experiments/kernels/so3_inter_lists3.hip wherever the two-tile kernel would run
-bool group_lists3_preferred(int c, int na, int ks, int layout) { return g_tiles == 3 && group_lists2_preferred(c, na, ks, layout); }
-// mode 4: the two-fp16-plane kernel of tools/experiments/kernels/so3_inter_lists_h2.hip
-bool group_listsh_preferred(int c, int na, int ks, int layout) { return g_tiles == 4 && group_lists2_preferred(c, na, ks, layout); }
-#endif
 
 int group_lists2_fwd(int b, int c, int p, int n, int nn, int na, int ks, float sigma, const float *feats,
                      const int32_t *idx, const float *gx, const float *rk, const int32_t *nonident, int layout, float *out,

@@ -35,7 +35,6 @@
 // reported in `status` and left to csrc/zpconv_bwd.hip.
 #include "common.h"
 #include "device_prims.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -49,15 +48,6 @@ constexpr int STAGE_G = AQ * KS * CH * 4;     // grad stage [anchor][k][c]
 constexpr int STAGE_S = NN * 4;               // byte offsets of the accumulator rows of the point's 64 neighbours
 constexpr int LDS_BYTES = 158 * 1024;      // 2 KB stay free on every CU: the index check's workgroups run BESIDE this kernel
 constexpr int RCAP = (LDS_BYTES - STAGE_G - STAGE_S) / ROWB - 1;      // referenced rows a cloud may have (+ one dump row)
-
-// Timing ablations (WRONG RESULTS), compiled only with `make ABLATION=1` and selected by EAP_ZPHOT_DEBUG (bit mask): 1 no LDS
-// accumulation, 2 no grad requests after the prologue, 4 no weight requests after the prologue, 8 no matrix instructions,
-// 16 no flush, 32 no point loop, 64 no barriers in the loop, 128 no staging writes
-#ifdef EAP_ABLATION
-#define ABL(bit) ((dbg & (bit)) != 0)
-#else
-#define ABL(bit) false
-#endif
 
 // One workgroup per cloud: the cloud's referenced support rows from its per-point lists idx0[b, p, :] -- a bit per row in LDS
 // (read before the atomic: after the first few hundred entries every bit is set), then ranks by a scan over the words:
@@ -156,7 +146,7 @@ __global__ __launch_bounds__(TM, 2) void zp_hot_kernel(int nb, int S, int np, in
                                                        const float *__restrict__ w, const int32_t *__restrict__ slot_off,
                                                        const int32_t *__restrict__ rows, const int32_t *__restrict__ n_rows,
                                                        const int32_t *__restrict__ status, float *__restrict__ gfeats,
-                                                       float *__restrict__ partial, int dbg) {
+                                                       float *__restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int naq = na >> 2, members = naq * (C / CH);
@@ -246,19 +236,15 @@ __global__ __launch_bounds__(TM, 2) void zp_hot_kernel(int nb, int S, int np, in
         // compiler sinks these reads below the MFMAs: two LDS round trips on the critical path of every point)
         float old[16];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) old[i] = ABL(1) && i ? 0.f : *reinterpret_cast<const float *>(acc_w + so[i]);
+        for (int i = 0; i < 16; ++i) old[i] = *reinterpret_cast<const float *>(acc_w + so[i]);
         __builtin_amdgcn_sched_barrier(0);
         f32x16 acc = zero16;
 #pragma unroll
-        for (int s = 0; s < KS2; ++s) {
-            if (ABL(8)) { acc[s] += A[s] * Bf[s]; continue; }
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(A[s], Bf[s], acc, 0, 0, 0);
-        }
+        for (int s = 0; s < KS2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(A[s], Bf[s], acc, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if (!ABL(4)) request_w(A, pn);
+        request_w(A, pn);
 #pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if (!ABL(1) || i == 0) *reinterpret_cast<float *>(acc_w + so[i]) = old[i] + acc[i];
+        for (int i = 0; i < 16; ++i) *reinterpret_cast<float *>(acc_w + so[i]) = old[i] + acc[i];
     };
 
     const int plast = p1 - 1;
@@ -267,20 +253,19 @@ __global__ __launch_bounds__(TM, 2) void zp_hot_kernel(int nb, int S, int np, in
     request_g(GY, min(p0 + 1, plast));
     request_w(AY, min(p0 + 1, plast));
     __syncthreads();                                   // the accumulators are zero
-    if (ABL(32)) {
-    } else if (two_stages) {
+    if (two_stages) {
         // stage (p - p0) & 1 holds point p.  Step p: matrix work from its stage, then point p + 1 (waiting in the OTHER
         // register set) goes into the other stage -- last read during step p - 1, which every wave left through that
         // step's barrier -- and the set is re-requested for p + 3.
         const unsigned st[2] = {stage0, stage0 + STAGE_G + STAGE_S};
         put(st[0], GX);
-        if (!ABL(2)) request_g(GX, min(p0 + 2, plast));
+        request_g(GX, min(p0 + 2, plast));
         __syncthreads();
         auto step = [&](int cur, float (&A)[KS2], GSet &Gn, int p) {
             work(st[cur], A, min(p + 2, plast));
-            if (!ABL(128)) put(st[cur ^ 1], Gn);
-            if (!ABL(2)) request_g(Gn, min(p + 3, plast));
-            if (!ABL(64)) __syncthreads();
+            put(st[cur ^ 1], Gn);
+            request_g(Gn, min(p + 3, plast));
+            __syncthreads();
         };
         for (int p = p0; p < p1; p += 2) {
             step(0, AX, GY, p);
@@ -288,13 +273,13 @@ __global__ __launch_bounds__(TM, 2) void zp_hot_kernel(int nb, int S, int np, in
         }
     } else {
         auto step = [&](GSet &G, float (&A)[KS2], int p) {
-            if (!ABL(128)) put(stage0, G);
-            if (!ABL(2)) request_g(G, min(p + 2, plast));
-            if (!ABL(64)) __syncthreads();
+            put(stage0, G);
+            request_g(G, min(p + 2, plast));
+            __syncthreads();
             // (the stage is read into registers at the top of work(); the second barrier lets the next put() overwrite it, and
             // keeps the accumulation steps of consecutive points apart)
             work(stage0, A, min(p + 2, plast));
-            if (!ABL(64)) __syncthreads();
+            __syncthreads();
         };
         for (int p = p0; p < p1; p += 2) {
             step(GX, AX, p);
@@ -304,8 +289,7 @@ __global__ __launch_bounds__(TM, 2) void zp_hot_kernel(int nb, int S, int np, in
     __syncthreads();
 
     // ---- flush: thread <-> (row, channel): the row's four anchors as one 16-byte word
-    if (ABL(16)) {
-    } else if (S == 1) {
+    if (S == 1) {
         for (int e = tid; e < R * CH; e += TM) {
             const int r = e / CH, c = e - r * CH;
             const int q = rows[(size_t)bi * nq + r];
@@ -418,13 +402,8 @@ extern "C" int eap_inter_zpconv_bwd_hot_f32(int b, int np, int nq, int na, int k
     const int members = (na / 4) * (c / CH), groups = b * L.S;
     const long long blocks = 8ll * members * ((groups + 7) / 8);
     if (blocks >= (1ll << 31)) return eap::bad_arg("inter_zpconv_backward (on-chip rows): too many workgroups");
-#ifdef EAP_ABLATION
-    const int dbg = getenv("EAP_ZPHOT_DEBUG") ? atoi(getenv("EAP_ZPHOT_DEBUG")) : 0;
-#else
-    const int dbg = 0;
-#endif
     hipLaunchKernelGGL(zp_hot_kernel, dim3((unsigned)blocks), dim3(TM), LDS_BYTES, s, b, L.S, np, nq, na, c, grad, w, slot_off, rows, n_rows,
-                       status, gfeats, partial, dbg);
+                       status, gfeats, partial);
     e = eap::check_launch("inter_zpconv_backward (on-chip rows)");
     if (e) return e;
     eap::set_kernel("zp_hot_kernel");

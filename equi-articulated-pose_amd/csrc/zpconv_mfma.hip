@@ -25,7 +25,6 @@
 #include "device_prims.h"
 #include <type_traits>
 #include <utility>
-#include <stdlib.h>
 
 namespace {
 
@@ -95,7 +94,7 @@ __device__ __forceinline__ f32x4 &wref(WSet &w) {
 __global__ __launch_bounds__(TM, 2) void zpconv_mfma_kernel(
     int C, int PF, int na, int ks, int P, int nn, int AG, int gsz, int ny, int nb,
     const float *__restrict__ F, const int32_t *__restrict__ idx0, const float *__restrict__ w,
-    const int32_t *__restrict__ skip, float *__restrict__ out, int dbg) {
+    const int32_t *__restrict__ skip, float *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     // ---- block -> (run of points, anchor group, cloud, channel slice).  The weights do not depend on the channel: the
@@ -149,7 +148,7 @@ __global__ __launch_bounds__(TM, 2) void zpconv_mfma_kernel(
             src_row[u] = min((unsigned)__builtin_amdgcn_readfirstlane(s_p[slot * SBK + 8 * (u >> 2) + 4 * par + (u & 3)]), (unsigned)PF - 1u);
     };
     auto issue = [&](int u, int buf) {
-        if (d_valid && !(dbg & 4))
+        if (d_valid)
             glds16s(fb + (size_t)src_row[u] * na, dma_off,
                     __builtin_amdgcn_readfirstlane(lds_f + (unsigned)buf * BUF_BYTES + (unsigned)(u * TM + wave_u * 64) * 16u));
     };
@@ -177,7 +176,7 @@ __global__ __launch_bounds__(TM, 2) void zpconv_mfma_kernel(
     constexpr int XT = 64 * 32;                                    // floats per tile
     // (32-bit byte offset per lane; the launcher bounds one 64-channel slice of the output below 4 GB)
     const unsigned x_off = (unsigned)(((size_t)(4 * (x_row >> 5)) * o_cs + (size_t)min(x_row & 31, ks - 1) * o_ks + 4 * min(x_piece, npg - 1)) * 4);
-    const bool x_on = (x_row & 31) < ks && x_piece < npg && !(dbg & 1);
+    const bool x_on = (x_row & 31) < ks && x_piece < npg;
     const int x_cmax = C - c0 - 4 * (x_row >> 5);                  // channels ch < x_cmax exist for this thread
     // tile j of the round -> register I = 8 g + j of the accumulators = channel tile I >> 4, register I & 15
     auto flush_store = [&](const float *tile0, int j, int row, int I) __attribute__((always_inline)) {
@@ -233,7 +232,6 @@ __global__ __launch_bounds__(TM, 2) void zpconv_mfma_kernel(
     const size_t row_jump = (size_t)na * ks * nn - (size_t)(spr - 1) * SBK;
     int wcc = 0;
     auto wload = [&](const float *wp, WSet &ws) __attribute__((always_inline)) {
-        if (dbg & 2) wp = w;
         asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(ws.a0l) : "v"(wlane_b), "s"(wp) : "memory");
         asm volatile("global_load_dwordx4 %0, %1, %2 offset:16" : "=v"(ws.a0h) : "v"(wlane_b), "s"(wp) : "memory");
         asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(ws.a1l) : "v"(wlane_b), "s"(wp + astride) : "memory");
@@ -383,15 +381,8 @@ int inter_zpconv_mfma_fwd(int b, int np, int nq, int na, int ks, int nn, int c, 
     const int ny = (c + CB - 1) / CB;
     const long long units = (long long)((np + RPB - 1) / RPB) * AG * b, blocks = 8 * ((units + 7) / 8) * ny;
     if (blocks >= (1ll << 31)) return eap::bad_arg("inter_zpconv_forward (matrix path): too many workgroups");
-    // EAP_ZP_DEBUG (timing ablations only: wrong results): 1 = no output stores, 2 = every weight load hits the same
-    // lines, 4 = no feature DMA
-#ifdef EAP_ABLATION      // only in a library built with `make ABLATION=1`; a production build never reads the variable
-    const int dbg = getenv("EAP_ZP_DEBUG") ? atoi(getenv("EAP_ZP_DEBUG")) : 0;
-#else
-    const int dbg = 0;
-#endif
     hipLaunchKernelGGL(zpconv_mfma_kernel, dim3((unsigned)blocks), dim3(TM), shmem, s, c, nq, na, ks, np, nn, AG, gsz, ny, b, feats, idx0, w,
-                       skip, out, dbg);
+                       skip, out);
     return eap::check_launch("inter_zpconv_forward (matrix path)");
 }
 
@@ -428,11 +419,6 @@ extern "C" int eap_inter_zpconv_fwd_ws_f32(int b, int np, int nq, int na, int ks
     eap::SideJoin joiner(s);              // (also on the error returns below)
     e = eap::zpconv_index_check(b, np, na * ks * ann, ann, idx, nullptr, nullptr, flag, side);
     if (e) return e;
-#ifdef EAP_EXPERIMENTS   // `make EXPERIMENTS=1`: the 32-neighbour re-cut of tools/experiments/kernels/zpconv_mfma2.hip behind eap_inter_zpconv_fwd_kernel(2)
-    if (eap::zp_fwd_kernel() == 2 && eap::inter_zpconv_mfma2_supported(np, nq, na, ks, ann, c))
-        e = eap::inter_zpconv_mfma2_fwd(b, np, nq, na, ks, ann, c, idx0, w, src, nobody, dst, s);
-    else
-#endif
     e = eap::inter_zpconv_mfma_fwd(b, np, nq, na, ks, ann, c, idx0, w, src, nobody, dst, s);
     if (e) return e;
     e = joiner.join();

@@ -29,7 +29,7 @@
 // streaming rate (8.8 B/clk/CU = 4.7 TB/s over the chip) but does not overlap the multiply phase
 // (the 139 KB tile leaves room for one workgroup per CU), and the feature rows of a point are
 // re-read for each of its three kernel-point tiles (983 KB each at C = 64; served by L2 only when
-// the neighbour rows are hot).  Variants tried and kept under tools/experiments/: MFMA with 8/16
+// the neighbour rows are hot).  Variants tried (no longer in the tree): MFMA with 8/16
 // anchors per workgroup (32-byte row segments: TA-bound), 4-kernel-point tiles with two
 // workgroups per CU or with dedicated loader waves (row re-reads double: MALL-bound), and
 // half-neighbour tiles with 4 loader + 8 compute waves persistent over 4 points (same speed).

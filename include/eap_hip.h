@@ -233,18 +233,14 @@ int eap_so3_inter_group_bwd_map_f32(int b, int c, int p, int n, int nn, int na, 
 /* Which entry-list grouping kernel serves eap_so3_inter_group_fwd*_f32 / eap_so3_inter_group_inv*_f32 when no anchor
  * permutation is in play: 2 (default) = the fp32-MFMA kernel with two channel tiles per wave where the channel count fills
  * 64-channel blocks (csrc/so3_inter_lists2.hip), 1 = always the one-tile fp32-MFMA kernel (csrc/so3_inter_lists.hip);
- * 0 = query.  Returns the value in force.  1 and 2 agree bit for bit (tests compare them).  (Measured-slower experiments --
- * a 3 x bf16 split grouping kernel, a re-cut zpconv forward -- live in tools/experiments/kernels/ and are compiled in by
- * `make EXPERIMENTS=1` only.) */
+ * 0 = query.  Returns the value in force.  1 and 2 agree bit for bit (tests compare them).  (Two measured-slower
+ * experiments -- a 3 x bf16 split grouping kernel, a re-cut zpconv forward -- are recorded in profiles/; their source is in commit
+ * 5d523ff.) */
 int eap_so3_group_lists_tiles(int tiles);
 /* Row end of the two-tile forward kernel writing the transposed intermediate: 1 (default) = MFMA operands exchanged so that a
  * lane holds four consecutive kernel points of a channel, 16-byte stores; 0 = dword stores in 96-byte runs.  Bit-identical
  * results.  Returns the previous setting; other values only query. */
 int eap_so3_group_lists_store16(int on);
-/* forward grouping of clouds WITH anchor permutations: 1 (default) = the entry-list kernel of csrc/so3_inter_inv.hip in its
- * forward mode (global -> LDS DMA rows), 0 = the register-staged kernel of csrc/so3_inter_mfma.hip (round 1); returns the
- * previous setting, any other argument only queries.  Same results to rounding; for A/B runs and tests. */
-int eap_so3_group_perm_fwd(int on);
 /* Clouds WITH anchor permutations on the two-tile kernel (csrc/so3_inter_lists2.hip, PERM; round 4): the operand's anchor
  * axis is COSET-MAJOR (eap_anchor_reorder_f32 with the `order` of vgtk.so3conv.functional._coset_tables), the block move of an
  * entry's permutation rides on the DMA source addresses, the in-block XOR is 8 selects per operand read, and everything that

@@ -755,49 +755,32 @@ def test_inter_zpconv_matrix_path_edges(dev):
     run of 8, a channel count that is not a multiple of 64, every neighbour the same support point (one inverse list
     holding every entry), and an empty batch."""
     import vgtk.cuda.zpconv as Z
-    from vgtk import _hip as _h
     rng = np.random.default_rng(11)
-    # (in a `make EXPERIMENTS=1` library the same cases also run on the 32-neighbour re-cut of tools/experiments/kernels/zpconv_mfma2.hip)
-    experiments = hasattr(_h.lib, 'eap_inter_zpconv_fwd_kernel')
-    for which_fwd in ((1, 2) if experiments else (1,)):
-        if experiments:
-            _h.lib.eap_inter_zpconv_fwd_kernel(which_fwd)
-        for (b, p, q, a, k, ann, c) in ((1, 1, 5, 60, 24, 64, 64), (2, 5, 9, 60, 24, 16, 80), (1, 11, 3, 28, 24, 32, 16),
-                                      (1, 1, 1, 4, 24, 4, 16), (3, 3, 5, 60, 24, 12, 16),       # scratch chunks far from 256-byte multiples
-                                      # csrc/zpconv_mfma2.hip (64 / 128 neighbours): runs of 8 + 8 + 3 points with a partial second
-                                      # channel slice; 28 anchors (a wave without anchors) at 128 neighbours; 17 kernel points
-                                      (2, 19, 40, 60, 24, 64, 80), (1, 9, 30, 28, 24, 128, 16), (2, 8, 50, 60, 17, 64, 64)):
-            idx = np.broadcast_to(rng.integers(0, q, (b, p, 1, 1, ann)), (b, p, a, k, ann)).astype(np.int32).copy()
-            if p == 5:
-                idx[:] = 2                                          # all entries reference support point 2
-            w = rng.random((b, p, a, k, ann)).astype(np.float32)
-            feats = rng.standard_normal((b, c, q, a)).astype(np.float32)
-            out = Z.inter_zpconv_forward(T(idx).to(dev), T(w).to(dev), T(feats).to(dev)).cpu().numpy()
-            ref = native.inter_zpconv_forward(idx, w, feats)
-            assert rel_err(out, ref) < 2e-6, (b, p, q, a, k, ann, c)
-            g = rng.standard_normal(ref.shape).astype(np.float32)
-            got = Z.inter_zpconv_backward(T(idx).to(dev), T(w).to(dev), T(g).to(dev), q).cpu().numpy()
-            assert rel_err(got, native.inter_zpconv_backward(idx, w, g, q)) < 1e-5, (b, p, q, a, k, ann, c)
-    if experiments:
-        _h.lib.eap_inter_zpconv_fwd_kernel(1)
+    for (b, p, q, a, k, ann, c) in ((1, 1, 5, 60, 24, 64, 64), (2, 5, 9, 60, 24, 16, 80), (1, 11, 3, 28, 24, 32, 16),
+                                  (1, 1, 1, 4, 24, 4, 16), (3, 3, 5, 60, 24, 12, 16),       # scratch chunks far from 256-byte multiples
+                                  # 64 / 128 neighbours: runs of 8 + 8 + 3 points with a partial second channel slice; 28 anchors
+                                  # (a wave without anchors) at 128 neighbours; 17 kernel points
+                                  (2, 19, 40, 60, 24, 64, 80), (1, 9, 30, 28, 24, 128, 16), (2, 8, 50, 60, 17, 64, 64)):
+        idx = np.broadcast_to(rng.integers(0, q, (b, p, 1, 1, ann)), (b, p, a, k, ann)).astype(np.int32).copy()
+        if p == 5:
+            idx[:] = 2                                          # all entries reference support point 2
+        w = rng.random((b, p, a, k, ann)).astype(np.float32)
+        feats = rng.standard_normal((b, c, q, a)).astype(np.float32)
+        out = Z.inter_zpconv_forward(T(idx).to(dev), T(w).to(dev), T(feats).to(dev)).cpu().numpy()
+        ref = native.inter_zpconv_forward(idx, w, feats)
+        assert rel_err(out, ref) < 2e-6, (b, p, q, a, k, ann, c)
+        g = rng.standard_normal(ref.shape).astype(np.float32)
+        got = Z.inter_zpconv_backward(T(idx).to(dev), T(w).to(dev), T(g).to(dev), q).cpu().numpy()
+        assert rel_err(got, native.inter_zpconv_backward(idx, w, g, q)) < 1e-5, (b, p, q, a, k, ann, c)
     # a benchmark-like shape, and a batch that mixes a broadcast-index cloud with an arbitrary 5-D index (served by
     # csrc/zpconv_rows.hip)
-    from vgtk import _hip
     b, p, q, a, k, ann, c = 2, 64, 64, 60, 24, 64, 128
     idx = np.broadcast_to(rng.integers(0, q, (b, p, 1, 1, ann)), (b, p, a, k, ann)).astype(np.int32).copy()
     w = rng.random((b, p, a, k, ann)).astype(np.float32)
     feats = rng.standard_normal((b, c, q, a)).astype(np.float32)
-    outs = {}
-    for which in ((2, 1) if experiments else (1,)):
-        was = _hip.lib.eap_inter_zpconv_fwd_kernel(which) if experiments else 1
-        try:
-            outs[which] = Z.inter_zpconv_forward(T(idx).to(dev), T(w).to(dev), T(feats).to(dev)).cpu().numpy()
-        finally:
-            if experiments:
-                _hip.lib.eap_inter_zpconv_fwd_kernel(was)
+    got = Z.inter_zpconv_forward(T(idx).to(dev), T(w).to(dev), T(feats).to(dev)).cpu().numpy()
     ref = native.inter_zpconv_forward(idx, w, feats)
-    for got in outs.values():
-        assert rel_err(got, ref) < 2e-6
+    assert rel_err(got, ref) < 2e-6
     idx[1, 3, 7, 5, :] = (idx[1, 3, 7, 5, :] + 1) % q                 # cloud 1: one (a, k) row differs -> arbitrary-index path
     out = Z.inter_zpconv_forward(T(idx).to(dev), T(w).to(dev), T(feats).to(dev)).cpu().numpy()
     assert rel_err(out, native.inter_zpconv_forward(idx, w, feats)) < 2e-6
@@ -831,14 +814,6 @@ def test_native_known_answers(dev):
     K.known_chamfer(on_gpu(chamfer.forward), on_gpu(chamfer.backward))
 
 
-def ref_valu(feats, idx, gx, rk, sigma, b, c, p, n, nn, na, ks, dev):
-    from vgtk import _hip
-    ref = torch.empty(b, c, ks, p, na, device=dev)
-    _hip.call('eap_so3_inter_group_fwd_valu_f32', ref, b, c, p, n, nn, na, ks, _hip._F32(sigma), _hip._ptr(feats),
-              _hip._ptr(idx), _hip._ptr(gx), _hip._ptr(rk), _hip._ptr(None), _hip._ptr(ref))
-    return ref
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('shape', [
     (2, 64, 37, 37, 64, 60, 24),      # the shipped geometry: 64 channels = one full block, anchor groups 16+16+16+12
@@ -867,8 +842,7 @@ def test_two_tile_grouping_kernel_equals_one_tile_kernel(dev, vg, shape):
     out = {}
     assert _hip.lib.eap_so3_group_lists_tiles(0) == 2
     try:
-        modes = (1, 2, 3) if _hip.lib.eap_so3_group_lists_tiles(3) == 3 else (1, 2)     # 3: `make EXPERIMENTS=1` libraries only
-        for tiles in modes:
+        for tiles in (1, 2):
             assert _hip.lib.eap_so3_group_lists_tiles(tiles) == tiles
             out[tiles] = (_hip.so3_inter_group_fwd(feats, idx, gx, rk, None, sigma),
                           _hip.so3_inter_group_fwd(feats, idx, gx, rk, None, sigma, blocked=2),
@@ -884,12 +858,6 @@ def test_two_tile_grouping_kernel_equals_one_tile_kernel(dev, vg, shape):
     finally:
         _hip.lib.eap_so3_group_lists_store16(was)
     assert was == 1 and torch.equal(narrow, out[2][1]), 'forward, transposed: 16-byte row-end stores differ from dword stores'
-    # mode 3 (tools/experiments/kernels/so3_inter_lists3.hip: the same products on the bf16 matrix cores from exact 3 x bf16 splits of the fp32
-    # operands, fp32 accumulation) agrees with the fp32-MFMA kernels to fp32 rounding
-    if 3 in out:
-        for a, bb, what in zip(out[2], out[3], ('forward', 'forward, transposed', 'backward Z')):
-            assert rel_err(bb.cpu().numpy(), a.cpu().numpy()) < 1e-6, what
-        assert rel_err(out[3][0].cpu().numpy(), ref_valu(feats, idx, gx, rk, sigma, b, c, p, n, nn, na, ks, dev).cpu().numpy()) < 5e-6
     ref = torch.empty_like(out[2][0])
     _hip.call('eap_so3_inter_group_fwd_valu_f32', ref, b, c, p, n, nn, na, ks, _hip._F32(sigma), _hip._ptr(feats),
               _hip._ptr(idx), _hip._ptr(gx), _hip._ptr(rk), _hip._ptr(None), _hip._ptr(ref))

@@ -1,5 +1,5 @@
 """tools/gpu/dense_rows_ab.py: the dense product's block variants against each other (eap_so3_dense_block_rows: 0 = default, 128 = 128-row
-blocks; 256 = eight waves on 256-row blocks, only with tools/experiments/so3_dense_eight_waves.patch applied): outputs bit-equal?  times of both directions at the bench shape (layer 2, O = 512)."""
+blocks): outputs bit-equal?  times of both directions at the bench shape (layer 2, O = 512)."""
 import os, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..', '..'))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'equi-articulated-pose_amd'))

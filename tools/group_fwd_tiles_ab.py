@@ -1,5 +1,6 @@
-"""tools/group_fwd_tiles_ab.py [B]: the forward grouping launch (transposed intermediate, layout 2) of the two deep layers with the shipped
-two-tile fp32-MFMA kernel (tiles 2) and, in `make EXPERIMENTS=1` builds, the 3 x bf16 (3) and 2 x fp16 plane (4) kernels."""
+"""tools/group_fwd_tiles_ab.py [B]: the forward grouping launch (transposed intermediate, layout 2) of the two deep layers with every
+grouping kernel generation the library accepts (eap_so3_group_lists_tiles: 2 = the shipped two-tile fp32-MFMA kernel; a value the
+library does not take is skipped)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'equi-articulated-pose_amd'))

@@ -38,7 +38,7 @@ for layer in (2, 1):
     cn = cnt.flatten().float()
     print(f'layer {layer} O={o} rcap={rcap}: list lengths mean {cn[cn > 0].mean().item():.0f} max {cn.max().item():.0f} min {cn[cn > 0].min().item():.0f}', flush=True)
     zref = None
-    for tiles, xmap in ((2, 1), (3, 1), (4, 1)):   # 3, 4: `make EXPERIMENTS=1` builds (3 x bf16 planes / 2 x fp16 planes on the 16-bit matrix cores)
+    for tiles, xmap in ((2, 1), (3, 1), (4, 1)):   # (a generation the library does not take is skipped)
         if _hip.lib.eap_so3_group_lists_tiles(tiles) != tiles:
             continue
         _hip.lib.eap_so3_group_lists_xcd_map(1, xmap)

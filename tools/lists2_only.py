@@ -1,7 +1,7 @@
-"""tools/lists2_ablation.py [B] -- where the time of the two-tile grouping kernel (csrc/so3_inter_lists2.hip) goes: the
-deepest layer's backward (O = 512, real inverse lists) and forward (C = 128) launches with parts of the kernel switched
-off (EAP_LISTS2_DEBUG bits; needs a library built with `make -C equi-articulated-pose_amd/csrc clean && make ... ABLATION=1`;
-results of the ablated runs are wrong by design).  Also the XCD map A/B (mode 1 / 2).  Median of 5 interleaved rounds."""
+"""tools/lists2_only.py [B] (was tools/lists2_ablation.py) -- the two-tile grouping kernel (csrc/so3_inter_lists2.hip) alone: the deepest layer's backward
+(O = 512, real inverse lists) and forward (C = 128) launches, then the XCD map A/B (eap_so3_group_lists_xcd_map, mode 1 / 2).
+Median of 5 runs.  (The timing ablations that switched parts of the kernel off are recorded in profiles/r0[234]_lists2_ablation.txt;
+their code left the tree with the ablation build.)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'equi-articulated-pose_amd'))
@@ -23,8 +23,6 @@ rk = L.rotated_kernels(conv.anchors, conv.kernels)
 rows, off, cnt, ent_p, ent_gx, rcap, _ = L._inverse_lists(idx, gx, P, 29, nonident)
 gy = torch.randn(B, o, P, NA, device=dev)
 feats = torch.randn(B, c, P, NA, device=dev)
-CASES = [('full kernel', 0), ('no feature DMA', 1), ('feature DMA of the same 8 rows (hits only)', 512), ('constant weights', 2), ('no row-end stores', 4), ('row-end stores in address order (wrong places)', 1024), ('no LDS operand reads', 16),
-         ('no DMA, no barrier', 9), ('no DMA, constant weights', 3), ('no DMA, no weights, no LDS reads', 19), ('MFMAs + barrier only', 23), ('MFMAs only', 31)]
 
 
 def timed(fn):
@@ -42,15 +40,8 @@ def fwd():
 
 
 for name, fn, fl in (('backward Z, O = 512', inv, 2.0 * B * o * KS * P * NN * NA), ('forward X (transposed), C = 128', fwd, 2.0 * B * c * KS * P * NN * NA)):
-    res = {k: [] for k, _ in CASES}
-    for _ in range(6):
-        for k, bits in CASES:
-            os.environ['EAP_LISTS2_DEBUG'] = str(bits)
-            res[k].append(timed(fn))
-    os.environ['EAP_LISTS2_DEBUG'] = '0'
-    for k, bits in CASES:
-        v = sorted(res[k][1:])
-        print(f'{name}: {k:44s} (bits {bits:2d}): median {v[2]:7.2f} ms = {fl / v[2] / 1e9 / 157.3:.3f} of peak (algorithmic)', flush=True)
+    v = sorted(timed(fn) for _ in range(6))[:5]
+    print(f'{name}: median {v[2]:7.2f} ms = {fl / v[2] / 1e9 / 157.3:.3f} of peak (algorithmic)', flush=True)
     which = 1 if fn is inv else 0
     for mode in (1, 2):
         _hip.lib.eap_so3_group_lists_xcd_map(which, mode)

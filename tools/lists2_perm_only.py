@@ -1,7 +1,7 @@
-"""tools/lists2_perm_ablation.py -- where the extra time of the PERMUTED two-tile grouping kernel (csrc/so3_inter_lists2.hip,
-PERM) goes: the deepest layer's backward launch (O = 512, real inverse lists, random per-point poses) with parts switched
-off (EAP_LISTS2_DEBUG bits; library built with `make ABLATION=1`; ablated results are wrong by design), next to the
-identity-pose launch on the same lists."""
+"""tools/lists2_perm_only.py (was tools/lists2_perm_ablation.py) -- where the extra time of the PERMUTED two-tile grouping kernel (csrc/so3_inter_lists2.hip,
+PERM) goes: the deepest layer's backward launch (O = 512, real inverse lists, random per-point poses) next to the identity-pose launch on
+the same lists and to the whole-row kernel.  (The timing ablations that switched parts of the kernel off are recorded in
+profiles/r04_lists2_perm_ablation.txt; their code left the tree with the ablation build.)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'equi-articulated-pose_amd'))
@@ -60,17 +60,7 @@ def whole_row():
     return _hip.so3_inter_group_inv(gy, rows, off, cnt, ent_p, ent_gx, rk, multinv, s, NN, ident, conv.anchors, coset)
 
 
-ABLATION = bool(os.environ.get('EAP_PERM_ABLATION'))         # library built with `make ABLATION=1`
-CASES = [('full kernel', 0)] + ([('no block move (own block by DMA)', 32), ('no in-block XOR', 64), ('neither', 96), ('no row-end stores', 4),
-                                 ('no feature DMA', 1), ('no LDS operand reads', 16), ('MFMAs only', 31 + 96)] if ABLATION else [])
-res = {k: [] for k, _ in CASES}
-for _ in range(6):
-    for k, bits in CASES:
-        os.environ['EAP_LISTS2_DEBUG'] = str(bits)
-        res[k].append(timed(perm2))
-os.environ['EAP_LISTS2_DEBUG'] = '0'
-for k, bits in CASES:
-    v = sorted(res[k][1:])
-    print(f'random poses, two-tile PERM kernel alone: {k:36s} (bits {bits:3d}): median {v[2]:7.2f} ms = {fl / v[2] / 1e9 / 157.3:.3f} of peak', flush=True)
+v = sorted(timed(perm2) for _ in range(6))[:5]
+print(f'random poses, two-tile PERM kernel alone: median {v[2]:7.2f} ms = {fl / v[2] / 1e9 / 157.3:.3f} of peak', flush=True)
 v = sorted(timed(whole_row) for _ in range(6))[:5]
 print(f'random poses, whole-row kernel (incl. the {t_re:.1f} ms re-order): median {v[2]:7.2f} ms', flush=True)

@@ -23,10 +23,12 @@ def key_of(name):
         elif ch == '(' and depth == 0:
             break
         out += ch
-    if out.startswith('gemm_dma_f32_kernel') or out.startswith('kc_gemm_kernel'):
-        out = re.sub(r',\s*0>$', '>', out)      # trailing default template argument of the GEMM (ablation switch)
-    m = re.match(r'(gemm_bf16x3_kernel|gemm_f16x2_kernel)<(\d+), (\d+), \d+, (\d+)(?:, (?:true|false))?>$', out)
-    if m:                                       # <MI, WN, ablation switch, B layout, pre-split weights> -> the name eap_last_kernel() reports
+    # (traces taken before the ablation switch left the template lists carry one more integer, always 0: kc_gemm_kernel<MI, FORM, 0>,
+    # gemm_dma_f32_kernel<..., false, false, 0> and the split kernels' <MI, WN, 0, B layout, pre-split weights>; both forms give the same key)
+    out = re.sub(r'^(kc_gemm_kernel<\d+, \d+), 0>$', r'\1>', out)
+    out = re.sub(r'^(gemm_dma_f32_kernel<.*(?:true|false)), 0>$', r'\1>', out)
+    m = re.match(r'(gemm_bf16x3_kernel|gemm_f16x2_kernel)<(\d+), (\d+), (?:0, )?(\d+), (?:true|false)>$', out)
+    if m:                                       # <MI, WN, B layout, pre-split weights> -> the name eap_last_kernel() reports
         out = '%s<%s, %s%s>' % (m.group(1), m.group(2), m.group(3), ('', ', nn', ', gather')[int(m.group(4))])
     return out if any(w in out for w in WANT) else None
 

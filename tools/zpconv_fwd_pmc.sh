@@ -1,5 +1,5 @@
 #!/bin/bash
-# counters of the two zpconv forward matrix kernels (tools/zpconv_fwd_ab.py)
+# counters of the zpconv forward matrix kernel (tools/zpconv_once.py)
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$1
@@ -7,7 +7,7 @@ mkdir -p $O
 cd /tmp
 for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVES" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS"; do
   tag=$(echo $c | tr ' ' '_' | cut -c1-40)
-  timeout 300 rocprofv3 --kernel-trace --pmc $c -d $O/pmc_$tag -o pmc --output-format csv -- python $R/tools/zpconv_fwd_ab.py > $O/pmc_$tag.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $c -d $O/pmc_$tag -o pmc --output-format csv -- python $R/tools/zpconv_once.py > $O/pmc_$tag.log 2>&1
 done
 cd $R
 python - <<PY
