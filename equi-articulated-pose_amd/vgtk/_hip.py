@@ -247,7 +247,8 @@ def gemm_reduce(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ld
     ops = (M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb), _I64(strideB))
     nt = not b_blocked and not transA and transB
     lead = (int(transA), int(transB))
-    if SPLIT_BF16_CONTRACTION and nt and lib.eap_gemm_bf16x3_reduce_f32_supported(*ops, _I64(ldc)):
+    # (the predicate never sees C, whose float4 stores the entry requires 16-byte aligned: checked here, so such a C falls through)
+    if SPLIT_BF16_CONTRACTION and nt and C.data_ptr() % 16 == 0 and lib.eap_gemm_bf16x3_reduce_f32_supported(*ops, _I64(ldc)):
         name, ws_words, lead = 'eap_gemm_bf16x3_reduce_f32', lib.eap_gemm_bf16x3_reduce_workspace, ()      # ('nt' only: no transposition flags)
     elif nt and lib.eap_gemm_skinny_reduce_f32_supported(*ops):
         # a small output over a long contraction (the first layer's weight gradient): streaming reduction, csrc/gemm_skinny.hip

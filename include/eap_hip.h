@@ -470,6 +470,14 @@ int eap_so3_intra_group_bwd_f32(int b, int c, int p, int na, int t, const float 
 
 /* ---- dense contraction (BasicSO3Conv.forward, so3conv/modules.py:L48-55) ------------------- */
 
+/* Operand contract of every GEMM entry below (pinned by tests/test_gpu_gemm_contract.py on buffers whose padding holds NaN):
+ *   - a leading dimension may exceed the logical width, a batch stride the size of an item, and a base may point anywhere
+ *     inside a larger allocation (subject to the alignment each entry or its `_supported` predicate states);
+ *   - nothing outside the logical elements of an input influences a result: rows, columns and k-tails a tile does not own are
+ *     selected as zero (or re-read from a valid row and discarded), never loaded from the padding and multiplied by zero;
+ *   - nothing outside [M, N] of each item of C is written: not the padding of a row (ldc > N), not the gap between two items,
+ *     not a word before the base or after the last row.  A residual is read at pitch ldc, inside [M, N] only. */
+
 /* Batched fp32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32), row-major:
  *   C_z[M,N] = op(A_z)[M,K] * op(B_z)[K,N]       z = 0..batch-1
  * transA = 0: A_z is [M,K] with leading dimension lda; 1: A_z is stored [K,M].  Same for B.
