@@ -231,17 +231,6 @@ def gemm_epilogue(transB, M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, bat
                                                        (scale, shift, slope, residual)))
 
 
-def gemm_nn_takes_split(M, N, K, A, lda, B, ldb):
-    """Would gemm(0, 0, ...) with these operands (one item) run on a split-operand kernel?"""
-    return bool(SPLIT_BF16_CONTRACTION and lib.eap_gemm_bf16x3_nn_f32_supported(M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(0)))
-
-
-def gemm_reduce_takes_split(M, N, K, A, lda, strideA, B, ldb, strideB, ldc):
-    """Would gemm_reduce(0, 1, ...) with these operands run on the split-bf16 kernel?"""
-    return bool(SPLIT_BF16_CONTRACTION and lib.eap_gemm_bf16x3_reduce_f32_supported(M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb),
-                                                                                  _I64(strideB), _I64(ldc)))
-
-
 def gemm_reduce(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, batch, b_blocked=False):
     tag = {'flops': 2.0 * M * N * K * batch, 'shape': ('gemm_reduce', int(transA), int(transB), M, N, K, batch)}
     ops = (M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb), _I64(strideB))
@@ -261,6 +250,90 @@ def gemm_reduce(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ld
             ops = ops[:7] + (_I64(N if transB else K),) + ops[8:]
     ws = torch.empty(max(int(ws_words(M, N, K, batch)), 1), dtype=torch.float32, device=C.device)
     call(name, C, *lead, *ops, _ptr(C), _I64(ldc), batch, _ptr(ws), tag=tag)
+
+
+# ---- the same products stated as tensor views -----------------------------------------------------
+# What vgtk/so3conv/functional.py calls: each operand a 2-D view [rows, cols] or a stack [batch, rows, cols] -- a slice of a larger buffer
+# (row pitch, item stride, storage offset), transposed or not.  The numbers of gemm / gemm_reduce / gemm_epilogue are read off the
+# views and checked against each other and against the views' storage before anything is launched.
+
+def operand(t, name='operand'):
+    """A float32 matrix view -> (trans, ld, stride, batch, rows, cols): what a GEMM entry is told about the memory behind it.  rows, cols
+    are the view's last two sizes; a 2-D view is one matrix shared by the batch (batch 1, stride 0), a 3-D view has batch = size(0) and
+    stride = stride(0).  trans = 0: the columns are contiguous (stride(-1) == 1) and ld = stride(-2) as torch reports it; trans = 1: the rows
+    are (stride(-2) == 1, the .transpose(-1, -2) of a row-major matrix) and ld = stride(-1).  A dimension of size 1 can make both readings
+    possible: trans = 0 wins.  Raises RuntimeError for another dtype or rank, when neither of the two strides is 1, and when the elements
+    addressed -- (batch - 1) * stride + (outer - 1) * ld + inner from the first -- do not fit the view's storage."""
+    shape, strides = t.shape, t.stride()
+    if t.dtype != torch.float32 or len(shape) not in (2, 3):
+        raise RuntimeError(f'{name}: a float32 view [rows, cols] or [batch, rows, cols], not {t.dtype} {tuple(shape)}')
+    rows, cols = shape[-2], shape[-1]
+    if strides[-1] == 1:
+        trans, ld, outer, inner = 0, strides[-2], rows, cols
+    elif strides[-2] == 1:
+        trans, ld, outer, inner = 1, strides[-1], cols, rows
+    else:
+        raise RuntimeError(f'{name}: neither the rows nor the columns are contiguous (strides {strides})')
+    batch, stride = (shape[0], strides[0]) if len(shape) == 3 else (1, 0)
+    extent = (batch - 1) * stride + (outer - 1) * ld + inner
+    if 4 * (t.storage_offset() + extent) > t.untyped_storage().nbytes():
+        raise RuntimeError(f'{name}: {tuple(shape)} with strides {strides} at offset {t.storage_offset()} addresses {extent} elements, '
+                           f'its storage holds {t.untyped_storage().nbytes() // 4}')
+    return trans, ld, stride, batch, rows, cols
+
+
+def _product(A, B, out, reduce=False):
+    """The numbers of out_z = A_z B_z (reduce: out = sum_z A_z B_z, out 2-D) from the three views, after the checks of `operand` and: the
+    inner sizes, the outer sizes and the batch counts agree, out is row-major and its rows and items do not overlap.
+    -> (transA, transB, M, N, K, lda, strideA, ldb, strideB, ldc, strideC, batch)"""
+    ta, lda, sa, ba, M, K = operand(A, 'A')
+    tb, ldb, sb, batch, Kb, N = operand(B, 'B')
+    tc, ldc, sc, bc, Mc, Nc = operand(out, 'out')
+    if B.dim() != 3 or out.dim() != 3 - reduce:
+        raise RuntimeError(f'B is a stack of matrices, out {"one matrix" if reduce else "a stack"}: got B {tuple(B.shape)}, out {tuple(out.shape)}')
+    if K != Kb or (M, N) != (Mc, Nc) or (A.dim() == 3 and ba != batch) or bc != (1 if reduce else batch):
+        raise RuntimeError(f'A {tuple(A.shape)} x B {tuple(B.shape)} -> out {tuple(out.shape)}: the sizes do not agree')
+    if tc:
+        raise RuntimeError(f'out must be row-major (strides {tuple(out.stride())})')
+    if (M > 1 and ldc < N) or (bc > 1 and sc < (M - 1) * ldc + N):
+        raise RuntimeError(f'out {tuple(out.shape)} with strides {tuple(out.stride())} overlaps itself')
+    return ta, tb, M, N, K, lda, sa, ldb, sb, ldc, sc, batch
+
+
+def matmul(A, B, out, b_bound=None):
+    """out_z = A_z B_z: `gemm` with its numbers taken from the views (b_bound: see gemm)."""
+    ta, tb, M, N, K, lda, sa, ldb, sb, ldc, sc, batch = _product(A, B, out)
+    gemm(ta, tb, M, N, K, A, lda, sa, B, ldb, sb, out, ldc, sc, batch, b_bound=b_bound)
+
+
+def matmul_reduce(A, B, out):
+    """out [M, N] = sum_z A_z B_z: `gemm_reduce` with its numbers taken from the views."""
+    ta, tb, M, N, K, lda, sa, ldb, sb, ldc, _, batch = _product(A, B, out, reduce=True)
+    gemm_reduce(ta, tb, M, N, K, A, lda, sa, B, ldb, sb, out, ldc, batch)
+
+
+def matmul_reduce_takes_split(A, B, out):
+    """Would matmul_reduce(A, B, out) run on the split-bf16 kernel?  Asks what gemm_reduce asks before it takes that kernel: besides the
+    kernel's own predicate (all gemm_reduce_takes_split asked), that the product is 'nt' and that out is 16-byte aligned."""
+    ta, tb, M, N, K, lda, sa, ldb, sb, ldc, _, _ = _product(A, B, out, reduce=True)
+    return bool(SPLIT_BF16_CONTRACTION and not ta and tb and out.data_ptr() % 16 == 0 and
+                lib.eap_gemm_bf16x3_reduce_f32_supported(M, N, K, _ptr(A), _I64(lda), _I64(sa), _ptr(B), _I64(ldb), _I64(sb), _I64(ldc)))
+
+
+def matmul_epilogue(A, B, out, scale, shift, slope, residual=None, b_bound=None):
+    """`gemm_epilogue` with its numbers taken from the views: A one row-major matrix shared by the batch; the residual a float32 tensor of
+    out's shape (trailing dimensions may be split or merged) whose elements sit at out's pitch and item stride: contiguous where out is, else
+    with out's strides.  -> False when the split kernel does not take the operands (nothing launched)."""
+    ta, tb, M, N, K, lda, sa, ldb, sb, ldc, sc, batch = _product(A, B, out)
+    if ta or (sa != 0 and batch != 1):
+        raise RuntimeError(f'A must be one row-major matrix shared by the batch, not {tuple(A.shape)} with strides {tuple(A.stride())}')
+    if residual is not None:
+        tight = residual.is_contiguous() and residual.numel() == batch * M * N and (ldc, sc) == (N, M * N)
+        if residual.dtype != torch.float32 or not (tight or (residual.shape == out.shape and residual.stride() == out.stride())):
+            raise RuntimeError(f'residual: float32 laid out like out {tuple(out.shape)} with strides {out.stride()}, not {residual.dtype} '
+                               f'{tuple(residual.shape)} with strides {residual.stride()}')
+        operand(residual.view(batch, M, N) if tight else residual, 'residual')
+    return gemm_epilogue(tb, M, N, K, A, lda, B, ldb, sb, out, ldc, sc, batch, scale, shift, slope, residual, b_bound)
 
 
 def so3_prep(q_xyz, s_xyz, idx, q_pose, s_pose, anchors, identity_anchor):

@@ -381,10 +381,9 @@ class _Contract(torch.autograd.Function):
             if not epilogue.inference:
                 raise RuntimeError('a folded epilogue is an inference-time fusion: build and use it under torch.no_grad()')
             res = None if epilogue.residual is None else epilogue.residual.contiguous().view(b, o, pa)
-            epilogue.applied = _hip.gemm_epilogue(0, o, pa, ck, W, ck, x, pa, ck * pa, y, pa, o * pa, b, epilogue.scale, epilogue.shift,
-                                                  epilogue.slope, res)
+            epilogue.applied = _hip.matmul_epilogue(W, x, y, epilogue.scale, epilogue.shift, epilogue.slope, res)
         if epilogue is None or not epilogue.applied:
-            _hip.gemm(0, 0, o, pa, ck, W, ck, 0, x, pa, ck * pa, y, pa, o * pa, b)
+            _hip.matmul(W, x, y)
         ctx.save_for_backward(W, x)
         return y
 
@@ -399,12 +398,12 @@ class _Contract(torch.autograd.Function):
             gx = torch.empty_like(x)          # W^T gy : [ck,o] [o,pa]
             if _hip.SPLIT_BF16_CONTRACTION and ck >= 128 and ck % 128 == 0 and o % 16 == 0:
                 Wt = W.t().contiguous()       # the split kernel reads its shared operand k-contiguous: [ck, o]
-                _hip.gemm(0, 0, ck, pa, o, Wt, o, 0, gy, pa, o * pa, gx, pa, ck * pa, b)
+                _hip.matmul(Wt, gy, gx)
             else:
-                _hip.gemm(1, 0, ck, pa, o, W, ck, 0, gy, pa, o * pa, gx, pa, ck * pa, b)
+                _hip.matmul(W.t(), gy, gx)
         if ctx.needs_input_grad[0]:
             gW = torch.empty_like(W)          # sum_b gy_b x_b^T : [o,pa] [pa,ck]
-            _hip.gemm_reduce(0, 1, o, ck, pa, gy, pa, o * pa, x, pa, ck * pa, gW, ck, b)
+            _hip.matmul_reduce(gy, x.transpose(1, 2), gW)
         return gW, gx, None
 
 
@@ -633,18 +632,21 @@ def _contract_into(W, x, y, layout, epilogue=None, b0=0, x_bound=None):
     _grouped_bound)."""
     b, c, ks, p, na = x.shape
     o = W.shape[0]
+    if layout == 2:
+        xt = x.view(b, p * na, c * ks).transpose(1, 2)  # the memory behind the nominal shape is X^T [b, pa, ck]
     if epilogue is not None and layout == 2:
         res = None if epilogue.residual is None else epilogue.residual[b0:b0 + b]
-        if _hip.gemm_epilogue(1, o, p * na, c * ks, W, c * ks, x, c * ks, c * ks * p * na, y, p * na, o * p * na, b,
-                              epilogue.scale, epilogue.shift, epilogue.slope, res, b_bound=x_bound):
+        if _hip.matmul_epilogue(W, xt, y, epilogue.scale, epilogue.shift, epilogue.slope, res, b_bound=x_bound):
             epilogue.applied = True
             return
         if b0 > 0 and epilogue.applied:
             raise RuntimeError('folded epilogue: the slabs of one contraction took different kernels')
     if layout == 2:                              # Y = W . (X^T)^T, both operands k-contiguous (csrc/gemm_dma_f32.hip)
-        _hip.gemm(0, 1, o, p * na, c * ks, W, c * ks, 0, x, c * ks, c * ks * p * na, y, p * na, o * p * na, b, b_bound=x_bound)
+        _hip.matmul(W, xt, y, b_bound=x_bound)
+    elif layout == 1:                            # blocked by 4: a storage without strides to read the numbers from -- the positional call
+        _hip.gemm(0, 0, o, p * na, c * ks, W, c * ks, 0, x, p * na, c * ks * p * na, y, p * na, o * p * na, b, b_blocked=True)
     else:
-        _hip.gemm(0, 0, o, p * na, c * ks, W, c * ks, 0, x, p * na, c * ks * p * na, y, p * na, o * p * na, b, b_blocked=layout == 1)
+        _hip.matmul(W, x.view(b, c * ks, p * na), y)
 
 
 def _grouped_bound(feats, idx):
@@ -711,14 +713,15 @@ def _weight_grad_from_z(z, fc, b, c, o, ks, ra, ldz=None):
     ldz = ra if ldz is None else ldz
     # (measured and dropped: 64 feature channels zero-padded to 128 rows to reach the split kernel -- 0.66 -> 0.53 ms per step, and the
     # kernel-against-kernel bar of tests/test_gpu_lists_and_modules.py::test_permuted_clouds_on_the_two_tile_kernel, 2e-6, went to 3.2e-6)
-    if _hip.gemm_reduce_takes_split(c, o * ks, ra, fc, ra, c * ra, z, ldz, o * ks * ldz, o * ks):
+    z = z.view(b, o * ks, ldz)[..., :ra]
+    dt = torch.empty(c, o * ks, dtype=torch.float32, device=z.device)
+    if _hip.matmul_reduce_takes_split(fc, z.transpose(1, 2), dt):
         # the transposed product Fc_b Z_b^T [c, o*ks] has the tile shape the split-bf16 kernel takes (>= 128 rows,
         # >= 256 columns); Z_b Fc_b^T with its 64-128 columns would stay on the fp32 pipe
-        dt = torch.empty(c, o * ks, dtype=torch.float32, device=z.device)
-        _hip.gemm_reduce(0, 1, c, o * ks, ra, fc, ra, c * ra, z, ldz, o * ks * ldz, dt, o * ks, b)
+        _hip.matmul_reduce(fc, z.transpose(1, 2), dt)
         return dt.view(c, o, ks).permute(1, 0, 2).reshape(o, c * ks).contiguous()
-    d = torch.empty(o * ks, c, dtype=torch.float32, device=z.device)    # sum_b Z_b Fc_b^T
-    _hip.gemm_reduce(0, 1, o * ks, c, ra, z, ldz, o * ks * ldz, fc, ra, c * ra, d, c, b)
+    d = dt.view(o * ks, c)                                              # sum_b Z_b Fc_b^T in the same o*ks*c floats
+    _hip.matmul_reduce(z, fc.transpose(1, 2), d)
     return d.view(o, ks, c).permute(0, 2, 1).reshape(o, c * ks).contiguous()
 
 
@@ -853,7 +856,7 @@ def _dense_g(fc4, W, geo):
         fc = torch.zeros(b, c, ld, dtype=torch.float32, device=fc4.device)
         fc[:, :, :ra] = fc4.reshape(b, c, ra)
     g = torch.empty(b, o * ks, ld, dtype=torch.float32, device=fc4.device)
-    _hip.gemm(0, 0, o * ks, ld, c, W3, c, 0, fc, ld, c * ld, g, ld, o * ks * ld, b)
+    _hip.matmul(W3, fc, g)
     return g.view(b, o, ks, ld), (None if ld == ra else ld), None
 
 
@@ -1039,7 +1042,7 @@ def _rows_grad_from_z(z, W2, c, rp, na, ldz, anchor_major, z_bound=None, reorder
     b_bound); reorder: the anchor axis of Z is coset-major, `reorder` = the position of every anchor in it."""
     b, (pad_c, oks) = z.shape[0], W2.shape
     gFc = torch.empty(b, pad_c, ldz, dtype=torch.float32, device=z.device)
-    _hip.gemm(0, 0, pad_c, ldz, oks, W2, oks, 0, z, ldz, oks * ldz, gFc, ldz, pad_c * ldz, b, b_bound=z_bound)
+    _hip.matmul(W2, z.view(b, oks, ldz), gFc, b_bound=z_bound)
     if anchor_major:
         return gFc[:, :c, :rp * na].reshape(b, c, na, rp).transpose(2, 3)
     gFc = gFc.view(b, c, rp, na)
@@ -1192,15 +1195,17 @@ def _backward_textbook(gy, W, feats, x, idx, gx, rk, mult, nonident, args, layou
         # (measured and dropped: every cloud's dY_b X^T_b on the split-operand 'nn' kernel instead of the batch-reducing fp32 kernel --
         # 512 x 3072 outputs over K = 30720 are 48 workgroups without a split of K: 15.5 -> 48 ms at 16 x 512 points)
         if layout == 2:     # X^T [pa, ck]: dW = dY X^T is a plain row-major product
-            _hip.gemm_reduce(0, 0, o, ck, pa, gy, pa, o * pa, x, ck, ck * pa, gW, ck, b)
+            _hip.matmul_reduce(gy.view(b, o, pa), x.view(b, pa, ck), gW)
+        elif layout == 1:   # blocked by 4: a storage without strides to read the numbers from -- the positional call
+            _hip.gemm_reduce(0, 1, o, ck, pa, gy, pa, o * pa, x, pa, ck * pa, gW, ck, b, b_blocked=True)
         else:
-            _hip.gemm_reduce(0, 1, o, ck, pa, gy, pa, o * pa, x, pa, ck * pa, gW, ck, b, b_blocked=layout == 1)
+            _hip.matmul_reduce(gy.view(b, o, pa), x.view(b, ck, pa).transpose(1, 2), gW)
     if need_f:
         gx_ = torch.empty_like(x.view(b, ck, pa))      # W^T gy
         # (W^T written out -- a few MB: the product is then 'nn' with a shared A operand, which the split-operand kernels take;
         # with the transposition left to the GEMM it ran on the fp32 matrix pipe: 15.6 of the 61.6 ms step at 16 x 512 points)
         Wt = W.t().contiguous()
-        _hip.gemm(0, 0, ck, pa, o, Wt, o, 0, gy.view(b, o, pa), pa, o * pa, gx_, pa, ck * pa, b)
+        _hip.matmul(Wt, gy.view(b, o, pa), gx_)
         gF = _hip.so3_inter_group_bwd(gx_.view(b, c, ks, p, na), idx, gx, rk, mult, args.sigma, n, args.ident)
     return gF, gW
 
@@ -1218,11 +1223,11 @@ def _backward_map(gy, W, feats, x, args, need_f, need_w):
         if x is None:
             x = _hip.so3_inter_group_fwd_map(feats, idx, gx, rk, amap, args.sigma)
         gW = torch.empty_like(W)          # sum_b gy_b x_b^T
-        _hip.gemm_reduce(0, 1, o, ck, pa, gy, pa, o * pa, x, pa, ck * pa, gW, ck, b)
+        _hip.matmul_reduce(gy.view(b, o, pa), x.view(b, ck, pa).transpose(1, 2), gW)
     if need_f:
         gx_ = torch.empty(b, ck, pa, dtype=torch.float32, device=gy.device)      # W^T gy
         Wt = W.t().contiguous()
-        _hip.gemm(0, 0, ck, pa, o, Wt, o, 0, gy.view(b, o, pa), pa, o * pa, gx_, pa, ck * pa, b)
+        _hip.matmul(Wt, gy.view(b, o, pa), gx_)
         gF = _hip.so3_inter_group_bwd_map(gx_.view(b, c, ks, p, na), idx, gx, rk, amap, args.sigma, n)
     return gF, gW
 
@@ -1362,7 +1367,7 @@ class _IntraConv(torch.autograd.Function):
                 c1 = min(c, c0 + INTRA_DW_SLICE)
                 g = _hip.so3_intra_group_fwd(feats[:, c0:c1].contiguous(), idx32)       # [b, cs, nt, p, na]
                 d = torch.empty(o, (c1 - c0) * nt, dtype=torch.float32, device=gy.device)
-                _hip.gemm_reduce(0, 1, o, (c1 - c0) * nt, pa, gy, pa, o * pa, g, pa, (c1 - c0) * nt * pa, d, (c1 - c0) * nt, b)
+                _hip.matmul_reduce(gy.view(b, o, pa), g.view(b, (c1 - c0) * nt, pa).transpose(1, 2), d)
                 gW[:, c0:c1] = d.view(o, c1 - c0, nt)
             gW = gW.view(o, c * nt)
         return gF, gW, None

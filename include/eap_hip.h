@@ -310,6 +310,9 @@ int eap_so3_inter_group_inv_f32(int b, int o, int p, int nn, int na, int ks, int
 /* dst [rows, na] = src with its anchor axis re-ordered, dst[., i] = src[., order[i]]: for na = 4 mod 8 the entry below takes gy's
  * rows by DMA and expects them in coset-major order already. */
 int eap_anchor_reorder_f32(int64_t rows, int na, const float *src, const uint8_t *order, float *dst, eap_stream_t stream);
+/* The same for [b, rows_per_cloud, na] with a flag per cloud: clouds whose nonident[b] is 0 are skipped (dst left unwritten). */
+int eap_anchor_reorder_clouds_f32(int b, int64_t rows_per_cloud, int na, const float *src, const uint8_t *order,
+                                  const int32_t *nonident, float *dst, eap_stream_t stream);
 int eap_so3_inter_group_inv_coset_f32(int b, int o, int p, int nn, int na, int ks, int rcap, float sigma,
                                       const float *gy, const int32_t *rows, const int32_t *off, const int32_t *cnt,
                                       const int32_t *ent_p, const float *ent_gx, const float *rk, const uint8_t *multinv,

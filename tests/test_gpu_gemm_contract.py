@@ -391,13 +391,24 @@ def dispatch(call, fn):
     return out, gemms[0]
 
 
-@pytest.mark.parametrize('M,N,K,batch,ta,tb,shared,tight_entry', [
+DISPATCHER_GEMM = [
     (128, 384, 48, 3, 0, 1, True, 'eap_gemm_bf16x3_f32'),
     (128, 384, 48, 3, 0, 0, True, 'eap_gemm_bf16x3_nn_f32'),
     (100, 260, 48, 2, 0, 1, False, 'eap_gemm_dma_f32'),
     (128, 384, 48, 3, 1, 0, False, 'eap_gemm_dma_f32'),
     (37, 19, 17, 2, 0, 0, False, 'eap_gemm_f32'),
-])
+]
+DISPATCHER_GEMM_EPILOGUE = [(128, 384, 48, 3, 1, True), (256, 256, 16, 1, 0, True), (100, 260, 48, 2, 1, False)]
+DISPATCHER_GEMM_REDUCE = [
+    (128, 256, 1024, 1, 0, 1, 'eap_gemm_bf16x3_reduce_f32', 'eap_gemm_bf16x3_reduce_f32'),
+    (40, 17, 4099, 2, 0, 1, 'eap_gemm_f32_reduce', 'eap_gemm_skinny_reduce_f32'),
+    (100, 40, 2080, 3, 0, 1, 'eap_gemm_dma_f32_reduce', 'eap_gemm_dma_f32_reduce'),
+    (100, 40, 2080, 3, 1, 0, 'eap_gemm_dma_f32_reduce', 'eap_gemm_dma_f32_reduce'),
+    (37, 19, 1043, 2, 0, 1, 'eap_gemm_f32_reduce', 'eap_gemm_f32_reduce'),
+]
+
+
+@pytest.mark.parametrize('M,N,K,batch,ta,tb,shared,tight_entry', DISPATCHER_GEMM)
 def test_dispatcher_gemm(dev, M, N, K, batch, ta, tb, shared, tight_entry):
     from vgtk import _hip
     for variant in gc.VARIANTS:
@@ -411,7 +422,7 @@ def test_dispatcher_gemm(dev, M, N, K, batch, ta, tb, shared, tight_entry):
             assert entry == 'eap_gemm_f32'
 
 
-@pytest.mark.parametrize('M,N,K,batch,tb,takes', [(128, 384, 48, 3, 1, True), (256, 256, 16, 1, 0, True), (100, 260, 48, 2, 1, False)])
+@pytest.mark.parametrize('M,N,K,batch,tb,takes', DISPATCHER_GEMM_EPILOGUE)
 def test_dispatcher_gemm_epilogue(dev, M, N, K, batch, tb, takes):
     """_hip.gemm_epilogue launches the split kernel where its predicate accepts the operands, and nothing at all where it does not
     (without a residual: the dispatcher passes one at C's item stride, the harness lays it out at its own)"""
@@ -434,13 +445,7 @@ def test_dispatcher_gemm_epilogue(dev, M, N, K, batch, tb, takes):
             assert not names and bool((C.buf.view(torch.int32) == gc.FILL_BITS).all())
 
 
-@pytest.mark.parametrize('M,N,K,batch,ta,tb,tight_entry,padded_entry', [
-    (128, 256, 1024, 1, 0, 1, 'eap_gemm_bf16x3_reduce_f32', 'eap_gemm_bf16x3_reduce_f32'),
-    (40, 17, 4099, 2, 0, 1, 'eap_gemm_f32_reduce', 'eap_gemm_skinny_reduce_f32'),
-    (100, 40, 2080, 3, 0, 1, 'eap_gemm_dma_f32_reduce', 'eap_gemm_dma_f32_reduce'),
-    (100, 40, 2080, 3, 1, 0, 'eap_gemm_dma_f32_reduce', 'eap_gemm_dma_f32_reduce'),
-    (37, 19, 1043, 2, 0, 1, 'eap_gemm_f32_reduce', 'eap_gemm_f32_reduce'),
-])
+@pytest.mark.parametrize('M,N,K,batch,ta,tb,tight_entry,padded_entry', DISPATCHER_GEMM_REDUCE)
 def test_dispatcher_gemm_reduce(dev, M, N, K, batch, ta, tb, tight_entry, padded_entry):
     from vgtk import _hip
     for variant in gc.VARIANTS + (C_ODD,):
@@ -469,3 +474,128 @@ def test_dispatcher_gemm_reduce_with_c_inside_its_storage(dev):
         assert _hip.lib.eap_gemm_bf16x3_reduce_f32_supported(M, N, K, P(A), I(A.ld), I(A.stride), P(B), I(B.ld), I(B.stride), I(C.ld))
         _, entry = dispatch(call, lambda: _hip.gemm_reduce(0, 1, M, N, K, A.tensor(), A.ld, A.stride, B.tensor(), B.ld, B.stride, C.tensor(), C.ld, 1))
         assert entry == 'eap_gemm_dma_f32_reduce'
+
+
+# ---- the same through the view-based calls -----------------------------------------------------------------------------------
+
+def views(call):
+    """the case's operands as strided views over A.tensor(), B.tensor(), C.tensor(): what _hip.matmul* take (a shared A and the C of a
+    reduction are 2-D; an operand stored transposed is the transpose of its stored matrix)"""
+    c = call.case
+
+    def view(op, trans, flat):
+        t = op.tensor()
+        v = torch.as_strided(t, (op.rows, op.cols), (op.ld, 1)) if flat else torch.as_strided(t, (op.nb, op.rows, op.cols), (op.item_stride, op.ld, 1))
+        return v.transpose(-1, -2) if trans else v
+    return view(call.A, c.transA, c.shared_a), view(call.B, c.transB, False), view(call.C, 0, c.reduce)
+
+
+def positional_pick(case, dev, fn):
+    """the entry the positional dispatcher launches for this case (fn(_hip, call): the positional call), on buffers of its own"""
+    from vgtk import _hip
+    call = case.materialise(dev)
+    _, names = launched(lambda: fn(_hip, call))
+    torch.cuda.synchronize()
+    gemms = [n for n in names if 'gemm' in n]
+    assert len(gemms) == 1, names
+    return gemms[0]
+
+
+def _gemm(_hip, call):
+    c, (A, B, C) = call.case, abc(call)
+    _hip.gemm(c.transA, c.transB, c.M, c.N, c.K, A.tensor(), A.ld, A.stride, B.tensor(), B.ld, B.stride, C.tensor(), C.ld, C.stride, c.batch)
+
+
+def _gemm_reduce(_hip, call):
+    c, (A, B, C) = call.case, abc(call)
+    _hip.gemm_reduce(c.transA, c.transB, c.M, c.N, c.K, A.tensor(), A.ld, A.stride, B.tensor(), B.ld, B.stride, C.tensor(), C.ld, c.batch)
+
+
+@pytest.mark.parametrize('M,N,K,batch,ta,tb,shared,tight_entry', DISPATCHER_GEMM)
+def test_views_gemm(dev, M, N, K, batch, ta, tb, shared, tight_entry):
+    """test_dispatcher_gemm through _hip.matmul: one entry, the one the positional call picks, the same contract"""
+    from vgtk import _hip
+    for variant in gc.VARIANTS:
+        case = Case('_hip.matmul', M, N, K, batch, ta, tb, variant, shared_a=shared)
+        call = case.materialise(dev)
+        _, entry = dispatch(call, lambda: _hip.matmul(*views(call)))
+        assert entry == positional_pick(case, dev, _gemm)
+        if variant == 'tight':
+            assert entry == tight_entry
+        if variant == 'odd':
+            assert entry == 'eap_gemm_f32'
+
+
+@pytest.mark.parametrize('M,N,K,batch,tb,takes', DISPATCHER_GEMM_EPILOGUE)
+def test_views_gemm_epilogue(dev, M, N, K, batch, tb, takes):
+    """test_dispatcher_gemm_epilogue through _hip.matmul_epilogue: the split kernel where it takes the operands, else False and nothing launched"""
+    from vgtk import _hip
+    for variant in gc.VARIANTS:
+        call = Case('_hip.matmul_epilogue', M, N, K, batch, 0, tb, variant, shared_a=True, epilogue='ep').materialise(dev)
+        A, B, C = abc(call)
+        out, names = launched(lambda: _hip.matmul_epilogue(*views(call), call.scale, call.shift, call.slope))
+        torch.cuda.synchronize()
+        assert out == (takes and variant != 'odd')
+        if out:
+            gemms = [n for n in names if 'gemm' in n]
+            assert len(gemms) == 1, names
+            gc.record(call, 'via dispatcher: ' + gemms[0], 0.0)
+            call.check()
+            assert accepts(gemms[0], call.case, A, B, C)
+        else:
+            assert not names and bool((C.buf.view(torch.int32) == gc.FILL_BITS).all())
+
+
+@pytest.mark.parametrize('M,N,K,batch,ta,tb,tight_entry,padded_entry', DISPATCHER_GEMM_REDUCE)
+def test_views_gemm_reduce(dev, M, N, K, batch, ta, tb, tight_entry, padded_entry):
+    """test_dispatcher_gemm_reduce through _hip.matmul_reduce"""
+    from vgtk import _hip
+    for variant in gc.VARIANTS + (C_ODD,):
+        for shared in strides_of_a(batch):
+            case = Case('_hip.matmul_reduce', M, N, K, batch, ta, tb, variant, shared_a=shared, reduce=True)
+            call = case.materialise(dev)
+            _, entry = dispatch(call, lambda: _hip.matmul_reduce(*views(call)))
+            assert entry == positional_pick(case, dev, _gemm_reduce)
+            if variant == 'tight':
+                assert entry == tight_entry
+            if variant == 'padded':
+                assert entry == padded_entry
+            if variant == 'odd':
+                assert entry == 'eap_gemm_f32_reduce'
+
+
+def test_views_gemm_reduce_with_c_inside_its_storage(dev):
+    """test_dispatcher_gemm_reduce_with_c_inside_its_storage through _hip.matmul_reduce; matmul_reduce_takes_split sees C and says no"""
+    from vgtk import _hip
+    M, N, K = 128, 256, 1024
+    for variant in ('tight', 'padded'):
+        call = Case('_hip.matmul_reduce', M, N, K, 1, 0, 1, variant, reduce=True, c_base_extra=1).materialise(dev)
+        A, B, C = abc(call)
+        assert C.ptr() % 16 == 4 and C.ld % 4 == 0
+        assert _hip.lib.eap_gemm_bf16x3_reduce_f32_supported(M, N, K, P(A), I(A.ld), I(A.stride), P(B), I(B.ld), I(B.stride), I(C.ld))
+        assert not _hip.matmul_reduce_takes_split(*views(call))
+        _, entry = dispatch(call, lambda: _hip.matmul_reduce(*views(call)))
+        assert entry == 'eap_gemm_dma_f32_reduce'
+
+
+def test_views_refuse_before_anything_is_launched(dev):
+    """host-side refusals: an input view that claims a column more than its storage holds, an out whose items overlap -- RuntimeError,
+    no entry launched, C untouched"""
+    from vgtk import _hip
+    M, N, K, batch = 37, 19, 17, 2
+    call = Case('_hip.matmul', M, N, K, batch, 0, 0, 'tight').materialise(dev)
+    A, B, C = views(call)
+    claims = torch.zeros(batch, K, N, dtype=torch.float32, device=dev)
+    claims.untyped_storage().resize_(4 * (claims.numel() - 1))                     # the last column of its last row is gone
+    overlapping = torch.as_strided(call.C.tensor(), (batch, M, N), (M * N - 1, N, 1))
+    rec = []
+    _hip.KERNEL_TIMES = rec
+    try:
+        for fn in (lambda: _hip.matmul(A, claims, C), lambda: _hip.matmul_reduce(A, claims, C[0]), lambda: _hip.matmul(A, B, overlapping),
+                   lambda: _hip.matmul_epilogue(A[0], B, overlapping, call.A.buf[:M], call.A.buf[:M], 0.25)):
+            with pytest.raises(RuntimeError):
+                fn()
+    finally:
+        _hip.KERNEL_TIMES = None
+    torch.cuda.synchronize()
+    assert rec == [] and bool((call.C.buf.view(torch.int32) == gc.FILL_BITS).all())
