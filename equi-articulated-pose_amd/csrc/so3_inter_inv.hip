@@ -21,14 +21,8 @@
 // so the rotated kernel points come from an LDS table instead of registers.
 #include "common.h"
 #include "device_prims.h"
+#include "kernel_weight.h"
 #include <algorithm>
-
-#ifdef EAP_INV_TRACE
-__device__ unsigned long long eap_inv_trace[8 * 16];
-#define TR(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); tr[i] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define TR(i)
-#endif
 
 namespace {
 
@@ -135,21 +129,9 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
     for (int ai = 0; ai < APW; ++ai)
         am[ai] = COSET ? __builtin_amdgcn_readfirstlane((int)order[min(a_beg + ai, na - 1)]) : min(a_beg + ai, na - 1);
     const int lk = lane & 31, lh = lane >> 5;
-    const int lkc = min(lk, ks - 1);
-    // kernel weight  w = relu(1 - |g - k|^2 / sigma) = relu(base_e + kc + g . k'),
-    //   base_e = 1 - |g|^2/sigma (once per entry),  k' = 2k/sigma,  kc = -|k|^2/sigma (constants):
-    // 3 FMAs + add + max per weight instead of 9 operations; unused kernel-point columns carry
-    // kc = -1e30 so their weight is 0
-    // evaluated with as few VALU instructions as it takes (they cost fp32-MFMA time on this part, csrc/so3_inter_lists.hip):
-    // two anchors per packed instruction, the relu as the clamp modifier of the last FMA
-    f32x2 kxp[APW / 2], kyp[APW / 2], kzp[APW / 2], kcp[APW / 2];
-#pragma unroll
-    for (int ai = 0; ai < APW; ++ai) {
-        const float *r3 = rk + ((size_t)am[ai] * ks + lkc) * 3;
-        const float x = r3[0], y = r3[1], z = r3[2];
-        kxp[ai >> 1][ai & 1] = 2.f * inv_sigma * x; kyp[ai >> 1][ai & 1] = 2.f * inv_sigma * y; kzp[ai >> 1][ai & 1] = 2.f * inv_sigma * z;
-        kcp[ai >> 1][ai & 1] = lk < ks ? -inv_sigma * (x * x + y * y + z * z) : -1e30f;
-    }
+    // per-lane weight constants of this wave's anchors (k = lane & 31), general form of the evaluation: csrc/kernel_weight.h
+    kernel_weight::Constants<APW> kw;
+    kw.load(rk, ks, lk, inv_sigma, [&](int ai) { return am[ai]; });
 
     f32x16 acc[APW];
 #pragma unroll
@@ -327,15 +309,9 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
     // mid() / end() run after the first / second half of the step's MFMAs (the DMA path requests
     // the next chunk's rows there, a few at a time, so the memory pipe never backs up into a wave)
     auto step_g = [&](const float4 g, const float (&fa)[APW], auto mid, auto end) {
-        const float base = 1.0f - inv_sigma * (g.x * g.x + g.y * g.y + g.z * g.z);
         // all weights of the step first (independent chains), then the MFMAs back to back
         f32x2 wv[APW / 2];
-#pragma unroll
-        for (int j = 0; j < APW / 2; ++j) {
-            f32x2 x = __builtin_elementwise_fma((f32x2){g.x, g.x}, kxp[j], kcp[j] + (f32x2){base, base});
-            x = __builtin_elementwise_fma((f32x2){g.y, g.y}, kyp[j], x);
-            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp\n\ts_nop 1" : "=v"(wv[j]) : "v"((f32x2){g.z, g.w}), "v"(kzp[j]), "v"(x));
-        }
+        kw.template eval<false>(g, kernel_weight::entry_base(g, inv_sigma), wv);
         // no per-anchor guard: a wave with fewer than APW anchors repeats its last one into
         // accumulators the epilogue never stores (its SIMD partner owns a full set anyway)
 #pragma unroll
@@ -352,9 +328,6 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
         step_g(s_g[gb * NBK + 2 * s + lh], fa, mid, end);
     };
 
-#ifdef EAP_INV_TRACE
-    unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#endif
     if constexpr (DMA && !HAS_MULT) {
         // No permutation: every LDS read of the chunk (operands of all four steps, offset vectors,
         // the next chunk's query points) is issued right after the barrier -- reads queued behind
@@ -364,7 +337,6 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
         int g0 = 0, g1 = 1, g2 = 2;                       // ring slots of chunks ch, ch+1, ch+2
         for (int ch = 0; ch < nchunk; ++ch) {
             const int buf = ch & 1, nb = buf ^ 1;
-            TR(0);
             const float *fbuf = s_f + (size_t)buf * NBK * CB * FP;
             float fa[4][APW];
             float4 gv[4];
@@ -376,7 +348,6 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
             prep_rows(g1);
             load_idx((ch + 2) * NBK);
             __builtin_amdgcn_sched_barrier(0);
-            TR(1);
             step_g(gv[0], fa[0], [&] { issue(0, nb); }, [&] { issue(1, nb); });
             __builtin_amdgcn_sched_barrier(0);
             step_g(gv[1], fa[1], [&] { issue(2, nb); }, [&] { issue(3, nb); });
@@ -384,19 +355,15 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
             step_g(gv[2], fa[2], [&] { issue(4, nb); }, [&] { issue(5, nb); });
             __builtin_amdgcn_sched_barrier(0);
             step_g(gv[3], fa[3], [&] { issue(6, nb); }, [&] { issue(7, nb); });
-            TR(2);
             store_idx(g2);
             dma_wait();
-            TR(3);
             __syncthreads();
-            TR(4);
             const int gt = g0; g0 = g1; g1 = g2; g2 = gt;
         }
     } else if constexpr (DMA) {
         int g0 = 0, g1 = 1, g2 = 2;                       // ring slots of chunks ch, ch+1, ch+2
         for (int ch = 0; ch < nchunk; ++ch) {
             const int buf = ch & 1, nb = buf ^ 1;
-            TR(0);
             const float *fbuf = s_f + (size_t)buf * NBK * CB * FP;
             float fa0[APW], fa1[APW];
             // operands of the first two steps before anything else, so the matrix pipe restarts
@@ -410,7 +377,6 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
             __builtin_amdgcn_sched_barrier(0);
             prep_rows(g1);
             __builtin_amdgcn_sched_barrier(0);
-            TR(1);
             step(g0, 0, fa0, [&] { issue(0, nb); }, [&] { issue(1, nb); issue(2, nb); });
             __builtin_amdgcn_sched_barrier(0);
             gather(fbuf, g0, 2, fa0);
@@ -422,23 +388,18 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
             step(g0, 2, fa0, [&] { issue(6, nb); }, [&] { issue(7, nb); });
             __builtin_amdgcn_sched_barrier(0);
             step(g0, 3, fa1, nothing, nothing);
-            TR(2);
             store_idx(g2);
             dma_wait();
-            TR(3);
             __syncthreads();
-            TR(4);
             const int gt = g0; g0 = g1; g1 = g2; g2 = gt;
         }
     } else
     for (int ch = 0; ch < nchunk; ++ch) {
         const int buf = ch & 1;
-        TR(0);
         if (ch + 1 < nchunk) {
             fetch((ch + 1) * NBK);
             fetch_index((ch + 2) * NBK);
         }
-        TR(1);
         const float *fbuf = s_f + (size_t)buf * NBK * CB * FP;
         float fa0[APW], fa1[APW];
         gather(fbuf, buf, 0, fa0);
@@ -456,18 +417,9 @@ __global__ __launch_bounds__(TM, 2) void so3_inter_group_inv_kernel(
         step(buf, 2, fa0, nothing, nothing);
         __builtin_amdgcn_sched_barrier(0);
         step(buf, 3, fa1, nothing, nothing);
-        TR(2);
         if (ch + 1 < nchunk) stash(buf ^ 1);
-        TR(3);
         __syncthreads();
-        TR(4);
     }
-#ifdef EAP_INV_TRACE
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0) {
-        for (int i = 0; i < 8; ++i) eap_inv_trace[wave * 16 + i] = tr[i];
-        eap_inv_trace[wave * 16 + 8] = nchunk;
-    }
-#endif
 
     // ---- epilogue: Z[b, o, k, ri, a'] (rows that are not referenced write zeros) ----------------
     float *s_o = s_f;
@@ -693,16 +645,5 @@ static int group_inv(int b, int o, int p, int nn, int na, int ks, int rcap, floa
     } else if (multinv) e = dma ? launch(so3_inter_group_inv_kernel<true, true>) : launch(so3_inter_group_inv_kernel<true, false>);
     else e = dma ? launch(so3_inter_group_inv_kernel<false, true>) : launch(so3_inter_group_inv_kernel<false, false>);
     if (e) return e;
-#ifdef EAP_INV_TRACE
-    {
-        unsigned long long h[8 * 16];
-        hipDeviceSynchronize();
-        hipMemcpyFromSymbol(h, HIP_SYMBOL(eap_inv_trace), sizeof(h));
-        for (int w = 0; w < 8 && h[w * 16 + 8] > 0; ++w)
-            fprintf(stderr, "inv trace wave %d: chunks %llu  fetch %llu  compute %llu  stash %llu  barrier %llu  (cycles/chunk)\n", w,
-                    h[w * 16 + 8], h[w * 16 + 1] / h[w * 16 + 8], h[w * 16 + 2] / h[w * 16 + 8], h[w * 16 + 3] / h[w * 16 + 8],
-                    h[w * 16 + 4] / h[w * 16 + 8]);
-    }
-#endif
     return eap::check_launch("so3_inter_group_inv");
 }

@@ -17,15 +17,11 @@
 //     row r sits in slot (w + r) mod 8 (the rotation is applied on the global-address side, for free), so
 //     the 32 channel lanes of an operand read land on different banks and ONE ds_read_b128 brings the
 //     wave's four anchors.
-//   * B operand: never in memory.  Lane (k = l&31, e = l>>5) evaluates
-//     w = clamp(1 - |g|^2/s - |kappa_k|^2/s + g.(2 A_a kappa_k / s)) in registers.  The fp32 MFMA and the
-//     vector ALU share their multipliers on this part (tools/microbench/mfma_waves.hip: every VALU
-//     instruction between MFMAs costs its 4 cycles of matrix time at ANY occupancy; the round-1 loop
-//     spent 150 VALU instructions per 16 MFMAs and sat at 95 % of the resulting 63 % ceiling), so the
-//     loop is written for VALU count: weights of two anchors per packed instruction (v_pk_add/v_pk_fma,
-//     relu = the clamp modifier of the last FMA: 2 instructions per weight instead of 5), the per-entry
-//     term evaluated once per chunk by 8 lanes and handed out by ds_bpermute, every LDS address an
-//     immediate offset of one register, no 64-bit address arithmetic: ~48 VALU per 16 MFMAs.
+//   * B operand: never in memory.  Lane (k = l&31, e = l>>5) evaluates its weights in registers, and because
+//     VALU instructions cost matrix time on this part the loop is written for VALU count (csrc/kernel_weight.h
+//     has the evaluation and the why): the per-entry term evaluated once per chunk by 8 lanes and handed out by
+//     ds_bpermute, every LDS address an immediate offset of one register, no 64-bit address arithmetic: ~48 VALU
+//     per 16 MFMAs.
 //   * The anchors of a row are split into two groups (32 + 28 at na = 60) handled by different
 //     workgroups: 4 anchors per wave = 64 accumulator VGPRs, under 128 VGPRs in total and 64 KB of
 //     LDS, so TWO workgroups share a CU.  A workgroup is alone for its chunk barrier, its DMA
@@ -36,6 +32,8 @@
 //     in the forward a workgroup streams through 8 consecutive rows without draining its pipeline.
 #include "common.h"
 #include "device_prims.h"
+#include "group_lists.h"
+#include "kernel_weight.h"
 #include <type_traits>
 
 namespace {
@@ -60,21 +58,12 @@ __global__ __launch_bounds__(TM, 4) void so3_group_lists_kernel(
     const float *__restrict__ rk, const int32_t *__restrict__ nonident, float *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
-    // ---- block -> (row, anchor group, channel slice, cloud); XCDs get whole (slice, cloud) pairs ----
+    // ---- block -> (row run, anchor group, channel slice, cloud): csrc/group_lists.h ----
     const int nrun = (R + RPB - 1) / RPB;                 // runs of RPB consecutive rows (RPB = 1 with lists)
-    const int ny = gridDim.y, nsl = ny * gridDim.z, per_slice = nrun * AG;
-    int qd = blockIdx.x, sl = blockIdx.y + ny * blockIdx.z;
-    if ((nsl & 7) == 0) {
-        const unsigned lin = blockIdx.x + (unsigned)per_slice * (blockIdx.y + (unsigned)ny * blockIdx.z);
-        const unsigned j = lin >> 3;
-        sl = (int)((lin & 7u) + 8u * (j / (unsigned)per_slice));
-        qd = (int)(j % (unsigned)per_slice);
-    } else {
-        qd = xcd_point(blockIdx.x, per_slice);           // contiguous rows per XCD (whole output lines in one L2)
-    }
-    const int run = qd / AG, ag = qd - run * AG;
+    int run, ag, sl;
+    group_lists::block_map(nrun, AG, run, ag, sl);
     const int r_begin = run * RPB, rows_blk = min(RPB, R - r_begin);
-    const int cy = sl % ny, bi = sl / ny, c0 = cy * CB;
+    const int ny = gridDim.y, cy = sl % ny, bi = sl / ny, c0 = cy * CB;
     if (nonident != nullptr && __builtin_amdgcn_readfirstlane(nonident[bi]) != 0) return;   // permuted cloud: not ours
 
     const int t = threadIdx.x, lane = t & 63;
@@ -89,48 +78,15 @@ __global__ __launch_bounds__(TM, 4) void so3_group_lists_kernel(
     float4 *s_g = reinterpret_cast<float4 *>(s_f + 2 * NBK * CB * PITCH);   // [3][NBK] ring
     int *s_p = reinterpret_cast<int *>(s_g + 3 * NBK);                      // [3][NBK] ring
 
-    // entries of the block: one list (backward), or the neighbours of rows_blk consecutive rows
-    // (forward; they are contiguous in idx / gx, and with nn a multiple of the chunk the flat chunk
-    // sequence never straddles two rows)
-    int n_ent, nchunk_row;
-    size_t e0;
-    if (LISTS) {
-        const int q = rows[(size_t)bi * R + r_begin];
-        n_ent = q >= 0 ? cnt[(size_t)bi * R + r_begin] : 0;
-        e0 = (size_t)bi * ent_stride + (q >= 0 ? off[(size_t)bi * R + r_begin] : 0);
-        nchunk_row = (n_ent + NBK - 1) / NBK;
-    } else {
-        n_ent = rows_blk * nn;
-        e0 = ((size_t)bi * R + r_begin) * nn;
-        nchunk_row = (nn + NBK - 1) / NBK;
-    }
-    const int nchunk = LISTS ? nchunk_row : rows_blk * nchunk_row;
+    // entries of the block: one list (backward), or the neighbours of rows_blk consecutive rows (forward)
+    const group_lists::Entries en = group_lists::entries<LISTS, NBK>(bi, R, r_begin, rows_blk, nn, ent_stride, rows, off, cnt);
+    const int n_ent = en.n_ent, nchunk_row = en.nchunk_row, nchunk = en.nchunk;
+    const size_t e0 = en.e0;
 
-    // ---- per-lane weight constants of this wave's anchors (k = lane & 31) -------------------------
-    // On this part the fp32 MFMA and the vector ALU share their multipliers (vector fp32 peak = matrix fp32 peak;
-    // tools/microbench/mfma_waves.hip: every VALU instruction between MFMAs costs its 4 cycles of matrix time at any
-    // occupancy), so the weight w = relu(1 - |g|^2/s - |kappa|^2/s + 2 g.kappa'/s) is evaluated with as few VALU
-    // instructions as it takes: everything goes through packed operations on two anchors at a time -- the
-    // per-entry term joins -|kappa|^2/s in one packed add, then three packed FMAs, and the relu is the clamp
-    // modifier of the last one (weights never exceed 1): 2 instructions per weight instead of 5.
-    f32x2 kxp[APW / 2], kyp[APW / 2], kzp[APW / 2], kcp[APW / 2];
-#pragma unroll
-    for (int ai = 0; ai < APW; ++ai) {
-        const int a = a0 + min(al_beg + ai, gcount - 1);
-        const float *r3 = rk + ((size_t)a * ks + min(lk, ks - 1)) * 3;
-        const float x = r3[0], y = r3[1], z = r3[2];
-        kxp[ai >> 1][ai & 1] = 2.f * inv_sigma * x;
-        kyp[ai >> 1][ai & 1] = 2.f * inv_sigma * y;
-        kzp[ai >> 1][ai & 1] = 2.f * inv_sigma * z;
-        kcp[ai >> 1][ai & 1] = lk < ks ? -inv_sigma * (x * x + y * y + z * z) : -1e30f;
-    }
-    // Kernel points rotated by the anchors all have the norm of the unrotated point, so -|kappa|^2/s is normally the same
-    // for the wave's four anchors (to rounding): it then joins the per-entry term with ONE plain add per k-step instead
-    // of two packed ones (a packed instruction costs the matrix pipe twice a plain one, tools/microbench/mfma_riders.hip).
-    // Arbitrary rk tables (norms that differ) keep the general form; the choice is wave-uniform.
-    const float kcl = kcp[0][0];
-    const bool kc_uniform = __all(fabsf(kcp[0][1] - kcl) <= 1e-6f * fabsf(kcl) && fabsf(kcp[1][0] - kcl) <= 1e-6f * fabsf(kcl) &&
-                                  fabsf(kcp[1][1] - kcl) <= 1e-6f * fabsf(kcl)) != 0;
+    // per-lane weight constants of this wave's anchors (k = lane & 31) and the form of their evaluation: csrc/kernel_weight.h
+    kernel_weight::Constants<APW> kw;
+    kw.load(rk, ks, lk, inv_sigma, [&](int ai) { return a0 + min(al_beg + ai, gcount - 1); });
+    const bool kc_uniform = kw.uniform();
     // operand read: the wave's four anchors are ONE 16-byte piece (piece wave_u) of channel row lk, stored at slot
     // (piece + row) mod 8 so that the 32 channel lanes of a read spread over the banks
     const float4 *fa_lane = reinterpret_cast<const float4 *>(s_f + (size_t)(lh * CB + lk) * PITCH + 4 * ((wave_u + lk) & 7));
@@ -188,15 +144,9 @@ __global__ __launch_bounds__(TM, 4) void so3_group_lists_kernel(
     }
     __syncthreads();
 
-    // per chunk: lane e (mod 8) evaluates the per-entry term 1 - |g_e|^2/s of the chunk's entry e, or a dead value
-    // for entries past the end of the list and for the forward's shadow rows; the k-steps fetch theirs by bpermute
+    // per chunk: the per-entry terms, dead for entries past the end of the list and for the forward's shadow rows
     auto chunk_bases = [&](int ch, int gslot) {
-        const int e = lane & (NBK - 1);
-        const float4 g = s_g[gslot * NBK + e];
-        float b = 1.0f - inv_sigma * (g.x * g.x + g.y * g.y + g.z * g.z);
-        bool dead = ch * NBK + e >= n_ent;
-        if (!LISTS) dead = dead || (unsigned)s_p[gslot * NBK + e] >= (unsigned)PF;
-        return __float_as_int(dead ? -1e30f : b);
+        return group_lists::chunk_bases<NBK, !LISTS>(s_g, s_p, gslot, ch, lane, n_ent, PF, inv_sigma);
     };
     // operands of one MFMA k-step (2 entries): the anchor pairs of this lane's channel row, the entry's offset
     // vector and its per-entry term
@@ -211,13 +161,7 @@ __global__ __launch_bounds__(TM, 4) void so3_group_lists_kernel(
     auto step = [&](auto kcu, const float4 g, float bk, const float4 fv, auto mid, auto end, bool first = false) {
         const float fa[APW] = {fv.x, fv.y, fv.z, fv.w};
         f32x2 wv[APW / 2];
-        const float bkc = bk + kcl;
-#pragma unroll
-        for (int j = 0; j < APW / 2; ++j) {
-            f32x2 x = __builtin_elementwise_fma((f32x2){g.x, g.x}, kxp[j], decltype(kcu)::value ? (f32x2){bkc, bkc} : kcp[j] + (f32x2){bk, bk});
-            x = __builtin_elementwise_fma((f32x2){g.y, g.y}, kyp[j], x);
-            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp\n\ts_nop 1" : "=v"(wv[j]) : "v"((f32x2){g.z, g.w}), "v"(kzp[j]), "v"(x));
-        }
+        kw.template eval<decltype(kcu)::value>(g, bk, wv);
         // unguarded: a wave whose last anchors fall off the group repeats its last one into
         // accumulators the epilogue never stores
         __builtin_amdgcn_s_setprio(3);                      // a wave with MFMAs ready goes first (-2.5 % on one box, A/B)
@@ -395,17 +339,12 @@ int launch(int blocked, int b, int C, int PF, int na, int fpitch, int ks, int R,
            const float *rk, const int32_t *nonident, float *out, hipStream_t s, const char *what) {
     Geometry g;
     if (!geometry(na, ks, g)) return eap::bad_arg("so3_group_lists: unsupported anchor / kernel-point count");
-    if (fpitch < na || (fpitch & 3) != 0) return eap::bad_arg("so3_group_lists: the feature row pitch must be a multiple of 4, at least the anchor count");
-    if ((long long)CB * PF * fpitch * 4 >= (1ll << 32) || PF >= (1 << 24) || fpitch * 4 >= (1 << 24))
-        return eap::bad_arg("so3_group_lists: 32 feature rows of a cloud exceed the 32-bit request offsets");
-    if (((long long)ks * R * na * 4 + 32ll * R * na + 64) * 4 >= (1ll << 31)) return eap::bad_arg("so3_group_lists: output rows too far apart for 32-bit store offsets");
+    if (int e = group_lists::check_operands("so3_group_lists", CB, PF, na, fpitch, ks, R)) return e;
     auto kern = blocked == 2 ? so3_group_lists_kernel<LISTS, LISTS ? 0 : 2> : blocked == 1 ? so3_group_lists_kernel<LISTS, LISTS ? 0 : 1>
                                                                                           : so3_group_lists_kernel<LISTS, 0>;
     int e = eap::allow_dynamic_lds(kern, g.shmem, what);
     if (e) return e;
-    // forward: a workgroup streams through a run of consecutive rows (the next row's entries and
-    // first chunk are in flight during the current row's last chunk)
-    const int RPB = LISTS ? 1 : ((nn % NBK) == 0 ? 8 : 1);
+    const int RPB = group_lists::rows_per_block(LISTS, nn, NBK);
     dim3 grid((R + RPB - 1) / RPB * g.AG, (C + CB - 1) / CB, b);
     hipLaunchKernelGGL(kern, grid, dim3(TM), g.shmem, s, C, PF, na, fpitch, ks, R, nn, ent_stride, g.AG, g.gsz, RPB, 1.0f / sigma, F,
                        rows, off, cnt, ent_p, reinterpret_cast<const float4 *>(ent_gx), rk, nonident, out);

@@ -8,7 +8,7 @@
 //
 // Why: on this part every vector-ALU instruction between two fp32 MFMAs costs its issue cycles of matrix time
 // (tools/microbench/mfma_waves.hip, mfma_riders.hip), and the weights -- the MFMA's B operand --
-// are evaluated in registers, ~3 plain-instruction equivalents each.  A weight depends on (entry, anchor, kernel point)
+// are evaluated in registers, ~3 plain-instruction equivalents each (csrc/kernel_weight.h).  A weight depends on (entry, anchor, kernel point)
 // but NOT on the channel, so the one lever left is channels per weight: a wave now feeds each weight register to two
 // v_mfma_f32_32x32x2_f32 (channel rows 0-31 and 32-63 of a 64-channel block) instead of one, halving the vector work per
 // matrix instruction; per-entry terms, ring reads and chunk barriers are shared the same way.
@@ -22,6 +22,8 @@
 // 64-byte row pitch, and still one contiguous 1 KB destination per global->LDS DMA instruction.
 #include "common.h"
 #include "device_prims.h"
+#include "group_lists.h"
+#include "kernel_weight.h"
 #include <type_traits>
 
 namespace {
@@ -84,8 +86,7 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
     //      number allows it, else a contiguous range of rows (whole output lines in one L2) ----
     const int nrun = (R + RPB - 1) / RPB;
     const int ny = gridDim.y, nsl = ny * gridDim.z, per_slice = nrun * AG;
-    int qd = blockIdx.x, sl = blockIdx.y + ny * blockIdx.z;
-    int run, ag;
+    int run, ag, sl;
     if (ag_major && ((nsl * AG) & 7) == 0) {
         // an XCD owns whole (slice, cloud, ANCHOR GROUP) triples: the rows of a cloud that its resident workgroups walk
         // at the same time are then 64-byte pieces, a quarter of the (slice, cloud) working set per point -- four times
@@ -97,16 +98,7 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
         ag = (int)(sl2 % (unsigned)AG);
         sl = (int)(sl2 / (unsigned)AG);
     } else {
-        if ((nsl & 7) == 0) {
-            const unsigned lin = blockIdx.x + (unsigned)per_slice * (blockIdx.y + (unsigned)ny * blockIdx.z);
-            const unsigned j = lin >> 3;
-            sl = (int)((lin & 7u) + 8u * (j / (unsigned)per_slice));
-            qd = (int)(j % (unsigned)per_slice);
-        } else {
-            qd = xcd_point(blockIdx.x, per_slice);
-        }
-        run = qd / AG;
-        ag = qd - run * AG;
+        group_lists::block_map(nrun, AG, run, ag, sl);       // (slice, cloud) pairs or row ranges: csrc/group_lists.h
     }
     const int r_begin = run * RPB, rows_blk = min(RPB, R - r_begin);
     const int cy = sl % ny, bi = sl / ny, c0 = cy * CB;
@@ -124,19 +116,9 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
     float4 *s_g = reinterpret_cast<float4 *>(s_f + 2 * NBK * CB * PITCH);   // [3][NBK] ring
     int *s_p = reinterpret_cast<int *>(s_g + 3 * NBK);                      // [3][NBK] ring (PERM: [3][NBK][4], byte offsets of the four pieces)
 
-    int n_ent, nchunk_row;
-    size_t e0;
-    if (LISTS) {
-        const int q = rows[(size_t)bi * R + r_begin];
-        n_ent = q >= 0 ? cnt[(size_t)bi * R + r_begin] : 0;
-        e0 = (size_t)bi * ent_stride + (q >= 0 ? off[(size_t)bi * R + r_begin] : 0);
-        nchunk_row = (n_ent + NBK - 1) / NBK;
-    } else {
-        n_ent = rows_blk * nn;
-        e0 = ((size_t)bi * R + r_begin) * nn;
-        nchunk_row = (nn + NBK - 1) / NBK;
-    }
-    const int nchunk = LISTS ? nchunk_row : rows_blk * nchunk_row;
+    const group_lists::Entries en = group_lists::entries<LISTS, NBK>(bi, R, r_begin, rows_blk, nn, ent_stride, rows, off, cnt);
+    const int n_ent = en.n_ent, nchunk_row = en.nchunk_row, nchunk = en.nchunk;
+    const size_t e0 = en.e0;
 
     // memory index of the wave's ai-th anchor (PERM: position a0 + al_beg + ai of the coset-major order)
     int am[APW];
@@ -146,21 +128,10 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
         am[ai] = PERM ? __builtin_amdgcn_readfirstlane((int)order[pos]) : pos;
     }
     const int blk_w = (a0 >> 2) + wave_u;                          // PERM: the wave's block of the order
-    // ---- per-lane weight constants of this wave's anchors (k = lane & 31): see csrc/so3_inter_lists.hip ----
-    f32x2 kxp[APW / 2], kyp[APW / 2], kzp[APW / 2], kcp[APW / 2];
-#pragma unroll
-    for (int ai = 0; ai < APW; ++ai) {
-        const int a = am[ai];
-        const float *r3 = rk + ((size_t)a * ks + min(lk, ks - 1)) * 3;
-        const float x = r3[0], y = r3[1], z = r3[2];
-        kxp[ai >> 1][ai & 1] = 2.f * inv_sigma * x;
-        kyp[ai >> 1][ai & 1] = 2.f * inv_sigma * y;
-        kzp[ai >> 1][ai & 1] = 2.f * inv_sigma * z;
-        kcp[ai >> 1][ai & 1] = lk < ks ? -inv_sigma * (x * x + y * y + z * z) : -1e30f;
-    }
-    const float kcl = kcp[0][0];
-    const bool kc_uniform = __all(fabsf(kcp[0][1] - kcl) <= 1e-6f * fabsf(kcl) && fabsf(kcp[1][0] - kcl) <= 1e-6f * fabsf(kcl) &&
-                                  fabsf(kcp[1][1] - kcl) <= 1e-6f * fabsf(kcl)) != 0;
+    // per-lane weight constants of this wave's anchors (k = lane & 31) and the form of their evaluation: csrc/kernel_weight.h
+    kernel_weight::Constants<APW> kw;
+    kw.load(rk, ks, lk, inv_sigma, [&](int ai) { return am[ai]; });
+    const bool kc_uniform = kw.uniform();
     // operand read: the wave's four anchors are ONE 16-byte piece (piece wave_u) of a channel row; tile 1 = rows + 32
     // (same slot: (32 >> 2) & 3 == 0)
     const float4 *fa_lane = reinterpret_cast<const float4 *>(s_f + (size_t)(lh * CB + lk) * PITCH + 4 * ((wave_u + (lk >> 2)) & 3));
@@ -217,13 +188,8 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
     }
     __syncthreads();
 
-    auto chunk_bases = [&](int ch, int gslot) {
-        const int e = lane & (NBK - 1);
-        const float4 g = s_g[gslot * NBK + e];
-        float b = 1.0f - inv_sigma * (g.x * g.x + g.y * g.y + g.z * g.z);
-        bool dead = ch * NBK + e >= n_ent;
-        if (!LISTS && !PERM) dead = dead || (unsigned)s_p[gslot * NBK + e] >= (unsigned)PF;     // (PERM: shadow entries carry a dead offset vector)
-        return __float_as_int(dead ? -1e30f : b);
+    auto chunk_bases = [&](int ch, int gslot) {       // (PERM: shadow entries carry a dead offset vector)
+        return group_lists::chunk_bases<NBK, !LISTS && !PERM>(s_g, s_p, gslot, ch, lane, n_ent, PF, inv_sigma);
     };
     // PERM: position j of the wave's block takes the value at position j ^ x of the source block
     auto unxor = [&](float4 &v, int x) {
@@ -249,13 +215,7 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
         const float fa0[APW] = {fv0.x, fv0.y, fv0.z, fv0.w};
         const float fa1[APW] = {fv1.x, fv1.y, fv1.z, fv1.w};
         f32x2 wv[APW / 2];
-        const float bkc = bk + kcl;
-#pragma unroll
-        for (int j = 0; j < APW / 2; ++j) {
-            f32x2 x = __builtin_elementwise_fma((f32x2){g.x, g.x}, kxp[j], decltype(kcu)::value ? (f32x2){bkc, bkc} : kcp[j] + (f32x2){bk, bk});
-            x = __builtin_elementwise_fma((f32x2){g.y, g.y}, kyp[j], x);
-            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp\n\ts_nop 1" : "=v"(wv[j]) : "v"((f32x2){g.z, g.w}), "v"(kzp[j]), "v"(x));
-        }
+        kw.template eval<decltype(kcu)::value>(g, bk, wv);
         __builtin_amdgcn_s_setprio(3);
         if (first) {
             const f32x16 zc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -445,11 +405,7 @@ template <bool LISTS>
 int launch2(int layout, int b, int C, int PF, int na, int fpitch, int ks, int R, int nn, int ent_stride, float sigma, const float *F,
             const int32_t *rows, const int32_t *off, const int32_t *cnt, const int32_t *ent_p, const float *ent_gx,
             const float *rk, const int32_t *nonident, float *out, hipStream_t s, const char *what, const uint8_t *order = nullptr) {
-    if (fpitch < na || (fpitch & 3) != 0) return eap::bad_arg("so3_group_lists2: the feature row pitch must be a multiple of 4, at least the anchor count");
-    if ((long long)CB * PF * fpitch * 4 >= (1ll << 32) || PF >= (1 << 24) || fpitch * 4 >= (1 << 24))
-        return eap::bad_arg("so3_group_lists2: 64 feature rows of a cloud exceed the 32-bit request offsets");
-    if (((long long)ks * R * na * 4 + 64ll * R * na + 64) * 4 >= (1ll << 31) || (long long)CB * ks * 4 >= (1ll << 31))
-        return eap::bad_arg("so3_group_lists2: output rows too far apart for 32-bit store offsets");
+    if (int e = group_lists::check_operands("so3_group_lists2", CB, PF, na, fpitch, ks, R)) return e;
     const bool perm = order != nullptr;          // ent_p / ent_gx are then the per-entry words of eap_so3_perm_entries_f32
     if (perm && ((na & 3) != 0 || fpitch != na)) return eap::bad_arg("so3_group_lists2: the permuted variant takes unpadded rows of a multiple of 4 anchors");
     const bool lane_order = !LISTS && layout == 4;
@@ -461,7 +417,7 @@ int launch2(int layout, int b, int C, int PF, int na, int fpitch, int ks, int R,
     int e = eap::allow_dynamic_lds(kern, shmem, what);
     if (e) return e;
     const int AG = (na + GSZ - 1) / GSZ;
-    const int RPB = LISTS ? 1 : ((nn % NBK) == 0 ? 8 : 1);
+    const int RPB = group_lists::rows_per_block(LISTS, nn, NBK);
     dim3 grid((R + RPB - 1) / RPB * AG, (C + CB - 1) / CB, b);
     hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, C, PF, na, fpitch, ks, R, nn, ent_stride, AG, RPB, (LISTS ? g_xcd_map_inv : g_xcd_map_fwd) == 2, 1.0f / sigma, F,
                        rows, off, cnt, ent_p, reinterpret_cast<const float4 *>(ent_gx), rk, nonident, out, order);

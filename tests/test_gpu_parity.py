@@ -578,6 +578,20 @@ def test_batchnorm_leaky_relu_block_epilogue(dev, vg, shape, training):
     assert int(fused.num_batches_tracked) == int(ref.num_batches_tracked)
 
 
+def _signed_permutation_kernels(kappa):
+    """rk[a] = A_a kappa for the 24 proper signed permutation matrices A_a (the rotations of the cube): [24, ks, 3]"""
+    import itertools
+    mats = []
+    for perm in itertools.permutations(range(3)):
+        for signs in itertools.product((1.0, -1.0), repeat=3):
+            m = torch.zeros(3, 3)
+            for i in range(3):
+                m[i, perm[i]] = signs[i]
+            if torch.det(m) > 0:
+                mats.append(m)
+    return torch.einsum('aij,kj->aki', torch.stack(mats), kappa).contiguous()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('shape', [
     # b, c, p, n_sup, nn, na, ks
@@ -586,19 +600,34 @@ def test_batchnorm_leaky_relu_block_epilogue(dev, vg, shape, training):
     (1, 64, 21, 30, 8, 64, 32),       # 64 anchors: two groups of 32, rotated LDS image, 32 kernel points
     (2, 17, 70, 70, 24, 60, 24),      # 60 anchors: groups 32 + 28; 3 chunks per row, rows streamed 8 at a time
     (1, 96, 9, 40, 16, 60, 24),       # fewer rows than a run
+    # rk = the 24 proper signed permutation matrices applied to one kernel: the norms agree across anchors, so the waves
+    # take the uniform-norm form of the weight (csrc/kernel_weight.h), which a random rk never does
+    (2, 17, 70, 70, 24, 24, 24, 'rotated'),      # one-tile kernel, channel tail, three chunks per row
+    (1, 96, 9, 40, 16, 24, 24, 'rotated'),       # one-tile kernel (96 % 64 = 32 channels left over), fewer rows than a run
+    (1, 100, 9, 40, 16, 24, 24, 'rotated'),      # two-tile kernel, anchor groups 16 + 8, channel tail
 ])
 def test_entry_list_grouping_kernel_shapes(dev, vg, shape):
     """csrc/so3_inter_lists.hip (forward dispatcher for >= 16 channels, and the backward's Z) against
     the VALU kernel / a dense torch evaluation with materialised weights, on anchor counts, kernel
     sizes and list lengths the golden layers do not cover; shadow rows (idx == n_sup) included."""
     from vgtk import _hip
-    b, c, p, n, nn, na, ks = shape
+    b, c, p, n, nn, na, ks = shape[:7]
     torch.manual_seed(5)
     feats = torch.randn(b, c, n, na, device=dev)
     idx = torch.randint(0, n + 1, (b, p, nn), device=dev, dtype=torch.int32)      # n = shadow row
     gx = torch.zeros(b, p, nn, 4, device=dev)
     gx[..., :3] = torch.randn(b, p, nn, 3, device=dev) * 0.05
-    rk = torch.randn(na, ks, 3, device=dev) * 0.05
+    if shape[7:] == ('rotated',):
+        rk = _signed_permutation_kernels(torch.randn(ks, 3) * 0.05).to(dev)
+        assert rk.shape == (na, ks, 3)
+        # every anchor's point is a signed permutation of the same three coordinates (exactly: the matrices hold 0 and +-1),
+        # so whatever the order and fusing of a three-term fp32 sum of their squares, each value is within 3 roundings of
+        # the same exact norm: 6 * 2^-24 < 4e-7 apart, inside the kernel's 1e-6
+        assert torch.equal(rk.abs().sort(dim=2).values, rk[:1].abs().sort(dim=2).values.expand_as(rk))
+        n2 = (rk * rk).sum(2)
+        assert float(((n2 - n2[:1]).abs() / n2[:1]).max()) <= 4e-7
+    else:
+        rk = torch.randn(na, ks, 3, device=dev) * 0.05
     sigma = 0.01
     got = _hip.so3_inter_group_fwd(feats, idx, gx, rk, None, sigma)
     ref = torch.empty_like(got)
