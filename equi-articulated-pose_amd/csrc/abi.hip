@@ -65,3 +65,7 @@ extern "C" const char *eap_last_kernel(void) {      // read-and-clear: a name is
     return out;
 }
 extern "C" int eap_abi_version(void) { return 1; }
+extern "C" int eap_launch_dims_ok(int64_t gx, int64_t gy, int64_t gz, int bx, int by, int bz) {      // host only: the rule, no launch
+    dim3 grid;
+    return eap::launch_dims("launch_dims_ok", gx, gy, gz, dim3((unsigned)bx, (unsigned)by, (unsigned)bz), &grid);
+}

@@ -295,7 +295,6 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_fromy_kernel(int c, lon
 }
 
 inline int nseg_of(long n) { return (int)((n + SEG - 1) / SEG); }
-inline bool ok_dims(int b, int c, long n) { return b > 0 && c > 0 && n > 0 && c <= 65535 && b <= 65535; }
 
 }  // namespace
 
@@ -303,38 +302,35 @@ extern "C" int eap_bn_act_segments(int64_t n) { return nseg_of((long)n); }
 
 extern "C" int eap_bn_stats_f32(int b, int c, int64_t n, const float *x, float *psum, float *psq, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (!ok_dims(b, c, n) || (n & 3) != 0) return eap::bad_arg("bn_stats: row length must be a multiple of 4; at most 65535 channels / clouds");
+    if ((n & 3) != 0) return eap::bad_arg("bn_stats: row length must be a multiple of 4");
     const int nseg = nseg_of(n);
-    hipLaunchKernelGGL(bn_stats_kernel<false>, dim3(nseg, c, b), dim3(TB), 0, eap::S(stream), c, (long)n, nseg, x, psum, psq, (const float *)nullptr, 1);
-    return eap::check_launch("bn_stats");
+    return eap::run_kernel("bn_stats", bn_stats_kernel<false>, nseg, c, b, dim3(TB), 0, eap::S(stream), c, (long)n, nseg, x, psum, psq, (const float *)nullptr, 1);
 }
 
 extern "C" int eap_bn_act_fwd_f32(int b, int c, int64_t n, float slope, const float *x, const float *scale,
                                   const float *shift, float *y, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (!ok_dims(b, c, n) || (n & 3) != 0) return eap::bad_arg("bn_act_fwd: row length must be a multiple of 4; at most 65535 channels / clouds");
-    hipLaunchKernelGGL((bn_act_fwd_kernel<false, false>), dim3(nseg_of(n), c, b), dim3(TB), 0, eap::S(stream), c, (long)n, slope, x, scale, shift,
-                       (const float *)nullptr, y);
-    return eap::check_launch("bn_act_fwd");
+    if ((n & 3) != 0) return eap::bad_arg("bn_act_fwd: row length must be a multiple of 4");
+    return eap::run_kernel("bn_act_fwd", bn_act_fwd_kernel<false, false>, nseg_of(n), c, b, dim3(TB), 0, eap::S(stream), c, (long)n, slope, x, scale, shift,
+                           (const float *)nullptr, y);
 }
 
 extern "C" int eap_bn_act_add_fwd_f32(int b, int c, int64_t n, float slope, const float *x, const float *scale,
                                       const float *shift, const float *res, float *y, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (!ok_dims(b, c, n) || (n & 3) != 0) return eap::bad_arg("bn_act_add_fwd: row length must be a multiple of 4; at most 65535 channels / clouds");
-    hipLaunchKernelGGL((bn_act_fwd_kernel<true, false>), dim3(nseg_of(n), c, b), dim3(TB), 0, eap::S(stream), c, (long)n, slope, x, scale, shift, res, y);
-    return eap::check_launch("bn_act_add_fwd");
+    if ((n & 3) != 0) return eap::bad_arg("bn_act_add_fwd: row length must be a multiple of 4");
+    return eap::run_kernel("bn_act_add_fwd", bn_act_fwd_kernel<true, false>, nseg_of(n), c, b, dim3(TB), 0, eap::S(stream), c, (long)n, slope, x, scale, shift,
+                           res, y);
 }
 
 extern "C" int eap_bn_act_bwd_reduce_f32(int b, int c, int64_t n, float slope, const float *gy, const float *x,
                                          const float *scale, const float *shift, const float *mean,
                                          const float *invstd, float *pg, float *pgx, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (!ok_dims(b, c, n) || (n & 3) != 0) return eap::bad_arg("bn_act_bwd_reduce: row length must be a multiple of 4; at most 65535 channels / clouds");
+    if ((n & 3) != 0) return eap::bad_arg("bn_act_bwd_reduce: row length must be a multiple of 4");
     const int nseg = nseg_of(n);
-    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<false>, dim3(nseg, c, b), dim3(TB), 0, eap::S(stream), c, (long)n, nseg, slope, gy, x,
-                       scale, shift, mean, invstd, pg, pgx);
-    return eap::check_launch("bn_act_bwd_reduce");
+    return eap::run_kernel("bn_act_bwd_reduce", bn_act_bwd_reduce_kernel<false>, nseg, c, b, dim3(TB), 0, eap::S(stream), c, (long)n, nseg, slope, gy, x,
+                           scale, shift, mean, invstd, pg, pgx);
 }
 
 extern "C" int eap_bn_act_bwd_apply_f32(int b, int c, int64_t n, float slope, const float *gy, const float *x,
@@ -342,10 +338,9 @@ extern "C" int eap_bn_act_bwd_apply_f32(int b, int c, int64_t n, float slope, co
                                         const float *invstd, const float *k2, const float *k3, float *gx,
                                         eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (!ok_dims(b, c, n) || (n & 3) != 0) return eap::bad_arg("bn_act_bwd_apply: row length must be a multiple of 4; at most 65535 channels / clouds");
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel<false>, dim3(nseg_of(n), c, b), dim3(TB), 0, eap::S(stream), c, (long)n, slope, gy, x,
-                       scale, shift, mean, invstd, k2, k3, gx, (const float *)nullptr, 1);
-    return eap::check_launch("bn_act_bwd_apply");
+    if ((n & 3) != 0) return eap::bad_arg("bn_act_bwd_apply: row length must be a multiple of 4");
+    return eap::run_kernel("bn_act_bwd_apply", bn_act_bwd_apply_kernel<false>, nseg_of(n), c, b, dim3(TB), 0, eap::S(stream), c, (long)n, slope, gy, x,
+                           scale, shift, mean, invstd, k2, k3, gx, (const float *)nullptr, 1);
 }
 
 extern "C" int eap_bn_act_bwd_apply_rowmax_f32(int b, int c, int64_t n, int na, float slope, const float *gy, const float *x,
@@ -353,17 +348,16 @@ extern "C" int eap_bn_act_bwd_apply_rowmax_f32(int b, int c, int64_t n, int na, 
                                                const float *invstd, const float *k2, const float *k3, float *gx, uint32_t *rowmax,
                                                eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (!ok_dims(b, c, n) || na <= 0 || (na & 3) != 0 || na > 256 || n % na != 0 ||
+    if (na <= 0 || (na & 3) != 0 || na > 256 || n % na != 0 ||
         ((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gx)) & 15) != 0)
         return eap::bad_arg("bn_act_bwd_apply_rowmax: rows of [points][na], na a multiple of 4 up to 256, 16-byte aligned tensors");
     hipStream_t s = eap::S(stream);
     if (int e = eap::hip_fail(hipMemsetAsync(rowmax, 0, sizeof(uint32_t) * (size_t)b * c * na, s), "bn_act_bwd_apply_rowmax memset")) return e;
     const int nq = na / 4, T = nq * (256 / nq);
     const long n4 = (long)(n / 4);
-    hipLaunchKernelGGL(bn_act_bwd_apply_rowmax_kernel, dim3((unsigned)((n4 + (long)RM_PIECES * T - 1) / ((long)RM_PIECES * T)), c, b), dim3(256), 0, s,
-                       c, n4, nq, slope, reinterpret_cast<const float4 *>(gy), reinterpret_cast<const float4 *>(x), scale, shift, mean, invstd, k2, k3,
-                       reinterpret_cast<float4 *>(gx), rowmax);
-    return eap::check_launch("bn_act_bwd_apply_rowmax");
+    return eap::run_kernel("bn_act_bwd_apply_rowmax", bn_act_bwd_apply_rowmax_kernel, eap::cdiv(n4, (long)RM_PIECES * T), c, b, dim3(256), 0, s, c, n4, nq,
+                           slope, reinterpret_cast<const float4 *>(gy), reinterpret_cast<const float4 *>(x), scale, shift, mean, invstd, k2, k3,
+                           reinterpret_cast<float4 *>(gx), rowmax);
 }
 
 // blocks per (cloud, channel) row of eap_bn_act_bwd_reduce_fromy_f32: the partial arrays are [c][b * blocks]
@@ -379,24 +373,23 @@ extern "C" int eap_bn_act_fromy_blocks(int64_t n, int na) {
 extern "C" int eap_bn_act_bwd_reduce_fromy_f32(int b, int c, int64_t n, int na, float slope, const float *gy, const float *y, const float *beta,
                                                const float *inv_gamma, float *pg, float *pgx, uint32_t *gmax, uint32_t *xmax, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (!ok_dims(b, c, n) || na <= 0 || (na & 3) != 0 || na > 256 || n % na != 0 || !(slope > 0.f) ||
+    if (na <= 0 || (na & 3) != 0 || na > 256 || n % na != 0 || !(slope > 0.f) ||
         ((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(y)) & 15) != 0)
         return eap::bad_arg("bn_act_bwd_reduce_fromy: rows of [points][na], na a multiple of 4 up to 256, 16-byte aligned tensors, a positive slope");
     hipStream_t s = eap::S(stream);
     if (int e = eap::hip_fail(hipMemsetAsync(gmax, 0, sizeof(uint32_t) * (size_t)b * c * na, s), "bn_act_bwd_reduce_fromy memset")) return e;
     if (int e = eap::hip_fail(hipMemsetAsync(xmax, 0, sizeof(uint32_t) * (size_t)b * c * na, s), "bn_act_bwd_reduce_fromy memset")) return e;
     const int nq = na / 4, nblk = eap_bn_act_fromy_blocks(n, na);
-    hipLaunchKernelGGL(bn_act_bwd_reduce_fromy_kernel, dim3((unsigned)nblk, c, b), dim3(256), 0, s, c, (long)(n / 4), nq, nblk, slope, 1.0f / slope,
-                       reinterpret_cast<const float4 *>(gy), reinterpret_cast<const float4 *>(y), beta, inv_gamma, pg, pgx, gmax, xmax);
-    return eap::check_launch("bn_act_bwd_reduce_fromy");
+    return eap::run_kernel("bn_act_bwd_reduce_fromy", bn_act_bwd_reduce_fromy_kernel, nblk, c, b, dim3(256), 0, s, c, (long)(n / 4), nq, nblk, slope,
+                           1.0f / slope, reinterpret_cast<const float4 *>(gy), reinterpret_cast<const float4 *>(y), beta, inv_gamma, pg, pgx, gmax, xmax);
 }
 
 // ---- per-cloud statistics over a point subset (the pose heads' batched per-cloud calls) ---------------------------
 namespace {
 inline int cloud_dims(const char *who, int b, int c, long n, int na, bool masked) {
     char buf[200];
-    if (!ok_dims(b, c, n) || (n & 3) != 0 || n >= (1l << 31)) {
-        snprintf(buf, sizeof(buf), "%s: row length must be a multiple of 4 below 2^31; at most 65535 channels / clouds", who);
+    if ((n & 3) != 0 || n >= (1l << 31)) {
+        snprintf(buf, sizeof(buf), "%s: row length must be a multiple of 4 below 2^31", who);
         return eap::bad_arg(buf);
     }
     if (masked && (na <= 0 || (na & 3) != 0 || n % na != 0)) {
@@ -413,17 +406,15 @@ extern "C" int eap_bn_stats_masked_f32(int b, int c, int64_t n, int na, const fl
     if (!mask) return eap::bad_arg("bn_stats_masked: mask is null");
     if (int e = cloud_dims("bn_stats_masked", b, c, (long)n, na, true)) return e;
     const int nseg = nseg_of(n);
-    hipLaunchKernelGGL(bn_stats_kernel<true>, dim3(nseg, c, b), dim3(TB), 0, eap::S(stream), c, (long)n, nseg, x, psum, psq, mask, na);
-    return eap::check_launch("bn_stats_masked");
+    return eap::run_kernel("bn_stats_masked", bn_stats_kernel<true>, nseg, c, b, dim3(TB), 0, eap::S(stream), c, (long)n, nseg, x, psum, psq, mask, na);
 }
 
 extern "C" int eap_bn_act_cloud_fwd_f32(int b, int c, int64_t n, float slope, const float *x, const float *scale, const float *shift,
                                         float *y, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
     if (int e = cloud_dims("bn_act_cloud_fwd", b, c, (long)n, 0, false)) return e;
-    hipLaunchKernelGGL((bn_act_fwd_kernel<false, true>), dim3(nseg_of(n), c, b), dim3(TB), 0, eap::S(stream), c, (long)n, slope, x, scale, shift,
-                       (const float *)nullptr, y);
-    return eap::check_launch("bn_act_cloud_fwd");
+    return eap::run_kernel("bn_act_cloud_fwd", bn_act_fwd_kernel<false, true>, nseg_of(n), c, b, dim3(TB), 0, eap::S(stream), c, (long)n, slope, x, scale,
+                           shift, (const float *)nullptr, y);
 }
 
 extern "C" int eap_bn_act_cloud_bwd_reduce_f32(int b, int c, int64_t n, float slope, const float *gy, const float *x, const float *scale,
@@ -432,9 +423,8 @@ extern "C" int eap_bn_act_cloud_bwd_reduce_f32(int b, int c, int64_t n, float sl
     if (b <= 0 || c <= 0 || n <= 0) return 0;
     if (int e = cloud_dims("bn_act_cloud_bwd_reduce", b, c, (long)n, 0, false)) return e;
     const int nseg = nseg_of(n);
-    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<true>, dim3(nseg, c, b), dim3(TB), 0, eap::S(stream), c, (long)n, nseg, slope, gy, x,
-                       scale, shift, mean, invstd, pg, pgx);
-    return eap::check_launch("bn_act_cloud_bwd_reduce");
+    return eap::run_kernel("bn_act_cloud_bwd_reduce", bn_act_bwd_reduce_kernel<true>, nseg, c, b, dim3(TB), 0, eap::S(stream), c, (long)n, nseg, slope, gy, x,
+                           scale, shift, mean, invstd, pg, pgx);
 }
 
 extern "C" int eap_bn_act_cloud_bwd_apply_f32(int b, int c, int64_t n, int na, float slope, const float *gy, const float *x,
@@ -442,7 +432,6 @@ extern "C" int eap_bn_act_cloud_bwd_apply_f32(int b, int c, int64_t n, int na, f
                                               const float *k2, const float *k3, const float *mask, float *gx, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
     if (int e = cloud_dims("bn_act_cloud_bwd_apply", b, c, (long)n, na, mask != nullptr)) return e;
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, dim3(nseg_of(n), c, b), dim3(TB), 0, eap::S(stream), c, (long)n, slope, gy, x,
-                       scale, shift, mean, invstd, k2, k3, gx, mask, mask ? na : 1);
-    return eap::check_launch("bn_act_cloud_bwd_apply");
+    return eap::run_kernel("bn_act_cloud_bwd_apply", bn_act_bwd_apply_kernel<true>, nseg_of(n), c, b, dim3(TB), 0, eap::S(stream), c, (long)n, slope, gy, x,
+                           scale, shift, mean, invstd, k2, k3, gx, mask, mask ? na : 1);
 }

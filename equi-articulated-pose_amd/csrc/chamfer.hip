@@ -73,9 +73,8 @@ extern "C" int eap_chamfer_fwd_f32(int b, int n, int m, const float *xyz1, const
     if (b <= 0) return 0;
     if (n <= 0 || m <= 0) return eap::bad_arg("chamfer_forward: empty cloud");
     hipStream_t s = eap::S(stream);
-    hipLaunchKernelGGL(chamfer_nn_kernel, dim3(eap::cdiv(n, CH_THREADS), b), dim3(CH_THREADS), 0, s, n, m, xyz1, xyz2, dist1, idx1);
-    hipLaunchKernelGGL(chamfer_nn_kernel, dim3(eap::cdiv(m, CH_THREADS), b), dim3(CH_THREADS), 0, s, m, n, xyz2, xyz1, dist2, idx2);
-    return eap::check_launch("chamfer_forward");
+    if (int e = eap::run_kernel("chamfer_forward", chamfer_nn_kernel, eap::cdiv(n, CH_THREADS), b, 1, dim3(CH_THREADS), 0, s, n, m, xyz1, xyz2, dist1, idx1)) return e;
+    return eap::run_kernel("chamfer_forward", chamfer_nn_kernel, eap::cdiv(m, CH_THREADS), b, 1, dim3(CH_THREADS), 0, s, m, n, xyz2, xyz1, dist2, idx2);
 }
 
 extern "C" int eap_chamfer_bwd_f32(int b, int n, int m, const float *xyz1, const float *xyz2,
@@ -86,7 +85,6 @@ extern "C" int eap_chamfer_bwd_f32(int b, int n, int m, const float *xyz1, const
     int e = eap::hip_fail(hipMemsetAsync(gxyz1, 0, sizeof(float) * (size_t)b * n * 3, s), "chamfer_backward memset");
     if (!e) e = eap::hip_fail(hipMemsetAsync(gxyz2, 0, sizeof(float) * (size_t)b * m * 3, s), "chamfer_backward memset");
     if (e || n <= 0 || m <= 0) return e;
-    hipLaunchKernelGGL(chamfer_grad_kernel, dim3(eap::cdiv(n, 256), b), dim3(256), 0, s, n, m, xyz1, xyz2, g1, idx1, gxyz1, gxyz2);
-    hipLaunchKernelGGL(chamfer_grad_kernel, dim3(eap::cdiv(m, 256), b), dim3(256), 0, s, m, n, xyz2, xyz1, g2, idx2, gxyz2, gxyz1);
-    return eap::check_launch("chamfer_backward");
+    if ((e = eap::run_kernel("chamfer_backward", chamfer_grad_kernel, eap::cdiv(n, 256), b, 1, dim3(256), 0, s, n, m, xyz1, xyz2, g1, idx1, gxyz1, gxyz2))) return e;
+    return eap::run_kernel("chamfer_backward", chamfer_grad_kernel, eap::cdiv(m, 256), b, 1, dim3(256), 0, s, m, n, xyz2, xyz1, g2, idx2, gxyz2, gxyz1);
 }

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "../../include/eap_hip.h"
 
 namespace eap {
@@ -41,13 +43,66 @@ static inline int hip_fail(hipError_t e, const char *what) {
 
 static inline hipStream_t S(eap_stream_t s) { return (hipStream_t)s; }
 
-static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
+static inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
-// lets `kernel` be launched with `bytes` of dynamic LDS (more than the 64 KB a kernel may use without asking); called before
-// every such launch
-template <typename K>
-static inline int allow_dynamic_lds(K *kernel, size_t bytes, const char *what) {
-    return hip_fail(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), what);
+// The launch limits, without a HIP call: every grid and block dimension >= 1, at most 1024 threads per block, gx * block.x < 2^32
+// (hip_runtime_api.h at the launch functions: "HIP does not support kernel launch with total work items defined in dimension with
+// size gridDim x blockDim >= 2^32"), gy and gz <= 65535.  -> 0 and *grid, or bad_arg with the sizes in the message.
+static inline int launch_dims(const char *what, long long gx, long long gy, long long gz, dim3 block, dim3 *grid) {
+    const bool block_ok = block.x >= 1 && block.y >= 1 && block.z >= 1 && block.x <= 1024 && block.y <= 1024 && block.z <= 1024 &&
+                          block.x * block.y * block.z <= 1024;
+    if (!block_ok || gx < 1 || gy < 1 || gz < 1 || gx > 0xffffffffLL / block.x || gy > 65535 || gz > 65535) {
+        char buf[256];
+        snprintf(buf, sizeof(buf), "%s: grid (%lld, %lld, %lld) x block (%u, %u, %u) is outside the launch limits: every size >= 1, block <= 1024 "
+                 "threads, grid.x * block.x < 2^32, grid.y and grid.z <= 65535", what, gx, gy, gz, block.x, block.y, block.z);
+        return bad_arg(buf);
+    }
+    *grid = dim3((unsigned)gx, (unsigned)gy, (unsigned)gz);
+    return 0;
+}
+
+// The opt-in a kernel needs before it is launched with `bytes` of dynamic LDS, made once per kernel and device and again only for a
+// larger request: the largest size set so far per (kernel, device id) in an open-addressed table, lock-free.  A size is published
+// only after hipFuncSetAttribute succeeded; a publisher that finds the entry changed under it sets the larger of the two again, so
+// the table never promises more than the attribute holds once the calls have returned.  (Two host threads that launch ONE kernel
+// on ONE device with DIFFERENT sizes at the same moment can still see the smaller attribute for an instant; the launch is then
+// refused by the runtime, an error.  Entries are meant to be called from one host thread per device, see SideJoin.)
+struct LdsOptIn {
+    std::atomic<const void *> kernel{nullptr};
+    std::atomic<unsigned> bytes[64] = {};
+};
+inline LdsOptIn g_lds_opt_in[256];
+
+static inline int allow_dynamic_lds(const void *kernel, size_t bytes, const char *what) {
+    int dev = 0;
+    if (int e = hip_fail(hipGetDevice(&dev), what)) return e;
+    std::atomic<unsigned> *seen = nullptr;        // (stays null past 64 devices or 256 kernels: the attribute is then set every time)
+    for (size_t i = 0, h = reinterpret_cast<uintptr_t>(kernel) >> 4; i < 256 && dev >= 0 && dev < 64; ++i) {
+        LdsOptIn &slot = g_lds_opt_in[(h + i) & 255];
+        const void *k = slot.kernel.load(std::memory_order_acquire);
+        if (k == nullptr && slot.kernel.compare_exchange_strong(k, kernel, std::memory_order_acq_rel)) k = kernel;
+        if (k == kernel) { seen = &slot.bytes[dev]; break; }
+    }
+    unsigned have = seen ? seen->load(std::memory_order_acquire) : 0u;
+    if (have >= bytes) return 0;
+    for (;;) {
+        if (int e = hip_fail(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), what)) return e;
+        if (!seen || seen->compare_exchange_strong(have, (unsigned)bytes, std::memory_order_acq_rel)) return 0;
+        if (have > bytes) bytes = have;           // published meanwhile, before or after our call: the larger of the two, once more
+    }
+}
+
+// Every kernel launch of the library: the limits above, the dynamic-LDS opt-in, the launch, the runtime's verdict -- in that order,
+// nothing launched past an error
+template <typename K, typename... Args>
+static inline int run_kernel(const char *what, K kernel, long long gx, long long gy, long long gz, dim3 block, size_t lds_bytes, hipStream_t s,
+                             Args... args) {
+    dim3 grid;
+    if (int e = launch_dims(what, gx, gy, gz, block, &grid)) return e;
+    if (lds_bytes)
+        if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), lds_bytes, what)) return e;
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
+    return check_launch(what);
 }
 
 // ---- 2. side-stream helpers -----------------------------------------------------------------------------------------

@@ -32,8 +32,7 @@ int launch_bwd(int b, int c, int n, int m, const T *g, const int32_t *idx, T *gp
     if (b <= 0 || c <= 0 || n <= 0) return 0;
     int e = eap::hip_fail(hipMemsetAsync(gp, 0, sizeof(T) * (size_t)b * c * n, s), "gather_bwd memset");
     if (e || m <= 0) return e;
-    hipLaunchKernelGGL(gather_bwd_kernel<T>, dim3(eap::cdiv(m, 256), c, b), dim3(256), 0, s, c, n, m, g, idx, gp);
-    return eap::check_launch("gather_points_backward");
+    return eap::run_kernel("gather_points_backward", gather_bwd_kernel<T>, eap::cdiv(m, 256), c, b, dim3(256), 0, s, c, n, m, g, idx, gp);
 }
 
 }  // namespace
@@ -41,9 +40,8 @@ int launch_bwd(int b, int c, int n, int m, const T *g, const int32_t *idx, T *gp
 extern "C" int eap_gather_points_fwd_f32(int b, int c, int n, int m, const float *pts,
                                          const int32_t *idx, float *out, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || m <= 0) return 0;
-    hipLaunchKernelGGL(gather_fwd_kernel<float>, dim3(eap::cdiv(m, 256), c, b), dim3(256), 0,
-                       eap::S(stream), c, n, m, pts, idx, out);
-    return eap::check_launch("gather_points_forward");
+    return eap::run_kernel("gather_points_forward", gather_fwd_kernel<float>, eap::cdiv(m, 256), c, b, dim3(256), 0, eap::S(stream), c, n, m, pts, idx,
+                           out);
 }
 extern "C" int eap_gather_points_bwd_f32(int b, int c, int n, int m, const float *grad_out,
                                          const int32_t *idx, float *grad_pts, eap_stream_t stream) {

@@ -549,7 +549,7 @@ void keep_pool_memory() {
 }
 
 template <int BMODE, int PL = 3>
-int launch_split(Args &g, int batch, hipStream_t stream, const char *who) {
+int launch_split(Args &g, long long batch, hipStream_t stream, const char *who) {
     // pays from a few thousand k-tiles per workgroup column upwards (+2.7 % on the deepest layer's contraction; on the 1-2 ms
     // pointwise contractions the extra launch and the allocation cost more than the saved vector work:
     // tools/split_modes_timing.py); the test switch value 2 forces it for every shape
@@ -564,39 +564,33 @@ int launch_split(Args &g, int batch, hipStream_t stream, const char *who) {
             pre = false;
         }
     }
-    if (pre) {
-        const long long pieces = (long long)g.M * (g.K / 4);
-        if constexpr (PL == 3)
-            hipLaunchKernelGGL(presplit_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, stream, g.M, g.K / 4, g.A, g.lda,
-                               reinterpret_cast<u32x4 *>(scratch));
-        else
-            hipLaunchKernelGGL(presplit_h_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, stream, g.M, g.K / 4, g.A, g.lda, g.absA,
-                               reinterpret_cast<u32x4 *>(scratch));
-        g.Apre = reinterpret_cast<const unsigned *>(scratch);
-    }
     struct Release {           // stream-ordered: the buffer is released after the product that reads it
         void *p; hipStream_t s;
         ~Release() { if (p) (void)hipFreeAsync(p, s); }
     } release{scratch, stream};
+    if (pre) {
+        const long long pieces = (long long)g.M * (g.K / 4);
+        int e;
+        if constexpr (PL == 3)
+            e = eap::run_kernel(who, presplit_kernel, eap::cdiv(pieces, 256), 1, 1, dim3(256), 0, stream, g.M, g.K / 4, g.A, g.lda, reinterpret_cast<u32x4 *>(scratch));
+        else
+            e = eap::run_kernel(who, presplit_h_kernel, eap::cdiv(pieces, 256), 1, 1, dim3(256), 0, stream, g.M, g.K / 4, g.A, g.lda, g.absA,
+                                reinterpret_cast<u32x4 *>(scratch));
+        if (e) return e;
+        g.Apre = reinterpret_cast<const unsigned *>(scratch);
+    }
     const bool tall = (g.M % 256) == 0;            // 256-row tiles; otherwise 128-row tiles (M is a multiple of 128)
     g.tiles_m = tall ? g.M / 256 : g.M / 128;
     g.tiles_n = (g.N + BN - 1) / BN;
     const size_t shmem = shmem_bytes(PL) + (BMODE == 2 ? TBL_BYTES : 0);
-    auto launch = [&](auto kern) {
-        int e = eap::allow_dynamic_lds(kern, shmem, who);
-        if (e) return e;
-        hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, batch), dim3(128 * WAVES_N), shmem, stream, g);
-        return 0;
-    };
-    int e;
+    void (*kern)(Args);
     if constexpr (PL == 2) {
-        if (pre) e = tall ? launch(gemm_f16x2_kernel<4, WAVES_N, BMODE, true>) : launch(gemm_f16x2_kernel<2, WAVES_N, BMODE, true>);
-        else e = tall ? launch(gemm_f16x2_kernel<4, WAVES_N, BMODE, false>) : launch(gemm_f16x2_kernel<2, WAVES_N, BMODE, false>);
+        if (pre) kern = tall ? gemm_f16x2_kernel<4, WAVES_N, BMODE, true> : gemm_f16x2_kernel<2, WAVES_N, BMODE, true>;
+        else kern = tall ? gemm_f16x2_kernel<4, WAVES_N, BMODE, false> : gemm_f16x2_kernel<2, WAVES_N, BMODE, false>;
     } else {
-        if (pre) e = tall ? launch(gemm_bf16x3_kernel<4, WAVES_N, BMODE, true>) : launch(gemm_bf16x3_kernel<2, WAVES_N, BMODE, true>);
-        else e = tall ? launch(gemm_bf16x3_kernel<4, WAVES_N, BMODE, false>) : launch(gemm_bf16x3_kernel<2, WAVES_N, BMODE, false>);
+        if (pre) kern = tall ? gemm_bf16x3_kernel<4, WAVES_N, BMODE, true> : gemm_bf16x3_kernel<2, WAVES_N, BMODE, true>;
+        else kern = tall ? gemm_bf16x3_kernel<4, WAVES_N, BMODE, false> : gemm_bf16x3_kernel<2, WAVES_N, BMODE, false>;
     }
-    if (e) return e;
     static const char *names[3][2] = {{"gemm_bf16x3_kernel<2, 4>", "gemm_bf16x3_kernel<4, 4>"},
                                       {"gemm_bf16x3_kernel<2, 4, nn>", "gemm_bf16x3_kernel<4, 4, nn>"},
                                       {"gemm_bf16x3_kernel<2, 4, gather>", "gemm_bf16x3_kernel<4, 4, gather>"}};
@@ -604,7 +598,7 @@ int launch_split(Args &g, int batch, hipStream_t stream, const char *who) {
                                        {"gemm_f16x2_kernel<2, 4, nn>", "gemm_f16x2_kernel<4, 4, nn>"},
                                        {"gemm_f16x2_kernel<2, 4, gather>", "gemm_f16x2_kernel<4, 4, gather>"}};
     eap::set_kernel((PL == 2 ? names2 : names)[BMODE][tall ? 1 : 0]);
-    return eap::check_launch(who);
+    return eap::run_kernel(who, kern, (long long)g.tiles_m * g.tiles_n, batch, 1, dim3(128 * WAVES_N), shmem, stream, g);
 }
 
 inline bool tile_dims_ok(int M, int N, int K) {
@@ -636,7 +630,6 @@ extern "C" int eap_gemm_bf16x3_f32(int M, int N, int K, const float *A, int64_t 
                                    float *C, int64_t ldc, int64_t strideC, int batch, eap_stream_t stream) {
     if (M <= 0 || N <= 0 || batch <= 0) return 0;
     if (!eap_gemm_bf16x3_f32_supported(M, N, K, A, lda, B, ldb, strideB)) return eap::bad_arg("gemm_bf16x3_f32: unsupported operands (ask eap_gemm_bf16x3_f32_supported)");
-    if (batch > 65535) return eap::bad_arg("gemm_bf16x3_f32: batch exceeds 65535");
     Args g{};
     g.M = M; g.N = N; g.K = K;
     g.A = A; g.lda = lda;
@@ -655,7 +648,6 @@ extern "C" int eap_gemm_bf16x3_ep_f32(int transB, int M, int N, int K, const flo
     if (!scale || !shift) return eap::bad_arg("gemm_bf16x3_ep_f32: scale and shift are required");
     const bool ok = transB ? eap_gemm_bf16x3_f32_supported(M, N, K, A, lda, B, ldb, strideB) : eap_gemm_bf16x3_nn_f32_supported(M, N, K, A, lda, B, ldb, strideB);
     if (!ok) return eap::bad_arg("gemm_bf16x3_ep_f32: unsupported operands (ask eap_gemm_bf16x3_f32_supported / _nn_f32_supported)");
-    if (batch > 65535) return eap::bad_arg("gemm_bf16x3_ep_f32: batch exceeds 65535");
     Args g{};
     g.M = M; g.N = N; g.K = K;
     g.A = A; g.lda = lda;
@@ -679,7 +671,6 @@ extern "C" int eap_gemm_bf16x3_nn_f32(int M, int N, int K, const float *A, int64
                                       float *C, int64_t ldc, int64_t strideC, int batch, eap_stream_t stream) {
     if (M <= 0 || N <= 0 || batch <= 0) return 0;
     if (!eap_gemm_bf16x3_nn_f32_supported(M, N, K, A, lda, B, ldb, strideB)) return eap::bad_arg("gemm_bf16x3_nn_f32: unsupported operands (ask eap_gemm_bf16x3_nn_f32_supported)");
-    if (batch > 65535) return eap::bad_arg("gemm_bf16x3_nn_f32: batch exceeds 65535");
     Args g{};
     g.M = M; g.N = N; g.K = K;
     g.A = A; g.lda = lda;
@@ -706,25 +697,23 @@ extern "C" int eap_absmax_rows_f32(const float *x, int batch, int rows, int cols
     if (cols <= 0 || (cols & 3) || (ld & 3) || (stride & 3) || ld < cols || (reinterpret_cast<uintptr_t>(x) & 15))
         return eap::bad_arg("absmax_rows_f32: rows of whole 16-byte pieces, 16-byte aligned");
     const long long total = (long long)batch * rows;
-    hipLaunchKernelGGL(absmax_rows_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, eap::S(stream), total, rows, cols / 4, x, (long long)ld,
-                       (long long)stride, reinterpret_cast<unsigned *>(out_bits));
-    return eap::check_launch("absmax_rows_f32");
+    return eap::run_kernel("absmax_rows_f32", absmax_rows_kernel, eap::cdiv(total, 4), 1, 1, dim3(256), 0, eap::S(stream), total, rows, cols / 4, x, (long long)ld,
+                           (long long)stride, reinterpret_cast<unsigned *>(out_bits));
 }
 
 extern "C" int eap_absmax_colgroups_f32(const float *x, int batch, int rows, int cols, int64_t ld, int64_t stride, int grp, int32_t *out_bits,
                                         eap_stream_t stream) {
     if (batch <= 0 || cols <= 0) return 0;
-    if (grp <= 0 || (grp & 3) || (cols % grp) || (ld & 3) || (stride & 3) || ld < cols || (reinterpret_cast<uintptr_t>(x) & 15) || batch > 65535)
-        return eap::bad_arg("absmax_colgroups_f32: groups of whole 16-byte pieces dividing the row, 16-byte aligned rows, batch <= 65535");
+    if (grp <= 0 || (grp & 3) || (cols % grp) || (ld & 3) || (stride & 3) || ld < cols || (reinterpret_cast<uintptr_t>(x) & 15))
+        return eap::bad_arg("absmax_colgroups_f32: groups of whole 16-byte pieces dividing the row, 16-byte aligned rows");
     if (int e = eap::hip_fail(hipMemsetAsync(out_bits, 0, (size_t)batch * (cols / grp) * 4, eap::S(stream)), "absmax_colgroups_f32")) return e;
     if (rows <= 0) return 0;
     const int cols4 = cols / 4, blocks = (cols4 + 255) / 256;
     // enough (column block, row slice, item) triples to fill the chip a few times over
     int slices = 1;
     while (slices < 64 && slices * 2 <= rows && (long long)blocks * batch * slices < 2048) slices *= 2;
-    hipLaunchKernelGGL(absmax_colgroups_kernel, dim3(blocks, slices, batch), dim3(256), 0, eap::S(stream), rows, cols4, grp / 4, slices, x, (long long)ld,
-                       (long long)stride, reinterpret_cast<unsigned *>(out_bits));
-    return eap::check_launch("absmax_colgroups_f32");
+    return eap::run_kernel("absmax_colgroups_f32", absmax_colgroups_kernel, blocks, slices, batch, dim3(256), 0, eap::S(stream), rows, cols4, grp / 4, slices, x,
+                           (long long)ld, (long long)stride, reinterpret_cast<unsigned *>(out_bits));
 }
 
 extern "C" int eap_so3_grouped_bound_f32(int b, int p, int nn, int n_sup, const int32_t *point_max_bits, const int32_t *idx, int32_t *out_bits,
@@ -732,9 +721,8 @@ extern "C" int eap_so3_grouped_bound_f32(int b, int p, int nn, int n_sup, const 
     if (b <= 0 || p <= 0) return 0;
     if (nn <= 0 || n_sup <= 0) return eap::bad_arg("so3_grouped_bound_f32: empty neighbour lists");
     const long long total = (long long)b * p;
-    hipLaunchKernelGGL(grouped_bound_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, eap::S(stream), total, p, nn, n_sup,
-                       reinterpret_cast<const unsigned *>(point_max_bits), idx, reinterpret_cast<unsigned *>(out_bits));
-    return eap::check_launch("so3_grouped_bound_f32");
+    return eap::run_kernel("so3_grouped_bound_f32", grouped_bound_kernel, eap::cdiv(total, 256), 1, 1, dim3(256), 0, eap::S(stream), total, p, nn, n_sup,
+                           reinterpret_cast<const unsigned *>(point_max_bits), idx, reinterpret_cast<unsigned *>(out_bits));
 }
 
 // C_z = A B_z (+ the row epilogue of eap_gemm_bf16x3_ep_f32 when scale != NULL); trans_b = 1: B_z [N,K] k-contiguous, 0: B_z [K,N]
@@ -749,7 +737,6 @@ extern "C" int eap_gemm_f16x2_f32(int trans_b, int M, int N, int K, const float 
     if ((scale == nullptr) != (shift == nullptr)) return eap::bad_arg("gemm_f16x2_f32: scale and shift come together");
     const bool ok = trans_b ? eap_gemm_bf16x3_f32_supported(M, N, K, A, lda, B, ldb, strideB) : eap_gemm_bf16x3_nn_f32_supported(M, N, K, A, lda, B, ldb, strideB);
     if (!ok) return eap::bad_arg("gemm_f16x2_f32: unsupported operands (ask eap_gemm_bf16x3_f32_supported / _nn_f32_supported)");
-    if (batch > 65535) return eap::bad_arg("gemm_f16x2_f32: batch exceeds 65535");
     Args g{};
     g.M = M; g.N = N; g.K = K;
     g.A = A; g.lda = lda;
@@ -769,7 +756,6 @@ extern "C" int eap_so3_intra_conv_f16x2_f32(int b, int o, int c, int p, int na, 
     if (!abs_w || !abs_f) return eap::bad_arg("so3_intra_conv_f16x2_f32: the operand magnitudes are required (eap_absmax_rows_f32 / _colgroups_f32)");
     if (!eap_so3_intra_conv_bf16x3_f32_supported(b, o, c, p, na, nt) || (reinterpret_cast<uintptr_t>(W) & 15))
         return eap::bad_arg("so3_intra_conv_f16x2_f32: unsupported shape (ask eap_so3_intra_conv_bf16x3_f32_supported)");
-    if (b > 65535) return eap::bad_arg("so3_intra_conv_f16x2_f32: batch exceeds 65535");
     Args g{};
     const long long pa = (long long)p * na;
     g.M = o; g.N = (int)pa; g.K = c * nt;
@@ -793,7 +779,6 @@ extern "C" int eap_so3_intra_conv_bf16x3_f32(int b, int o, int c, int p, int na,
     if (b <= 0 || o <= 0 || p <= 0) return 0;
     if (!eap_so3_intra_conv_bf16x3_f32_supported(b, o, c, p, na, nt) || (reinterpret_cast<uintptr_t>(W) & 15))
         return eap::bad_arg("so3_intra_conv_bf16x3_f32: unsupported shape (ask eap_so3_intra_conv_bf16x3_f32_supported)");
-    if (b > 65535) return eap::bad_arg("so3_intra_conv_bf16x3_f32: batch exceeds 65535");
     Args g{};
     const long long pa = (long long)p * na;
     g.M = o; g.N = (int)pa; g.K = c * nt;
@@ -850,16 +835,14 @@ extern "C" int eap_gemm_bf16x3_reduce_f32(int M, int N, int K, const float *A, i
         (reinterpret_cast<uintptr_t>(workspace) & 15))
         return eap::bad_arg("gemm_bf16x3_reduce_f32: unsupported operands (ask eap_gemm_bf16x3_reduce_f32_supported)");
     const int slabs = reduce_slabs(M, N, K, batch);
-    if ((long long)batch * slabs > 65535) return eap::bad_arg("gemm_bf16x3_reduce_f32: batch x slabs exceeds 65535");
     Args g{};
     g.M = M; g.N = N; g.K = K;
     g.A = A; g.lda = lda; g.sA = strideA;
     g.B = B; g.ldb = ldb; g.sB = strideB;
     g.C = workspace; g.ldc = N; g.sC = (long long)M * N;
     g.slabs = slabs; g.kslab = K / slabs;          // one slab: z is the item and the kernel's k-loop covers K
-    if (int e = launch_split<0>(g, batch * slabs, eap::S(stream), "gemm_bf16x3_reduce_f32")) return e;
+    if (int e = launch_split<0>(g, (long long)batch * slabs, eap::S(stream), "gemm_bf16x3_reduce_f32")) return e;
     const long long mn4 = (long long)M * N / 4;
-    hipLaunchKernelGGL(split_reduce_kernel, dim3((unsigned)((mn4 + 255) / 256)), dim3(256), 0, eap::S(stream), mn4, batch * slabs,
-                       reinterpret_cast<const f32x4 *>(workspace), C, N, (long long)ldc);
-    return eap::check_launch("gemm_bf16x3_reduce_f32 (sum of the partials)");
+    return eap::run_kernel("gemm_bf16x3_reduce_f32 (sum of the partials)", split_reduce_kernel, eap::cdiv(mn4, 256), 1, 1, dim3(256), 0, eap::S(stream), mn4,
+                           batch * slabs, reinterpret_cast<const f32x4 *>(workspace), C, N, (long long)ldc);
 }

@@ -310,38 +310,31 @@ __global__ __launch_bounds__(NT, 1) void gemm_dma_f32_kernel(DmaArgs g) {
 }
 
 template <int WM, int WN, int MI, int NI, bool AKM, bool BKN>
-int launch_one(DmaArgs g, int zcount, hipStream_t s) {
+int launch_one(DmaArgs g, long long zcount, hipStream_t s) {
     constexpr int BM = 32 * MI * WM, BN = 32 * NI * WN;
     g.tiles_m = (g.M + BM - 1) / BM;
     g.tiles_n = (g.N + BN - 1) / BN;
     const size_t shmem = (size_t)STAGES * (BM + BN) * BK * 4;
-    auto kern = gemm_dma_f32_kernel<WM, WN, MI, NI, AKM, BKN>;
-    int e = eap::allow_dynamic_lds(kern, shmem, "gemm_dma_f32 shared memory");
-    if (e) return e;
-    hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, zcount), dim3(NT), shmem, s, g);
-    {
-        char nm[96];
-        snprintf(nm, sizeof(nm), "gemm_dma_f32_kernel<%d, %d, %d, %d, %s, %s>", WM, WN, MI, NI, AKM ? "true" : "false", BKN ? "true" : "false");
-        eap::set_kernel(nm);
-    }
-    return eap::check_launch("gemm_dma_f32");
+    char nm[96];
+    snprintf(nm, sizeof(nm), "gemm_dma_f32_kernel<%d, %d, %d, %d, %s, %s>", WM, WN, MI, NI, AKM ? "true" : "false", BKN ? "true" : "false");
+    eap::set_kernel(nm);
+    return eap::run_kernel("gemm_dma_f32", gemm_dma_f32_kernel<WM, WN, MI, NI, AKM, BKN>, (long long)g.tiles_m * g.tiles_n, zcount, 1, dim3(NT), shmem, s, g);
 }
 
 template <bool AKM, bool BKN>
-int launch_shape(const DmaArgs &g, int zcount, hipStream_t s) {
+int launch_shape(const DmaArgs &g, long long zcount, hipStream_t s) {
     // block tile 256 x 256 (wave tile 128 x 128); for M <= 128: 128 x 512 (the same wave tile) when that still leaves
     // four workgroups per CU, else 128 x 256; 256 x 128 for N <= 128; 64 x 512 / 512 x 64 for a side of at most 64
     // a 64-wide side: 64 x 512 / 512 x 64 tiles (half of a 128-row tile would be padding)
     if (g.M <= 64 && g.N > 64) return launch_one<1, 4, 2, 4, AKM, BKN>(g, zcount, s);
     if (g.N <= 64 && g.M > 64) return launch_one<4, 1, 4, 2, AKM, BKN>(g, zcount, s);
-    if (g.M <= 128 && (long long)((g.N + 511) / 512) * zcount >= 1024) return launch_one<1, 4, 4, 4, AKM, BKN>(g, zcount, s);
+    if (g.M <= 128 && (g.N + 511) / 512 * zcount >= 1024) return launch_one<1, 4, 4, 4, AKM, BKN>(g, zcount, s);
     if (g.M <= 128) return launch_one<1, 4, 4, 2, AKM, BKN>(g, zcount, s);
     if (g.N <= 128) return launch_one<4, 1, 2, 4, AKM, BKN>(g, zcount, s);
     return launch_one<2, 2, 4, 4, AKM, BKN>(g, zcount, s);
 }
 
-int launch(bool akm, bool bkn, const DmaArgs &g, int zcount, hipStream_t s) {
-    if (zcount > 65535) return eap::bad_arg("gemm_dma_f32: batch * splits exceeds 65535");
+int launch(bool akm, bool bkn, const DmaArgs &g, long long zcount, hipStream_t s) {
     if (akm) return bkn ? launch_shape<true, true>(g, zcount, s) : launch_shape<true, false>(g, zcount, s);
     return bkn ? launch_shape<false, true>(g, zcount, s) : launch_shape<false, false>(g, zcount, s);
 }
@@ -404,7 +397,7 @@ extern "C" int eap_gemm_dma_f32_reduce(int transA, int transB, int M, int N, int
     const int splits = pick_splits(M, N, K, batch);
     const int kchunk = ((K / BK + splits - 1) / splits) * BK;
     DmaArgs g{M, N, K, A, lda, strideA, B, ldb, strideB, workspace, N, (long long)M * N, 0, 0, splits, kchunk};
-    int e = launch(transA != 0, transB == 0, g, batch * splits, s);
+    int e = launch(transA != 0, transB == 0, g, (long long)batch * splits, s);
     if (e) return e;
     return eap::reduce_slabs(workspace, C, (long long)M * N, N, batch * splits, ldc, s, "gemm_dma_f32_reduce");
 }

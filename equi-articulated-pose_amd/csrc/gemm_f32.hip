@@ -257,28 +257,20 @@ __global__ void reduce_slabs_kernel(long long mn, int N, int slabs, const float 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int NWM, int NWN, int WTM>
-int launch(bool ta, bool tb, const GemmArgs &g, int zcount, hipStream_t s) {
+int launch(bool ta, bool tb, const GemmArgs &g, long long zcount, hipStream_t s) {
     const bool vec = aligned16(g.A) && aligned16(g.B) && g.lda % 4 == 0 && g.ldb % 4 == 0 &&
                      g.sA % 4 == 0 && g.sB % 4 == 0;
-    dim3 grid(g.tiles_m * g.tiles_n, zcount), block(64 * NWM * NWN);
-#define EAP_GEMM_LAUNCH(TA, TB)                                                                              \
-    do {                                                                                                     \
-        if (vec) hipLaunchKernelGGL((gemm_f32_kernel<NWM, NWN, WTM, TA, TB, true>), grid, block, 0, s, g);   \
-        else hipLaunchKernelGGL((gemm_f32_kernel<NWM, NWN, WTM, TA, TB, false>), grid, block, 0, s, g);      \
-    } while (0)
-    if (g.gidx) {   // implicit intra conv: A = W [M,K] row-major, B gathered
-        if (vec) hipLaunchKernelGGL((gemm_f32_kernel<NWM, NWN, WTM, false, false, true, true>), grid, block, 0, s, g);
-        else hipLaunchKernelGGL((gemm_f32_kernel<NWM, NWN, WTM, false, false, false, true>), grid, block, 0, s, g);
-    } else if (!ta && !tb) EAP_GEMM_LAUNCH(false, false);
-    else if (ta && !tb) EAP_GEMM_LAUNCH(true, false);
-    else if (!ta && tb) EAP_GEMM_LAUNCH(false, true);
-    else EAP_GEMM_LAUNCH(true, true);
-#undef EAP_GEMM_LAUNCH
-    return eap::check_launch("gemm_f32");
+    void (*kern)(GemmArgs);
+    if (g.gidx)   // implicit intra conv: A = W [M,K] row-major, B gathered
+        kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, false, false, true, true> : gemm_f32_kernel<NWM, NWN, WTM, false, false, false, true>;
+    else if (!ta && !tb) kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, false, false, true> : gemm_f32_kernel<NWM, NWN, WTM, false, false, false>;
+    else if (ta && !tb) kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, true, false, true> : gemm_f32_kernel<NWM, NWN, WTM, true, false, false>;
+    else if (!ta && tb) kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, false, true, true> : gemm_f32_kernel<NWM, NWN, WTM, false, true, false>;
+    else kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, true, true, true> : gemm_f32_kernel<NWM, NWN, WTM, true, true, false>;
+    return eap::run_kernel("gemm_f32", kern, (long long)g.tiles_m * g.tiles_n, zcount, 1, dim3(64 * NWM * NWN), 0, s, g);
 }
 
-int run(bool ta, bool tb, GemmArgs g, int zcount, hipStream_t s) {
-    if (zcount > 65535) return eap::bad_arg("gemm_f32: batch*splits exceeds 65535");
+int run(bool ta, bool tb, GemmArgs g, long long zcount, hipStream_t s) {
     // block tile 64x128 for M <= 64, 256x128 from M = 256 (+2% on the L2-layer shape over 128x128), else 128x128
     const int bm = g.M <= 64 ? 64 : g.M >= 256 ? 256 : 128;
     g.tiles_m = (g.M + bm - 1) / bm;
@@ -306,7 +298,7 @@ int run_reduce(int transA, int transB, int M, int N, int K, const float *A, int6
     const int splits = pick_splits(M, N, K, batch);
     int kchunk = ((K + splits - 1) / splits + BK - 1) / BK * BK;
     GemmArgs g{M, N, K, A, lda, strideA, B, ldb, strideB, workspace, N, (long long)M * N, splits, kchunk, 0, 0, nullptr, 0, 0, bblk};
-    int e = run(transA != 0, transB != 0, g, batch * splits, s);
+    int e = run(transA != 0, transB != 0, g, (long long)batch * splits, s);
     if (e) return e;
     return eap::reduce_slabs(workspace, C, (long long)M * N, N, batch * splits, ldc, s, "gemm_f32_reduce");
 }
@@ -314,8 +306,7 @@ int run_reduce(int transA, int transB, int M, int N, int K, const float *A, int6
 }  // namespace
 
 int eap::reduce_slabs(const float *ws, float *C, long long mn, int N, int slabs, long long ldc, hipStream_t s, const char *what) {
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(eap::cdiv(mn, 256)), dim3(256), 0, s, mn, N, slabs, ws, C, ldc);
-    return eap::check_launch(what);
+    return eap::run_kernel(what, reduce_slabs_kernel, eap::cdiv(mn, 256), 1, 1, dim3(256), 0, s, mn, N, slabs, ws, C, ldc);
 }
 
 extern "C" int eap_gemm_f32(int transA, int transB, int M, int N, int K, const float *A, int64_t lda,

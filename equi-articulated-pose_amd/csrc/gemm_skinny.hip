@@ -154,16 +154,10 @@ extern "C" int eap_gemm_skinny_reduce_f32(int M, int N, int K, const float *A, i
     int kchunk = (K + splits - 1) / splits;
     kchunk = ((kchunk + 4 * KSTEP - 1) / (4 * KSTEP)) * (4 * KSTEP);
     splits = (K + kchunk - 1) / kchunk;                       // (never more than pick_splits: the workspace covers it)
-    if (M > 32)
-        hipLaunchKernelGGL(gemm_skinny_kernel<2>, dim3(splits, batch), dim3(NT), 0, s, M, N, K, kchunk, splits, A, (long long)lda, (long long)strideA, B,
-                           (long long)ldb, (long long)strideB, workspace);
-    else
-        hipLaunchKernelGGL(gemm_skinny_kernel<1>, dim3(splits, batch), dim3(NT), 0, s, M, N, K, kchunk, splits, A, (long long)lda, (long long)strideA, B,
-                           (long long)ldb, (long long)strideB, workspace);
-    int e = eap::check_launch("gemm_skinny_reduce");
+    int e = eap::run_kernel("gemm_skinny_reduce", M > 32 ? gemm_skinny_kernel<2> : gemm_skinny_kernel<1>, splits, batch, 1, dim3(NT), 0, s, M, N, K, kchunk, splits,
+                            A, (long long)lda, (long long)strideA, B, (long long)ldb, (long long)strideB, workspace);
     if (e) return e;
     const int mn = M * N;
-    hipLaunchKernelGGL(skinny_sum_kernel, dim3((mn + 3) / 4), dim3(256), 0, s, mn, N, batch * splits, workspace, C, (long long)ldc);
     eap::set_kernel(M > 32 ? "gemm_skinny_kernel<2>" : "gemm_skinny_kernel<1>");
-    return eap::check_launch("gemm_skinny_reduce (sum)");
+    return eap::run_kernel("gemm_skinny_reduce (sum)", skinny_sum_kernel, eap::cdiv(mn, 4), 1, 1, dim3(256), 0, s, mn, N, batch * splits, workspace, C, (long long)ldc);
 }

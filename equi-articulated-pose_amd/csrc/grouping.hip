@@ -78,11 +78,8 @@ int launch_ball_query(int b, int n, int m, float radius, int nsample, const T *n
                       const T *xyz, int32_t *idx, hipStream_t s) {
     if (b <= 0 || m <= 0 || nsample <= 0) return 0;
     if (n <= 0) return eap::bad_arg("ball_query: empty support cloud");
-    dim3 grid(eap::cdiv(m, BQ_THREADS), b);
     const T r2 = (T)(radius * radius);  // float product first, grouping_cuda_kernel.cu:L82
-    hipLaunchKernelGGL(ball_query_kernel<T>, grid, dim3(BQ_THREADS), 0, s, n, m, r2, nsample,
-                       new_xyz, xyz, idx);
-    return eap::check_launch("ball_query");
+    return eap::run_kernel("ball_query", ball_query_kernel<T>, eap::cdiv(m, BQ_THREADS), b, 1, dim3(BQ_THREADS), 0, s, n, m, r2, nsample, new_xyz, xyz, idx);
 }
 
 
@@ -211,24 +208,21 @@ extern "C" int eap_furthest_point_sampling_f32(int b, int n, int m, const float 
     if (n <= 0) return eap::bad_arg("furthest_point_sampling: empty cloud");
     int threads = 1;
     while (threads * 2 <= n && threads < 1024) threads *= 2;   // opt_n_threads, grouping_cuda_kernel.cu:L29-33
-    hipLaunchKernelGGL(fps_kernel, dim3(b), dim3(threads), 0, eap::S(stream), n, m, xyz, temp, idx);
-    return eap::check_launch("furthest_point_sampling");
+    return eap::run_kernel("furthest_point_sampling", fps_kernel, b, 1, 1, dim3(threads), 0, eap::S(stream), n, m, xyz, temp, idx);
 }
 
 extern "C" int eap_anchor_query_f32(int b, int np, int nn, int na, int ks, const float *grouped_xyz,
                                     const float *anchors, const float *kernel_pts, float *w,
                                     eap_stream_t stream) {
     if (b <= 0 || np <= 0 || nn <= 0) return 0;
-    hipLaunchKernelGGL(anchor_query_kernel, dim3(eap::cdiv((long long)np * nn, 256), b), dim3(256), 0,
-                       eap::S(stream), np, nn, na, ks, grouped_xyz, anchors, kernel_pts, w);
-    return eap::check_launch("anchor_query");
+    return eap::run_kernel("anchor_query", anchor_query_kernel, eap::cdiv((long long)np * nn, 256), b, 1, dim3(256), 0, eap::S(stream), np, nn, na, ks, grouped_xyz,
+                           anchors, kernel_pts, w);
 }
 
 extern "C" int eap_initial_anchor_query_f32(int b, int nc, int m, int na, int ks, float radius, float sigma,
                                             const float *centers, const float *xyz, const float *kernel_pts,
                                             float *w, float *cnt, eap_stream_t stream) {
     if (b <= 0 || nc <= 0 || na <= 0 || ks <= 0) return 0;
-    hipLaunchKernelGGL(initial_anchor_query_kernel, dim3(nc, b), dim3(256), 0, eap::S(stream), nc, m, na, ks,
-                       radius, sigma, centers, xyz, kernel_pts, w, cnt);
-    return eap::check_launch("initial_anchor_query");
+    return eap::run_kernel("initial_anchor_query", initial_anchor_query_kernel, nc, b, 1, dim3(256), 0, eap::S(stream), nc, m, na, ks, radius, sigma, centers, xyz,
+                           kernel_pts, w, cnt);
 }

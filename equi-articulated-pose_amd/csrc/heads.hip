@@ -204,52 +204,46 @@ __global__ __launch_bounds__(256) void masked_max_bwd_kernel(int c, int n, int n
 extern "C" int eap_anchor_attn_pool_fwd_f32(int b, int c, int n, int na, float temperature, const float *x, const float *logits,
                                             float *out, float *conf, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0 || b > 65535) return eap::bad_arg("anchor_attn_pool: anchors must be a multiple of 4, at most 64; b <= 65535");
-    hipLaunchKernelGGL(anchor_attn_pool_kernel<false>, dim3(eap::cdiv(n, 16), b), dim3(256), 0, eap::S(stream), c, n, na, temperature, x,
-                       logits, nullptr, out, conf, nullptr, nullptr);
-    return eap::check_launch("anchor_attn_pool_fwd");
+    if (na <= 0 || na > 64 || (na & 3) != 0) return eap::bad_arg("anchor_attn_pool: anchors must be a multiple of 4, at most 64");
+    return eap::run_kernel("anchor_attn_pool_fwd", anchor_attn_pool_kernel<false>, eap::cdiv(n, 16), b, 1, dim3(256), 0, eap::S(stream), c, n, na, temperature, x,
+                           logits, nullptr, out, conf, nullptr, nullptr);
 }
 
 extern "C" int eap_anchor_attn_pool_bwd_f32(int b, int c, int n, int na, float temperature, const float *x, const float *logits,
                                             const float *g, float *dx, float *dlogits, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0 || b > 65535) return eap::bad_arg("anchor_attn_pool: anchors must be a multiple of 4, at most 64; b <= 65535");
-    hipLaunchKernelGGL(anchor_attn_pool_kernel<true>, dim3(eap::cdiv(n, 16), b), dim3(256), 0, eap::S(stream), c, n, na, temperature, x,
-                       logits, g, nullptr, nullptr, dx, dlogits);
-    return eap::check_launch("anchor_attn_pool_bwd");
+    if (na <= 0 || na > 64 || (na & 3) != 0) return eap::bad_arg("anchor_attn_pool: anchors must be a multiple of 4, at most 64");
+    return eap::run_kernel("anchor_attn_pool_bwd", anchor_attn_pool_kernel<true>, eap::cdiv(n, 16), b, 1, dim3(256), 0, eap::S(stream), c, n, na, temperature, x,
+                           logits, g, nullptr, nullptr, dx, dlogits);
 }
 
 extern "C" int eap_slot_masked_mean_fwd_f32(int b, int ns, int c, int n, int na, const float *x, const float *mask,
                                             const float *inv_den, float *out, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0 || ns <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0 || ns > MAXS || b > 65535)
-        return eap::bad_arg("slot_masked_mean: anchors must be a multiple of 4, at most 64; at most 8 slots; b <= 65535");
-    hipLaunchKernelGGL(slot_mean_fwd_kernel, dim3(c, b), dim3(256), 0, eap::S(stream), c, n, na, ns, x, mask, inv_den, out);
-    return eap::check_launch("slot_masked_mean_fwd");
+    if (na <= 0 || na > 64 || (na & 3) != 0 || ns > MAXS)
+        return eap::bad_arg("slot_masked_mean: anchors must be a multiple of 4, at most 64; at most 8 slots");
+    return eap::run_kernel("slot_masked_mean_fwd", slot_mean_fwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, ns, x, mask, inv_den, out);
 }
 
 extern "C" int eap_slot_masked_mean_bwd_f32(int b, int ns, int c, int n, int na, const float *g, const float *mask,
                                             const float *inv_den, float *dx, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0 || ns <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0 || ns > MAXS || b > 65535)
-        return eap::bad_arg("slot_masked_mean: anchors must be a multiple of 4, at most 64; at most 8 slots; b <= 65535");
-    hipLaunchKernelGGL(slot_mean_bwd_kernel, dim3(c, b), dim3(256), 0, eap::S(stream), c, n, na, ns, g, mask, inv_den, dx);
-    return eap::check_launch("slot_masked_mean_bwd");
+    if (na <= 0 || na > 64 || (na & 3) != 0 || ns > MAXS)
+        return eap::bad_arg("slot_masked_mean: anchors must be a multiple of 4, at most 64; at most 8 slots");
+    return eap::run_kernel("slot_masked_mean_bwd", slot_mean_bwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, ns, g, mask, inv_den, dx);
 }
 
 extern "C" int eap_masked_max_fwd_f32(int b, int c, int n, int na, const float *x, const float *mask, float *out, int32_t *arg,
                                       eap_stream_t stream) {
     if (b <= 0 || c <= 0) return 0;
     if (n <= 0) return eap::bad_arg("masked_max: no points");
-    if (na <= 0 || na > 64 || (na & 3) != 0 || b > 65535) return eap::bad_arg("masked_max: anchors must be a multiple of 4, at most 64; b <= 65535");
-    hipLaunchKernelGGL(masked_max_fwd_kernel, dim3(c, b), dim3(256), 0, eap::S(stream), c, n, na, x, mask, out, arg);
-    return eap::check_launch("masked_max_fwd");
+    if (na <= 0 || na > 64 || (na & 3) != 0) return eap::bad_arg("masked_max: anchors must be a multiple of 4, at most 64");
+    return eap::run_kernel("masked_max_fwd", masked_max_fwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, x, mask, out, arg);
 }
 
 extern "C" int eap_masked_max_bwd_f32(int b, int c, int n, int na, const float *g, const int32_t *arg, const float *mask, float *dx,
                                       eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0 || b > 65535) return eap::bad_arg("masked_max: anchors must be a multiple of 4, at most 64; b <= 65535");
-    hipLaunchKernelGGL(masked_max_bwd_kernel, dim3(c, b), dim3(256), 0, eap::S(stream), c, n, na, g, arg, mask, dx);
-    return eap::check_launch("masked_max_bwd");
+    if (na <= 0 || na > 64 || (na & 3) != 0) return eap::bad_arg("masked_max: anchors must be a multiple of 4, at most 64");
+    return eap::run_kernel("masked_max_bwd", masked_max_bwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, g, arg, mask, dx);
 }

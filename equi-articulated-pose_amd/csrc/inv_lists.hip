@@ -190,17 +190,12 @@ extern "C" int eap_inv_lists_rows(int b, int p, int n, int nn, const int32_t *id
     int e = eap::hip_fail(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)b * n, s), "inv_lists_rows memset");
     if (e) return e;
     const int per_cloud = p * nn;
-    const int blocks = (int)eap::cdiv(per_cloud, 8192) > 0 ? (int)eap::cdiv(per_cloud, 8192) : 1;
-    hipLaunchKernelGGL(inv_count_kernel, dim3(blocks, b), dim3(256), sizeof(int) * n, s, per_cloud, n, idx, counts);
-    e = eap::check_launch("inv_lists_rows (count)");
+    e = eap::run_kernel("inv_lists_rows (count)", inv_count_kernel, eap::cdiv(per_cloud, 8192), b, 1, dim3(256), sizeof(int) * n, s, per_cloud, n, idx, counts);
     if (e) return e;
     int n2 = RT;
     while (n2 < n) n2 <<= 1;
     const size_t shmem = sizeof(unsigned long long) * n2;
-    e = eap::allow_dynamic_lds(inv_rows_kernel, shmem, "inv_lists_rows shared memory");
-    if (e) return e;
-    hipLaunchKernelGGL(inv_rows_kernel, dim3(b), dim3(RT), shmem, s, n, n2, counts, rows, off, cnt, n_rows);
-    return eap::check_launch("inv_lists_rows (sort)");
+    return eap::run_kernel("inv_lists_rows (sort)", inv_rows_kernel, b, 1, 1, dim3(RT), shmem, s, n, n2, counts, rows, off, cnt, n_rows);
 }
 
 extern "C" int eap_inv_lists_fill(int b, int p, int n, int nn, int rcap, const int32_t *idx, const float *gx,
@@ -209,28 +204,25 @@ extern "C" int eap_inv_lists_fill(int b, int p, int n, int nn, int rcap, const i
     if (b <= 0 || p <= 0 || nn <= 0 || rcap <= 0) return 0;
     if (((long long)p * nn & 3) != 0) return eap::bad_arg("inv_lists_fill: p * nn must be a multiple of 4");
     if (rcap > n) return eap::bad_arg("inv_lists_fill: rcap exceeds the number of support points");
-    hipLaunchKernelGGL(inv_fill_kernel, dim3(rcap, b), dim3(256), 0, eap::S(stream), p * nn, nn, n, n, idx,
-                       reinterpret_cast<const float4 *>(gx), rows, off, ent_p, reinterpret_cast<float4 *>(ent_gx));
-    return eap::check_launch("inv_lists_fill");
+    return eap::run_kernel("inv_lists_fill", inv_fill_kernel, rcap, b, 1, dim3(256), 0, eap::S(stream), p * nn, nn, n, n, idx, reinterpret_cast<const float4 *>(gx),
+                           rows, off, ent_p, reinterpret_cast<float4 *>(ent_gx));
 }
 
 extern "C" int eap_rows_gather_f32(int b, int c, int n, int na, int rcap, int rows_ld, const int32_t *rows,
                                    const float *src, float *dst, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || rcap <= 0) return 0;
-    if ((na & 3) != 0 || c > 65535 || b > 65535) return eap::bad_arg("rows_gather: na must be a multiple of 4; c, b <= 65535");
-    hipLaunchKernelGGL(rows_gather_kernel, dim3(eap::cdiv((long long)rcap * (na / 4), 256), c, b), dim3(256), 0, eap::S(stream),
-                       c, n, na / 4, rcap, rows_ld, rows, reinterpret_cast<const float4 *>(src), reinterpret_cast<float4 *>(dst));
-    return eap::check_launch("rows_gather");
+    if ((na & 3) != 0) return eap::bad_arg("rows_gather: na must be a multiple of 4");
+    return eap::run_kernel("rows_gather", rows_gather_kernel, eap::cdiv((long long)rcap * (na / 4), 256), c, b, dim3(256), 0, eap::S(stream), c, n, na / 4, rcap, rows_ld,
+                           rows, reinterpret_cast<const float4 *>(src), reinterpret_cast<float4 *>(dst));
 }
 
 extern "C" int eap_rows_scatter_f32(int b, int c, int n, int na, int rcap, int rows_ld, const int32_t *rows,
                                     const float *src, float *dst, eap_stream_t stream) {
     if (b <= 0 || c <= 0) return 0;
-    if ((na & 3) != 0 || c > 65535 || b > 65535) return eap::bad_arg("rows_scatter: na must be a multiple of 4; c, b <= 65535");
+    if ((na & 3) != 0) return eap::bad_arg("rows_scatter: na must be a multiple of 4");
     hipStream_t s = eap::S(stream);
     int e = eap::hip_fail(hipMemsetAsync(dst, 0, sizeof(float) * (size_t)b * c * n * na, s), "rows_scatter memset");
     if (e || rcap <= 0) return e;
-    hipLaunchKernelGGL(rows_scatter_kernel, dim3(eap::cdiv((long long)rcap * (na / 4), 256), c, b), dim3(256), 0, s,
-                       c, n, na / 4, rcap, rows_ld, rows, reinterpret_cast<const float4 *>(src), reinterpret_cast<float4 *>(dst));
-    return eap::check_launch("rows_scatter");
+    return eap::run_kernel("rows_scatter", rows_scatter_kernel, eap::cdiv((long long)rcap * (na / 4), 256), c, b, dim3(256), 0, s, c, n, na / 4, rcap, rows_ld, rows,
+                           reinterpret_cast<const float4 *>(src), reinterpret_cast<float4 *>(dst));
 }

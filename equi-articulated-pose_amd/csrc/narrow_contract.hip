@@ -148,21 +148,17 @@ extern "C" int eap_narrow_contract_supported(int b, int o, int c, int64_t n) { r
 extern "C" int eap_narrow_contract_fwd_f32(int b, int o, int c, int64_t n, const float *W, const float *x, float *y, eap_stream_t stream) {
     if (b <= 0 || n <= 0) return 0;
     if (!dims_ok(b, o, c, (long)n)) return eap::bad_arg("narrow_contract_fwd: 1-4 output channels, at most 2048 input channels, row length a multiple of 4");
-    by_rows(o, [&](auto oc) {
-        hipLaunchKernelGGL(narrow_fwd_kernel<decltype(oc)::value>, dim3(eap::cdiv(n / 4, TB), b), dim3(TB), 0, eap::S(stream), c, (long)n, W, x, y);
-        return 0;
+    return by_rows(o, [&](auto oc) {
+        return eap::run_kernel("narrow_contract_fwd", narrow_fwd_kernel<decltype(oc)::value>, eap::cdiv(n / 4, TB), b, 1, dim3(TB), 0, eap::S(stream), c, (long)n, W, x, y);
     });
-    return eap::check_launch("narrow_contract_fwd");
 }
 
 extern "C" int eap_narrow_contract_dx_f32(int b, int o, int c, int64_t n, const float *W, const float *g, float *dx, eap_stream_t stream) {
     if (b <= 0 || n <= 0) return 0;
     if (!dims_ok(b, o, c, (long)n)) return eap::bad_arg("narrow_contract_dx: 1-4 output channels, at most 2048 input channels, row length a multiple of 4");
-    by_rows(o, [&](auto oc) {
-        hipLaunchKernelGGL(narrow_dx_kernel<decltype(oc)::value>, dim3(eap::cdiv(n / 4, TB), b), dim3(TB), 0, eap::S(stream), c, (long)n, W, g, dx);
-        return 0;
+    return by_rows(o, [&](auto oc) {
+        return eap::run_kernel("narrow_contract_dx", narrow_dx_kernel<decltype(oc)::value>, eap::cdiv(n / 4, TB), b, 1, dim3(TB), 0, eap::S(stream), c, (long)n, W, g, dx);
     });
-    return eap::check_launch("narrow_contract_dx");
 }
 
 // number of [b][o][c] partials eap_narrow_contract_dw_f32 writes (the caller sums them in order)
@@ -174,10 +170,8 @@ extern "C" int eap_narrow_contract_dw_f32(int b, int o, int c, int64_t n, const 
     const int slabs = dw_slabs((long)n);
     long slab_cols = ((long)n + slabs - 1) / slabs;
     slab_cols = (slab_cols + TB * 4 - 1) / (TB * 4) * (TB * 4);
-    by_rows(o, [&](auto oc) {
-        hipLaunchKernelGGL(narrow_dw_kernel<decltype(oc)::value>, dim3(slabs, (c + CS - 1) / CS, b), dim3(TB), 0, eap::S(stream), c, (long)n,
-                           slab_cols, g, x, partial);
-        return 0;
+    return by_rows(o, [&](auto oc) {
+        return eap::run_kernel("narrow_contract_dw", narrow_dw_kernel<decltype(oc)::value>, slabs, (c + CS - 1) / CS, b, dim3(TB), 0, eap::S(stream), c, (long)n, slab_cols,
+                               g, x, partial);
     });
-    return eap::check_launch("narrow_contract_dw");
 }

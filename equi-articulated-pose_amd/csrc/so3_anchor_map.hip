@@ -83,8 +83,6 @@ extern "C" int eap_so3_anchor_map_f32(int b, int p, int n, int nn, int na, const
     int e = eap::hip_fail(hipMemsetAsync(nontrivial, 0, sizeof(int32_t) * b, eap::S(stream)), "so3_anchor_map memset");
     if (e || p <= 0 || nn <= 0) return e;
     if (n <= 0) return eap::bad_arg("so3_anchor_map: no support points");
-    dim3 grid(eap::cdiv((long long)p * nn, 256), b);
-    hipLaunchKernelGGL(so3_anchor_map_kernel, grid, dim3(256), 0, eap::S(stream), p, n, nn, na, idx, q_pose, s_pose, anchors,
-                       reinterpret_cast<uint32_t *>(amap), nontrivial);
-    return eap::check_launch("so3_anchor_map");
+    return eap::run_kernel("so3_anchor_map", so3_anchor_map_kernel, eap::cdiv((long long)p * nn, 256), b, 1, dim3(256), 0, eap::S(stream), p, n, nn, na, idx,
+                           q_pose, s_pose, anchors, reinterpret_cast<uint32_t *>(amap), nontrivial);
 }

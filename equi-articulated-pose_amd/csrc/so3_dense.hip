@@ -1025,22 +1025,8 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
 template <int MI, int FORM>
 int kc_launch(const KcArgs &g, hipStream_t s) {
     constexpr size_t shmem = 4 * (2 * (size_t)MI * 2048u + 2048u) + KC_LIST_BYTES;      // the ring + the k-step list
-    // per DEVICE (a process may drive several GPUs: the attribute belongs to the function object of the current device) and
-    // race-free: a bit per device id, set after the call succeeded -- two threads may both make the (idempotent) call
-    static std::atomic<unsigned long long> set_on{0};
-    int dev = 0;
-    if (int e = eap::hip_fail(hipGetDevice(&dev), "so3_dense: hipGetDevice")) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(set_on.load(std::memory_order_acquire) & bit)) {
-        if (int e = eap::allow_dynamic_lds(kc_gemm_kernel<MI, FORM>, shmem, "so3_dense: shared memory attribute"))
-            return e;
-        set_on.fetch_or(bit, std::memory_order_release);
-    }
-    const long long blocks = (long long)g.zcount * g.tiles_m * g.blocks_n;
-    if (blocks > 0x7fffffffLL) return eap::bad_arg("so3_dense: too many workgroups");
-    hipLaunchKernelGGL((kc_gemm_kernel<MI, FORM>), dim3((unsigned)blocks), dim3(256), shmem, s, g);
     eap::set_kernel(MI == 8 ? (FORM ? "kc_gemm_kernel<8, 1>" : "kc_gemm_kernel<8, 0>") : (FORM ? "kc_gemm_kernel<4, 1>" : "kc_gemm_kernel<4, 0>"));
-    return eap::check_launch("so3_dense product");
+    return eap::run_kernel("so3_dense product", kc_gemm_kernel<MI, FORM>, (long long)g.zcount * g.tiles_m * g.blocks_n, 1, 1, dim3(256), shmem, s, g);
 }
 
 int g_dense_form = 1;
@@ -1089,26 +1075,22 @@ template <int W>
 int dense_member(int b, int p, int n_sup, int nn, int rp, int rows_ld, const int32_t *idx, const int32_t *rows, const int32_t *n_rows, int32_t *slot_of,
                  uint32_t *memb, int32_t *flags, eap_stream_t stream) {
     if (b <= 0 || p <= 0) return 0;
-    if (rp <= 0 || rp > 32 * W || b > 65535)
-        return eap::bad_arg(W == MEMB_WORDS ? "so3_dense_member: 0 < rp <= 512, b <= 65535" : "so3_dense_member_wide: 0 < rp <= 1024, b <= 65535");
+    if (rp <= 0 || rp > 32 * W) return eap::bad_arg(W == MEMB_WORDS ? "so3_dense_member: 0 < rp <= 512" : "so3_dense_member_wide: 0 < rp <= 1024");
     hipStream_t s = eap::S(stream);
     if (int e = eap::hip_fail(hipMemsetAsync(slot_of, 0xff, sizeof(int32_t) * (size_t)b * n_sup, s), "so3_dense_member memset")) return e;
     if (int e = eap::hip_fail(hipMemsetAsync(flags, 0, sizeof(int32_t) * (size_t)b, s), "so3_dense_member memset")) return e;
-    hipLaunchKernelGGL(dense_slots_kernel, dim3(eap::cdiv(rp, 256), b), dim3(256), 0, s, n_sup, rp, rows_ld, rows, n_rows, slot_of);
-    hipLaunchKernelGGL(dense_member_kernel<W>, dim3(eap::cdiv(p, 256), b), dim3(256), 0, s, p, n_sup, nn, rp, idx, slot_of, memb, flags);
-    return eap::check_launch("so3_dense_member");
+    if (int e = eap::run_kernel("so3_dense_member", dense_slots_kernel, eap::cdiv(rp, 256), b, 1, dim3(256), 0, s, n_sup, rp, rows_ld, rows, n_rows, slot_of)) return e;
+    return eap::run_kernel("so3_dense_member", dense_member_kernel<W>, eap::cdiv(p, 256), b, 1, dim3(256), 0, s, p, n_sup, nn, rp, idx, slot_of, memb, flags);
 }
 
 template <int W>
 int dense_masks(int b, int p, int ks, int rp, int dir, const uint32_t *memb, uint64_t *mask, eap_stream_t stream) {
     if (b <= 0) return 0;
-    if (!dense_shape_ok(p, 4, ks, rp, 256, W) || b > 65535) return eap::bad_arg("so3_dense_masks: shape not taken");
+    if (!dense_shape_ok(p, 4, ks, rp, 256, W)) return eap::bad_arg("so3_dense_masks: shape not taken");
     const int n = dir ? p : ks * rp, kd = dir ? ceil_to(ks * rp, KC_BK) : p;
     const int wtiles = 4 * ((n + 255) / 256), steps = kd / KC_BK;
-    if (((long long)wtiles * steps + 3) / 4 > 0x7fffffffLL) return eap::bad_arg("so3_dense_masks: too many workgroups");
-    hipLaunchKernelGGL(dense_mask_kernel<W>, dim3((unsigned)eap::cdiv((long long)wtiles * steps, 4), b), dim3(256), 0, eap::S(stream), p, ks, rp, dir, wtiles, steps, memb,
-                       reinterpret_cast<unsigned *>(mask));
-    return eap::check_launch("so3_dense_masks");
+    return eap::run_kernel("so3_dense_masks", dense_mask_kernel<W>, eap::cdiv((long long)wtiles * steps, 4), b, 1, dim3(256), 0, eap::S(stream), p, ks, rp, dir, wtiles, steps,
+                           memb, reinterpret_cast<unsigned *>(mask));
 }
 }  // namespace
 
@@ -1136,15 +1118,15 @@ extern "C" int eap_so3_dense_tables_f32(int b, int p, int n_sup, int na, int ks,
                                         const float *s_xyz, const int32_t *rows, const float *rk, const float *row_rot, float *centre, float *pt,
                                         float *kr, eap_stream_t stream) {
     if (b <= 0) return 0;
-    if (b > 65535 || na > 65535 || !(sigma > 0.f)) return eap::bad_arg("so3_dense_tables: b, na <= 65535, sigma > 0");
+    if (!(sigma > 0.f)) return eap::bad_arg("so3_dense_tables: sigma > 0");
     hipStream_t s = eap::S(stream);
     const int p_pad = ceil_to(p, KC_BK), kd_pad = ceil_to(ks * rp, KC_BK);
-    hipLaunchKernelGGL(dense_centre_kernel, dim3(b), dim3(256), 0, s, n_sup, s_xyz, centre);
-    hipLaunchKernelGGL(dense_points_kernel, dim3(eap::cdiv(p_pad, 256), b), dim3(256), 0, s, p, p_pad, g_dense_form, 1.0f / sigma, q_xyz, centre,
-                       reinterpret_cast<f32x4 *>(pt));
-    hipLaunchKernelGGL(dense_rows_kernel, dim3(eap::cdiv(kd_pad, 256), na, b), dim3(256), 0, s, n_sup, na, ks, rp, kd_pad, rows_ld, g_dense_form, 1.0f / sigma, s_xyz,
-                       centre, rows, rk, row_rot, reinterpret_cast<f32x4 *>(kr));
-    return eap::check_launch("so3_dense_tables");
+    if (int e = eap::run_kernel("so3_dense_tables", dense_centre_kernel, b, 1, 1, dim3(256), 0, s, n_sup, s_xyz, centre)) return e;
+    if (int e = eap::run_kernel("so3_dense_tables", dense_points_kernel, eap::cdiv(p_pad, 256), b, 1, dim3(256), 0, s, p, p_pad, g_dense_form, 1.0f / sigma, q_xyz, centre,
+                                reinterpret_cast<f32x4 *>(pt)))
+        return e;
+    return eap::run_kernel("so3_dense_tables", dense_rows_kernel, eap::cdiv(kd_pad, 256), na, b, dim3(256), 0, s, n_sup, na, ks, rp, kd_pad, rows_ld, g_dense_form, 1.0f / sigma,
+                           s_xyz, centre, rows, rk, row_rot, reinterpret_cast<f32x4 *>(kr));
 }
 
 // seg / seg_pitch: a row's l elements in l / seg segments of seg elements whose starts are seg_pitch floats apart (seg <= 0: one
@@ -1164,20 +1146,19 @@ extern "C" int eap_so3_dense_split_f32(int b, int m, int l, int na, int seg, int
         seg = l;
     }
     if (seg <= 0) { seg = l; seg_pitch = (int64_t)l * na; }
-    if ((m % 32) != 0 || (na % 4) != 0 || na > 64 || b > 65535 || m > 65535 * 32 || (reinterpret_cast<uintptr_t>(src) & 15) || l % seg != 0 ||
+    if ((m % 32) != 0 || (na % 4) != 0 || na > 64 || (reinterpret_cast<uintptr_t>(src) & 15) || l % seg != 0 ||
         (seg_pitch & 3) != 0 || (colmap == nullptr && seg_pitch < (int64_t)seg * na) || (mapped && ((seg % 16) != 0 || ((l / seg) % 2) != 0)))
         return eap::bad_arg("so3_dense_split: m % 32, na % 4, na <= 64, 16-byte aligned source, whole segments of a 16-byte aligned pitch (mapped: seg % 16, an even number of segments)");
     hipStream_t s = eap::S(stream);
     const int kb_total = ceil_to(l, KC_BK) / 16;
     float *scale2 = scale + (size_t)b * na * m;
-    if (rowmax != nullptr)
-        hipLaunchKernelGGL(dense_scale_kernel, dim3(eap::cdiv((long long)b * m * na, 256)), dim3(256), 0, s, (long long)b * m * na, m, na, rowmax, scale, scale2);
-    else
-        hipLaunchKernelGGL(dense_rowmax_kernel, dim3(m, b), dim3(256), 0, s, m, l, na, seg, (long long)(seg_pitch / 4), colmap, reinterpret_cast<const f32x4 *>(src), scale, scale2);
-    if ((long long)kb_total * (m / 32) * b > 0x7fffffffLL) return eap::bad_arg("so3_dense_split: too many workgroups");
-    hipLaunchKernelGGL(dense_split_kernel<false>, dim3((unsigned)((long long)kb_total * (m / 32) * b)), dim3(256), 0, s, b, m, l, na, kb_total, seg, (long long)(seg_pitch / 4), mapped ? 1 : 0,
-                       n_rows, colmap, reinterpret_cast<const f32x4 *>(src), scale2, reinterpret_cast<u32x4 *>(planes), SplitBn{nullptr, nullptr, 1.f, 1.f});
-    return eap::check_launch("so3_dense_split");
+    const int e = rowmax != nullptr
+                      ? eap::run_kernel("so3_dense_split", dense_scale_kernel, eap::cdiv((long long)b * m * na, 256), 1, 1, dim3(256), 0, s, (long long)b * m * na, m, na, rowmax, scale, scale2)
+                      : eap::run_kernel("so3_dense_split", dense_rowmax_kernel, m, b, 1, dim3(256), 0, s, m, l, na, seg, (long long)(seg_pitch / 4), colmap,
+                                        reinterpret_cast<const f32x4 *>(src), scale, scale2);
+    if (e) return e;
+    return eap::run_kernel("so3_dense_split", dense_split_kernel<false>, (long long)kb_total * (m / 32) * b, 1, 1, dim3(256), 0, s, b, m, l, na, kb_total, seg, (long long)(seg_pitch / 4),
+                           mapped ? 1 : 0, n_rows, colmap, reinterpret_cast<const f32x4 *>(src), scale2, reinterpret_cast<u32x4 *>(planes), SplitBn{nullptr, nullptr, 1.f, 1.f});
 }
 
 // eap_so3_dense_split_f32 for dY = the gradient behind a training-mode BatchNorm + leaky_relu, formed on the way in (dense_split_kernel<true>):
@@ -1188,19 +1169,19 @@ extern "C" int eap_so3_dense_split_bn_f32(int b, int m, int l, int l_src, int na
                                           const float *act, const float *coef, float slope, float *scale, void *planes, eap_stream_t stream) {
     if (b <= 0) return 0;
     if (colmap == nullptr && l != l_src) return eap::bad_arg("so3_dense_split_bn: without a column map l = l_src");
-    if ((m % 32) != 0 || (na % 4) != 0 || na > 64 || b > 65535 || m > 65535 * 32 || ((reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(act)) & 15) ||
+    if ((m % 32) != 0 || (na % 4) != 0 || na > 64 || ((reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(act)) & 15) ||
         (colmap != nullptr && ((l & 7) != 0 || (reinterpret_cast<uintptr_t>(colmap) & 15) != 0)) || rowbound == nullptr || coef == nullptr || !(slope > 0.f))
         return eap::bad_arg("so3_dense_split_bn: m % 32, na % 4, na <= 64, 16-byte aligned sources, a bound per row, a positive slope (column map: 16-byte aligned, l % 8)");
     hipStream_t s = eap::S(stream);
     const int kb_total = ceil_to(l, KC_BK) / 16;
     float *scale2 = scale + (size_t)b * na * m;
-    hipLaunchKernelGGL(dense_scale_kernel, dim3(eap::cdiv((long long)b * m * na, 256)), dim3(256), 0, s, (long long)b * m * na, m, na, rowbound, scale, scale2);
-    if ((long long)kb_total * (m / 32) * b > 0x7fffffffLL) return eap::bad_arg("so3_dense_split_bn: too many workgroups");
+    if (int e = eap::run_kernel("so3_dense_split_bn", dense_scale_kernel, eap::cdiv((long long)b * m * na, 256), 1, 1, dim3(256), 0, s, (long long)b * m * na, m, na, rowbound, scale,
+                                scale2))
+        return e;
     const int seg = colmap ? l : l_src;
-    hipLaunchKernelGGL(dense_split_kernel<true>, dim3((unsigned)((long long)kb_total * (m / 32) * b)), dim3(256), 0, s, b, m, l, na, kb_total, seg, (long long)l_src * na / 4, 0,
-                       nullptr, colmap, reinterpret_cast<const f32x4 *>(grad), scale2, reinterpret_cast<u32x4 *>(planes),
-                       SplitBn{reinterpret_cast<const f32x4 *>(act), coef, slope, 1.0f / slope});
-    return eap::check_launch("so3_dense_split_bn");
+    return eap::run_kernel("so3_dense_split_bn", dense_split_kernel<true>, (long long)kb_total * (m / 32) * b, 1, 1, dim3(256), 0, s, b, m, l, na, kb_total, seg,
+                           (long long)l_src * na / 4, 0, nullptr, colmap, reinterpret_cast<const f32x4 *>(grad), scale2, reinterpret_cast<u32x4 *>(planes),
+                           SplitBn{reinterpret_cast<const f32x4 *>(act), coef, slope, 1.0f / slope});
 }
 
 // eap_so3_dense_untranspose_map_f32 / eap_so3_dense_untranspose_f32 (map null) with y = leaky_relu(bn_scale[o] yt + bn_shift[o], slope) on the
@@ -1209,11 +1190,10 @@ extern "C" int eap_so3_dense_split_bn_f32(int b, int m, int l, int l_src, int na
 extern "C" int eap_so3_dense_untranspose_bnact_f32(int b, int o, int p, int na, int p_dst, const int32_t *map, const float *yt, const float *bn_scale,
                                                    const float *bn_shift, float slope, float *y, eap_stream_t stream) {
     if (b <= 0) return 0;
-    if ((long long)eap::cdiv(p, 64) * o * b > 0x7fffffffLL || bn_scale == nullptr || bn_shift == nullptr || (map != nullptr && p_dst <= 0) || (map == nullptr && p_dst != p))
+    if (bn_scale == nullptr || bn_shift == nullptr || (map != nullptr && p_dst <= 0) || (map == nullptr && p_dst != p))
         return eap::bad_arg("so3_dense_untranspose_bnact: scale and shift per channel; p_dst = p without a map");
-    hipLaunchKernelGGL(dense_untranspose_kernel, dim3((unsigned)((long long)eap::cdiv(p, 64) * o * b)), dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na,
-                       p_dst, map, nullptr, yt, y, nullptr, nullptr, bn_scale, bn_shift, slope);
-    return eap::check_launch("so3_dense_untranspose_bnact");
+    return eap::run_kernel("so3_dense_untranspose_bnact", dense_untranspose_kernel, (long long)eap::cdiv(p, 64) * o * b, 1, 1, dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na,
+                           p_dst, map, nullptr, yt, y, nullptr, nullptr, bn_scale, bn_shift, slope);
 }
 
 // ldz (dir 0): floats between consecutive (o, k) rows of Z, >= na rp (the columns past na rp are not written)
@@ -1230,7 +1210,7 @@ extern "C" int eap_so3_dense_gplanes_supported(int o, int c, int na, int ks, int
 extern "C" int eap_so3_dense_gplanes_f32(int b, int o, int c, int na, int ks, int rp, const float *W3, const float *Ft, const int32_t *n_rows,
                                          const float *bound, float *scale, void *planes, eap_stream_t stream) {
     if (b <= 0) return 0;
-    if (!eap_so3_dense_gplanes_supported(o, c, na, ks, rp) || (long long)b * na > 65535 ||
+    if (!eap_so3_dense_gplanes_supported(o, c, na, ks, rp) ||
         ((reinterpret_cast<uintptr_t>(W3) | reinterpret_cast<uintptr_t>(Ft) | reinterpret_cast<uintptr_t>(planes)) & 15) != 0)
         return eap::bad_arg("so3_dense_gplanes: shape not taken (eap_so3_dense_gplanes_supported), 16-byte aligned operands");
     const int kb_total = ceil_to(ks * rp, KC_BK) / 16;
@@ -1239,15 +1219,8 @@ extern "C" int eap_so3_dense_gplanes_f32(int b, int o, int c, int na, int ks, in
     const int fit = (int)((84u * 1024u) / ((size_t)(2 * c + 16) * 2)) / 16 * 16;
     const int rch = min(rp, max(fit, 32));
     const size_t shmem = (size_t)rch * (2 * c + 16) * 2;
-    hipStream_t s = eap::S(stream);
-    auto launch = [&](auto kern) -> int {
-        if (int e = eap::allow_dynamic_lds(kern, shmem, "so3_dense_gplanes: shared memory attribute"))
-            return e;
-        hipLaunchKernelGGL(kern, dim3(eap::cdiv(o / 32, 4), b * na), dim3(256), shmem, s, o, na, ks, rp, rch, kb_total, W3, Ft, n_rows, bound, scale,
-                           reinterpret_cast<u32x4 *>(planes));
-        return eap::check_launch("so3_dense_gplanes");
-    };
-    return c == 128 ? launch(dense_gplanes_kernel<8>) : launch(dense_gplanes_kernel<4>);
+    return eap::run_kernel("so3_dense_gplanes", c == 128 ? dense_gplanes_kernel<8> : dense_gplanes_kernel<4>, eap::cdiv(o / 32, 4), (long long)b * na, 1, dim3(256), shmem,
+                           eap::S(stream), o, na, ks, rp, rch, kb_total, W3, Ft, n_rows, bound, scale, reinterpret_cast<u32x4 *>(planes));
 }
 
 // steps (may be null): the k-step lists of eap_so3_dense_steps for this direction -- column blocks run their listed k-steps only
@@ -1285,8 +1258,8 @@ extern "C" int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int
     g.n_rows = n_rows; g.ks = ks; g.trim = dir ? 2 : 1;       // (columns / k axis are dense indices either way; without n_rows every slot counts)
     if (n_rows == nullptr) g.trim = dir ? 0 : 3;
     if (dir == 0 && n_rows != nullptr) {
-        hipLaunchKernelGGL(dense_zero_tail_kernel, dim3(o * ks, b), dim3(256), 0, eap::S(stream), o * ks, na, rp, (long long)ldz, n_rows, out);
-        if (int e = eap::check_launch("so3_dense zero tail")) return e;
+        if (int e = eap::run_kernel("so3_dense zero tail", dense_zero_tail_kernel, (long long)o * ks, b, 1, dim3(256), 0, eap::S(stream), o * ks, na, rp, (long long)ldz, n_rows, out))
+            return e;
     }
     if (!wide) return g_dense_form ? kc_launch<4, 1>(g, eap::S(stream)) : kc_launch<4, 0>(g, eap::S(stream));
     return g_dense_form ? kc_launch<8, 1>(g, eap::S(stream)) : kc_launch<8, 0>(g, eap::S(stream));
@@ -1302,18 +1275,14 @@ extern "C" int eap_so3_dense_product_f32(int dir, int b, int o, int p, int na, i
 extern "C" int eap_so3_dense_point_keys(int b, int p, const uint32_t *memb, int32_t *keys, eap_stream_t stream) {
     if (b <= 0 || p <= 0) return 0;
     const long long total = (long long)b * p;
-    if ((total + 255) / 256 > 0x7fffffffLL) return eap::bad_arg("so3_dense_point_keys: too many workgroups");
-    hipLaunchKernelGGL(dense_keys_kernel<MEMB_WORDS>, dim3((unsigned)eap::cdiv(total, 256)), dim3(256), 0, eap::S(stream), total, memb, keys);
-    return eap::check_launch("so3_dense_point_keys");
+    return eap::run_kernel("so3_dense_point_keys", dense_keys_kernel<MEMB_WORDS>, eap::cdiv(total, 256), 1, 1, dim3(256), 0, eap::S(stream), total, memb, keys);
 }
 
 // memb uint32 [b,p,32] -> keys int64 [b,p], bit g = a row of group g < 64 (rp <= 1024)
 extern "C" int eap_so3_dense_point_keys_wide(int b, int p, const uint32_t *memb, int64_t *keys, eap_stream_t stream) {
     if (b <= 0 || p <= 0) return 0;
     const long long total = (long long)b * p;
-    if ((total + 255) / 256 > 0x7fffffffLL) return eap::bad_arg("so3_dense_point_keys_wide: too many workgroups");
-    hipLaunchKernelGGL(dense_keys_kernel<MEMB_WORDS_WIDE>, dim3((unsigned)eap::cdiv(total, 256)), dim3(256), 0, eap::S(stream), total, memb, keys);
-    return eap::check_launch("so3_dense_point_keys_wide");
+    return eap::run_kernel("so3_dense_point_keys_wide", dense_keys_kernel<MEMB_WORDS_WIDE>, eap::cdiv(total, 256), 1, 1, dim3(256), 0, eap::S(stream), total, memb, keys);
 }
 
 // int32 words of the k-step lists of one direction: [b][column blocks of 256][k-steps + 1]
@@ -1326,13 +1295,12 @@ extern "C" int64_t eap_so3_dense_steps_words(int b, int p, int ks, int rp, int d
 namespace {
 int dense_steps(int words, int b, int p, int ks, int rp, int dir, int skip, const int32_t *n_rows, const uint64_t *mask, int32_t *steps, eap_stream_t stream) {
     if (b <= 0) return 0;
-    if (!dense_shape_ok(p, 4, ks, rp, 256, words) || b > 65535) return eap::bad_arg("so3_dense_steps: shape not taken");
+    if (!dense_shape_ok(p, 4, ks, rp, 256, words)) return eap::bad_arg("so3_dense_steps: shape not taken");
     const int n = dir ? p : ks * rp, kd = dir ? ceil_to(ks * rp, KC_BK) : p;
     const int blocks_n = (n + 255) / 256, KS = kd / KC_BK;
     if ((size_t)KS * sizeof(int) > 48 * 1024) return eap::bad_arg("so3_dense_steps: more than 12288 k-steps");
-    hipLaunchKernelGGL(dense_steps_kernel, dim3(blocks_n, b), dim3(256), sizeof(int) * (size_t)KS, eap::S(stream), KS, blocks_n, 4 * blocks_n, dir, ks, rp, skip,
-                       n_rows, reinterpret_cast<const unsigned *>(mask), steps);
-    return eap::check_launch("so3_dense_steps");
+    return eap::run_kernel("so3_dense_steps", dense_steps_kernel, blocks_n, b, 1, dim3(256), sizeof(int) * (size_t)KS, eap::S(stream), KS, blocks_n, 4 * blocks_n, dir, ks, rp, skip,
+                           n_rows, reinterpret_cast<const unsigned *>(mask), steps);
 }
 }  // namespace
 
@@ -1350,10 +1318,8 @@ extern "C" int eap_so3_dense_steps_wide(int b, int p, int ks, int rp, int dir, i
 // psum, psq (may be null): float [o][b * ceil(p / 64)] partial sums of (y - y[0,o,0,0]) and of its square per 64-point chunk
 extern "C" int eap_so3_dense_untranspose_f32(int b, int o, int p, int na, const float *yt, float *y, float *psum, float *psq, eap_stream_t stream) {
     if (b <= 0) return 0;
-    if ((long long)eap::cdiv(p, 64) * o * b > 0x7fffffffLL) return eap::bad_arg("so3_dense_untranspose: too many workgroups");
-    hipLaunchKernelGGL(dense_untranspose_kernel, dim3((unsigned)((long long)eap::cdiv(p, 64) * o * b)), dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na, p, nullptr, nullptr,
-                       yt, y, psum, psum ? psq : nullptr);
-    return eap::check_launch("so3_dense_untranspose");
+    return eap::run_kernel("so3_dense_untranspose", dense_untranspose_kernel, (long long)eap::cdiv(p, 64) * o * b, 1, 1, dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na,
+                           p, nullptr, nullptr, yt, y, psum, psum ? psq : nullptr, nullptr, nullptr, 1.f);
 }
 
 // the same re-ordering into a Y [b,o,p_dst,na] that other launches fill too: column pp of cloud b goes to point map[b][pp] (int32 [b,p];
@@ -1361,10 +1327,9 @@ extern "C" int eap_so3_dense_untranspose_f32(int b, int o, int p, int na, const 
 extern "C" int eap_so3_dense_untranspose_map_f32(int b, int o, int p, int na, int p_dst, const int32_t *map, const float *yt, float *y,
                                                  eap_stream_t stream) {
     if (b <= 0) return 0;
-    if (o > 65535 || b > 65535 || map == nullptr || p_dst <= 0) return eap::bad_arg("so3_dense_untranspose_map: o, b <= 65535, a map, p_dst > 0");
-    hipLaunchKernelGGL(dense_untranspose_kernel, dim3((unsigned)((long long)eap::cdiv(p, 64) * o * b)), dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na, p_dst, map, nullptr,
-                       yt, y, nullptr, nullptr);
-    return eap::check_launch("so3_dense_untranspose_map");
+    if (map == nullptr || p_dst <= 0) return eap::bad_arg("so3_dense_untranspose_map: a map, p_dst > 0");
+    return eap::run_kernel("so3_dense_untranspose_map", dense_untranspose_kernel, (long long)eap::cdiv(p, 64) * o * b, 1, 1, dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na,
+                           p_dst, map, nullptr, yt, y, nullptr, nullptr, nullptr, nullptr, 1.f);
 }
 
 // ... and with the channel moments of eap_so3_dense_untranspose_f32 (over the columns whose map entry is not negative); pivot_pos int32 [1]
@@ -1372,9 +1337,8 @@ extern "C" int eap_so3_dense_untranspose_map_f32(int b, int o, int p, int na, in
 extern "C" int eap_so3_dense_untranspose_map_stats_f32(int b, int o, int p, int na, int p_dst, const int32_t *map, const int32_t *pivot_pos, const float *yt,
                                                        float *y, float *psum, float *psq, eap_stream_t stream) {
     if (b <= 0) return 0;
-    if (o > 65535 || b > 65535 || map == nullptr || pivot_pos == nullptr || p_dst <= 0 || psum == nullptr || psq == nullptr)
-        return eap::bad_arg("so3_dense_untranspose_map_stats: o, b <= 65535, a map, the pivot column, both partial arrays");
-    hipLaunchKernelGGL(dense_untranspose_kernel, dim3((unsigned)((long long)eap::cdiv(p, 64) * o * b)), dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na, p_dst, map,
-                       pivot_pos, yt, y, psum, psq);
-    return eap::check_launch("so3_dense_untranspose_map_stats");
+    if (map == nullptr || pivot_pos == nullptr || p_dst <= 0 || psum == nullptr || psq == nullptr)
+        return eap::bad_arg("so3_dense_untranspose_map_stats: a map, the pivot column, both partial arrays");
+    return eap::run_kernel("so3_dense_untranspose_map_stats", dense_untranspose_kernel, (long long)eap::cdiv(p, 64) * o * b, 1, 1, dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na,
+                           p_dst, map, pivot_pos, yt, y, psum, psq, nullptr, nullptr, 1.f);
 }

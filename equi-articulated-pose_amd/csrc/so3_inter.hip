@@ -281,28 +281,24 @@ extern "C" int eap_so3_prep_f32(int b, int p, int n, int nn, int na, const float
         int e = eap::hip_fail(hipMemsetAsync(nonident, 0, sizeof(int32_t) * b, eap::S(stream)), "so3_prep memset");
         if (e) return e;
     }
-    dim3 grid(eap::cdiv((long long)p * nn, 256), b);
-    hipLaunchKernelGGL(so3_prep_kernel, grid, dim3(256), 0, eap::S(stream), p, n, nn, na, q_xyz, s_xyz,
-                       idx, q_pose, s_pose, anchors, identity_anchor, reinterpret_cast<float4 *>(gx), nonident);
-    return eap::check_launch("so3_prep");
+    return eap::run_kernel("so3_prep", so3_prep_kernel, eap::cdiv((long long)p * nn, 256), b, 1, dim3(256), 0, eap::S(stream), p, n, nn, na, q_xyz, s_xyz, idx, q_pose,
+                           s_pose, anchors, identity_anchor, reinterpret_cast<float4 *>(gx), nonident);
 }
 
 extern "C" int eap_so3_inter_weights_f32(int b, int p, int nn, int na, int ks, float sigma,
                                          const float *gx, const float *rk, float *w,
                                          eap_stream_t stream) {
     if (b <= 0 || p <= 0 || nn <= 0 || na <= 0 || ks <= 0) return 0;
-    hipLaunchKernelGGL(so3_inter_weights_kernel, dim3(p, b), dim3(256), 16 * (size_t)nn, eap::S(stream),
-                       p, nn, na, ks, sigma, reinterpret_cast<const float4 *>(gx), rk, w);
-    return eap::check_launch("so3_inter_weights");
+    return eap::run_kernel("so3_inter_weights", so3_inter_weights_kernel, p, b, 1, dim3(256), 16 * (size_t)nn, eap::S(stream), p, nn, na, ks, sigma,
+                           reinterpret_cast<const float4 *>(gx), rk, w);
 }
 
 extern "C" int eap_so3_anchor_perm(int b, int p, int nn, int na, const float *gx, const uint8_t *mult,
                                    int64_t *perm, eap_stream_t stream) {
     const long long total = (long long)b * p * nn * na;
     if (total <= 0) return 0;
-    hipLaunchKernelGGL(so3_anchor_perm_kernel, dim3(eap::cdiv(total, 256)), dim3(256), 0, eap::S(stream),
-                       total, na, reinterpret_cast<const float4 *>(gx), mult, perm);
-    return eap::check_launch("so3_anchor_perm");
+    return eap::run_kernel("so3_anchor_perm", so3_anchor_perm_kernel, eap::cdiv(total, 256), 1, 1, dim3(256), 0, eap::S(stream), total, na,
+                           reinterpret_cast<const float4 *>(gx), mult, perm);
 }
 
 namespace {
@@ -311,16 +307,10 @@ int launch_group_fwd(int b, int c, int p, int n, int nn, int na, int ks, float s
                      const float *feats, const int32_t *idx, const float *gx, const float *rk,
                      const uint8_t *mult, float *out, hipStream_t s) {
     const size_t shmem = 20 * (size_t)nn + (mult ? (size_t)na * na : 0);
-    dim3 grid(p, b), block(G_THREADS);
-    const float inv_sigma = 1.0f / sigma;
-    const float4 *g4 = reinterpret_cast<const float4 *>(gx);
-    if (c == 1)
-        hipLaunchKernelGGL((so3_inter_group_fwd_kernel<KPW, 1>), grid, block, shmem, s, c, p, n, nn, na, ks, inv_sigma, feats, idx, g4, rk, mult, out);
-    else if (c <= 8)
-        hipLaunchKernelGGL((so3_inter_group_fwd_kernel<KPW, 4>), grid, block, shmem, s, c, p, n, nn, na, ks, inv_sigma, feats, idx, g4, rk, mult, out);
-    else
-        hipLaunchKernelGGL((so3_inter_group_fwd_kernel<KPW, 16>), grid, block, shmem, s, c, p, n, nn, na, ks, inv_sigma, feats, idx, g4, rk, mult, out);
-    return eap::check_launch("so3_inter_group_fwd");
+    auto kern = so3_inter_group_fwd_kernel<KPW, 1>;
+    if (c > 1) kern = c <= 8 ? so3_inter_group_fwd_kernel<KPW, 4> : so3_inter_group_fwd_kernel<KPW, 16>;
+    return eap::run_kernel("so3_inter_group_fwd", kern, p, b, 1, dim3(G_THREADS), shmem, s, c, p, n, nn, na, ks, 1.0f / sigma, feats, idx,
+                           reinterpret_cast<const float4 *>(gx), rk, mult, out);
 }
 }  // namespace
 
@@ -414,11 +404,6 @@ extern "C" int eap_so3_inter_group_bwd_f32(int b, int c, int p, int n, int nn, i
     int e = eap::hip_fail(hipMemsetAsync(gfeats, 0, sizeof(float) * (size_t)b * c * n * na, s), "so3_inter_group_bwd memset");
     if (e || p <= 0 || nn <= 0 || ks <= 0) return e;
     const size_t shmem = 20 * (size_t)nn + (mult ? (size_t)na * na : 0);
-    const float4 *g4 = reinterpret_cast<const float4 *>(gx);
-    dim3 grid(p, b), block(G_THREADS);
-    if (ks <= 24)
-        hipLaunchKernelGGL((so3_inter_group_bwd_kernel<24, 2>), grid, block, shmem, s, c, p, n, nn, na, ks, 1.0f / sigma, gout, idx, g4, rk, mult, gfeats);
-    else
-        hipLaunchKernelGGL((so3_inter_group_bwd_kernel<32, 2>), grid, block, shmem, s, c, p, n, nn, na, ks, 1.0f / sigma, gout, idx, g4, rk, mult, gfeats);
-    return eap::check_launch("so3_inter_group_bwd");
+    return eap::run_kernel("so3_inter_group_bwd", ks <= 24 ? so3_inter_group_bwd_kernel<24, 2> : so3_inter_group_bwd_kernel<32, 2>, p, b, 1, dim3(G_THREADS), shmem, s,
+                           c, p, n, nn, na, ks, 1.0f / sigma, gout, idx, reinterpret_cast<const float4 *>(gx), rk, mult, gfeats);
 }

@@ -229,14 +229,10 @@ extern "C" int eap_so3_inter_group_bwd_slab_f32(int b, int c, int p, int n, int 
     int e = eap::hip_fail(hipMemsetAsync(workspace, 0, sizeof(float) * ws_floats, s), "so3_inter_group_bwd_slab memset");
     if (e) return e;
     const size_t shmem = sizeof(float) * (2 * NB * KS * 64 + NW * CW * 64 + 64 * RP + 4) + 20 * (size_t)nn + 4 * ((size_t)nn / NB + 1) + (mult ? (size_t)na * na : 0);
-    e = eap::allow_dynamic_lds(so3_inter_group_bwd_slab_kernel, shmem, "so3_inter_group_bwd_slab shared memory");
-    if (e) return e;
-    hipLaunchKernelGGL(so3_inter_group_bwd_slab_kernel, dim3(ps, nch, b), dim3(T_), shmem, s, c, p, n, nn, na, ks,
-                       1.0f / sigma, nch, ps, ppb, identity_anchor, gout, idx, reinterpret_cast<const float4 *>(gx), rk, mult, workspace);
-    e = eap::check_launch("so3_inter_group_bwd_slab");
+    e = eap::run_kernel("so3_inter_group_bwd_slab", so3_inter_group_bwd_slab_kernel, ps, nch, b, dim3(T_), shmem, s, c, p, n, nn, na, ks, 1.0f / sigma, nch,
+                        ps, ppb, identity_anchor, gout, idx, reinterpret_cast<const float4 *>(gx), rk, mult, workspace);
     if (e) return e;
     const long long total = (long long)b * c * n * na;
-    hipLaunchKernelGGL(so3_inter_group_bwd_reduce_kernel, dim3(eap::cdiv(total, 256)), dim3(256), 0, s, total, c, n,
-                       na, nch, ps, workspace, gfeats);
-    return eap::check_launch("so3_inter_group_bwd_reduce");
+    return eap::run_kernel("so3_inter_group_bwd_reduce", so3_inter_group_bwd_reduce_kernel, eap::cdiv(total, 256), 1, 1, dim3(256), 0, s, total, c, n, na,
+                           nch, ps, workspace, gfeats);
 }

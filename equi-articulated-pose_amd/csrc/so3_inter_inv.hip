@@ -506,12 +506,10 @@ int eap::group_fwd_perm_lists(int b, int c, int p, int n, int nn, int na, int ks
     if (sizeof(float) * (8 * (size_t)ks + 4) * na > stage_b) return -1;
     const size_t shmem = stage_b + 16 * 3 * NBK + 16 * NBK + 16 * 3 * (size_t)na + (size_t)na * na;
     if (shmem > 160 * 1024) return -1;
-    auto kern = so3_inter_group_inv_kernel<true, true, true>;
-    if (int e = eap::allow_dynamic_lds(kern, shmem, "so3_inter_group_fwd (permuted) shared memory")) return e;
-    hipLaunchKernelGGL(kern, dim3(p, (c + CB - 1) / CB, b), dim3(TM), shmem, s, c, n, nn, na, ks, p, 1.0f / sigma, -1, feats,
-                       (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, idx, reinterpret_cast<const float4 *>(gx), rk,
-                       mult, (const float *)nullptr, out, blocked, nonident, (const uint8_t *)nullptr);
-    return eap::check_launch("so3_inter_group_fwd (permuted clouds, entry-list kernel)");
+    return eap::run_kernel("so3_inter_group_fwd (permuted clouds, entry-list kernel)", so3_inter_group_inv_kernel<true, true, true>, p, (c + CB - 1) / CB, b,
+                           dim3(TM), shmem, s, c, n, nn, na, ks, p, 1.0f / sigma, -1, feats, (const int32_t *)nullptr, (const int32_t *)nullptr,
+                           (const int32_t *)nullptr, idx, reinterpret_cast<const float4 *>(gx), rk, mult, (const float *)nullptr, out, blocked, nonident,
+                           (const uint8_t *)nullptr);
 }
 
 // gy rows padded to `gy_pitch` floats (a multiple of 4, >= na; e.g. 64: every row starts a 256-byte line):
@@ -557,9 +555,8 @@ extern "C" int eap_anchor_reorder_f32(int64_t rows, int na, const float *src, co
     if ((na & 3) != 0 || (reinterpret_cast<uintptr_t>(order) & 3) || (reinterpret_cast<uintptr_t>(dst) & 15))
         return eap::bad_arg("anchor_reorder: na must be a multiple of 4, order 4-byte and dst 16-byte aligned");
     const long long words = rows * (na >> 2);
-    hipLaunchKernelGGL(anchor_reorder_kernel, dim3((unsigned)std::min<long long>((words + 255) / 256, 16384)), dim3(256), 0, eap::S(stream), words, na >> 2, na, src, order,
-                       reinterpret_cast<float4 *>(dst), 0ll, (const int32_t *)nullptr);
-    return eap::check_launch("anchor_reorder");
+    return eap::run_kernel("anchor_reorder", anchor_reorder_kernel, std::min<long long>(eap::cdiv(words, 256), 16384), 1, 1, dim3(256), 0, eap::S(stream), words,
+                           na >> 2, na, src, order, reinterpret_cast<float4 *>(dst), 0ll, (const int32_t *)nullptr);
 }
 
 // the same for [b, rows_per_cloud, na] with a per-cloud flag: clouds whose nonident[b] is 0 are skipped (dst left unwritten)
@@ -569,9 +566,8 @@ extern "C" int eap_anchor_reorder_clouds_f32(int b, int64_t rows_per_cloud, int 
     if ((na & 3) != 0 || (reinterpret_cast<uintptr_t>(order) & 3) || (reinterpret_cast<uintptr_t>(dst) & 15))
         return eap::bad_arg("anchor_reorder_clouds: na must be a multiple of 4, order 4-byte and dst 16-byte aligned");
     const long long per = rows_per_cloud * (na >> 2), words = per * b;
-    hipLaunchKernelGGL(anchor_reorder_kernel, dim3((unsigned)std::min<long long>((words + 255) / 256, 16384)), dim3(256), 0, eap::S(stream), words, na >> 2, na, src, order,
-                       reinterpret_cast<float4 *>(dst), per, nonident);
-    return eap::check_launch("anchor_reorder_clouds");
+    return eap::run_kernel("anchor_reorder_clouds", anchor_reorder_kernel, std::min<long long>(eap::cdiv(words, 256), 16384), 1, 1, dim3(256), 0, eap::S(stream),
+                           words, na >> 2, na, src, order, reinterpret_cast<float4 *>(dst), per, nonident);
 }
 
 extern "C" int eap_so3_inter_group_inv_f32(int b, int o, int p, int nn, int na, int ks, int rcap,
@@ -622,28 +618,13 @@ static int group_inv(int b, int o, int p, int nn, int na, int ks, int rcap, floa
     if (sizeof(float) * 8 * (size_t)ks * na > stage_b) return eap::bad_arg("so3_inter_group_inv: epilogue tile too large");
     size_t shmem = stage_b + 16 * 3 * NBK + 16 * NBK + (multinv ? 16 * 3 * (size_t)na + (size_t)na * na : 0);
     if (shmem > 160 * 1024) return eap::bad_arg("so3_inter_group_inv: LDS budget exceeded");
-    dim3 grid(rcap, (o + CB - 1) / CB, b);
-    const float4 *g4 = reinterpret_cast<const float4 *>(ent_gx);
-    auto launch = [&](auto kern) {
-        int e = eap::allow_dynamic_lds(kern, shmem, "so3_inter_group_inv shared memory");
-        if (e) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, o, p, nn, na, ks, rcap, 1.0f / sigma, identity_anchor, gy, rows, off, cnt, ent_p, g4, rk, multinv, anchors, z,
-                           0, (const int32_t *)nullptr, (const uint8_t *)nullptr);
-        return 0;
-    };
-    int e;
-    if (multinv && coset_order) {
-        // (the code table travels in the `multinv` argument slot; with the DMA loader gy's anchor axis is ALREADY coset-major)
-        auto go = [&](auto kern) {
-            int e2 = eap::allow_dynamic_lds(kern, shmem, "so3_inter_group_inv shared memory");
-            if (e2) return e2;
-            hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, o, p, nn, na, ks, rcap, 1.0f / sigma, identity_anchor, gy, rows, off, cnt, ent_p, g4, rk, coset_code,
-                               anchors, z, 0, (const int32_t *)nullptr, coset_order);
-            return 0;
-        };
-        e = dma ? go(so3_inter_group_inv_kernel<true, true, false, true>) : go(so3_inter_group_inv_kernel<true, false, false, true>);
-    } else if (multinv) e = dma ? launch(so3_inter_group_inv_kernel<true, true>) : launch(so3_inter_group_inv_kernel<true, false>);
-    else e = dma ? launch(so3_inter_group_inv_kernel<false, true>) : launch(so3_inter_group_inv_kernel<false, false>);
-    if (e) return e;
-    return eap::check_launch("so3_inter_group_inv");
+    // with the coset tables the code table travels in the `multinv` argument slot (and with the DMA loader gy's anchor axis is ALREADY
+    // coset-major)
+    const bool coset = multinv && coset_order;
+    const auto kern = coset     ? (dma ? so3_inter_group_inv_kernel<true, true, false, true> : so3_inter_group_inv_kernel<true, false, false, true>)
+                      : multinv ? (dma ? so3_inter_group_inv_kernel<true, true> : so3_inter_group_inv_kernel<true, false>)
+                                : (dma ? so3_inter_group_inv_kernel<false, true> : so3_inter_group_inv_kernel<false, false>);
+    return eap::run_kernel("so3_inter_group_inv", kern, rcap, (o + CB - 1) / CB, b, dim3(TM), shmem, s, o, p, nn, na, ks, rcap, 1.0f / sigma, identity_anchor, gy,
+                           rows, off, cnt, ent_p, reinterpret_cast<const float4 *>(ent_gx), rk, coset ? coset_code : multinv, anchors, z, 0,
+                           (const int32_t *)nullptr, coset ? coset_order : (const uint8_t *)nullptr);
 }

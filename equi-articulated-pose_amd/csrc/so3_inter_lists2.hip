@@ -414,18 +414,15 @@ int launch2(int layout, int b, int C, int PF, int na, int fpitch, int ks, int R,
     auto kern = perm ? (lane_order ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 4, true> : wide ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 3, true> : layout == 2 ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 2, true> : so3_group_lists2_kernel<LISTS, 0, true>)
                      : (lane_order ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 4> : wide ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 3> : layout == 2 ? so3_group_lists2_kernel<LISTS, LISTS ? 0 : 2> : so3_group_lists2_kernel<LISTS, 0>);
     const size_t shmem = perm ? SHMEM_PERM : SHMEM;
-    int e = eap::allow_dynamic_lds(kern, shmem, what);
-    if (e) return e;
     const int AG = (na + GSZ - 1) / GSZ;
     const int RPB = group_lists::rows_per_block(LISTS, nn, NBK);
-    dim3 grid((R + RPB - 1) / RPB * AG, (C + CB - 1) / CB, b);
-    hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, C, PF, na, fpitch, ks, R, nn, ent_stride, AG, RPB, (LISTS ? g_xcd_map_inv : g_xcd_map_fwd) == 2, 1.0f / sigma, F,
-                       rows, off, cnt, ent_p, reinterpret_cast<const float4 *>(ent_gx), rk, nonident, out, order);
     if (lane_order) eap::set_kernel(perm ? "so3_group_lists2_kernel<false, 4, true>" : "so3_group_lists2_kernel<false, 4>");
     else
     eap::set_kernel(perm ? (LISTS ? "so3_group_lists2_kernel<true, 0, true>" : wide ? "so3_group_lists2_kernel<false, 3, true>" : layout == 2 ? "so3_group_lists2_kernel<false, 2, true>" : "so3_group_lists2_kernel<false, 0, true>")
                          : (LISTS ? "so3_group_lists2_kernel<true, 0>" : wide ? "so3_group_lists2_kernel<false, 3>" : layout == 2 ? "so3_group_lists2_kernel<false, 2>" : "so3_group_lists2_kernel<false, 0>"));
-    return eap::check_launch(what);
+    return eap::run_kernel(what, kern, eap::cdiv(R, RPB) * AG, (C + CB - 1) / CB, b, dim3(TM), shmem, s, C, PF, na, fpitch, ks, R, nn, ent_stride, AG, RPB,
+                           (LISTS ? g_xcd_map_inv : g_xcd_map_fwd) == 2, 1.0f / sigma, F, rows, off, cnt, ent_p, reinterpret_cast<const float4 *>(ent_gx), rk, nonident, out,
+                           order);
 }
 
 }  // namespace
@@ -546,10 +543,9 @@ extern "C" int eap_so3_perm_entries_f32(int b, int per_cloud, int na, int n_supp
     if ((na & 3) != 0 || na > 60 || (long long)n_support * na * 4 >= (1ll << 31) || (reinterpret_cast<uintptr_t>(code) & 3) != 0)
         return eap::bad_arg("so3_perm_entries: na a multiple of 4 up to 60, point rows within 2^31 bytes, code table 4-byte aligned");
     const long long total = (long long)b * per_cloud;
-    hipLaunchKernelGGL(perm_entries_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, eap::S(stream), total, per_cloud, nonident, na, n_support, identity_anchor,
-                       anchors != nullptr, ent_p, reinterpret_cast<const float4 *>(ent_gx), code, anchors, reinterpret_cast<uint4 *>(ent_pc),
-                       reinterpret_cast<float4 *>(ent_gx2));
-    return eap::check_launch("so3_perm_entries");
+    return eap::run_kernel("so3_perm_entries", perm_entries_kernel, eap::cdiv(total, 256), 1, 1, dim3(256), 0, eap::S(stream), total, per_cloud, nonident, na, n_support,
+                           identity_anchor, anchors != nullptr, ent_p, reinterpret_cast<const float4 *>(ent_gx), code, anchors, reinterpret_cast<uint4 *>(ent_pc),
+                           reinterpret_cast<float4 *>(ent_gx2));
 }
 
 // Z of the re-associated backward (csrc/so3_inter_inv.hip) for clouds WITH anchor permutations, on the two-tile kernel.

@@ -121,17 +121,11 @@ template <int KPW>
 int launch_fwd_map(int b, int c, int p, int n, int nn, int na, int ks, float sigma, const float *feats, const int32_t *idx,
                    const float *gx, const float *rk, const uint8_t *amap, float *out, hipStream_t s) {
     const size_t shmem = 20 * (size_t)nn + (size_t)nn * na;
-    dim3 grid(p, b), block(T_);
-    const float inv_sigma = 1.0f / sigma;
-    const float4 *g4 = reinterpret_cast<const float4 *>(gx);
     const int ncg = 64 / na;
-    if (c <= ncg)
-        hipLaunchKernelGGL((so3_inter_group_fwd_map_kernel<KPW, 1>), grid, block, shmem, s, c, p, n, nn, na, ks, inv_sigma, feats, idx, g4, rk, amap, out);
-    else if (c <= 4 * ncg)
-        hipLaunchKernelGGL((so3_inter_group_fwd_map_kernel<KPW, 4>), grid, block, shmem, s, c, p, n, nn, na, ks, inv_sigma, feats, idx, g4, rk, amap, out);
-    else
-        hipLaunchKernelGGL((so3_inter_group_fwd_map_kernel<KPW, 8>), grid, block, shmem, s, c, p, n, nn, na, ks, inv_sigma, feats, idx, g4, rk, amap, out);
-    return eap::check_launch("so3_inter_group_fwd_map");
+    auto kern = so3_inter_group_fwd_map_kernel<KPW, 1>;
+    if (c > ncg) kern = c <= 4 * ncg ? so3_inter_group_fwd_map_kernel<KPW, 4> : so3_inter_group_fwd_map_kernel<KPW, 8>;
+    return eap::run_kernel("so3_inter_group_fwd_map", kern, p, b, 1, dim3(T_), shmem, s, c, p, n, nn, na, ks, 1.0f / sigma, feats, idx,
+                           reinterpret_cast<const float4 *>(gx), rk, amap, out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -333,17 +327,10 @@ extern "C" int eap_so3_inter_group_bwd_map_f32(int b, int c, int p, int n, int n
     const size_t ws_floats = (size_t)b * nch * ps * n * ccb * na;
     int e = eap::hip_fail(hipMemsetAsync(workspace, 0, sizeof(float) * ws_floats, s), "so3_inter_group_bwd_map memset");
     if (e) return e;
-    const float4 *g4 = reinterpret_cast<const float4 *>(gx);
-    if (ks <= 24)
-        hipLaunchKernelGGL((so3_inter_group_bwd_map_kernel<24>), dim3(ps, nch, b), dim3(T_), shmem, s, c, p, n, nn, na, ks, 1.0f / sigma,
-                           nch, ps, ppb, gout, idx, g4, rk, amap, workspace);
-    else
-        hipLaunchKernelGGL((so3_inter_group_bwd_map_kernel<32>), dim3(ps, nch, b), dim3(T_), shmem, s, c, p, n, nn, na, ks, 1.0f / sigma,
-                           nch, ps, ppb, gout, idx, g4, rk, amap, workspace);
-    e = eap::check_launch("so3_inter_group_bwd_map");
+    e = eap::run_kernel("so3_inter_group_bwd_map", ks <= 24 ? so3_inter_group_bwd_map_kernel<24> : so3_inter_group_bwd_map_kernel<32>, ps, nch, b, dim3(T_),
+                        shmem, s, c, p, n, nn, na, ks, 1.0f / sigma, nch, ps, ppb, gout, idx, reinterpret_cast<const float4 *>(gx), rk, amap, workspace);
     if (e) return e;
     const long long total = (long long)b * c * n * na;
-    hipLaunchKernelGGL(so3_inter_group_bwd_map_reduce_kernel, dim3(eap::cdiv(total, 256)), dim3(256), 0, s, total, c, n, na, nch, ps, ccb,
-                       workspace, gfeats);
-    return eap::check_launch("so3_inter_group_bwd_map_reduce");
+    return eap::run_kernel("so3_inter_group_bwd_map_reduce", so3_inter_group_bwd_map_reduce_kernel, eap::cdiv(total, 256), 1, 1, dim3(256), 0, s, total, c, n,
+                           na, nch, ps, ccb, workspace, gfeats);
 }

@@ -314,23 +314,10 @@ int eap::group_fwd_mfma(int b, int c, int p, int n, int nn, int na, int ks, floa
     size_t shmem = sizeof(float) * 2 * NBK * CB * FP_ + 20 * (size_t)nn_pad + (mult ? (size_t)na * na : 0);
     const size_t epi = sizeof(float) * (8 * (size_t)ks + 4) * na;      // the transposed epilogue pads its rows by 4 floats
     if (epi > sizeof(float) * 2 * NBK * CB * FP_) return eap::bad_arg("so3_inter_group_fwd_mfma: epilogue tile too large");
-    dim3 grid(p, (c + CB - 1) / CB, b);
-    const float4 *g4 = reinterpret_cast<const float4 *>(gx);
-    const float inv_sigma = 1.0f / sigma;
-    int e = 0;
-#define EAP_MFMA_LAUNCH(APW_, EXACT_, MULT_)                                                                  \
-    do {                                                                                                      \
-        auto kern = so3_inter_group_fwd_mfma_kernel<APW_, EXACT_, MULT_>;                                     \
-        e = eap::allow_dynamic_lds(kern, shmem, "so3_inter_group_fwd_mfma shared memory");                    \
-        if (e) return e;                                                                                      \
-        hipLaunchKernelGGL(kern, grid, dim3(TM), shmem, s, c, p, n, nn, na, ks, inv_sigma, feats, idx, g4,    \
-                           rk, mult, nonident, skip_plain, blocked, out);                                     \
-    } while (0)
-    if ((na & 3) == 0) { if (mult) EAP_MFMA_LAUNCH(8, true, true); else EAP_MFMA_LAUNCH(8, true, false); }
-    else if (mult) EAP_MFMA_LAUNCH(8, false, true);
-    else EAP_MFMA_LAUNCH(8, false, false);
-#undef EAP_MFMA_LAUNCH
-    return eap::check_launch("so3_inter_group_fwd_mfma");
+    const auto kern = (na & 3) == 0 ? (mult ? so3_inter_group_fwd_mfma_kernel<8, true, true> : so3_inter_group_fwd_mfma_kernel<8, true, false>)
+                                    : (mult ? so3_inter_group_fwd_mfma_kernel<8, false, true> : so3_inter_group_fwd_mfma_kernel<8, false, false>);
+    return eap::run_kernel("so3_inter_group_fwd_mfma", kern, p, (c + CB - 1) / CB, b, dim3(TM), shmem, s, c, p, n, nn, na, ks, 1.0f / sigma, feats, idx,
+                           reinterpret_cast<const float4 *>(gx), rk, mult, nonident, skip_plain, blocked, out);
 }
 
 extern "C" int eap_so3_inter_group_fwd_mfma_f32(int b, int c, int p, int n, int nn, int na, int ks,

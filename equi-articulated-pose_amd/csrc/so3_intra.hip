@@ -78,9 +78,8 @@ extern "C" int eap_so3_intra_group_fwd_f32(int b, int c, int p, int na, int t, c
     const long long rows = (long long)b * c * p;
     if (rows <= 0 || t <= 0 || na <= 0) return 0;
     if (na > 64) return eap::bad_arg("so3_intra_group_fwd: at most 64 anchors");
-    hipLaunchKernelGGL(so3_intra_group_fwd_kernel, dim3(eap::cdiv(rows, ROWS)), dim3(64 * ROWS), 0,
-                       eap::S(stream), rows, c, p, na, t, feats, intra_idx, out);
-    return eap::check_launch("so3_intra_group_fwd");
+    return eap::run_kernel("so3_intra_group_fwd", so3_intra_group_fwd_kernel, eap::cdiv(rows, ROWS), 1, 1, dim3(64 * ROWS), 0, eap::S(stream), rows, c, p, na, t,
+                           feats, intra_idx, out);
 }
 
 extern "C" int eap_so3_intra_group_bwd_f32(int b, int c, int p, int na, int t, const float *gout,
@@ -92,7 +91,6 @@ extern "C" int eap_so3_intra_group_bwd_f32(int b, int c, int p, int na, int t, c
         return eap::hip_fail(hipMemsetAsync(gfeats, 0, sizeof(float) * rows * na, eap::S(stream)), "so3_intra_group_bwd memset");
     const int rows_per_block = 64;
     const size_t shmem = sizeof(int32_t) * ((size_t)2 * na * t + na + 1);
-    hipLaunchKernelGGL(so3_intra_group_bwd_kernel, dim3(eap::cdiv(rows, rows_per_block)), dim3(64 * ROWS),
-                       shmem, eap::S(stream), rows, rows_per_block, c, p, na, t, gout, intra_idx, gfeats);
-    return eap::check_launch("so3_intra_group_bwd");
+    return eap::run_kernel("so3_intra_group_bwd", so3_intra_group_bwd_kernel, eap::cdiv(rows, rows_per_block), 1, 1, dim3(64 * ROWS), shmem, eap::S(stream), rows,
+                           rows_per_block, c, p, na, t, gout, intra_idx, gfeats);
 }

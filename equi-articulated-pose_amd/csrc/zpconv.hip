@@ -115,12 +115,8 @@ int launch_inter(int b, int np, int nq, int na, int ks, int ann, int c, const in
     }
     const size_t shmem = (sizeof(T) + sizeof(int32_t)) * (size_t)na * (KC * ann + 1);
     if (shmem > 160 * 1024) return eap::bad_arg("inter_zpconv: neighbourhood too large for LDS staging");
-    auto kern = inter_zpconv_kernel<T, 8, BWD>;
-    int e = eap::allow_dynamic_lds(kern, shmem, "inter_zpconv shared memory");
-    if (e) return e;
-    dim3 grid(np, 1, b);
-    hipLaunchKernelGGL(kern, grid, dim3(ZP_THREADS), shmem, s, np, nq, na, ks, ann, c, idx, w, src, dst, only_flagged);
-    return eap::check_launch(BWD ? "inter_zpconv_backward" : "inter_zpconv_forward");
+    return eap::run_kernel(BWD ? "inter_zpconv_backward" : "inter_zpconv_forward", inter_zpconv_kernel<T, 8, BWD>, np, 1, b, dim3(ZP_THREADS), shmem, s,
+                           np, nq, na, ks, ann, c, idx, w, src, dst, only_flagged);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -160,10 +156,8 @@ int launch_intra(int b, int np, int na_in, int na_out, int ks, int ann, int c, c
         if (e) return e;
     }
     if (ks <= 0 || na_out <= 0) return 0;
-    dim3 grid(eap::cdiv(np, 4), c, b);
-    hipLaunchKernelGGL((intra_zpconv_kernel<T, BWD>), grid, dim3(256), 0, s, np, na_in, na_out, ks,
-                       ann, c, idx, w, src, dst);
-    return eap::check_launch(BWD ? "intra_zpconv_backward" : "intra_zpconv_forward");
+    return eap::run_kernel(BWD ? "intra_zpconv_backward" : "intra_zpconv_forward", intra_zpconv_kernel<T, BWD>, eap::cdiv(np, 4), c, b, dim3(256), 0, s,
+                           np, na_in, na_out, ks, ann, c, idx, w, src, dst);
 }
 
 }  // namespace

@@ -247,19 +247,13 @@ extern "C" int eap_inter_zpconv_bwd_ws_f32(int b, int np, int nq, int na, int ks
     // T, 64 channels per pass
     {
         const size_t shmem = sizeof(float) * NWV * 64 * TP;
-        e = eap::allow_dynamic_lds(zpconv_bwd_t_kernel<true>, shmem, "inter_zpconv_backward shared memory");
-        if (e) return e;
-        e = eap::allow_dynamic_lds(zpconv_bwd_t_kernel<false>, shmem, "inter_zpconv_backward shared memory");
-        if (e) return e;
         const long long total = (long long)b * np * (na >> 2);
         const int upw = 4;
-        const long long blocks = (total + (long long)NWV * upw - 1) / ((long long)NWV * upw);
-        if (blocks >= (1ll << 31)) return eap::bad_arg("inter_zpconv_backward: too many workgroups");
+        const long long blocks = eap::cdiv(total, (long long)NWV * upw);
         for (int c0 = 0; c0 < c; c0 += 64) {
             const bool full = ks == 2 * KS2 && ann == 64 && c0 + 64 <= c;
-            hipLaunchKernelGGL(full ? zpconv_bwd_t_kernel<true> : zpconv_bwd_t_kernel<false>, dim3((unsigned)blocks), dim3(TM), shmem, s, c, na, ks,
-                               np, ann, c0, upw, b, grad, w, flag, T);
-            e = eap::check_launch("inter_zpconv_backward (products)");
+            e = eap::run_kernel("inter_zpconv_backward (products)", full ? zpconv_bwd_t_kernel<true> : zpconv_bwd_t_kernel<false>, blocks, 1, 1, dim3(TM), shmem, s,
+                                c, na, ks, np, ann, c0, upw, b, grad, w, flag, T);
             if (e) return e;
         }
     }
@@ -267,9 +261,8 @@ extern "C" int eap_inter_zpconv_bwd_ws_f32(int b, int np, int nq, int na, int ks
     if (e) return e;
     e = eap_inv_lists_fill(b, np, nq, ann, nq, idx0, eid, rows, off, ent_p, ent_e, stream);
     if (e) return e;
-    hipLaunchKernelGGL(zpconv_bwd_sum_kernel, dim3((na + 15) / 16, nq, b), dim3(256), 0, s, c, na, nq, np, ann, rows, off, cnt,
-                       reinterpret_cast<const float4 *>(ent_e), flag, T, gfeats);
-    e = eap::check_launch("inter_zpconv_backward (sums)");
+    e = eap::run_kernel("inter_zpconv_backward (sums)", zpconv_bwd_sum_kernel, (na + 15) / 16, nq, b, dim3(256), 0, s, c, na, nq, np, ann, rows, off, cnt,
+                        reinterpret_cast<const float4 *>(ent_e), flag, T, gfeats);
     if (e) return e;
     return eap::inter_zpconv_bwd_flagged(b, np, nq, na, ks, ann, c, idx, w, grad, gfeats, flag, s);
 }

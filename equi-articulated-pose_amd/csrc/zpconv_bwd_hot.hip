@@ -382,15 +382,13 @@ extern "C" int eap_inter_zpconv_bwd_hot_f32(int b, int np, int nq, int na, int k
     // idx0 = every point's first (a,k) row (what the kernels below walk), the cloud's referenced rows and the slot of every list entry
     e = eap::zpconv_first_rows(b, np, na * ks * ann, ann, idx, idx0, s);
     if (e) return e;
-    hipLaunchKernelGGL(zp_hot_rows_kernel, dim3(b), dim3(1024), 0, s, np, nq, idx0, rows, n_rows, slot_of, status);
-    hipLaunchKernelGGL(zp_hot_slot_off_kernel, dim3(eap::cdiv((long long)np * NN, 256), b), dim3(256), 0, s, np, nq, idx0, slot_of, n_rows, status,
-                       slot_off);
-    e = eap::check_launch("inter_zpconv_backward (on-chip rows) slots");
+    e = eap::run_kernel("inter_zpconv_backward (on-chip rows) slots", zp_hot_rows_kernel, b, 1, 1, dim3(1024), 0, s, np, nq, idx0, rows, n_rows, slot_of, status);
+    if (e) return e;
+    e = eap::run_kernel("inter_zpconv_backward (on-chip rows) slots", zp_hot_slot_off_kernel, eap::cdiv((long long)np * NN, 256), b, 1, dim3(256), 0, s, np, nq,
+                        idx0, slot_of, n_rows, status, slot_off);
     if (e) return e;
     // rows nobody references receive no gradient (clouds left to the other path are zeroed again there)
     e = eap::hip_fail(hipMemsetAsync(gfeats, 0, sizeof(float) * (size_t)b * c * nq * na, s), "inter_zpconv_backward (on-chip rows) memset");
-    if (e) return e;
-    e = eap::allow_dynamic_lds(zp_hot_kernel, LDS_BYTES, "inter_zpconv_backward (on-chip rows) shared memory");
     if (e) return e;
     // The comparison of every other (a,k) row with the first -- the op's 12 GB index read -- streams on the side stream BESIDE
     // the matrix kernel (forked here: behind the short kernels above, which its 32768 workgroups would starve of wave slots;
@@ -401,22 +399,19 @@ extern "C" int eap_inter_zpconv_bwd_hot_f32(int b, int np, int nq, int na, int k
     eap::SideJoin joiner(s);              // (also on the error returns below)
     const int members = (na / 4) * (c / CH), groups = b * L.S;
     const long long blocks = 8ll * members * ((groups + 7) / 8);
-    if (blocks >= (1ll << 31)) return eap::bad_arg("inter_zpconv_backward (on-chip rows): too many workgroups");
-    hipLaunchKernelGGL(zp_hot_kernel, dim3((unsigned)blocks), dim3(TM), LDS_BYTES, s, b, L.S, np, nq, na, c, grad, w, slot_off, rows, n_rows,
-                       status, gfeats, partial);
-    e = eap::check_launch("inter_zpconv_backward (on-chip rows)");
+    e = eap::run_kernel("inter_zpconv_backward (on-chip rows)", zp_hot_kernel, blocks, 1, 1, dim3(TM), LDS_BYTES, s, b, L.S, np, nq, na, c, grad, w, slot_off,
+                        rows, n_rows, status, gfeats, partial);
     if (e) return e;
     eap::set_kernel("zp_hot_kernel");
     // (submitted behind the matrix kernel, whose workgroups take their CUs first)
     e = eap::zpconv_index_check(b, np, na * ks * ann, ann, idx, nullptr, nullptr, flag, side);
     if (e) return e;
     if (L.S > 1) {
-        hipLaunchKernelGGL(zp_hot_reduce_kernel, dim3(members, b), dim3(256), 0, s, L.S, nq, na, c, partial, rows, n_rows, status, gfeats);
-        e = eap::check_launch("inter_zpconv_backward (on-chip rows) reduce");
+        e = eap::run_kernel("inter_zpconv_backward (on-chip rows) reduce", zp_hot_reduce_kernel, members, b, 1, dim3(256), 0, s, L.S, nq, na, c, partial, rows,
+                            n_rows, status, gfeats);
         if (e) return e;
     }
     e = joiner.join();
     if (e) return e;
-    hipLaunchKernelGGL(zp_hot_status_kernel, dim3(eap::cdiv(b, 256)), dim3(256), 0, s, b, flag, status);
-    return eap::check_launch("inter_zpconv_backward (on-chip rows) status");
+    return eap::run_kernel("inter_zpconv_backward (on-chip rows) status", zp_hot_status_kernel, eap::cdiv(b, 256), 1, 1, dim3(256), 0, s, b, flag, status);
 }

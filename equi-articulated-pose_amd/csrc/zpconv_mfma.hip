@@ -353,16 +353,14 @@ __global__ __launch_bounds__(TM, 2) void zpconv_mfma_kernel(
 namespace eap {
 
 int zpconv_index_check(int b, int np, int per_point, int nn, const int32_t *idx, int32_t *idx0, float *eid, int32_t *flag, hipStream_t s) {
-    hipLaunchKernelGGL(zpconv_index_check_kernel, dim3(np, b), dim3(CT), (size_t)nn * 4, s, np, per_point, nn, idx, idx0,
-                       reinterpret_cast<float4 *>(eid), flag);
-    return eap::check_launch("inter_zpconv (index check)");
+    return eap::run_kernel("inter_zpconv (index check)", zpconv_index_check_kernel, np, b, 1, dim3(CT), (size_t)nn * 4, s, np, per_point, nn, idx, idx0,
+                           reinterpret_cast<float4 *>(eid), flag);
 }
 
 int zpconv_first_rows(int b, int np, int per_point, int nn, const int32_t *idx, int32_t *idx0, hipStream_t s) {
     const long long rows4 = (long long)b * np * (nn >> 2);
-    hipLaunchKernelGGL(zpconv_first_rows_kernel, dim3(eap::cdiv(rows4, 256)), dim3(256), 0, s, rows4, nn >> 2, (long long)(per_point >> 2),
-                       reinterpret_cast<const int4 *>(idx), reinterpret_cast<int4 *>(idx0));
-    return eap::check_launch("inter_zpconv (first rows)");
+    return eap::run_kernel("inter_zpconv (first rows)", zpconv_first_rows_kernel, eap::cdiv(rows4, 256), 1, 1, dim3(256), 0, s, rows4, nn >> 2,
+                           (long long)(per_point >> 2), reinterpret_cast<const int4 *>(idx), reinterpret_cast<int4 *>(idx0));
 }
 
 bool inter_zpconv_mfma_supported(int np, int nq, int na, int ks, int nn, int c) {
@@ -376,14 +374,10 @@ int inter_zpconv_mfma_fwd(int b, int np, int nq, int na, int ks, int nn, int c, 
                           const float *feats, const int32_t *skip, float *out, hipStream_t s) {
     const int AG = na > 32 ? 2 : 1, gsz = AG == 1 ? na : ((na / 2 + 3) & ~3);
     const size_t shmem = 2 * (size_t)BUF_BYTES + 4 * 3 * SBK;
-    int e = eap::allow_dynamic_lds(zpconv_mfma_kernel, shmem, "inter_zpconv_forward (matrix path) shared memory");
-    if (e) return e;
     const int ny = (c + CB - 1) / CB;
     const long long units = (long long)((np + RPB - 1) / RPB) * AG * b, blocks = 8 * ((units + 7) / 8) * ny;
-    if (blocks >= (1ll << 31)) return eap::bad_arg("inter_zpconv_forward (matrix path): too many workgroups");
-    hipLaunchKernelGGL(zpconv_mfma_kernel, dim3((unsigned)blocks), dim3(TM), shmem, s, c, nq, na, ks, np, nn, AG, gsz, ny, b, feats, idx0, w,
-                       skip, out);
-    return eap::check_launch("inter_zpconv_forward (matrix path)");
+    return eap::run_kernel("inter_zpconv_forward (matrix path)", zpconv_mfma_kernel, blocks, 1, 1, dim3(TM), shmem, s, c, nq, na, ks, np, nn, AG, gsz, ny, b, feats, idx0, w,
+                           skip, out);
 }
 
 }  // namespace eap

@@ -230,11 +230,8 @@ int inter_zpconv_rows_fwd(int b, int np, int nq, int na, int ks, int nn, int c, 
                           const float *feats, float *out, const int32_t *only_flagged, hipStream_t s) {
     const int nkt = (ks + KT - 1) / KT;
     const size_t shmem = sizeof(float) * KT * (size_t)nn * w_pitch(na) + 4 * (size_t)nn;
-    int e = eap::allow_dynamic_lds(inter_zpconv_rows_kernel, shmem, "inter_zpconv_forward shared memory");
-    if (e) return e;
-    dim3 grid(np * nkt, (c + NWV * CT - 1) / (NWV * CT), b);
-    hipLaunchKernelGGL(inter_zpconv_rows_kernel, grid, dim3(TM), shmem, s, np, nq, na, ks, nn, c, nkt, idx, w, feats, only_flagged, out);
-    return eap::check_launch("inter_zpconv_forward (rows)");
+    return eap::run_kernel("inter_zpconv_forward (rows)", inter_zpconv_rows_kernel, (long long)np * nkt, (c + NWV * CT - 1) / (NWV * CT), b, dim3(TM), shmem, s, np, nq,
+                           na, ks, nn, c, nkt, idx, w, feats, only_flagged, out);
 }
 
 }  // namespace eap

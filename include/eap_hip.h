@@ -31,6 +31,14 @@ extern "C" {
 typedef void *eap_stream_t;
 
 const char *eap_last_error(void);
+/* The limits every kernel launch of the library is checked against BEFORE it is made (csrc/common.h, launch_dims): every grid and
+ * block size >= 1, at most 1024 threads per block, gx * bx < 2^32, gy and gz <= 65535.  The x rule is HIP's own, stated at the
+ * launch functions of hip_runtime_api.h ("HIP does not support kernel launch with total work items defined in dimension with
+ * size gridDim x blockDim >= 2^32"); 65535 is the y / z grid limit.  An entry whose shape needs more returns
+ * hipErrorInvalidValue with the six sizes in eap_last_error() and launches nothing.  This entry applies the same function to the
+ * sizes given, on the host alone: 0, or hipErrorInvalidValue with eap_last_error() set (a negative block size reads as its
+ * unsigned value). */
+int eap_launch_dims_ok(int64_t gx, int64_t gy, int64_t gz, int bx, int by, int bz);
 /* Name, with its template arguments, of the dominant HIP kernel the calling thread's last entry launched ("" when the
  * entry does not record one); reading clears it.  Lets a profiler-less caller (bench.py) attribute launch times to kernels. */
 const char *eap_last_kernel(void);
