@@ -21,12 +21,10 @@
 // v_mfma_f32_32x32x16_f16 -- with fp32 accumulation, |error| <= 2^-21 sum |a||b| + 2^-25 sum |a|.
 //
 // The generated operand.  With x~ = x - centre (the cloud's centroid) and u = x~_r - A_a kappa_k, one float4 table per side
-// (kr[a][(k,r)] and pt[p], both evaluated in float64 and rounded once), two forms (template FORM, eap_so3_dense_form):
-//   1 (default)  w = clamp(1 - |u - x~_p|^2 / sigma): 3 subtractions, 3 multiply-adds for the square, one fma with the [0, 1]
-//                clamp as its output modifier -- the reference's own order of operations up to the association of
-//                x_r - x_p - A_a kappa_k, absolute error ~2e-7 on a weight (what the reference's fp32 evaluation has itself);
-//   0            the square expanded: w = clamp([1 - |u|^2/sigma] + [-|x~_p|^2/sigma] + u . [2 x~_p / sigma]): 1 add + 3 fma, but
-//                partial sums up to ~6.5 at the bench radii -> ~7e-7 absolute (bar on the weights: 2e-6, tests/test_gpu_dense.py).
+// (kr[a][(k,r)] = (u, 0) and pt[p] = (x~_p, 0), both evaluated in float64 and rounded once), the weight comes from the squared distance:
+//   w = clamp(1 - |u - x~_p|^2 / sigma): 3 subtractions, 3 multiply-adds for the square, one fma with the [0, 1] clamp as its
+//   output modifier -- the reference's own order of operations up to the association of x_r - x_p - A_a kappa_k, absolute error
+//   ~2e-7 on a weight (what the reference's fp32 evaluation has itself; bar on the weights: 2e-6, tests/test_gpu_dense.py).
 // The weights are NOT scaled: l = fp16(w - fp16(w)) is a subnormal for w < 0.12 and then carries an absolute error <= 2^-25,
 // below the evaluation error above.  The mask is one bit per generated weight -- a dword per lane and k-step, riding in the
 // operand ring -- and enters as the ADDEND of the weight's last fma (1.0 for a list member, else 0.0: the clamp then returns 0).
@@ -268,41 +266,38 @@ __global__ __launch_bounds__(256) void dense_centre_kernel(int n, const float *_
     if (threadIdx.x == 3) centre[b * 4 + 3] = 0.f;
 }
 
-// pt[b][i] for the query points: FORM 1 (x~, 0); FORM 0 (2 x~/sigma, -|x~|^2/sigma); entries i >= p: zeros
-__global__ __launch_bounds__(256) void dense_points_kernel(int p, int p_pad, int form, float inv_sigma, const float *__restrict__ q_xyz,
+// pt[b][i] for the query points: (x~, 0); entries i >= p: zeros
+__global__ __launch_bounds__(256) void dense_points_kernel(int p, int p_pad, const float *__restrict__ q_xyz,
                                                            const float *__restrict__ centre, f32x4 *__restrict__ pt) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= p_pad) return;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (i < p) {
-        const double is = (double)inv_sigma;
         const double x = (double)q_xyz[((size_t)b * 3 + 0) * p + i] - (double)centre[b * 4 + 0];
         const double y = (double)q_xyz[((size_t)b * 3 + 1) * p + i] - (double)centre[b * 4 + 1];
         const double z = (double)q_xyz[((size_t)b * 3 + 2) * p + i] - (double)centre[b * 4 + 2];
-        if (form) v = (f32x4){(float)x, (float)y, (float)z, 0.f};
-        else v = (f32x4){(float)(2.0 * is * x), (float)(2.0 * is * y), (float)(2.0 * is * z), (float)(-is * (x * x + y * y + z * z))};
+        v = (f32x4){(float)x, (float)y, (float)z, 0.f};
     }
     pt[(size_t)b * p_pad + i] = v;
 }
 
-// kr[b][a][dense index of (k, r)], u = x~_row(r) - rk[a][k]: FORM 1 (u, 0); FORM 0 (u, 1 - |u|^2/sigma); entries past ks rp and empty
-// slots: far away (FORM 1) / zeros (FORM 0) -- weight 0 either way, and their mask bits are 0.
+// kr[b][a][dense index of (k, r)], u = x~_row(r) - rk[a][k]: (u, 0); entries past ks rp and empty slots: far away -- weight 0, and their
+// mask bits are 0.
 // row_rot (may be null) float [b][rows_ld][9]: a rotation M per row slot, u = x~_row(r) - M rk[a][k] -- clouds whose points carry ONE
 // pose rotation per rigid part: the reference rotates the offset by R_rel = R_p R_r^T (so3conv/functional.py:L1112-1160) and
 // |R_rel (x_r - x_p) - A kappa| = |x_r - x_p - R_rel^T A kappa|, so for the query points of one part M = R_rel^T depends on the row only
-__global__ __launch_bounds__(256) void dense_rows_kernel(int n_sup, int na, int ks, int rp, int kd_pad, int rows_ld, int form, float inv_sigma,
+__global__ __launch_bounds__(256) void dense_rows_kernel(int n_sup, int na, int ks, int rp, int kd_pad, int rows_ld,
                                                          const float *__restrict__ s_xyz, const float *__restrict__ centre,
                                                          const int32_t *__restrict__ rows, const float *__restrict__ rk,
                                                          const float *__restrict__ row_rot, f32x4 *__restrict__ kr) {
     const int b = blockIdx.z, a = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= kd_pad) return;
-    f32x4 v = form ? (f32x4){1e4f, 1e4f, 1e4f, 0.f} : (f32x4){0.f, 0.f, 0.f, 0.f};
+    f32x4 v = {1e4f, 1e4f, 1e4f, 0.f};
     if (i < ks * rp) {
         int k, r;
         dense_kr(i, ks, k, r);
         const int row = rows[(size_t)b * rows_ld + r];
         if ((unsigned)row < (unsigned)n_sup) {
-            const double is = (double)inv_sigma;
             const float *kp = rk + ((size_t)a * ks + k) * 3;
             double k0 = (double)kp[0], k1 = (double)kp[1], k2 = (double)kp[2];
             if (row_rot != nullptr) {
@@ -313,7 +308,7 @@ __global__ __launch_bounds__(256) void dense_rows_kernel(int n_sup, int na, int 
             const double x = (double)s_xyz[((size_t)b * 3 + 0) * n_sup + row] - (double)centre[b * 4 + 0] - k0;
             const double y = (double)s_xyz[((size_t)b * 3 + 1) * n_sup + row] - (double)centre[b * 4 + 1] - k1;
             const double z = (double)s_xyz[((size_t)b * 3 + 2) * n_sup + row] - (double)centre[b * 4 + 2] - k2;
-            v = (f32x4){(float)x, (float)y, (float)z, form ? 0.f : (float)(1.0 - is * (x * x + y * y + z * z))};
+            v = (f32x4){(float)x, (float)y, (float)z, 0.f};
         }
     }
     kr[((size_t)b * na + a) * kd_pad + i] = v;
@@ -730,7 +725,7 @@ struct KcArgs {
     const f32x4 *strT; long long strB, strA;     // k-side table: element kk of (cloud, anchor) at strT[b strB + a strA + kk]
     const f32x4 *colT; long long colB, colA;     // column-side table
     const unsigned *mask;                 // [b][mask_tiles wave tiles][KS][64 lanes] mask bits
-    float neg_inv_sigma;                  // FORM 1
+    float neg_inv_sigma;
     const int32_t *n_rows; int ks, trim;  // referenced rows per cloud; trim 1: the columns are dense indices cut at the cloud's prefix (backward), 3: not cut,
                                           // 2: the k axis is cut at the cloud's prefix (forward), 0: not cut
     float *C; long long cB, cA, ldm; int rp; long long kstride;     // element (row, n) of (b, a) at C[b cB + a cA + row ldm + (n / rp) kstride + n % rp]
@@ -738,7 +733,7 @@ struct KcArgs {
     const int32_t *steps;                 // (may be null) [b][blocks_n][KS + 1]: count, then the k-steps this column block runs (dense_steps_kernel)
 };
 
-template <int MI, int FORM>
+template <int MI>
 __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g) {
     static_assert(MI == 8 || MI == 4, "the DMA piece schedule below: 8 or 4 KB of the stored operand per wave and k-step");
     constexpr unsigned WB = MI * 1024u;                    // bytes of the stored operand a wave moves per k-step
@@ -855,7 +850,7 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
     // for ONE k-block at a time (read at the end of the k-block that consumed the previous ones)
     constexpr bool LEAN = MI == 4;
     typedef float f32x3 __attribute__((ext_vector_type(3)));
-    using SV = std::conditional_t<(LEAN && FORM == 1), f32x3, f32x4>;
+    using SV = std::conditional_t<LEAN, f32x3, f32x4>;
     // B operand of one k-block: [tile j][plane] 8 halves per lane
     struct BFrag { u32x4 h[2], l[2]; };
     auto frag_a = [&](const unsigned char *st, int sub, int plane, u32x4 (&f)[MI]) __attribute__((always_inline)) {
@@ -871,14 +866,9 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
             const SV s = sv[e0 + e];
             const int keep = (int)(mb << (31 - (16 * tb + 8 * j + e0 + e))) >> 31;
             const float one = __int_as_float(keep & 0x3f800000);
-            if constexpr (FORM == 1) {
-                const float tx = cc[j].x - s.x, ty = cc[j].y - s.y, tz = cc[j].z - s.z;
-                const float d2 = fmaf(tz, tz, fmaf(ty, ty, tx * tx));
-                v[e] = __builtin_amdgcn_fmed3f(fmaf(d2, nis, one), 0.f, 1.f);                    // (v_fma_f32 ... clamp)
-            } else {
-                const float y = fmaf(cc[j].y, s.y, fmaf(cc[j].x, s.x, (cc[j].w - 1.0f) + s.w));
-                v[e] = __builtin_amdgcn_fmed3f(fmaf(cc[j].z, s.z, y) + one, 0.f, 1.f);
-            }
+            const float tx = cc[j].x - s.x, ty = cc[j].y - s.y, tz = cc[j].z - s.z;
+            const float d2 = fmaf(tz, tz, fmaf(ty, ty, tx * tx));
+            v[e] = __builtin_amdgcn_fmed3f(fmaf(d2, nis, one), 0.f, 1.f);                    // (v_fma_f32 ... clamp)
         }
         unsigned h, l;
         split2(v[0], v[1], h, l);
@@ -911,7 +901,7 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
         u32x4 al[MI];
         // vector instructions per matrix instruction of the three products (MI = 4: half the matrix work per generated weight --
         // the kernel is bound by the weight evaluation there) and LDS reads behind the first / second MI matrix instructions
-        constexpr int NV1 = (MI == 8 ? 3 : 6) + (FORM ? 1 : 0), NV3 = (MI == 8 ? 2 : 4) + (FORM ? 1 : 0);
+        constexpr int NV1 = MI == 8 ? 4 : 7, NV3 = MI == 8 ? 3 : 5;
         SB();
         frag_a(st, sub, 1, al);
         if constexpr (!LEAN) load_sv(nnstr, nsv);
@@ -1022,34 +1012,16 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
     }
 }
 
-template <int MI, int FORM>
+template <int MI>
 int kc_launch(const KcArgs &g, hipStream_t s) {
     constexpr size_t shmem = 4 * (2 * (size_t)MI * 2048u + 2048u) + KC_LIST_BYTES;      // the ring + the k-step list
-    eap::set_kernel(MI == 8 ? (FORM ? "kc_gemm_kernel<8, 1>" : "kc_gemm_kernel<8, 0>") : (FORM ? "kc_gemm_kernel<4, 1>" : "kc_gemm_kernel<4, 0>"));
-    return eap::run_kernel("so3_dense product", kc_gemm_kernel<MI, FORM>, (long long)g.zcount * g.tiles_m * g.blocks_n, 1, 1, dim3(256), shmem, s, g);
+    eap::set_kernel(MI == 8 ? "kc_gemm_kernel<8, 1>" : "kc_gemm_kernel<4, 1>");     // the key of this kernel in profiles/r06_pmc_traffic.json (bench.py --full)
+    return eap::run_kernel("so3_dense product", kc_gemm_kernel<MI>, (long long)g.zcount * g.tiles_m * g.blocks_n, 1, 1, dim3(256), shmem, s, g);
 }
-
-int g_dense_form = 1;
-int g_dense_rows = 0;       // 0: 256-row blocks where o % 256 == 0, else 128; 128: always 128-row blocks (A/B runs)
 
 inline int ceil_to(int v, int q) { return (v + q - 1) / q * q; }
 
 }  // namespace
-
-// 1 (default): the weights from the squared distance; 0: from the expanded square (see the head of this file).  The tables and the
-// product of one layer must be built under the same setting.  -> the previous setting
-// rows per workgroup of the product: 0 = 256 where the width allows (default), 128 = always 128 (two workgroups per CU); -> old setting
-extern "C" int eap_so3_dense_block_rows(int rows) {
-    const int old = g_dense_rows;
-    if (rows == 0 || rows == 128) g_dense_rows = rows;
-    return old;
-}
-
-extern "C" int eap_so3_dense_form(int form) {
-    const int old = g_dense_form;
-    if (form == 0 || form == 1) g_dense_form = form;
-    return old;
-}
 
 namespace {
 // the shapes the product takes at `words` membership words per point (rp <= 32 words)
@@ -1122,10 +1094,10 @@ extern "C" int eap_so3_dense_tables_f32(int b, int p, int n_sup, int na, int ks,
     hipStream_t s = eap::S(stream);
     const int p_pad = ceil_to(p, KC_BK), kd_pad = ceil_to(ks * rp, KC_BK);
     if (int e = eap::run_kernel("so3_dense_tables", dense_centre_kernel, b, 1, 1, dim3(256), 0, s, n_sup, s_xyz, centre)) return e;
-    if (int e = eap::run_kernel("so3_dense_tables", dense_points_kernel, eap::cdiv(p_pad, 256), b, 1, dim3(256), 0, s, p, p_pad, g_dense_form, 1.0f / sigma, q_xyz, centre,
+    if (int e = eap::run_kernel("so3_dense_tables", dense_points_kernel, eap::cdiv(p_pad, 256), b, 1, dim3(256), 0, s, p, p_pad, q_xyz, centre,
                                 reinterpret_cast<f32x4 *>(pt)))
         return e;
-    return eap::run_kernel("so3_dense_tables", dense_rows_kernel, eap::cdiv(kd_pad, 256), na, b, dim3(256), 0, s, n_sup, na, ks, rp, kd_pad, rows_ld, g_dense_form, 1.0f / sigma,
+    return eap::run_kernel("so3_dense_tables", dense_rows_kernel, eap::cdiv(kd_pad, 256), na, b, dim3(256), 0, s, n_sup, na, ks, rp, kd_pad, rows_ld,
                            s_xyz, centre, rows, rk, row_rot, reinterpret_cast<f32x4 *>(kr));
 }
 
@@ -1234,7 +1206,7 @@ extern "C" int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int
     g.MT = o / 32; g.na = na; g.zcount = b * na; g.row_slots = rp;
     g.N = dir ? p : ks * rp;
     g.KS = (dir ? kd_pad : p) / KC_BK;
-    const bool wide = (o % 256) == 0 && g_dense_rows != 128;     // 256-row blocks; else 128-row blocks (half the matrix work per generated weight, two workgroups per CU)
+    const bool wide = (o % 256) == 0;     // 256-row blocks; else 128-row blocks (half the matrix work per generated weight, two workgroups per CU)
     g.tiles_m = wide ? o / 256 : o / 128;
     g.blocks_n = (g.N + 255) / 256;
     g.mask_tiles = 4 * g.blocks_n;
@@ -1261,8 +1233,7 @@ extern "C" int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int
         if (int e = eap::run_kernel("so3_dense zero tail", dense_zero_tail_kernel, (long long)o * ks, b, 1, dim3(256), 0, eap::S(stream), o * ks, na, rp, (long long)ldz, n_rows, out))
             return e;
     }
-    if (!wide) return g_dense_form ? kc_launch<4, 1>(g, eap::S(stream)) : kc_launch<4, 0>(g, eap::S(stream));
-    return g_dense_form ? kc_launch<8, 1>(g, eap::S(stream)) : kc_launch<8, 0>(g, eap::S(stream));
+    return wide ? kc_launch<8>(g, eap::S(stream)) : kc_launch<4>(g, eap::S(stream));
 }
 
 extern "C" int eap_so3_dense_product_f32(int dir, int b, int o, int p, int na, int ks, int rp, int64_t ldz, float sigma, const int32_t *n_rows,

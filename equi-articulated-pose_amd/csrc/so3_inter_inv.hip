@@ -512,20 +512,6 @@ int eap::group_fwd_perm_lists(int b, int c, int p, int n, int nn, int na, int ks
                            (const uint8_t *)nullptr);
 }
 
-// gy rows padded to `gy_pitch` floats (a multiple of 4, >= na; e.g. 64: every row starts a 256-byte line):
-// same result, only the entry-list kernel (no anchor permutation) takes it
-extern "C" int eap_so3_inter_group_inv_pitch_f32(int b, int o, int p, int nn, int na, int gy_pitch, int ks, int rcap,
-                                                 float sigma, const float *gy, const int32_t *rows,
-                                                 const int32_t *off, const int32_t *cnt,
-                                                 const int32_t *ent_p, const float *ent_gx, const float *rk,
-                                                 float *z, eap_stream_t stream) {
-    if (b <= 0 || o <= 0 || rcap <= 0 || na <= 0 || ks <= 0) return 0;
-    if (!eap::group_lists_supported(na, ks)) return eap::bad_arg("so3_inter_group_inv_pitch: unsupported anchor / kernel-point count");
-    if (eap::group_lists2_preferred(o, na, ks, 0))
-        return eap::group_lists2_inv(b, o, p, nn, na, gy_pitch, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, eap::S(stream));
-    return eap::group_lists_inv(b, o, p, nn, na, gy_pitch, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, z, eap::S(stream));
-}
-
 static int group_inv(int b, int o, int p, int nn, int na, int ks, int rcap, float sigma, const float *gy, const int32_t *rows,
                      const int32_t *off, const int32_t *cnt, const int32_t *ent_p, const float *ent_gx, const float *rk,
                      const uint8_t *multinv, const float *anchors, int identity_anchor, const uint8_t *coset_order,

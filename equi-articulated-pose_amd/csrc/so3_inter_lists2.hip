@@ -75,7 +75,7 @@ static_assert(CB * SL == TM, "one DMA instruction per entry: thread t <-> (row t
 // tensors that follow); the forward's transposed output has one row per anchor and comes back in memory order.
 template <bool LISTS, int LAYOUT, bool PERM = false>
 __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
-    int C, int PF, int na, int fpitch, int ks, int R, int nn, int ent_stride, int AG, int RPB, int ag_major, float inv_sigma,
+    int C, int PF, int na, int fpitch, int ks, int R, int nn, int ent_stride, int AG, int RPB, float inv_sigma,
     const float *__restrict__ F, const int32_t *__restrict__ rows, const int32_t *__restrict__ off,
     const int32_t *__restrict__ cnt, const int32_t *__restrict__ ent_p, const float4 *__restrict__ ent_gx,
     const float *__restrict__ rk, const int32_t *__restrict__ nonident, float *__restrict__ out,
@@ -85,21 +85,9 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
     // ---- block -> (row run, anchor group, channel slice, cloud); an XCD gets whole (slice, cloud) pairs when their
     //      number allows it, else a contiguous range of rows (whole output lines in one L2) ----
     const int nrun = (R + RPB - 1) / RPB;
-    const int ny = gridDim.y, nsl = ny * gridDim.z, per_slice = nrun * AG;
+    const int ny = gridDim.y;
     int run, ag, sl;
-    if (ag_major && ((nsl * AG) & 7) == 0) {
-        // an XCD owns whole (slice, cloud, ANCHOR GROUP) triples: the rows of a cloud that its resident workgroups walk
-        // at the same time are then 64-byte pieces, a quarter of the (slice, cloud) working set per point -- four times
-        // as many points of the walk stay in the 4 MB L2, and all 64 resident workgroups (not 16 x 4) share them
-        const unsigned lin = blockIdx.x + (unsigned)per_slice * (blockIdx.y + (unsigned)ny * blockIdx.z);
-        const unsigned j = lin >> 3;
-        const unsigned sl2 = (lin & 7u) + 8u * (j / (unsigned)nrun);
-        run = (int)(j % (unsigned)nrun);
-        ag = (int)(sl2 % (unsigned)AG);
-        sl = (int)(sl2 / (unsigned)AG);
-    } else {
-        group_lists::block_map(nrun, AG, run, ag, sl);       // (slice, cloud) pairs or row ranges: csrc/group_lists.h
-    }
+    group_lists::block_map(nrun, AG, run, ag, sl);           // csrc/group_lists.h
     const int r_begin = run * RPB, rows_blk = min(RPB, R - r_begin);
     const int cy = sl % ny, bi = sl / ny, c0 = cy * CB;
     if (nonident != nullptr && (__builtin_amdgcn_readfirstlane(nonident[bi]) != 0) != PERM) return;   // permuted clouds: the PERM kernel's, the others: not
@@ -396,7 +384,6 @@ __global__ __launch_bounds__(TM, 2) void so3_group_lists2_kernel(
 constexpr size_t SHMEM = 2 * BUF_BYTES + 16 * 3 * NBK + 16 * NBK;
 constexpr size_t SHMEM_PERM = 2 * BUF_BYTES + 16 * 3 * NBK + 16 * 3 * NBK;
 
-int g_xcd_map_fwd = 1, g_xcd_map_inv = 1;       // eap_so3_group_lists_xcd_map
 int g_store16 = 1;                              // eap_so3_group_lists_store16
 
 int g_perm_lists2 = 1;                          // eap_so3_group_perm_lists2
@@ -421,7 +408,7 @@ int launch2(int layout, int b, int C, int PF, int na, int fpitch, int ks, int R,
     eap::set_kernel(perm ? (LISTS ? "so3_group_lists2_kernel<true, 0, true>" : wide ? "so3_group_lists2_kernel<false, 3, true>" : layout == 2 ? "so3_group_lists2_kernel<false, 2, true>" : "so3_group_lists2_kernel<false, 0, true>")
                          : (LISTS ? "so3_group_lists2_kernel<true, 0>" : wide ? "so3_group_lists2_kernel<false, 3>" : layout == 2 ? "so3_group_lists2_kernel<false, 2>" : "so3_group_lists2_kernel<false, 0>"));
     return eap::run_kernel(what, kern, eap::cdiv(R, RPB) * AG, (C + CB - 1) / CB, b, dim3(TM), shmem, s, C, PF, na, fpitch, ks, R, nn, ent_stride, AG, RPB,
-                           (LISTS ? g_xcd_map_inv : g_xcd_map_fwd) == 2, 1.0f / sigma, F, rows, off, cnt, ent_p, reinterpret_cast<const float4 *>(ent_gx), rk, nonident, out,
+                           1.0f / sigma, F, rows, off, cnt, ent_p, reinterpret_cast<const float4 *>(ent_gx), rk, nonident, out,
                            order);
 }
 
@@ -451,14 +438,6 @@ extern "C" int eap_so3_group_perm_lists2(int on) {
     const int was = g_perm_lists2;
     if (on == 0 || on == 1) g_perm_lists2 = on;
     return was;
-}
-
-// Which unit of work an XCD (one L2) owns in the two-tile kernel: 1 = whole (channel slice, cloud) pairs, 2 = whole
-// (channel slice, cloud, anchor group) triples.  `which` 0 = forward, 1 = backward (inverse lists); mode 0 = query.
-extern "C" int eap_so3_group_lists_xcd_map(int which, int mode) {
-    int &m = which ? g_xcd_map_inv : g_xcd_map_fwd;
-    if (mode == 1 || mode == 2) m = mode;
-    return m;
 }
 
 namespace eap {

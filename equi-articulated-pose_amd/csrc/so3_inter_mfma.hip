@@ -319,10 +319,3 @@ int eap::group_fwd_mfma(int b, int c, int p, int n, int nn, int na, int ks, floa
     return eap::run_kernel("so3_inter_group_fwd_mfma", kern, p, (c + CB - 1) / CB, b, dim3(TM), shmem, s, c, p, n, nn, na, ks, 1.0f / sigma, feats, idx,
                            reinterpret_cast<const float4 *>(gx), rk, mult, nonident, skip_plain, blocked, out);
 }
-
-extern "C" int eap_so3_inter_group_fwd_mfma_f32(int b, int c, int p, int n, int nn, int na, int ks,
-                                                float sigma, const float *feats, const int32_t *idx,
-                                                const float *gx, const float *rk, const uint8_t *mult,
-                                                const int32_t *nonident, float *out, eap_stream_t stream) {
-    return eap::group_fwd_mfma(b, c, p, n, nn, na, ks, sigma, feats, idx, gx, rk, mult, nonident, 0, 0, out, eap::S(stream));
-}

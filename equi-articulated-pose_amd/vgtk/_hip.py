@@ -95,16 +95,14 @@ def suffix(t):
 
 # csrc/gemm_dma_f32.hip (DMA-fed three-stage ring) serves every GEMM whose operands it can take (K a multiple of 16,
 # 16-byte aligned rows); csrc/gemm_f32.hip the rest (first layer K = 24, blocked intermediates, odd shapes).
-# EAP_DMA_GEMM=0 forces the older kernel everywhere (A/B runs).
-USE_DMA_GEMM = os.environ.get('EAP_DMA_GEMM', '1') != '0'
 lib.eap_gemm_dma_f32_reduce_workspace.restype = ctypes.c_int64
 lib.eap_gemm_skinny_reduce_workspace.restype = ctypes.c_int64
 lib.eap_gemm_bf16x3_reduce_workspace.restype = ctypes.c_int64
 
 
 def _dma_ok(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB):
-    return USE_DMA_GEMM and bool(lib.eap_gemm_dma_f32_supported(int(transA), int(transB), M, N, K, _ptr(A), _I64(lda), _I64(strideA),
-                                                              _ptr(B), _I64(ldb), _I64(strideB)))
+    return bool(lib.eap_gemm_dma_f32_supported(int(transA), int(transB), M, N, K, _ptr(A), _I64(lda), _I64(strideA),
+                                               _ptr(B), _I64(ldb), _I64(strideB)))
 
 
 # Contractions whose A operand is shared by the batch (the inter conv's forward contraction on the transposed
@@ -126,7 +124,7 @@ def _split_planes_from_env():
     return int(v)
 
 
-SPLIT_PLANES = _split_planes_from_env()      # (the environment switch is for A/B runs)
+SPLIT_PLANES = _split_planes_from_env()      # (EAP_SPLIT_PLANES: a numerics mode, README.md "Numerics")
 
 
 SPLIT_PLANES_SCAN_ROWS = 384     # see _planes2 (tests set it to 0 to reach the two-plane kernel at every shape)
@@ -647,8 +645,8 @@ def so3_dense_narrow(memb, rp):
 # (64 -> 128) of the k-steps drop out; skipped steps would have added exact zeros, so the result is bit-equal to running them all
 # in the same point order.  The point order is internal: the backward reads dY through it as a column map, the forward's re-ordering
 # pass writes Y through it.  SORT_DENSE_POINTS = False: index order and every k-step, as round 5 (A/B runs, tests).
-SORT_DENSE_POINTS = os.environ.get('EAP_DENSE_SORT', '1') != '0'
-SKIP_DENSE_STEPS = os.environ.get('EAP_DENSE_SKIP', '1') != '0'
+SORT_DENSE_POINTS = True
+SKIP_DENSE_STEPS = True
 lib.eap_so3_dense_steps_words.restype = ctypes.c_int64
 
 
@@ -817,7 +815,7 @@ def so3_dense_gplanes(fc4, W3, geo):
     return scale, planes
 
 
-GPLANES = os.environ.get('EAP_DENSE_GPLANES', '1') != '0'      # 0: G by a GEMM + the split pass, as round 5 (A/B runs, tests)
+GPLANES = True      # False: G by a GEMM + the split pass, as round 5 (tests)
 
 
 def so3_dense_fwd(g, geo, p, c=0, ldg=None, out=None, col_map=None, operand=None, o=None):

@@ -205,7 +205,6 @@ def _group_tables_inverse(mult):
 
 _COSETS = {}
 STORE_ORDER_COLUMNS = True     # streamed forward: the transposed intermediate's columns in the grouping kernel's store order
-COSET_OPERAND = True      # permuted-pose backward: coset-major LDS operand (False: per-anchor byte-table lookups, for A/B runs)
 
 
 def _coset_tables(table, ident):
@@ -421,8 +420,7 @@ def _inv_lists_supported(idx, n_sup, na, ks):
     return na % 4 == 0 and ks <= 32 and n_sup <= INV_LISTS_MAX_ROWS and (idx.shape[1] * idx.shape[2]) % 4 == 0
 
 
-LISTS_ON_SIDE_STREAM = True     # inverse neighbour lists built beside the forward's grouping / contraction kernels
-_SIDE_STREAMS = {}
+_SIDE_STREAMS = {}      # the inverse neighbour lists are built beside the forward's grouping / contraction kernels
 
 
 def _side_stream(dev):
@@ -442,7 +440,7 @@ class _ListHead:
 
     def __init__(self, idx, n_sup, nonident, gx=None, prefill=False, dense_probe=None):
         """prefill (with gx): also the second half (csrc/inv_lists.hip fill: the entries of every referenced row) right away,
-        for all rows -- the launch needs no host value that way.  Everything runs on a SIDE stream (LISTS_ON_SIDE_STREAM): these
+        for all rows -- the launch needs no host value that way.  Everything runs on a SIDE stream: these
         are small latency-bound kernels (0.3 + 0.45 ms per layer) that nothing in the forward waits for, and the grouping and
         contraction kernels that follow on the main stream leave them room; the backward waits for `event`.
         dense_probe = (rotation blocks or None, ...): also the membership bits of the dense product (csrc/so3_dense.hip) and
@@ -451,13 +449,12 @@ class _ListHead:
         more than 512 rows is probed with the 32-word table (vgtk._hip.so3_dense_member); decide() narrows it once the count is known."""
         dev = idx.device
         main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev) if LISTS_ON_SIDE_STREAM else main
+        side = _side_stream(dev)
         self.memb = None
-        if side is not main:
-            side.wait_stream(main)                        # idx / gx / nonident were produced on the main stream
-            for t in (idx, gx, nonident) + tuple(x[1] if isinstance(x, tuple) else x for x in (dense_probe or ())):
-                if t is not None:
-                    t.record_stream(side)                 # (read on the side stream: the allocator must not recycle them under it)
+        side.wait_stream(main)                            # idx / gx / nonident were produced on the main stream
+        for t in (idx, gx, nonident) + tuple(x[1] if isinstance(x, tuple) else x for x in (dense_probe or ())):
+            if t is not None:
+                t.record_stream(side)                     # (read on the side stream: the allocator must not recycle them under it)
         with torch.cuda.stream(side):
             self.rows, self.off, self.cnt, self.n_rows = _hip.inv_lists_rows(idx, n_sup)
             flag = nonident.max() if nonident is not None else torch.ones((), dtype=torch.int32, device=dev)
@@ -487,23 +484,21 @@ class _ListHead:
             self.entries = _hip.inv_lists_fill(idx, gx, self.rows, self.off, n_sup) if (prefill and gx is not None) else None
             self.event = torch.cuda.Event()
             self.event.record(side)
-        if side is not main:                              # allocated under the side stream, used (and freed) under the main one
-            for t in (self.rows, self.off, self.cnt, self.n_rows, self.memb) + (self.entries or ()):
-                if t is not None:
-                    t.record_stream(main)
+        for t in (self.rows, self.off, self.cnt, self.n_rows, self.memb) + (self.entries or ()):      # allocated under the side stream, used (and freed) under the main one
+            if t is not None:
+                t.record_stream(main)
 
     def fill(self, idx, gx, n_sup):
         """the second half of the lists after all (a forward that probed for the dense product and did not take it)"""
         dev = idx.device
         main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev) if LISTS_ON_SIDE_STREAM else main
+        side = _side_stream(dev)
         with torch.cuda.stream(side):
             self.entries = _hip.inv_lists_fill(idx, gx, self.rows, self.off, n_sup)
             self.event = torch.cuda.Event()
             self.event.record(side)
-        if side is not main:
-            for t in self.entries:
-                t.record_stream(main)
+        for t in self.entries:
+            t.record_stream(main)
 
     def wait(self):
         """the current stream waits for the lists (device side; no host stall)"""
@@ -556,8 +551,7 @@ def _inverse_lists(idx, gx, n_sup, ident, nonident=None):
 #                 (141 TFLOP/s on the deepest layer; hipBLASLt on the same operands: 150 -- tools/gemm_only.py times both)
 #   'blocked'     X blocked by anchor quads, contraction = csrc/gemm_f32.hip (eap_gemm_f32_xb)
 #   'reference'   X [C*K, P*A] as the reference's einsum writes it
-X_LAYOUT = os.environ.get('EAP_X_LAYOUT', 'transposed')
-BLOCKED_X = True     # test knob: False forces the reference layout
+X_LAYOUT = 'transposed'
 
 
 # The intermediate X [B, C*K, P*A] of the fused conv (24 GB at C = 128, B = 8) is scratch, not state: the re-associated
@@ -565,7 +559,7 @@ BLOCKED_X = True     # test knob: False forces the reference layout
 # textbook backward (many referenced rows) needs it for dW = dY X^T; which regime a layer is in is known on the host
 # only when its backward runs, so the layer's previous decision is the hint: after a 'dx' backward the next forward of
 # the same weights keeps X, and a wrong guess costs one re-run of the grouping kernel in the backward.
-X_CHUNK_CLOUDS = int(os.environ.get('EAP_X_CHUNK_CLOUDS', '8'))   # measured: 2 / 4 / 8 clouds per slab = 146.8 / 146.9 / 145.6 ms per step
+X_CHUNK_CLOUDS = 8   # measured: 2 / 4 / 8 clouds per slab = 146.8 / 146.9 / 145.6 ms per step
 _KEEP_X_HINT = {}           # id(W) -> (weakref(W), bool)
 
 
@@ -667,22 +661,22 @@ FORWARD_LOG = None       # the same for the forward: {'channels', 'dense': the d
 # rotation, no padded lists) and a cloud references few enough rows: it does rows / nsample times the flops of the list kernels on
 # a pipe ~4.5 x as fast.  Both directions take it up to DENSE_ROW_FACTOR x nsample rows at any width it supports ('off' never; 'force'
 # whenever the shapes are taken: tests).
-DENSE_MODE = os.environ.get('EAP_DENSE', 'auto')
+DENSE_MODE = os.environ.get('EAP_DENSE', 'auto')      # (a numerics mode, README.md "Numerics": 'off' = the fp32 list kernels)
 DENSE_ROW_FACTOR = 5.0
 # ... and beyond that row count (up to the 1024 row slots the wide membership words hold) while a point's list touches few enough 16-row groups: with
 # the listed k-steps the product executes ~ groups_touched x 16 / nsample times the algorithmic flops (x 3 on the fp16 pipe at ~1.3 PFLOP/s)
 # against the list kernels' 0.46 of the fp32 peak -- it wins below ~24 groups; 16 leaves margin for the per-block overheads
-DENSE_MAX_GROUPS = float(os.environ.get('EAP_DENSE_MAX_GROUPS', '16'))
+DENSE_MAX_GROUPS = 16.0
 # the same bound for clouds of more than 512 referenced rows (the 32-word tables); a knob of its own so that it can be raised for them alone.
 # Measured at 24 (the 64 -> 128 layer of 8 x 4096-point clouds with the 512-point radii, ~21 groups touched): the 128-row product costs what
 # the list kernels cost and the leg does not gain (profiles/dense_wide_rows.txt) -- 16 stays
-DENSE_MAX_GROUPS_WIDE = float(os.environ.get('EAP_DENSE_MAX_GROUPS_WIDE', '16'))
+DENSE_MAX_GROUPS_WIDE = 16.0
 # the forward at widths that fill 128-row blocks only (the 64 -> 128 layer): with every k-step it tied with grouping + contraction
 # (round 5: 9.0 against 9.1 ms); with the empty k-steps skipped (round 6) the product wins: 4.2 + 1.3 + 0.9 ms against 5.7 + 3.3, same run
 # 129.2 against 128.0 clouds/s before the operand kernel, more after it
-DENSE_FWD_NARROW = os.environ.get('EAP_DENSE_FWD_128', '1') != '0'
+DENSE_FWD_NARROW = True
 # a training-mode BatchNorm + leaky_relu behind a conv whose forward runs the dense product joins the conv's node (TrainEpilogue)
-FUSE_CONV_NORM = os.environ.get('EAP_FUSE_CONV_NORM', '1') != '0'
+FUSE_CONV_NORM = True
 
 
 def _dense_rows(rcap, n):
@@ -730,7 +724,6 @@ def _weight_grad_from_z(z, fc, b, c, o, ks, ra, ldz=None):
 # R_rel (so3conv/functional.py:L1112-1160; csrc/so3_inter.hip so3_prep_kernel) -- both depend on (part of p, part of r) only.  The dense
 # product then runs once per part over that part's query points: its k-side table takes R_rel^T per ROW (a row's part is fixed), the
 # stored operand is built from the rows' features with their anchor axis permuted per row.  DENSE_MAX_PARTS bounds the launches.
-DENSE_PARTS = os.environ.get('EAP_DENSE_PARTS', '1') != '0'
 DENSE_MAX_PARTS = 6
 _POSE_PARTS = {}            # (storage pointer, version, shape) of a pose tensor -> (weakref, _PoseParts or None)
 
@@ -923,7 +916,7 @@ class _DensePlan:
                 and (needs_grad or o % 256 == 0 or DENSE_FWD_NARROW or DENSE_MODE == 'force')
                 and _hip.so3_dense_supported(p, na, ks, 16, o)):
             probe = (geometry[2], geometry[3])
-            if (DENSE_PARTS and geometry[3] is not None and geometry[0] is geometry[1] and geometry[2] is geometry[3] and p == n):
+            if (geometry[3] is not None and geometry[0] is geometry[1] and geometry[2] is geometry[3] and p == n):
                 self.parts = _pose_parts(geometry[3])      # (one host read per pose tensor)
                 if self.parts is not None:
                     probe = ()                             # the rotations are accounted for per part: no "exactly the identity" requirement
@@ -986,7 +979,7 @@ def _forward_lists(feats, W, args, layout, keep, folded, head, fill):
     if fill:
         head.fill(idx, gx, n)                          # (the probe postponed it; a dense backward does not need the entries)
     y = torch.empty(b, o, p, na, dtype=torch.float32, device=feats.device)
-    coset = _coset_tables(mult, args.ident) if (mult is not None and nonident is not None and layout == 2 and COSET_OPERAND) else None
+    coset = _coset_tables(mult, args.ident) if (mult is not None and nonident is not None and layout == 2) else None
     x_bound = _grouped_bound(feats, idx) if layout == 2 else None          # [b, p] words
     step = max(1, b if keep else X_CHUNK_CLOUDS)          # (a kept X is one slab of all clouds)
     # where X is scratch between the grouping and the contraction its columns may be in the order the grouping kernel's
@@ -1160,7 +1153,7 @@ def _backward_lists(gy, W, feats, idx, gx, rk, mult, args, head, rcap, any_nonid
     off, cnt = head.off[:, :rcap].contiguous(), head.cnt[:, :rcap].contiguous()
     ent_p, ent_gx = head.entries if head.entries is not None else _hip.inv_lists_fill(idx, gx, head.rows, head.off, rcap)
     multinv = _group_tables_inverse(mult) if (mult is not None and any_nonident) else None
-    coset = _coset_tables(multinv, args.ident) if (multinv is not None and COSET_OPERAND) else None
+    coset = _coset_tables(multinv, args.ident) if multinv is not None else None
     z_order = z_pos = None
     if coset is not None and _hip.so3_group_perm_lists2_takes(o, na, ks, p):
         # permuted clouds on the two-tile kernel (csrc/so3_inter_lists2.hip, PERM): gy and Z with a coset-major anchor
@@ -1189,7 +1182,7 @@ def _backward_textbook(gy, W, feats, x, idx, gx, rk, mult, nonident, args, layou
     gF = gW = None
     if x is None:                                     # wrong guess (or the first step): one more run of the grouping kernel
         x = _hip.so3_inter_group_fwd(feats, idx, gx, rk, mult, args.sigma, nonident, blocked=layout,
-                                     coset=_coset_tables(mult, args.ident) if (mult is not None and layout == 2 and COSET_OPERAND) else None)
+                                     coset=_coset_tables(mult, args.ident) if (mult is not None and layout == 2) else None)
     if need_w:
         gW = torch.empty_like(W)          # sum_b gy_b x_b^T
         # (measured and dropped: every cloud's dY_b X^T_b on the split-operand 'nn' kernel instead of the batch-reducing fp32 kernel --
@@ -1249,7 +1242,7 @@ class _InterConv(torch.autograd.Function):
         # X is internal to this Function: where the kernels allow it, it is kept blocked by anchor
         # quads ([b,p,a/4,c,k,4]) -- coalesced row-end stores in the grouping kernel -- and the GEMMs
         # read it as a blocked B operand (include/eap_hip.h, "blocked intermediate")
-        can = BLOCKED_X and X_LAYOUT != 'reference' and _hip.so3_inter_group_fwd_can_block(
+        can = X_LAYOUT != 'reference' and _hip.so3_inter_group_fwd_can_block(
             feats.shape[1], feats.shape[2], feats.shape[3], rk.shape[1], mult is not None, nonident is not None)
         layout = 0 if not can else (2 if X_LAYOUT == 'transposed' else 1)
         _, c, n, na = feats.shape

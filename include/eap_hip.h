@@ -181,13 +181,8 @@ int eap_so3_inter_group_fwd_f32(int b, int c, int p, int n, int nn, int na, int 
                                 const float *feats, const int32_t *idx, const float *gx,
                                 const float *rk, const uint8_t *mult, const int32_t *nonident,
                                 float *out, eap_stream_t stream);
-/* The two implementations behind so3_inter_group_fwd, exported for tests and profiling:
- * _mfma (c >= 16): v_mfma_f32_32x32x2_f32 with the kernel weights generated in registers as the
- * B operand; _valu: lanes = anchors, register tile of channels x kernel points. */
-int eap_so3_inter_group_fwd_mfma_f32(int b, int c, int p, int n, int nn, int na, int ks, float sigma,
-                                     const float *feats, const int32_t *idx, const float *gx,
-                                     const float *rk, const uint8_t *mult, const int32_t *nonident,
-                                     float *out, eap_stream_t stream);
+/* The implementation behind so3_inter_group_fwd for c < 16, exported for tests: lanes = anchors, register tile of
+ * channels x kernel points. */
 int eap_so3_inter_group_fwd_valu_f32(int b, int c, int p, int n, int nn, int na, int ks, float sigma,
                                      const float *feats, const int32_t *idx, const float *gx,
                                      const float *rk, const uint8_t *mult, float *out,
@@ -289,9 +284,6 @@ int eap_so3_inter_group_fwd_tp_f32(int b, int c, int p, int n, int nn, int na, i
 int eap_so3_inter_group_inv_perm2_f32(int b, int o, int p, int nn, int na, int ks, int rcap, float sigma, const float *gy,
                                       const int32_t *rows, const int32_t *off, const int32_t *cnt, const int32_t *ent_pc,
                                       const float *ent_gx2, const float *rk, const uint8_t *order, float *z, eap_stream_t stream);
-/* Block -> XCD map of the two-tile kernel: mode 1 = an XCD (one L2) owns whole (channel slice, cloud) pairs, 2 = whole
- * (channel slice, cloud, anchor group) triples; which = 0 forward, 1 backward; mode 0 = query.  Same results either way. */
-int eap_so3_group_lists_xcd_map(int which, int mode);
 
 /* so3_inter_group_inv: the feature gradient of the whole inter convolution by re-association,
  *   dF[c,q,a'] = sum_{o,k} W[o,(c,k)] Z[o,k,q,a'],
@@ -327,13 +319,6 @@ int eap_so3_inter_group_inv_coset_f32(int b, int o, int p, int nn, int na, int k
                                       const float *anchors, int identity_anchor, const uint8_t *coset_order,
                                       const uint8_t *coset_code, float *z, eap_stream_t stream);
 
-/* so3_inter_group_inv without anchor permutation, gy stored with a row pitch: gy [b,o,p,gy_pitch], gy_pitch a
- * multiple of 4 and >= na (64 makes every 60-anchor row start on a 256-byte boundary). */
-int eap_so3_inter_group_inv_pitch_f32(int b, int o, int p, int nn, int na, int gy_pitch, int ks, int rcap,
-                                      float sigma, const float *gy, const int32_t *rows, const int32_t *off,
-                                      const int32_t *cnt, const int32_t *ent_p, const float *ent_gx,
-                                      const float *rk, float *z, eap_stream_t stream);
-
 /* Inverse neighbour lists for so3_inter_group_inv, built on the device (the autograd transpose of the
  * gather at so3conv/functional.py:L1221-1252 needs, per referenced support row, the (point, slot) pairs
  * that reference it).  idx int32 [b,p,nn] with values in [0,n) (other values are ignored), n <= 16384.
@@ -367,8 +352,7 @@ int eap_rows_scatter_f32(int b, int c, int n, int na, int rcap, int rows_ld, con
  * on the fp16 matrix cores with two planes per operand and fp32 accumulation (the arithmetic of eap_gemm_f16x2_f32).  Inside, the
  * (k, r) axis runs in the DENSE INDEX order d = (r / 16) 16 ks + 16 k + r % 16; a cloud with n_rows[b] < rp referenced rows uses a
  * prefix of it, and with n_rows given the products stop there (dir 0 zeroes the slots past ceil16(n_rows[b]) in Z).
- *   eap_so3_dense_form        how the weights are evaluated: 1 (default) from the squared distance, 0 from the expanded square
- *                             (fewer instructions, ~3 x the rounding error); tables and product under the same setting; -> old setting
+ * The weights are evaluated from the squared distance, in the reference's own order of operations (csrc/so3_dense.hip).
  *   eap_so3_dense_supported   p % 32 == 0, na % 4 == 0, na <= 64, ks % 2 == 0, rp % 16 == 0, rp <= 1024 (eap_so3_dense_max_rows), o % 128 == 0 (256-row
  *                             blocks when o % 256 == 0).  The product, table, split and operand entries take every such rp; the entries that take
  *                             `memb` come in two widths: the plain ones below (memb [b,p,16], int32 keys, rp <= 512) and the *_wide ones further down
@@ -410,8 +394,6 @@ int eap_rows_scatter_f32(int b, int c, int n, int na, int rcap, int rows_ld, con
  *                             longer than 1024 k-steps are ignored: every k-step runs).  Skipped k-steps would have added exact zeros:
  *                             bit-equal to running them all in the same point order.  so3conv/functional.py:L1221-1261 */
 int eap_so3_dense_supported(int p, int na, int ks, int rp, int o);
-int eap_so3_dense_form(int form);
-int eap_so3_dense_block_rows(int rows);      /* 0 (default): 256-row blocks where o % 256 == 0; 128: always 128-row blocks; -> old setting */
 int eap_so3_dense_member(int b, int p, int n, int nn, int rp, int rows_ld, const int32_t *idx, const int32_t *rows,
                          const int32_t *n_rows, int32_t *slot_of, uint32_t *memb, int32_t *flags, eap_stream_t stream);
 int64_t eap_so3_dense_mask_words(int b, int p, int ks, int rp, int dir);

@@ -1,6 +1,6 @@
 #!/bin/bash
 # counters of the dense product kernel alone (tools/gpu/dense_time.py): matrix-pipe busy, clock, wave states, LDS
-export TMPDIR=/tmp FORMS=1 REPS=2
+export TMPDIR=/tmp REPS=2
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$1
 mkdir -p $O

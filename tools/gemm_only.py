@@ -1,5 +1,5 @@
 """tools/gemm_only.py -- the contraction GEMMs in isolation at the benchmark's shapes (B clouds of 4096 points),
-every implementation side by side: csrc/gemm_dma_f32.hip (DMA ring), csrc/gemm_f32.hip (register staging) and the
+the implementations side by side: csrc/gemm_bf16x3.hip (split operands), csrc/gemm_dma_f32.hip (DMA ring) and the
 vendor library (torch.matmul -> hipBLASLt) as the yardstick.  Interleaved rounds, median of the rounds."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,24 +27,6 @@ def bench(fns, flops, rounds=5):
         print(f'   {k:28s} median {v[len(v) // 2]:8.3f} ms  min {v[0]:8.3f} ms  {flops / v[len(v) // 2] / 1e9:7.1f} TFLOP/s', flush=True)
 
 
-def old(*a, **k):
-    _hip.USE_DMA_GEMM = False
-    _hip.SPLIT_BF16_CONTRACTION = False
-    try:
-        _hip.gemm(*a, **k)
-    finally:
-        _hip.USE_DMA_GEMM = True
-        _hip.SPLIT_BF16_CONTRACTION = True
-
-
-def old_reduce(*a, **k):
-    _hip.USE_DMA_GEMM = False
-    try:
-        _hip.gemm_reduce(*a, **k)
-    finally:
-        _hip.USE_DMA_GEMM = True
-
-
 ONLY_FIRST = len(sys.argv) > 2 and sys.argv[2] == 'first'
 for (O, CK) in ((512, 3072),) if ONLY_FIRST else ((512, 3072), (128, 1536)):
     W = torch.randn(O, CK, device=dev)
@@ -59,7 +41,6 @@ for (O, CK) in ((512, 3072),) if ONLY_FIRST else ((512, 3072), (128, 1536)):
             _hip.SPLIT_BF16_CONTRACTION = True
     bench({'gemm_bf16x3 (3 x bf16 split)': lambda: _hip.gemm(0, 1, O, PA, CK, W, CK, 0, XT, CK, CK * PA, Y, PA, O * PA, B),
            'gemm_dma_f32 (TN)': fp32_ring,
-           'gemm_f32 (TN, reg. staging)': lambda: old(0, 1, O, PA, CK, W, CK, 0, XT, CK, CK * PA, Y, PA, O * PA, B),
            'hipBLASLt (torch.matmul)': lambda: torch.matmul(W, XT.transpose(1, 2), out=Y)}, 2.0 * O * CK * PA * B)
     del XT, Y
 if ONLY_FIRST:
@@ -71,11 +52,9 @@ W2 = torch.randn(C, O * KS, device=dev)
 gF = torch.empty(B, C, RA, device=dev)
 print(f'dF rows [{C} x {RA}] = W2[{C} x {O * KS}] . Z, batch {B}')
 bench({'gemm_dma_f32 (NN)': lambda: _hip.gemm(0, 0, C, RA, O * KS, W2, O * KS, 0, Z, RA, O * KS * RA, gF, RA, C * RA, B),
-       'gemm_f32': lambda: old(0, 0, C, RA, O * KS, W2, O * KS, 0, Z, RA, O * KS * RA, gF, RA, C * RA, B),
        'hipBLASLt': lambda: torch.matmul(W2, Z, out=gF)}, 2.0 * C * RA * O * KS * B)
 Fc = torch.randn(B, C, RA, device=dev)
 d = torch.empty(O * KS, C, device=dev)
 print(f'dW [{O * KS} x {C}] = sum_b Z_b . Fc_b^T (K = {RA}), batch {B}')
 bench({'gemm_dma_f32 reduce': lambda: _hip.gemm_reduce(0, 1, O * KS, C, RA, Z, RA, O * KS * RA, Fc, RA, C * RA, d, C, B),
-       'gemm_f32 reduce': lambda: old_reduce(0, 1, O * KS, C, RA, Z, RA, O * KS * RA, Fc, RA, C * RA, d, C, B),
        'hipBLASLt + sum': lambda: torch.matmul(Z, Fc.transpose(1, 2)).sum(0)}, 2.0 * C * RA * O * KS * B)

@@ -32,16 +32,15 @@ for layer in (2, 1):
     variants = {k: v.contiguous() for k, v in variants.items()}
 
     def run(ep):
-        _hip.call('eap_so3_inter_group_inv_pitch_f32', z, B, o, P, NN, NA, NA, KS, rcap, _hip._F32(s), _hip._ptr(gy), _hip._ptr(rows),
-                  _hip._ptr(off), _hip._ptr(cnt), _hip._ptr(ep), _hip._ptr(ent_gx), _hip._ptr(rk), _hip._ptr(z))
+        _hip.call('eap_so3_inter_group_inv_f32', z, B, o, P, NN, NA, KS, rcap, _hip._F32(s), _hip._ptr(gy), _hip._ptr(rows),
+                  _hip._ptr(off), _hip._ptr(cnt), _hip._ptr(ep), _hip._ptr(ent_gx), _hip._ptr(rk), _hip._ptr(None), _hip._ptr(None), 0, _hip._ptr(z))
     fl = 2.0 * B * o * KS * P * NN * NA
     cn = cnt.flatten().float()
     print(f'layer {layer} O={o} rcap={rcap}: list lengths mean {cn[cn > 0].mean().item():.0f} max {cn.max().item():.0f} min {cn[cn > 0].min().item():.0f}', flush=True)
     zref = None
-    for tiles, xmap in ((2, 1), (3, 1), (4, 1)):   # (a generation the library does not take is skipped)
+    for tiles in (2, 3, 4):   # (a generation the library does not take is skipped)
         if _hip.lib.eap_so3_group_lists_tiles(tiles) != tiles:
             continue
-        _hip.lib.eap_so3_group_lists_xcd_map(1, xmap)
         run(variants['real'])
         zd = z.double()
         if zref is None:
@@ -60,6 +59,5 @@ for layer in (2, 1):
                 res[k].append(e0.elapsed_time(e1))
         for k, v in res.items():
             v.sort()
-            print(f'layer {layer} O={o} tiles/wave {tiles} xcd map {xmap}: rows {k:9s}: median {v[2]:.2f} ms  min {v[0]:.2f} ms  {fl / v[2] / 1e9:.1f} TFLOP/s algorithmic = {fl / v[2] / 1e9 / 157.3:.3f} of peak', flush=True)
+            print(f'layer {layer} O={o} tiles/wave {tiles}: rows {k:9s}: median {v[2]:.2f} ms  min {v[0]:.2f} ms  {fl / v[2] / 1e9:.1f} TFLOP/s algorithmic = {fl / v[2] / 1e9 / 157.3:.3f} of peak', flush=True)
     _hip.lib.eap_so3_group_lists_tiles(2)
-    _hip.lib.eap_so3_group_lists_xcd_map(1, 1)

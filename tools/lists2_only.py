@@ -1,5 +1,5 @@
 """tools/lists2_only.py [B] (was tools/lists2_ablation.py) -- the two-tile grouping kernel (csrc/so3_inter_lists2.hip) alone: the deepest layer's backward
-(O = 512, real inverse lists) and forward (C = 128) launches, then the XCD map A/B (eap_so3_group_lists_xcd_map, mode 1 / 2).
+(O = 512, real inverse lists) and forward (C = 128) launches.
 Median of 5 runs.  (The timing ablations that switched parts of the kernel off are recorded in profiles/r0[234]_lists2_ablation.txt;
 their code left the tree with the ablation build.)"""
 import os, sys
@@ -42,9 +42,3 @@ def fwd():
 for name, fn, fl in (('backward Z, O = 512', inv, 2.0 * B * o * KS * P * NN * NA), ('forward X (transposed), C = 128', fwd, 2.0 * B * c * KS * P * NN * NA)):
     v = sorted(timed(fn) for _ in range(6))[:5]
     print(f'{name}: median {v[2]:7.2f} ms = {fl / v[2] / 1e9 / 157.3:.3f} of peak (algorithmic)', flush=True)
-    which = 1 if fn is inv else 0
-    for mode in (1, 2):
-        _hip.lib.eap_so3_group_lists_xcd_map(which, mode)
-        v = sorted(timed(fn) for _ in range(6))[:5]
-        print(f'{name}: XCD map {mode}: median {v[2]:7.2f} ms = {fl / v[2] / 1e9 / 157.3:.3f} of peak', flush=True)
-    _hip.lib.eap_so3_group_lists_xcd_map(which, 1)

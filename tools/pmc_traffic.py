@@ -26,6 +26,9 @@ def key_of(name):
     # (traces taken before the ablation switch left the template lists carry one more integer, always 0: kc_gemm_kernel<MI, FORM, 0>,
     # gemm_dma_f32_kernel<..., false, false, 0> and the split kernels' <MI, WN, 0, B layout, pre-split weights>; both forms give the same key)
     out = re.sub(r'^(kc_gemm_kernel<\d+, \d+), 0>$', r'\1>', out)
+    # (the kernel has one weight form since and the profiler spells it kc_gemm_kernel<MI>; eap_last_kernel() and the counter files
+    # keep the key of that form, kc_gemm_kernel<MI, 1>: csrc/so3_dense.hip kc_launch)
+    out = re.sub(r'^kc_gemm_kernel<(\d+)>$', r'kc_gemm_kernel<\1, 1>', out)
     out = re.sub(r'^(gemm_dma_f32_kernel<.*(?:true|false)), 0>$', r'\1>', out)
     m = re.match(r'(gemm_bf16x3_kernel|gemm_f16x2_kernel)<(\d+), (\d+), (?:0, )?(\d+), (?:true|false)>$', out)
     if m:                                       # <MI, WN, B layout, pre-split weights> -> the name eap_last_kernel() reports
