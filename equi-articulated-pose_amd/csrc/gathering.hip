@@ -17,6 +17,13 @@ __global__ void gather_fwd_kernel(int c, int n, int m, const T *__restrict__ pts
     out[((size_t)bi * c + ci) * m + j] = (float)pts[((size_t)bi * c + ci) * n + a];
 }
 
+// (T)->float: one round-to-nearest-even conversion per element (the output is float32 whatever the input, gathering_cuda.cpp:L38-39)
+template <typename T>
+int launch_fwd(int b, int c, int n, int m, const T *pts, const int32_t *idx, float *out, hipStream_t s) {
+    if (b <= 0 || c <= 0 || m <= 0) return 0;
+    return eap::run_kernel("gather_points_forward", gather_fwd_kernel<T>, eap::cdiv(m, 256), c, b, dim3(256), 0, s, c, n, m, pts, idx, out);
+}
+
 template <typename T>
 __global__ void gather_bwd_kernel(int c, int n, int m, const T *__restrict__ grad_out,
                                   const int32_t *__restrict__ idx, T *__restrict__ grad_pts) {
@@ -39,9 +46,11 @@ int launch_bwd(int b, int c, int n, int m, const T *g, const int32_t *idx, T *gp
 
 extern "C" int eap_gather_points_fwd_f32(int b, int c, int n, int m, const float *pts,
                                          const int32_t *idx, float *out, eap_stream_t stream) {
-    if (b <= 0 || c <= 0 || m <= 0) return 0;
-    return eap::run_kernel("gather_points_forward", gather_fwd_kernel<float>, eap::cdiv(m, 256), c, b, dim3(256), 0, eap::S(stream), c, n, m, pts, idx,
-                           out);
+    return launch_fwd<float>(b, c, n, m, pts, idx, out, eap::S(stream));
+}
+extern "C" int eap_gather_points_fwd_f64(int b, int c, int n, int m, const double *pts,
+                                         const int32_t *idx, float *out, eap_stream_t stream) {
+    return launch_fwd<double>(b, c, n, m, pts, idx, out, eap::S(stream));
 }
 extern "C" int eap_gather_points_bwd_f32(int b, int c, int n, int m, const float *grad_out,
                                          const int32_t *idx, float *grad_pts, eap_stream_t stream) {

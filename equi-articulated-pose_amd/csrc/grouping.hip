@@ -9,8 +9,10 @@
 // first tile.
 //
 // Bit-exactness: d2 is evaluated as ((dx*dx + dy*dy) + dz*dz) with one rounding per operation
-// (__fmul_rn/__fadd_rn never contract to FMA), the same order as grouping_cuda_kernel.cu:L93-94
-// and as the CPU oracle; the neighbour lists are therefore identical integer-for-integer.
+// (mul_rn/add_rn below never contract to FMA), the same order as grouping_cuda_kernel.cu:L93-94
+// and as the CPU oracle; the neighbour lists are therefore identical integer-for-integer.  Every
+// kernel here is one template over the scalar type (float, double), as the reference dispatches
+// these ops with AT_DISPATCH_FLOATING_TYPES.
 #include "common.h"
 
 namespace {
@@ -18,13 +20,31 @@ namespace {
 constexpr int BQ_THREADS = 64;
 constexpr int BQ_TILE = 1024;
 
-__device__ __forceinline__ float d2_exact(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+// One rounding per operation in the operands' own type, never contracted (this file is built with -ffp-contract=off):
+// the float and the double form of every chain below run the same operations in the same order.
+__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ double add_rn(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
+__device__ __forceinline__ double sub_rn(double a, double b) { return __dsub_rn(a, b); }
+__device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ double mul_rn(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
+__device__ __forceinline__ double div_rn(double a, double b) { return __ddiv_rn(a, b); }
+__device__ __forceinline__ float sqrt_t(float a) { return sqrtf(a); }
+__device__ __forceinline__ double sqrt_t(double a) { return sqrt(a); }
+__device__ __forceinline__ float acos_t(float a) { return acosf(a); }
+__device__ __forceinline__ double acos_t(double a) { return acos(a); }
+__device__ __forceinline__ float min_t(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ double min_t(double a, double b) { return fmin(a, b); }
+
+// (x*x + y*y) + z*z
+template <typename T>
+__device__ __forceinline__ T sq3(T x, T y, T z) {
+    return add_rn(add_rn(mul_rn(x, x), mul_rn(y, y)), mul_rn(z, z));
 }
-__device__ __forceinline__ double d2_exact(double ax, double ay, double az, double bx, double by, double bz) {
-    const double dx = __dsub_rn(ax, bx), dy = __dsub_rn(ay, by), dz = __dsub_rn(az, bz);
-    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+template <typename T>
+__device__ __forceinline__ T d2_exact(T ax, T ay, T az, T bx, T by, T bz) {
+    return sq3(sub_rn(ax, bx), sub_rn(ay, by), sub_rn(az, bz));
 }
 
 template <typename T>
@@ -87,39 +107,41 @@ int launch_ball_query(int b, int n, int m, float radius, int nsample, const T *n
 // furthest point sampling (grouping_cuda.cpp:L160-174, kernel grouping_cuda_kernel.cu:L352-466).
 // Inherently sequential in m; one block per cloud.  Off the shipped models' path (stride is 1),
 // kept for API completeness.  The winner of each round must match the reference exactly, ties
-// included: per-thread first strict maximum over k = tid, tid+T, ..., then a halving tree that
-// keeps the lower slot on ties -- the same reduction shape, with T = the reference's block size
-// (largest power of two <= n, capped at 1024).
+// included: per-thread first strict maximum over k = tid, tid+nt, ..., then a halving tree that
+// keeps the lower slot on ties -- the same reduction shape, with nt = the reference's block size
+// (largest power of two <= n, capped at 1024).  temp, the shared distances and the constants are of the
+// cloud's own type (float: 8 KB of LDS, double: 12 KB).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void fps_kernel(int n, int m, const float *__restrict__ xyz,
-                                                  float *__restrict__ temp, int32_t *__restrict__ idx) {
-    __shared__ float s_d[1024];
+template <typename T>
+__global__ __launch_bounds__(1024) void fps_kernel(int n, int m, const T *__restrict__ xyz,
+                                                  T *__restrict__ temp, int32_t *__restrict__ idx) {
+    __shared__ T s_d[1024];
     __shared__ int s_i[1024];
-    const int bi = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+    const int bi = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     xyz += (size_t)bi * 3 * n;
     temp += (size_t)bi * n;
     idx += (size_t)bi * m;
-    for (int k = tid; k < n; k += T) temp[k] = 1e10f;
+    for (int k = tid; k < n; k += nt) temp[k] = (T)1e10;
     int old = 0;
     if (tid == 0) idx[0] = 0;
     __syncthreads();
     for (int j = 1; j < m; ++j) {
-        const float x1 = xyz[old], y1 = xyz[n + old], z1 = xyz[2 * n + old];
-        float best = -1.f;
+        const T x1 = xyz[old], y1 = xyz[n + old], z1 = xyz[2 * n + old];
+        T best = (T)-1;
         int besti = 0;
-        for (int k = tid; k < n; k += T) {
-            const float x2 = xyz[k], y2 = xyz[n + k], z2 = xyz[2 * n + k];
-            const float mag = __fadd_rn(__fadd_rn(__fmul_rn(x2, x2), __fmul_rn(y2, y2)), __fmul_rn(z2, z2));
-            if (mag <= 1e-3f) continue;
-            const float d = d2_exact(x2, y2, z2, x1, y1, z1);
-            const float d2 = fminf(d, temp[k]);
+        for (int k = tid; k < n; k += nt) {
+            const T x2 = xyz[k], y2 = xyz[n + k], z2 = xyz[2 * n + k];
+            const T mag = sq3(x2, y2, z2);
+            if (mag <= (T)1e-3) continue;
+            const T d = d2_exact(x2, y2, z2, x1, y1, z1);
+            const T d2 = min_t(d, temp[k]);
             temp[k] = d2;
             if (d2 > best) { best = d2; besti = k; }
         }
         s_d[tid] = best;
         s_i[tid] = besti;
         __syncthreads();
-        for (int s = T >> 1; s >= 1; s >>= 1) {
+        for (int s = nt >> 1; s >= 1; s >>= 1) {
             if (tid < s && s_d[tid + s] > s_d[tid]) { s_d[tid] = s_d[tid + s]; s_i[tid] = s_i[tid + s]; }
             __syncthreads();
         }
@@ -133,25 +155,26 @@ __global__ __launch_bounds__(1024) void fps_kernel(int n, int m, const float *__
 // anchor_query, S^2 variant (grouping_cuda.cpp:L88-108, kernel .cu:L181-247):
 //   w[b,p,a,k,n] = (kw - |x|)^2 + ((kh - theta) |x|)^2,  theta = acos(x . anchor_a / |x|)
 // ---------------------------------------------------------------------------------------------
-__global__ void anchor_query_kernel(int np, int nn, int na, int ks, const float *__restrict__ gxyz,
-                                    const float *__restrict__ anchors, const float *__restrict__ kpts,
-                                    float *__restrict__ w) {
+template <typename T>
+__global__ void anchor_query_kernel(int np, int nn, int na, int ks, const T *__restrict__ gxyz,
+                                    const T *__restrict__ anchors, const T *__restrict__ kpts,
+                                    T *__restrict__ w) {
     const int bi = blockIdx.y;
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (long long)np * nn) return;
     const int pi = (int)(e / nn), ni = (int)(e % nn);
-    const float *g = gxyz + (size_t)bi * 3 * np * nn;
-    const float x = g[e], y = g[(size_t)np * nn + e], z = g[(size_t)2 * np * nn + e];
-    const float norm = __fadd_rn(sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z))), 1e-6f);
-    float *wp = w + (((size_t)bi * np + pi) * na) * ks * nn + ni;
+    const T *g = gxyz + (size_t)bi * 3 * np * nn;
+    const T x = g[e], y = g[(size_t)np * nn + e], z = g[(size_t)2 * np * nn + e];
+    const T norm = add_rn(sqrt_t(sq3(x, y, z)), (T)1e-6);
+    T *wp = w + (((size_t)bi * np + pi) * na) * ks * nn + ni;
     for (int ai = 0; ai < na; ++ai) {
-        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(x, anchors[ai * 3]), __fmul_rn(y, anchors[ai * 3 + 1])),
-                                    __fmul_rn(z, anchors[ai * 3 + 2]));
-        const float theta = acosf(__fdiv_rn(dot, norm));
+        const T dot = add_rn(add_rn(mul_rn(x, anchors[ai * 3]), mul_rn(y, anchors[ai * 3 + 1])),
+                             mul_rn(z, anchors[ai * 3 + 2]));
+        const T theta = acos_t(div_rn(dot, norm));
         for (int ki = 0; ki < ks; ++ki) {
-            const float a = __fsub_rn(kpts[ki * 2], norm);
-            const float c = __fmul_rn(__fsub_rn(kpts[ki * 2 + 1], theta), norm);
-            wp[((size_t)ai * ks + ki) * nn] = __fadd_rn(__fmul_rn(a, a), __fmul_rn(c, c));
+            const T a = sub_rn(kpts[ki * 2], norm);
+            const T c = mul_rn(sub_rn(kpts[ki * 2 + 1], theta), norm);
+            wp[((size_t)ai * ks + ki) * nn] = add_rn(mul_rn(a, a), mul_rn(c, c));
         }
     }
 }
@@ -162,31 +185,58 @@ __global__ void anchor_query_kernel(int np, int nn, int na, int ks, const float 
 // every output element (kernel point, centre, anchor) owns a lane that sums over the fragment
 // points in index order -- deterministic, no atomics.
 // ---------------------------------------------------------------------------------------------
-__global__ void initial_anchor_query_kernel(int nc, int m, int na, int ks, float radius, float sigma,
-                                            const float *__restrict__ centers, const float *__restrict__ xyz,
-                                            const float *__restrict__ kpts, float *__restrict__ w,
-                                            float *__restrict__ cnt) {
+template <typename T>
+__global__ void initial_anchor_query_kernel(int nc, int m, int na, int ks, T radius, T sigma,
+                                            const T *__restrict__ centers, const T *__restrict__ xyz,
+                                            const T *__restrict__ kpts, T *__restrict__ w,
+                                            T *__restrict__ cnt) {
     const int pn = blockIdx.x, bi = blockIdx.y;
-    const float *C = centers + (size_t)bi * 3 * nc;
-    const float cx = C[pn], cy = C[nc + pn], cz = C[2 * nc + pn];
+    const T *C = centers + (size_t)bi * 3 * nc;
+    const T cx = C[pn], cy = C[nc + pn], cz = C[2 * nc + pn];
     for (int e = threadIdx.x; e < ks * na; e += blockDim.x) {
         const int kn = e / na, an = e - kn * na;
-        const float kx = __fadd_rn(kpts[e * 3], cx), ky = __fadd_rn(kpts[e * 3 + 1], cy), kz = __fadd_rn(kpts[e * 3 + 2], cz);
-        float sw = 0.f, sc = 0.f;
+        const T kx = add_rn(kpts[e * 3], cx), ky = add_rn(kpts[e * 3 + 1], cy), kz = add_rn(kpts[e * 3 + 2], cz);
+        T sw = (T)0, sc = (T)0;
         for (int pm = 0; pm < m; ++pm) {
-            const float x = xyz[3 * pm], y = xyz[3 * pm + 1], z = xyz[3 * pm + 2];
-            const float dc = sqrtf(d2_exact(cx, cy, cz, x, y, z));
+            const T x = xyz[3 * pm], y = xyz[3 * pm + 1], z = xyz[3 * pm + 2];
+            const T dc = sqrt_t(d2_exact(cx, cy, cz, x, y, z));
             if (dc <= radius) {
-                const float dk = sqrtf(d2_exact(kx, ky, kz, x, y, z));
-                const float wt = __fsub_rn(1.f, __fdiv_rn(__fmul_rn(dk, dk), sigma));
-                if (wt > 0.f) sw = __fadd_rn(sw, wt);
-                sc = __fadd_rn(sc, 1.f);
+                const T dk = sqrt_t(d2_exact(kx, ky, kz, x, y, z));
+                const T wt = sub_rn((T)1, div_rn(mul_rn(dk, dk), sigma));
+                if (wt > (T)0) sw = add_rn(sw, wt);
+                sc = add_rn(sc, (T)1);
             }
         }
         const size_t o = (((size_t)bi * ks + kn) * nc + pn) * na + an;
         w[o] = sw;
         cnt[o] = sc;
     }
+}
+
+template <typename T>
+int launch_fps(int b, int n, int m, const T *xyz, T *temp, int32_t *idx, hipStream_t s) {
+    if (b <= 0 || m <= 0) return 0;
+    if (n <= 0) return eap::bad_arg("furthest_point_sampling: empty cloud");
+    int threads = 1;
+    while (threads * 2 <= n && threads < 1024) threads *= 2;   // opt_n_threads, grouping_cuda_kernel.cu:L29-33
+    return eap::run_kernel("furthest_point_sampling", fps_kernel<T>, b, 1, 1, dim3(threads), 0, s, n, m, xyz, temp, idx);
+}
+
+template <typename T>
+int launch_anchor_query(int b, int np, int nn, int na, int ks, const T *grouped_xyz, const T *anchors,
+                        const T *kernel_pts, T *w, hipStream_t s) {
+    if (b <= 0 || np <= 0 || nn <= 0) return 0;
+    return eap::run_kernel("anchor_query", anchor_query_kernel<T>, eap::cdiv((long long)np * nn, 256), b, 1, dim3(256), 0, s, np, nn, na, ks, grouped_xyz,
+                           anchors, kernel_pts, w);
+}
+
+template <typename T>
+int launch_initial_anchor_query(int b, int nc, int m, int na, int ks, float radius, float sigma, const T *centers,
+                                const T *xyz, const T *kernel_pts, T *w, T *cnt, hipStream_t s) {
+    if (b <= 0 || nc <= 0 || na <= 0 || ks <= 0) return 0;
+    // radius and sigma arrive as float (grouping_cuda.cpp:L138) and are widened once, where the kernel compares and divides in T
+    return eap::run_kernel("initial_anchor_query", initial_anchor_query_kernel<T>, nc, b, 1, dim3(256), 0, s, nc, m, na, ks, (T)radius, (T)sigma, centers,
+                           xyz, kernel_pts, w, cnt);
 }
 
 }  // namespace
@@ -204,25 +254,31 @@ extern "C" int eap_ball_query_f64(int b, int n, int m, float radius, int nsample
 
 extern "C" int eap_furthest_point_sampling_f32(int b, int n, int m, const float *xyz, float *temp,
                                                int32_t *idx, eap_stream_t stream) {
-    if (b <= 0 || m <= 0) return 0;
-    if (n <= 0) return eap::bad_arg("furthest_point_sampling: empty cloud");
-    int threads = 1;
-    while (threads * 2 <= n && threads < 1024) threads *= 2;   // opt_n_threads, grouping_cuda_kernel.cu:L29-33
-    return eap::run_kernel("furthest_point_sampling", fps_kernel, b, 1, 1, dim3(threads), 0, eap::S(stream), n, m, xyz, temp, idx);
+    return launch_fps<float>(b, n, m, xyz, temp, idx, eap::S(stream));
+}
+extern "C" int eap_furthest_point_sampling_f64(int b, int n, int m, const double *xyz, double *temp,
+                                               int32_t *idx, eap_stream_t stream) {
+    return launch_fps<double>(b, n, m, xyz, temp, idx, eap::S(stream));
 }
 
 extern "C" int eap_anchor_query_f32(int b, int np, int nn, int na, int ks, const float *grouped_xyz,
                                     const float *anchors, const float *kernel_pts, float *w,
                                     eap_stream_t stream) {
-    if (b <= 0 || np <= 0 || nn <= 0) return 0;
-    return eap::run_kernel("anchor_query", anchor_query_kernel, eap::cdiv((long long)np * nn, 256), b, 1, dim3(256), 0, eap::S(stream), np, nn, na, ks, grouped_xyz,
-                           anchors, kernel_pts, w);
+    return launch_anchor_query<float>(b, np, nn, na, ks, grouped_xyz, anchors, kernel_pts, w, eap::S(stream));
+}
+extern "C" int eap_anchor_query_f64(int b, int np, int nn, int na, int ks, const double *grouped_xyz,
+                                    const double *anchors, const double *kernel_pts, double *w,
+                                    eap_stream_t stream) {
+    return launch_anchor_query<double>(b, np, nn, na, ks, grouped_xyz, anchors, kernel_pts, w, eap::S(stream));
 }
 
 extern "C" int eap_initial_anchor_query_f32(int b, int nc, int m, int na, int ks, float radius, float sigma,
                                             const float *centers, const float *xyz, const float *kernel_pts,
                                             float *w, float *cnt, eap_stream_t stream) {
-    if (b <= 0 || nc <= 0 || na <= 0 || ks <= 0) return 0;
-    return eap::run_kernel("initial_anchor_query", initial_anchor_query_kernel, nc, b, 1, dim3(256), 0, eap::S(stream), nc, m, na, ks, radius, sigma, centers, xyz,
-                           kernel_pts, w, cnt);
+    return launch_initial_anchor_query<float>(b, nc, m, na, ks, radius, sigma, centers, xyz, kernel_pts, w, cnt, eap::S(stream));
+}
+extern "C" int eap_initial_anchor_query_f64(int b, int nc, int m, int na, int ks, float radius, float sigma,
+                                            const double *centers, const double *xyz, const double *kernel_pts,
+                                            double *w, double *cnt, eap_stream_t stream) {
+    return launch_initial_anchor_query<double>(b, nc, m, na, ks, radius, sigma, centers, xyz, kernel_pts, w, cnt, eap::S(stream));
 }

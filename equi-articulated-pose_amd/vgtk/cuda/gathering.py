@@ -8,14 +8,12 @@ def gather_points_forward(pts, idx):
     """(pts T [B,C,N], idx int32 [B,M]) -> float32 [B,C,M]; gathering_cuda.cpp:L29-43
     (the reference allocates a Float output whatever the input dtype)."""
     _hip.check_input(pts, idx)
-    if pts.dtype != torch.float32:
-        raise RuntimeError('gather_points_forward: float32 points only')
     if idx.dtype != torch.int32:
         raise RuntimeError('gather_points_forward: idx must be int32')
     b, c, n = pts.shape
     m = idx.shape[1]
     out = torch.empty(b, c, m, dtype=torch.float32, device=pts.device)
-    _hip.call('eap_gather_points_fwd_f32', out, b, c, n, m, _hip._ptr(pts), _hip._ptr(idx), _hip._ptr(out))
+    _hip.call('eap_gather_points_fwd_' + _hip.suffix(pts), out, b, c, n, m, _hip._ptr(pts), _hip._ptr(idx), _hip._ptr(out))
     return out
 
 

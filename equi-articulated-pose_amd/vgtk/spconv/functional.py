@@ -39,15 +39,17 @@ def add_shadow_feature(x):
 class Gathering(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, idx):
-        """points [nb,c,np], idx int32 [nb,m] -> [nb,c,m]"""
+        """points T [nb,c,np], idx int32 [nb,m] -> float32 [nb,c,m]"""
         ctx.save_for_backward(idx)
         ctx.npoint = points.size(2)
+        ctx.points_dtype = points.dtype
         return gather.gather_points_forward(points.contiguous(), idx.contiguous())
 
     @staticmethod
     def backward(ctx, grad):
         idx, = ctx.saved_tensors
-        return gather.gather_points_backward(grad.contiguous(), idx, ctx.npoint), None
+        # (the float32 gradient of the float32 output, handed back in the dtype of the points)
+        return gather.gather_points_backward(grad.contiguous(), idx, ctx.npoint).to(ctx.points_dtype), None
 
 
 class IntraZPConvGrouping(torch.autograd.Function):

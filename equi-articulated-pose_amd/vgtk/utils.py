@@ -6,7 +6,7 @@ import vgtk.cuda.gathering as cuda_gather
 
 
 def batch_gather(x, idx, dim=1):
-    """[b,c,n] x [b,m] -> float32 [b,c,m] through the native gather (no autograd on this route, as in the reference)."""
+    """float32 or float64 [b,c,n] x [b,m] -> float32 [b,c,m] through the native gather (no autograd on this route, as in the reference)."""
     return cuda_gather.gather_points_forward(x.contiguous(), idx.int().contiguous())
 
 

@@ -58,11 +58,19 @@ int eap_ball_query_f64(int b, int n, int m, float radius, int nsample, const dou
  * xyz [b,3,n] -> idx int32 [b,m]; temp [b,n] is scratch (initialised by the call). */
 int eap_furthest_point_sampling_f32(int b, int n, int m, const float *xyz, float *temp,
                                     int32_t *idx, eap_stream_t stream);
+/* the double instantiation of grouping_cuda_kernel.cu:L638-726: distances, temp, the 1e10 / -1 start
+ * values and the 1e-3 skip threshold in double; same block size and tie rules. */
+int eap_furthest_point_sampling_f64(int b, int n, int m, const double *xyz, double *temp,
+                                    int32_t *idx, eap_stream_t stream);
 
 /* anchor_query (S^2 variant): grouping_cuda.cpp:L88-108, kernel .cu:L181-247.
  * grouped_xyz [b,3,np,nn], anchors [na,3], kernel_pts [ks,2] -> w [b,np,na,ks,nn]. */
 int eap_anchor_query_f32(int b, int np, int nn, int na, int ks, const float *grouped_xyz,
                          const float *anchors, const float *kernel_pts, float *w,
+                         eap_stream_t stream);
+/* the double dispatch of grouping_cuda_kernel.cu:L510: sqrt, acos and the + 1e-6 in double. */
+int eap_anchor_query_f64(int b, int np, int nn, int na, int ks, const double *grouped_xyz,
+                         const double *anchors, const double *kernel_pts, double *w,
                          eap_stream_t stream);
 
 /* initial_anchor_query: grouping_cuda.cpp:L138-158, kernel .cu:L117-167.
@@ -70,11 +78,20 @@ int eap_anchor_query_f32(int b, int np, int nn, int na, int ks, const float *gro
 int eap_initial_anchor_query_f32(int b, int nc, int m, int na, int ks, float radius, float sigma,
                                  const float *centers, const float *xyz, const float *kernel_pts,
                                  float *w, float *cnt, eap_stream_t stream);
+/* the double dispatch of grouping_cuda_kernel.cu:L562: radius and sigma stay float arguments and are
+ * widened where they are compared and divided by. */
+int eap_initial_anchor_query_f64(int b, int nc, int m, int na, int ks, float radius, float sigma,
+                                 const double *centers, const double *xyz, const double *kernel_pts,
+                                 double *w, double *cnt, eap_stream_t stream);
 
 /* ---- gathering (vgtk/vgtk/cuda/gathering_cuda.cpp) ---------------------------------------- */
 
 /* gather_points_forward: gathering_cuda.cpp:L29-43. pts [b,c,n], idx [b,m] -> out f32 [b,c,m]. */
 int eap_gather_points_fwd_f32(int b, int c, int n, int m, const float *pts, const int32_t *idx,
+                              float *out, eap_stream_t stream);
+/* the double dispatch of gathering_cuda_kernel.cu:L117: out stays f32 (gathering_cuda.cpp:L38-39),
+ * every element converted once, round to nearest even. */
+int eap_gather_points_fwd_f64(int b, int c, int n, int m, const double *pts, const int32_t *idx,
                               float *out, eap_stream_t stream);
 /* gather_points_backward: gathering_cuda.cpp:L45-60. grad_out [b,c,m] -> grad_pts [b,c,n]. */
 int eap_gather_points_bwd_f32(int b, int c, int n, int m, const float *grad_out,
