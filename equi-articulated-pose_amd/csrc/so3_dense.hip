@@ -381,12 +381,20 @@ __global__ __launch_bounds__(256) void dense_scale_kernel(long long total, int m
 
 // planes[z = b na + a][k-block kb][row tile mt][plane][lane] (16 bytes): lane (i = lane & 31, kg = lane >> 5) holds the 8
 // contraction elements 16 kb + 8 kg .. + 7 of row 32 mt + i -- what a lane of v_mfma_f32_32x32x16_f16 takes as its A operand.
-// One block per (b, mt, kb): thread (anchor quad aq = t % nq, row group t / nq) takes the 8 elements of (row, kg) for its four
-// anchors -- 8 float4 loads 4 na bytes apart, the nq threads of a row covering each element's 4 na contiguous bytes -- and
-// writes its 8 pieces; the 64 pieces of a 1 KB run come from one block within a few hundred cycles.
+// One block per (b, mt, kb, k half kg) = 32 rows x 8 elements x na anchors.  In: thread (anchor quad aq = t % nq, row group t / nq) takes
+// the 8 elements of a row for its four anchors -- 8 float4 loads 4 na bytes apart, the nq threads of a row covering each element's 4 na
+// contiguous bytes: whole rows, also through a column map -- two rows per thread and round, sixteen (BN: thirty-two) 16-byte loads in
+// flight.  Out: the converted 16-byte pieces go through an LDS image [anchor][plane][row] (na KB: two blocks per CU at 60 anchors, one
+// loading while the other stores), and a wave instruction then writes the 32 pieces of (anchor, h) and the 32 of (anchor, l) -- the two
+// 512-byte halves kg of their 1 KB runs, whole 128-byte lines -- with consecutive lanes on consecutive 16 bytes.  (Before: straight
+// from the registers, a wave store put 64..80-byte fragments into 15 planes, four times over; and a block of both halves would need
+// 2 na KB of LDS, one block per CU.)  A row's pieces are rotated by its anchor quad in the image: the nq lanes of one row write nq banks.
+// 128 -> 512 layer of the bench, BatchNorm form: 3.21 -> 2.81 ms, 2.78 -> 2.52 GB written, 19 % fewer vector instructions; the 1.28 x fetch of
+// 240-byte rows that straddle 128-byte lines stays (profiles/dense_passes.txt).
 // mapped (the forward's G, seg = rp, l = ks rp): element l of a row is the pair (k, r) with DENSE INDEX l, found at segment k,
 // position r; k-blocks past the cloud's own prefix (n_rows) are not written -- the product never reads them.
-// colmap: as dense_rowmax_kernel's (the columns of dY that are one rigid part's query points)
+// colmap: as dense_rowmax_kernel's (the columns of dY that are one rigid part's query points); read once per thread -- a block's items
+// share their 8 columns -- and the mask of the columns that exist (`live`) comes from it
 // BN (template): the operand is the gradient BEHIND a training-mode BatchNorm + leaky_relu (csrc/bn_act.hip), formed here from the
 // gradient in front of it (T = dL/dy') and the activated output Y2 = y' itself instead of being written out and read back:
 //     pre = y' > 0 ? y' : y' / slope,  xhat = (pre - beta) / gamma,  g = y' > 0 ? dy' : slope dy',  gx = k1 g - k2 - k3 xhat
@@ -395,75 +403,75 @@ __global__ __launch_bounds__(256) void dense_scale_kernel(long long total, int m
 // the conv output for its backward.  SPConvNets/utils/base_so3poseconv.py:L214-221.
 struct SplitBn { const f32x4 *Y2; const float *coef; float slope, inv_slope; };
 template <bool BN>
-__global__ __launch_bounds__(256) void dense_split_kernel(int nb, int m, int l, int na, int kb_total, int seg, long long seg_pitch4, int mapped,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void dense_split_kernel(int m, int l, int na, int kb_total, int seg, long long seg_pitch4, int mapped,
                                                           const int32_t *__restrict__ n_rows, const int32_t *__restrict__ colmap,
                                                           const f32x4 *__restrict__ T, const float *__restrict__ scale2,
                                                           u32x4 *__restrict__ planes, SplitBn bn) {
-    // block -> (k-block kb fastest, row tile mt, cloud b).  (Measured and dropped: all k-blocks of one (mt, b) on one XCD, so that the
+    extern __shared__ u32x4 image[];                            // [na][plane][32 rows]
+    // block -> (k half kg fastest, k-block kb, row tile mt, cloud b).  (Measured and dropped: all k-blocks of one (mt, b) on one XCD, so that the
     // partial lines a column map's scattered 240-byte rows share meet in one L2 -- 3.16 -> 3.56 ms unmapped, 3.35 -> 3.72 mapped.)
     const int t = threadIdx.x;
-    const int mts = m >> 5;
-    const int kb = (int)(blockIdx.x % (unsigned)kb_total), grp_ = (int)(blockIdx.x / (unsigned)kb_total), mt = grp_ % mts, b = grp_ / mts;
-    (void)nb;
+    const int MT = m >> 5;
+    const unsigned blk = blockIdx.x >> 1;
+    const int kg = (int)(blockIdx.x & 1u), kb = (int)(blk % (unsigned)kb_total), grp_ = (int)(blk / (unsigned)kb_total), mt = grp_ % MT, b = grp_ / MT;
     const int nq = na >> 2, RG = 256 / nq;                      // rows per pass
     const int aq = t % nq, rr = t / nq;
-    if (rr >= RG) return;
-    const int MT = m >> 5, nseg = l / seg;
-    if (mapped && n_rows != nullptr && 16 * kb >= ((min(n_rows[b], seg) + 15) & ~15) * nseg) return;
-    // item = (row i, k half kg); two items per round: sixteen independent 16-byte loads in flight per thread
-    for (int it0 = rr; it0 < 64; it0 += 2 * RG) {
+    const int nseg = l / seg;
+    if (mapped && n_rows != nullptr && 16 * kb >= ((min(n_rows[b], seg) + 15) & ~15) * nseg) return;      // (block-uniform)
+    const int l0 = 16 * kb + 8 * kg;                            // the block's 8 elements: l0 + e
+    // at[e]: where element e sits in its source row, in 16-byte pieces of an anchor quad's column (32 bits: the launcher checks a row's
+    // extent); keep[e]: all ones if the element exists (a column the map names, inside l), else zero.  Block-uniform, and the loads
+    // below are unconditional -- an absent element reads element l0's address and is masked to +0 afterwards -- so that a thread's loads
+    // issue back to back; a block without any element (the empty half of the last k-block) reads nothing.
+    unsigned at[8], keep[8];
+    int live = 0;
+    if (colmap != nullptr) {
+        // (l is a multiple of 8 here -- the launcher checks -- so the 8 map entries are two aligned 16-byte words)
+        int ci[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+        if (l0 < l) {
+            const int4 c0 = *reinterpret_cast<const int4 *>(colmap + (size_t)b * l + l0), c1 = *reinterpret_cast<const int4 *>(colmap + (size_t)b * l + l0 + 4);
+            ci[0] = c0.x; ci[1] = c0.y; ci[2] = c0.z; ci[3] = c0.w; ci[4] = c1.x; ci[5] = c1.y; ci[6] = c1.z; ci[7] = c1.w;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { keep[e] = ci[e] >= 0 ? ~0u : 0u; at[e] = (unsigned)max(ci[e], 0) * (unsigned)nq; live |= (int)(keep[e] & 1u) << e; }
+    } else {
+        int sg = l0 / seg, sr = l0 - sg * seg;                  // segment and position of element l0 + e
+        if (mapped) dense_kr(l0, nseg, sg, sr);                 // (8 consecutive dense indices: one kernel point, 8 consecutive slots)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            keep[e] = l0 + e < l ? ~0u : 0u;
+            at[e] = keep[e] ? (unsigned)sg * (unsigned)seg_pitch4 + (unsigned)sr * (unsigned)nq : 0u;
+            live |= (int)(keep[e] & 1u) << e;
+            if (++sr == seg) { sr = 0; ++sg; }
+        }
+#pragma unroll
+        for (int e = 1; e < 8; ++e) at[e] = keep[e] ? at[e] : at[0];
+    }
+    if (live == 0)
+        for (int i = t; i < 64 * na; i += 256) image[i] = (u32x4){0u, 0u, 0u, 0u};
+    // item = row i of the tile; two items per round
+    for (int it0 = rr; it0 < 32 && rr < RG && live != 0; it0 += 2 * RG) {
         f32x4 q[2][8];
         f32x4 q2[BN ? 2 : 1][BN ? 8 : 1];
-        int rowv[2], lanef[2];
+        int rowv[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            const int it = min(it0 + u * RG, 63);
-            const int i = it & 31, kg = it >> 5, row = 32 * mt + i, l0 = 16 * kb + 8 * kg;
-            rowv[u] = row; lanef[u] = i + 32 * kg;
+            const int row = 32 * mt + min(it0 + u * RG, 31);      // (past the tile: the last row again, not stored)
+            rowv[u] = row;
             const size_t row_off = ((size_t)b * m + row) * (colmap ? (size_t)1 : (size_t)nseg) * seg_pitch4 + aq;
-            const f32x4 *src = T + row_off;
-            int sg = l0 / seg, sr = l0 - sg * seg;                // segment and position of element l0 + e
-            if (mapped) dense_kr(l0, nseg, sg, sr);               // (8 consecutive dense indices: one kernel point, 8 consecutive slots)
-            if (colmap != nullptr) {
-                // (l is a multiple of 8 here -- the launcher checks -- so the 8 map entries are two aligned 16-byte words)
-                int ci[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-                if (l0 < l) {
-                    const int4 c0 = *reinterpret_cast<const int4 *>(colmap + (size_t)b * l + l0), c1 = *reinterpret_cast<const int4 *>(colmap + (size_t)b * l + l0 + 4);
-                    ci[0] = c0.x; ci[1] = c0.y; ci[2] = c0.z; ci[3] = c0.w; ci[4] = c1.x; ci[5] = c1.y; ci[6] = c1.z; ci[7] = c1.w;
-                }
 #pragma unroll
-                for (int e = 0; e < 8; ++e) q[u][e] = ci[e] >= 0 ? src[(size_t)ci[e] * nq] : (f32x4){0.f, 0.f, 0.f, 0.f};
-                if constexpr (BN) {
+            for (int e = 0; e < 8; ++e) q[u][e] = T[row_off + at[e]];
+            if constexpr (BN) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) q2[u][e] = ci[e] >= 0 ? bn.Y2[row_off + (size_t)ci[e] * nq] : (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const bool in = l0 + e < l;
-                    const size_t at = (size_t)sg * seg_pitch4 + (size_t)sr * nq;
-                    q[u][e] = in ? src[at] : (f32x4){0.f, 0.f, 0.f, 0.f};
-                    if constexpr (BN) q2[u][e] = in ? bn.Y2[row_off + at] : (f32x4){0.f, 0.f, 0.f, 0.f};
-                    if (++sr == seg) { sr = 0; ++sg; }
-                }
+                for (int e = 0; e < 8; ++e) q2[u][e] = bn.Y2[row_off + at[e]];
             }
         }
+        __builtin_amdgcn_sched_barrier(0);                        // (every load above is issued before the first value is used)
         if constexpr (BN) {
-            // columns that do not exist (map < 0, past l) must stay exact zeros: their y' reads as 0 above, which alone would give -k2
+            // columns that do not exist (map < 0, past l) must stay exact zeros
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const int it = min(it0 + u * RG, 63);
-                const int l0 = 16 * kb + 8 * (it >> 5);
                 const float k1 = bn.coef[rowv[u]], k2 = bn.coef[m + rowv[u]], k3 = bn.coef[2 * m + rowv[u]], be = bn.coef[3 * m + rowv[u]], ig = bn.coef[4 * m + rowv[u]];
-                int live = 0;                                   // bit e: element e of this item exists
-                if (colmap != nullptr) {
-                    if (l0 < l) {
-                        const int4 c0 = *reinterpret_cast<const int4 *>(colmap + (size_t)b * l + l0), c1 = *reinterpret_cast<const int4 *>(colmap + (size_t)b * l + l0 + 4);
-                        live = (c0.x >= 0) | (c0.y >= 0) << 1 | (c0.z >= 0) << 2 | (c0.w >= 0) << 3 | (c1.x >= 0) << 4 | (c1.y >= 0) << 5 | (c1.z >= 0) << 6 | (c1.w >= 0) << 7;
-                    }
-                } else {
-                    for (int e = 0; e < 8; ++e) live |= (l0 + e < l) << e;
-                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
 #pragma unroll
@@ -472,24 +480,39 @@ __global__ __launch_bounds__(256) void dense_split_kernel(int nb, int m, int l, 
                         const bool pos = yv > 0.f;
                         const float gg = pos ? gv : gv * bn.slope, pre = pos ? yv : yv * bn.inv_slope;
                         const float gx = fmaf(gg, k1, -k2) - ((pre - be) * ig) * k3;
-                        q[u][e][j] = ((live >> e) & 1) ? gx : 0.f;
+                        q[u][e][j] = __uint_as_float(__float_as_uint(gx) & keep[e]);
                     }
             }
+        } else if (live != 255) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) q[u][e][j] = __uint_as_float(__float_as_uint(q[u][e][j]) & keep[e]);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            if (it0 + u * RG >= 64) break;
+            const int i = it0 + u * RG;
+            if (i >= 32) break;
             const f32x4 sc = *reinterpret_cast<const f32x4 *>(scale2 + ((size_t)b * m + rowv[u]) * na + 4 * aq);
+            u32x4 *dst = image + 256 * aq + ((i + aq) & 31);     // anchor 4 aq + j: + 64 j; plane l: + 32
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 unsigned h[4], lo[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) split2(q[u][2 * e][j] * sc[j], q[u][2 * e + 1][j] * sc[j], h[e], lo[e]);
-                u32x4 *dst = planes + ((((size_t)b * na + 4 * aq + j) * kb_total + kb) * MT + mt) * 128 + lanef[u];
-                dst[0] = (u32x4){h[0], h[1], h[2], h[3]};
-                dst[64] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
+                dst[64 * j] = (u32x4){h[0], h[1], h[2], h[3]};
+                dst[64 * j + 32] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
             }
         }
+    }
+    __syncthreads();
+    // wave w, pass k: anchor a = 4 k + w; lanes 0..31 the rows of plane h, lanes 32..63 those of plane l
+    const int w = t >> 6, pl = (t >> 5) & 1, i = t & 31;
+    for (int k = 0; k < nq; ++k) {
+        const int a = 4 * k + w;
+        planes[((((size_t)b * na + a) * kb_total + kb) * MT + mt) * 128 + 64 * pl + 32 * kg + i] = image[64 * a + 32 * pl + ((i + k) & 31)];
     }
 }
 
@@ -636,7 +659,8 @@ __global__ __launch_bounds__(256) void dense_gplanes_kernel(int m, int na, int k
     }
 }
 
-// Yt[b][a][o][p] -> Y[b][o][p][a]: block (p chunk of 64, o, b) through a [na][65] LDS tile.  psum / psq (may be null): the block's
+// Yt[b][a][o][p] -> Y[b][o][p][a] WITH the partial moments (the forms without them: dense_untranspose_tile_kernel below): block (p chunk
+// of 64, o, b) through a [na][65] LDS tile.  psum / psq: the block's
 // sum and sum of squares of (y - pivot), pivot = Y[0][o][0][0] -- the partial moments the BatchNorm that follows would otherwise
 // read the whole tensor for (csrc/bn_act.hip bn_stats_kernel: the same pivot, summed in float64 by the caller), at
 // [o][b * chunks + chunk].
@@ -646,9 +670,7 @@ __global__ __launch_bounds__(256) void dense_gplanes_kernel(int m, int na, int k
 __global__ __launch_bounds__(256) void dense_untranspose_kernel(int nb, int o_total, int p, int na, int p_dst, const int32_t *__restrict__ map,
                                                                 const int32_t *__restrict__ pivot_pos,
                                                                 const float *__restrict__ yt, float *__restrict__ y,
-                                                                float *__restrict__ psum, float *__restrict__ psq,
-                                                                const float *__restrict__ bn_scale = nullptr, const float *__restrict__ bn_shift = nullptr,
-                                                                float slope = 1.f) {
+                                                                float *__restrict__ psum, float *__restrict__ psq) {
     extern __shared__ float tile[];
     __shared__ float red[2][256];
     // block -> (chunk of 64 columns fastest, o, b).  (An XCD-owning map -- all chunks of one (o, b) in one L2 -- did not help the mapped
@@ -681,12 +703,7 @@ __global__ __launch_bounds__(256) void dense_untranspose_kernel(int nb, int o_to
         const int q = map ? map[(size_t)b * p + p0 + pp] : p0 + pp;
         if (map != nullptr && (unsigned)q >= (unsigned)p_dst) continue;
         const float *src = tile + (4 * a4) * 65 + pp;
-        f32x4 v = {src[0], src[65], src[130], src[195]};
-        if (bn_scale != nullptr) {                                         // (block-uniform) BatchNorm + leaky_relu of channel o on the way out
-            const float sc = bn_scale[o], sh = bn_shift[o];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float u = fmaf(v[e], sc, sh); v[e] = u > 0.f ? u : u * slope; }
-        }
+        const f32x4 v = {src[0], src[65], src[130], src[195]};
         *reinterpret_cast<f32x4 *>(rows_y + (size_t)q * na + 4 * a4) = v;
     }
     if (psum == nullptr) return;                                           // (block-uniform)
@@ -697,6 +714,82 @@ __global__ __launch_bounds__(256) void dense_untranspose_kernel(int nb, int o_to
     if (t == 0) {
         const size_t at = ((size_t)o * nb_z + b) * nchunk_x + (p0 >> 6);
         psum[at] = red[0][0]; psq[at] = red[1][0];
+    }
+}
+
+// The same re-ordering without the moments (the plain, the mapped and the BatchNorm + activation form; the two forms that return
+// partial moments stay on dense_untranspose_kernel above: their chunks of 64 columns and their summation order are the interface).
+// Block (chunk of UT_PTS columns, o, b): every lane loads 16 bytes -- four consecutive columns of one anchor, a wave instruction
+// covering 2 x 512 contiguous bytes -- with all of a thread's (at most 8) loads in flight at once, through a [na][UT_PTS] LDS tile
+// (30 KB at 60 anchors: five blocks per CU, so that some load while others store), out as 16-byte stores of whole rows of na floats.
+// Row a of the tile is rotated by 4 ((a >> 2) & 7) columns: the four dword reads of a store lane (anchors 4 a4 .. + 3 of column pp)
+// then fall on bank (pp + 4 (a4 & 7)) % 32 -- two lanes per bank instead of eight -- and the 16-byte writes stay aligned.
+// p % 4 != 0 (no caller of the package): dword loads.
+constexpr int UT_PTS = 128;
+__global__ __launch_bounds__(256, 5) void dense_untranspose_tile_kernel(int o_total, int p, int na, int p_dst, const int32_t *__restrict__ map,
+                                                                     const float *__restrict__ yt, float *__restrict__ y,
+                                                                     const float *__restrict__ bn_scale, const float *__restrict__ bn_shift, float slope) {
+    constexpr int UT_LD = UT_PTS / 16;                                     // 16-byte loads per thread at 64 anchors
+    extern __shared__ float tile[];
+    __shared__ int dst_row[UT_PTS];
+    const int chunks = (p + UT_PTS - 1) / UT_PTS, t = threadIdx.x;
+    // Blocks are dealt round-robin over the 8 XCDs; block x of the grid takes tile (x % 8) (n / 8) + x / 8, so that the tiles of one (o, b)
+    // -- 32 at 4096 points, their rows scattered over one 983 KB slab of Y by the map -- run on ONE XCD at about the same time and the
+    // 128-byte lines that neighbouring 240-byte rows share are completed in one L2 instead of leaving two of them in pieces.  Through the
+    // bench's point order, 128 -> 512 layer: 2.05 -> 1.63 ms (a random permutation: 2.46 -> 1.63; no map: 1.51 -> 1.39).  (The parent
+    // kernel gained nothing from the same mapping: its block shape was the limit, not the scatter.)
+    unsigned bid = blockIdx.x;
+    if (const unsigned n8 = gridDim.x / 8u; bid < 8u * n8) bid = (bid % 8u) * n8 + bid / 8u;
+    const int p0 = (int)(bid % (unsigned)chunks) * UT_PTS, grp_ = (int)(bid / (unsigned)chunks), o = grp_ % o_total, b = grp_ / o_total;
+    const int np = min(UT_PTS, p - p0);
+    if (t < UT_PTS) dst_row[t] = t >= np ? -1 : map ? map[(size_t)b * p + p0 + t] : p0 + t;
+    const size_t a_pitch = (size_t)o_total * p;                            // floats between the anchors of Yt
+    const float *src = yt + ((size_t)b * na * o_total + o) * p + p0;
+    if ((p & 3) == 0) {                                                    // (uniform; np % 4 == 0 then: a 16-byte piece is inside the chunk or outside)
+        f32x4 v[UT_LD];
+#pragma unroll
+        for (int k = 0; k < UT_LD; ++k) {
+            const int i = t + 256 * k, a = i / (UT_PTS / 4), c = 4 * (i % (UT_PTS / 4));
+            if (a < na && c < np) v[k] = *reinterpret_cast<const f32x4 *>(src + (size_t)a * a_pitch + c);
+        }
+#pragma unroll
+        for (int k = 0; k < UT_LD; ++k) {
+            const int i = t + 256 * k, a = i / (UT_PTS / 4), c = 4 * (i % (UT_PTS / 4));
+            if (a < na && c < np) *reinterpret_cast<f32x4 *>(tile + a * UT_PTS + ((c + 4 * ((a >> 2) & 7)) & (UT_PTS - 1))) = v[k];
+        }
+    } else {
+        for (int i = t; i < na * UT_PTS; i += 256) {
+            const int a = i / UT_PTS, c = i % UT_PTS;
+            if (c < np) tile[a * UT_PTS + ((c + 4 * ((a >> 2) & 7)) & (UT_PTS - 1))] = src[(size_t)a * a_pitch + c];
+        }
+    }
+    __syncthreads();
+    // thread (anchor quad a4, row group rr) stores the pieces a4 of the columns rr, rr + RG, ...: consecutive lanes, consecutive 16 bytes
+    const int nq = na >> 2, RG = 256 / nq, a4 = t % nq, rr = t / nq;
+    if (rr >= RG) return;
+    const int rows_dst = map ? p_dst : p, rot = 4 * (a4 & 7);
+    const float *quad = tile + (4 * a4) * UT_PTS;
+    float *rows_y = y + ((size_t)b * o_total + o) * (size_t)rows_dst * na + 4 * a4;
+    float sc = 1.f, sh = 0.f;
+    if (bn_scale != nullptr) { sc = bn_scale[o]; sh = bn_shift[o]; }
+    for (int pp0 = rr; pp0 < np; pp0 += 4 * RG) {
+        f32x4 v[4];
+        int q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {                                      // (past the chunk: the last column again, not stored)
+            const int pp = min(pp0 + u * RG, UT_PTS - 1), c = (pp + rot) & (UT_PTS - 1);
+            q[u] = pp0 + u * RG < np ? dst_row[pp] : -1;
+            v[u] = (f32x4){quad[c], quad[UT_PTS + c], quad[2 * UT_PTS + c], quad[3 * UT_PTS + c]};
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if ((unsigned)q[u] >= (unsigned)rows_dst) continue;            // padding columns of a map, columns past the chunk
+            if (bn_scale != nullptr) {                                     // (uniform) BatchNorm + leaky_relu of channel o on the way out
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { const float w = fmaf(v[u][e], sc, sh); v[u][e] = w > 0.f ? w : w * slope; }
+            }
+            *reinterpret_cast<f32x4 *>(rows_y + (size_t)q[u] * na) = v[u];
+        }
     }
 }
 
@@ -1121,6 +1214,8 @@ extern "C" int eap_so3_dense_split_f32(int b, int m, int l, int na, int seg, int
     if ((m % 32) != 0 || (na % 4) != 0 || na > 64 || (reinterpret_cast<uintptr_t>(src) & 15) || l % seg != 0 ||
         (seg_pitch & 3) != 0 || (colmap == nullptr && seg_pitch < (int64_t)seg * na) || (mapped && ((seg % 16) != 0 || ((l / seg) % 2) != 0)))
         return eap::bad_arg("so3_dense_split: m % 32, na % 4, na <= 64, 16-byte aligned source, whole segments of a 16-byte aligned pitch (mapped: seg % 16, an even number of segments)");
+    // (the split addresses a row's 16-byte pieces with 32 bits; m >= 32 rows of that extent are more than any device holds)
+    if ((colmap ? (int64_t)1 : (int64_t)(l / seg)) * (seg_pitch / 4) > 0x7fffffffLL) return eap::bad_arg("so3_dense_split: a source row of at most 2^31 16-byte pieces");
     hipStream_t s = eap::S(stream);
     const int kb_total = ceil_to(l, KC_BK) / 16;
     float *scale2 = scale + (size_t)b * na * m;
@@ -1129,7 +1224,7 @@ extern "C" int eap_so3_dense_split_f32(int b, int m, int l, int na, int seg, int
                       : eap::run_kernel("so3_dense_split", dense_rowmax_kernel, m, b, 1, dim3(256), 0, s, m, l, na, seg, (long long)(seg_pitch / 4), colmap,
                                         reinterpret_cast<const f32x4 *>(src), scale, scale2);
     if (e) return e;
-    return eap::run_kernel("so3_dense_split", dense_split_kernel<false>, (long long)kb_total * (m / 32) * b, 1, 1, dim3(256), 0, s, b, m, l, na, kb_total, seg, (long long)(seg_pitch / 4),
+    return eap::run_kernel("so3_dense_split", dense_split_kernel<false>, (long long)kb_total * (m / 32) * b * 2, 1, 1, dim3(256), (size_t)na * 1024, s, m, l, na, kb_total, seg, (long long)(seg_pitch / 4),
                            mapped ? 1 : 0, n_rows, colmap, reinterpret_cast<const f32x4 *>(src), scale2, reinterpret_cast<u32x4 *>(planes), SplitBn{nullptr, nullptr, 1.f, 1.f});
 }
 
@@ -1144,6 +1239,7 @@ extern "C" int eap_so3_dense_split_bn_f32(int b, int m, int l, int l_src, int na
     if ((m % 32) != 0 || (na % 4) != 0 || na > 64 || ((reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(act)) & 15) ||
         (colmap != nullptr && ((l & 7) != 0 || (reinterpret_cast<uintptr_t>(colmap) & 15) != 0)) || rowbound == nullptr || coef == nullptr || !(slope > 0.f))
         return eap::bad_arg("so3_dense_split_bn: m % 32, na % 4, na <= 64, 16-byte aligned sources, a bound per row, a positive slope (column map: 16-byte aligned, l % 8)");
+    if ((int64_t)l_src * na / 4 > 0x7fffffffLL) return eap::bad_arg("so3_dense_split_bn: a source row of at most 2^31 16-byte pieces");
     hipStream_t s = eap::S(stream);
     const int kb_total = ceil_to(l, KC_BK) / 16;
     float *scale2 = scale + (size_t)b * na * m;
@@ -1151,10 +1247,33 @@ extern "C" int eap_so3_dense_split_bn_f32(int b, int m, int l, int l_src, int na
                                 scale2))
         return e;
     const int seg = colmap ? l : l_src;
-    return eap::run_kernel("so3_dense_split_bn", dense_split_kernel<true>, (long long)kb_total * (m / 32) * b, 1, 1, dim3(256), 0, s, b, m, l, na, kb_total, seg,
+    return eap::run_kernel("so3_dense_split_bn", dense_split_kernel<true>, (long long)kb_total * (m / 32) * b * 2, 1, 1, dim3(256), (size_t)na * 1024, s, m, l, na, kb_total, seg,
                            (long long)l_src * na / 4, 0, nullptr, colmap, reinterpret_cast<const f32x4 *>(grad), scale2, reinterpret_cast<u32x4 *>(planes),
                            SplitBn{reinterpret_cast<const f32x4 *>(act), coef, slope, 1.0f / slope});
 }
+
+namespace {
+// what the four re-ordering entries ask of their arguments beyond their own: rows of na floats as na / 4 16-byte pieces over a tile of
+// at most 64 anchors, both tensors 16-byte aligned (the 16-byte loads and stores).  Checked before any device call.
+int untranspose_args(const char *what, int o, int p, int na, const float *yt, const float *y) {
+    char buf[256];
+    const char *why = nullptr;
+    if (o <= 0 || p <= 0) why = "o > 0 and p > 0";
+    else if (na <= 0 || (na % 4) != 0) why = "na % 4 == 0 (rows of Y are stored as 16-byte pieces)";
+    else if (na > 64) why = "na <= 64 (the tile of a block)";
+    else if (yt == nullptr || (reinterpret_cast<uintptr_t>(yt) & 15) != 0) why = "yt 16-byte aligned";
+    else if (y == nullptr || (reinterpret_cast<uintptr_t>(y) & 15) != 0) why = "y 16-byte aligned";
+    if (why == nullptr) return 0;
+    snprintf(buf, sizeof(buf), "%s: %s", what, why);
+    return eap::bad_arg(buf);
+}
+
+int untranspose_tile(const char *what, int b, int o, int p, int na, int p_dst, const int32_t *map, const float *yt, float *y, const float *bn_scale,
+                     const float *bn_shift, float slope, eap_stream_t stream) {
+    return eap::run_kernel(what, dense_untranspose_tile_kernel, (long long)eap::cdiv(p, UT_PTS) * o * b, 1, 1, dim3(256), sizeof(float) * (size_t)na * UT_PTS,
+                           eap::S(stream), o, p, na, p_dst, map, yt, y, bn_scale, bn_shift, slope);
+}
+}  // namespace
 
 // eap_so3_dense_untranspose_map_f32 / eap_so3_dense_untranspose_f32 (map null) with y = leaky_relu(bn_scale[o] yt + bn_shift[o], slope) on the
 // way out: the training-mode BatchNorm + activation behind the dense forward without a pass of its own (the moments come from a
@@ -1164,8 +1283,8 @@ extern "C" int eap_so3_dense_untranspose_bnact_f32(int b, int o, int p, int na, 
     if (b <= 0) return 0;
     if (bn_scale == nullptr || bn_shift == nullptr || (map != nullptr && p_dst <= 0) || (map == nullptr && p_dst != p))
         return eap::bad_arg("so3_dense_untranspose_bnact: scale and shift per channel; p_dst = p without a map");
-    return eap::run_kernel("so3_dense_untranspose_bnact", dense_untranspose_kernel, (long long)eap::cdiv(p, 64) * o * b, 1, 1, dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na,
-                           p_dst, map, nullptr, yt, y, nullptr, nullptr, bn_scale, bn_shift, slope);
+    if (int e = untranspose_args("so3_dense_untranspose_bnact", o, p, na, yt, y)) return e;
+    return untranspose_tile("so3_dense_untranspose_bnact", b, o, p, na, p_dst, map, yt, y, bn_scale, bn_shift, slope, stream);
 }
 
 // ldz (dir 0): floats between consecutive (o, k) rows of Z, >= na rp (the columns past na rp are not written)
@@ -1289,8 +1408,11 @@ extern "C" int eap_so3_dense_steps_wide(int b, int p, int ks, int rp, int dir, i
 // psum, psq (may be null): float [o][b * ceil(p / 64)] partial sums of (y - y[0,o,0,0]) and of its square per 64-point chunk
 extern "C" int eap_so3_dense_untranspose_f32(int b, int o, int p, int na, const float *yt, float *y, float *psum, float *psq, eap_stream_t stream) {
     if (b <= 0) return 0;
+    if (int e = untranspose_args("so3_dense_untranspose", o, p, na, yt, y)) return e;
+    if (psum == nullptr) return untranspose_tile("so3_dense_untranspose", b, o, p, na, p, nullptr, yt, y, nullptr, nullptr, 1.f, stream);
+    if (psq == nullptr) return eap::bad_arg("so3_dense_untranspose: both partial arrays or neither");
     return eap::run_kernel("so3_dense_untranspose", dense_untranspose_kernel, (long long)eap::cdiv(p, 64) * o * b, 1, 1, dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na,
-                           p, nullptr, nullptr, yt, y, psum, psum ? psq : nullptr, nullptr, nullptr, 1.f);
+                           p, nullptr, nullptr, yt, y, psum, psq);
 }
 
 // the same re-ordering into a Y [b,o,p_dst,na] that other launches fill too: column pp of cloud b goes to point map[b][pp] (int32 [b,p];
@@ -1299,8 +1421,8 @@ extern "C" int eap_so3_dense_untranspose_map_f32(int b, int o, int p, int na, in
                                                  eap_stream_t stream) {
     if (b <= 0) return 0;
     if (map == nullptr || p_dst <= 0) return eap::bad_arg("so3_dense_untranspose_map: a map, p_dst > 0");
-    return eap::run_kernel("so3_dense_untranspose_map", dense_untranspose_kernel, (long long)eap::cdiv(p, 64) * o * b, 1, 1, dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na,
-                           p_dst, map, nullptr, yt, y, nullptr, nullptr, nullptr, nullptr, 1.f);
+    if (int e = untranspose_args("so3_dense_untranspose_map", o, p, na, yt, y)) return e;
+    return untranspose_tile("so3_dense_untranspose_map", b, o, p, na, p_dst, map, yt, y, nullptr, nullptr, 1.f, stream);
 }
 
 // ... and with the channel moments of eap_so3_dense_untranspose_f32 (over the columns whose map entry is not negative); pivot_pos int32 [1]
@@ -1310,6 +1432,7 @@ extern "C" int eap_so3_dense_untranspose_map_stats_f32(int b, int o, int p, int 
     if (b <= 0) return 0;
     if (map == nullptr || pivot_pos == nullptr || p_dst <= 0 || psum == nullptr || psq == nullptr)
         return eap::bad_arg("so3_dense_untranspose_map_stats: a map, the pivot column, both partial arrays");
+    if (int e = untranspose_args("so3_dense_untranspose_map_stats", o, p, na, yt, y)) return e;
     return eap::run_kernel("so3_dense_untranspose_map_stats", dense_untranspose_kernel, (long long)eap::cdiv(p, 64) * o * b, 1, 1, dim3(256), sizeof(float) * (size_t)na * 65, eap::S(stream), b, o, p, na,
-                           p_dst, map, pivot_pos, yt, y, psum, psq, nullptr, nullptr, 1.f);
+                           p_dst, map, pivot_pos, yt, y, psum, psq);
 }

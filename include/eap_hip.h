@@ -398,6 +398,9 @@ int eap_rows_scatter_f32(int b, int c, int n, int na, int rcap, int rows_ld, con
  *                             map[b,pp] (int32 [b,p]; negative: padding, dropped) -- the rigid parts of posed clouds, one launch each
  *   eap_so3_dense_untranspose_map_stats_f32   ... with the moments of eap_so3_dense_untranspose_f32 (columns whose map entry is >= 0);
  *                             pivot_pos int32 [1] on the device: the column of cloud 0 that is point 0 (the pivot stays Y[0,o,0,0])
+ *                             All four re-ordering entries (these three and eap_so3_dense_untranspose_bnact_f32) move a row of Y as na / 4
+ *                             16-byte pieces through a tile of at most 64 anchors: na % 4 == 0, na <= 64, yt and y 16-byte aligned, else
+ *                             hipErrorInvalidValue with the condition in eap_last_error(), before anything is launched
  * Occupancy-sorted query points (round 6).  The reference's ball query keeps the first nsample hits in index order
  * (grouping_cuda_kernel.cu:L68-113), so a point's list names rows of only 0.45-0.7 of a cloud's 16-row groups; with a cloud's query
  * points sorted by WHICH groups they touch the 0/1 mask of the product is block-sparse and whole k-steps drop out:
