@@ -1,5 +1,7 @@
 """extensions.chamfer_dist -- ChamferFunction / ChamferDistance with the reference's interface
-(extensions/chamfer_dist/__init__.py:L13-45), computed by the HIP kernels in csrc/chamfer.hip."""
+(extensions/chamfer_dist/__init__.py:L13-45), computed by the HIP kernels in csrc/chamfer.hip.  float32 or float64: every result
+comes back in the width of the clouds.  The backward is bit-identical run to run in float64, and in float32 under
+torch.use_deterministic_algorithms(True) (chamfer.backward)."""
 import torch
 
 import chamfer
@@ -52,7 +54,7 @@ def orbit_reconstruction_distances(transformed_pts, ori_pts, hard_one_hot_labels
     chamfer on the chamfer kernels (csrc/chamfer.hip), SURVEY.md 8(f) row 2.
 
     transformed_pts [B,S,A,M,3]  per-slot, per-anchor reconstructions
-    ori_pts         [B,3,N]      the input cloud
+    ori_pts         [B,3,N]      the input cloud (the width of transformed_pts: float32 or float64)
     hard_one_hot_labels [B,N,S]  0/1 point-to-slot assignment
     ->  (minn_dist_ori_to_recon_all_pts [B,S,A,N],  min over M of the unmasked distances
          minn_dist_recon_to_ori_all_pts [B,S,A],    mean over M of the min over N, unmasked
@@ -68,7 +70,7 @@ def orbit_reconstruction_distances(transformed_pts, ori_pts, hard_one_hot_labels
     in_slot = hard_one_hot_labels.transpose(1, 2) >= 0.5                             # [B,S,N]
     # masked: points outside the slot are moved out of reach; the reference's 99999 entries are what
     # an empty slot's minimum sees, hence the clamp
-    far = torch.full_like(ori, 1e4)
+    far = torch.full_like(ori, 1e4)                                                  # (ori's width, like the 99999 below)
     ori_masked = torch.where(in_slot[..., None], ori[:, None].expand(b, s, n, 3), far[:, None].expand(b, s, n, 3))
     ori_masked = ori_masked[:, :, None].expand(b, s, a, n, 3).reshape(b * s * a, n, 3)
     r2o_masked, _ = ChamferFunction.apply(recon, ori_masked)

@@ -646,11 +646,29 @@ int eap_so3_intra_conv_f32(int b, int o, int c, int p, int na, int nt, const flo
  * xyz1 [b,n,3], xyz2 [b,m,3] -> dist1 [b,n], dist2 [b,m], idx1 int32 [b,n], idx2 int32 [b,m]. */
 int eap_chamfer_fwd_f32(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist1,
                         float *dist2, int32_t *idx1, int32_t *idx2, eap_stream_t stream);
+/* the same in float64 (chamfer_cuda.cpp:L22-25, chamfer.cu:L15-171 with the scalar type changed, as the header of the reference's
+ * extensions/chamfer_dist/test.py asks for): one rounding per operation, (dx*dx + dy*dy) + dz*dz, first minimum wins. */
+int eap_chamfer_fwd_f64(int b, int n, int m, const double *xyz1, const double *xyz2, double *dist1,
+                        double *dist2, int32_t *idx1, int32_t *idx2, eap_stream_t stream);
 /* chamfer.backward: chamfer_cuda.cpp:L27-34, chamfer.cu:L173-231.
- * -> gxyz1 [b,n,3], gxyz2 [b,m,3] (zero-initialised by the call). */
+ * -> gxyz1 [b,n,3], gxyz2 [b,m,3] (zero-initialised by the call).  A scatter with float atomicAdd, as the reference's: a point that
+ * several points of the other cloud pick is summed in an order that differs between runs (eap_chamfer_bwd_ordered_* does not). */
 int eap_chamfer_bwd_f32(int b, int n, int m, const float *xyz1, const float *xyz2,
                         const int32_t *idx1, const int32_t *idx2, const float *g1, const float *g2,
                         float *gxyz1, float *gxyz2, eap_stream_t stream);
+/* chamfer.backward (chamfer_cuda.cpp:L27-34, chamfer.cu:L173-231) as a gather with a fixed summation order: no atomics, bit-identical
+ * run to run, every output element written once (no zero-initialisation).  With v1[i] = (g1[i]*2) * (xyz1[i] - xyz2[idx1[i]]) and
+ * v2[j] = (g2[j]*2) * (xyz2[j] - xyz1[idx2[j]]):
+ *   gxyz1[b,i] = ((0 + v1[i]) + sum over j ascending with idx2[b,j] == i of (-v2[j]))
+ *   gxyz2[b,j] = ((0 + sum over i ascending with idx1[b,i] == j of (-v1[i])) + v2[j])
+ * -- the order of a serial run of the reference's two kernel launches.  An index outside its cloud contributes nothing and is not
+ * dereferenced.  O(n * m) index compares per direction (the forward's loop shape). */
+int eap_chamfer_bwd_ordered_f32(int b, int n, int m, const float *xyz1, const float *xyz2,
+                                const int32_t *idx1, const int32_t *idx2, const float *g1, const float *g2,
+                                float *gxyz1, float *gxyz2, eap_stream_t stream);
+int eap_chamfer_bwd_ordered_f64(int b, int n, int m, const double *xyz1, const double *xyz2,
+                                const int32_t *idx1, const int32_t *idx2, const double *g1, const double *g2,
+                                double *gxyz1, double *gxyz2, eap_stream_t stream);
 
 /* ---- block-layer epilogue: BatchNorm2d (batch statistics) + leaky_relu ------------------------- */
 /* SPConvNets/utils/base_so3poseconv.py:L214-221 (`feat = self.norm(x.feats); feat = self.relu(feat)`),
