@@ -1004,6 +1004,67 @@ def bn_act_bwd_apply(gy, x, b, c, n, scale, shift, mean, invstd, k2, k3, slope):
     return gx
 
 
+# ---- the first inter conv layer with its norm, without the conv output (csrc/narrow_conv.hip) -------------------
+# W [o, ck] and the grouped input x [b, ck, n] in the reference layout, ck = C*K <= 32; the conv output is recomputed in every pass
+
+NARROW_CONV_MAX_CK = 32
+
+
+def narrow_conv_takes(o, ck, n):
+    return 1 <= ck <= NARROW_CONV_MAX_CK and o >= 32 and o % 32 == 0 and n % 4 == 0 and n < (1 << 25)
+
+
+def _narrow_partials(x, b, o, n):
+    nseg = int(lib.eap_narrow_conv_segments(_I64(n)))
+    return (torch.empty(o, b * nseg, dtype=torch.float32, device=x.device),
+            torch.empty(o, b * nseg, dtype=torch.float32, device=x.device))
+
+
+def narrow_conv_stats(W, x):
+    """-> (sum, sumsq) of y - pivot per channel (float64 [o]) and pivot (float64 [o]) for y = W x, which is not written"""
+    check_input(W, x)
+    b, ck, n = x.shape
+    o = W.shape[0]
+    ps, pq = _narrow_partials(x, b, o, n)
+    pivot = torch.empty(o, dtype=torch.float32, device=x.device)
+    call('eap_narrow_conv_stats_f32', x, b, o, ck, _I64(n), _ptr(W), _ptr(x), _ptr(pivot), _ptr(ps), _ptr(pq))
+    return ps.sum(1, dtype=torch.float64), pq.sum(1, dtype=torch.float64), pivot.double()
+
+
+def narrow_conv_bnact_fwd(W, x, scale, shift, slope):
+    """-> y' [b, o, n] = leaky_relu(scale (W x) + shift)"""
+    check_input(W, x, scale, shift)
+    b, ck, n = x.shape
+    o = W.shape[0]
+    y = torch.empty(b, o, n, dtype=torch.float32, device=x.device)
+    call('eap_narrow_conv_bnact_fwd_f32', x, b, o, ck, _I64(n), _F32(slope), _ptr(W), _ptr(x), _ptr(scale), _ptr(shift), _ptr(y))
+    return y
+
+
+def narrow_conv_bwd_reduce(gy, x, W, scale, shift, mean, invstd, slope):
+    """-> sum(g), sum(g xhat) per channel, float64 [o]"""
+    check_input(gy, x, W, scale, shift, mean, invstd)
+    b, ck, n = x.shape
+    o = W.shape[0]
+    pg, pgx = _narrow_partials(x, b, o, n)
+    call('eap_narrow_conv_bwd_reduce_f32', x, b, o, ck, _I64(n), _F32(slope), _ptr(gy), _ptr(x), _ptr(W), _ptr(scale), _ptr(shift),
+         _ptr(mean), _ptr(invstd), _ptr(pg), _ptr(pgx))
+    return pg.sum(1, dtype=torch.float64), pgx.sum(1, dtype=torch.float64)
+
+
+def narrow_conv_bwd_dw(gy, x, W, scale, shift, mean, invstd, k2, k3, slope):
+    """-> dW [o, ck] = sum gx x^T with gx = scale g - k2 - xhat k3 never written"""
+    check_input(gy, x, W, scale, shift, mean, invstd, k2, k3)
+    b, ck, n = x.shape
+    o = W.shape[0]
+    nseg = int(lib.eap_narrow_conv_segments(_I64(n)))
+    partial = torch.empty(b * nseg, o, ck, dtype=torch.float32, device=x.device)
+    dW = torch.empty(o, ck, dtype=torch.float32, device=x.device)
+    call('eap_narrow_conv_bwd_dw_f32', x, b, o, ck, _I64(n), _F32(slope), _ptr(gy), _ptr(x), _ptr(W), _ptr(scale), _ptr(shift),
+         _ptr(mean), _ptr(invstd), _ptr(k2), _ptr(k3), _ptr(partial), _ptr(dW))
+    return dW
+
+
 # per-cloud statistics over a point subset (the pose heads' batched per-cloud calls); scale .. k3 are [b, c]
 
 def bn_stats_masked(x, b, c, n, na, mask):

@@ -161,14 +161,15 @@ def conv_norm_act(conv, norm, x, **conv_kwargs):
     InterSO3Conv / InterSO3PoseConv and a BatchNormLeakyReLU -> (inter_idx, inter_w, sample_idx, cloud with the activated
     features).  In inference (norm in eval mode, gradients off) the normalisation and the activation ride in the
     contraction's epilogue -- the feature map is written once, no pass of its own; in training the norm joins the conv's autograd
-    node where the conv runs the dense product; otherwise conv and norm run as usual."""
+    node where the conv runs the dense product, or where it has at most 32 contraction indices and an input without gradient (the
+    first layer: regime 'narrow input'); otherwise conv and norm run as usual."""
     from vgtk.spconv import SphericalPointCloud, SphericalPointCloudPose
     from .functional import TrainEpilogue
     fold = not norm.training and not torch.is_grad_enabled()
     ep = norm.folded() if fold else None
     if ep is None and norm.training and isinstance(norm, BatchNormLeakyReLU) and norm.negative_slope > 0:
-        # training: where the conv runs the dense product the normalisation joins its autograd node (no pass of its own in either
-        # direction, the conv output is never written: vgtk/so3conv/functional.py TrainEpilogue)
+        # training: where the conv runs the dense product, and at the first layer, the normalisation joins its autograd node (no pass of
+        # its own in either direction, the conv output is never written: vgtk/so3conv/functional.py TrainEpilogue)
         ep = TrainEpilogue(norm)
     if ep is not None:
         conv_kwargs = dict(conv_kwargs, epilogue=ep)

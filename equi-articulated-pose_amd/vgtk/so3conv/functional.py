@@ -595,6 +595,8 @@ class TrainEpilogue:
       backward  one reduction pass over (dL/dy', y') -> the gradient behind the norm is formed WHILE it is split into the backward product's
                 planes (never written either).  The pre-activation is recovered from y' (leaky_relu with a positive slope is invertible):
                 the node keeps its output, not the conv output.
+    A conv with at most 32 contraction indices C*K whose input needs no gradient (the first layer) takes the norm into its node too, regime
+    'narrow input' (_forward_narrow): it keeps the grouped input X and recomputes the conv output from it in every pass.
     Otherwise (list kernels, posed parts, ...) `applied` stays False and the caller runs the norm module as a pass of its own.
     A channel whose gamma is exactly 0 has a constant output: its input gradient is exactly 0 either way, its d gamma is reported as 0."""
 
@@ -613,7 +615,8 @@ class TrainEpilogue:
         if norm.running_mean is not None:
             update_running_stats(norm.running_mean, norm.running_var, mean, var, total, norm.momentum)
         gamma = norm.weight.detach().double()
-        scale, shift, _ = affine_from_moments(mean, var, gamma, norm.bias.detach(), norm.eps)
+        scale, shift, invstd = affine_from_moments(mean, var, gamma, norm.bias.detach(), norm.eps)
+        self.stats = (mean, invstd)          # float64 [o]: what a node that recomputes the conv output normalises with in its backward
         inv_gamma = torch.where(gamma == 0, torch.zeros_like(gamma), 1.0 / gamma).float()
         # (copies, not views of the parameters: the backward must see the values this forward normalised with)
         self.saved = (scale, norm.bias.detach().float().clone(), inv_gamma.contiguous(), total)
@@ -1016,6 +1019,43 @@ def _forward_map(feats, W, args, keep, folded):
     return y, x
 
 
+# ---- regime 'narrow input': C*K <= 32 contraction indices, no input gradient, training-mode norm in the node (csrc/narrow_conv.hip) ----
+# The conv output y = W X is a C*K-term dot product per element (24 at the first layer) and 2.7 x the size of X at O = 64: the node keeps
+# X [b, C*K, P*A] (reference layout) and recomputes y in each of its four passes; neither y nor y' is saved, no lists are built, and the
+# only host wait is the one the moments already have (SyncBatchNorm's exchange).
+
+def _forward_narrow(feats, W, args, train_ep):
+    """-> (y' [b,o,p,a], x [b, ck, p*a], bn): grouping as always (identity poses, one rotation per cloud, permuted poses: only the grouping
+    sees them), moments of W X through TrainEpilogue.moments (running statistics, SyncBatchNorm), one pass that writes y'."""
+    idx, rk = args.idx, args.rk
+    b, c, _, na = feats.shape
+    p, ks, o = idx.shape[1], rk.shape[1], W.shape[0]
+    x = _hip.so3_inter_group_fwd(feats, idx, args.gx, rk, args.mult, args.sigma, args.nonident).view(b, c * ks, p * na)
+    s1, s2, pivot = _hip.narrow_conv_stats(W, x)
+    scale, shift, slope = train_ep.moments(s1, s2, pivot, b * p * na)
+    y = _hip.narrow_conv_bnact_fwd(W, x, scale, shift, slope).view(b, o, p, na)
+    train_ep.applied = True
+    mean, invstd = train_ep.stats
+    return y, x, (scale, shift, mean.float(), invstd.float(), train_ep.saved[3], slope, bool(train_ep.norm.sync))
+
+
+def _backward_narrow(gy, W, x, bn, need_w):
+    """-> (gW, d gamma, d beta): one reduction pass over (dL/dy', X), then dW = sum gx X^T with the gradient behind the norm formed in
+    registers (vgtk.so3conv.blocks._BNAct.backward's arithmetic)"""
+    from .blocks import all_reduce_sums
+    scale, shift, mean, invstd, count, slope, sync = bn
+    b, o = gy.shape[0], gy.shape[1]
+    gy = gy.view(b, o, -1)
+    sg, sgx = _hip.narrow_conv_bwd_reduce(gy, x, W, scale, shift, mean, invstd, slope)
+    gW = None
+    if need_w:
+        tg, tgx = all_reduce_sums(sg, sgx, sync=sync)          # whole-batch means (SyncBatchNorm backward)
+        k2 = (scale.double() * tg / count).float()
+        k3 = (scale.double() * tgx / count).float()
+        gW = _hip.narrow_conv_bwd_dw(gy, x, W, scale, shift, mean, invstd, k2, k3, slope)
+    return gW, sgx.float(), sg.float()
+
+
 # ---- the gradient tail: dF and dW from Z --------------------------------------------------------------------------------------------
 # Z [b, o*ks, ldz] holds per row the (referenced row, anchor) pairs of a cloud: rp * na columns, (row, anchor) order from the list kernels,
 # (anchor, row) order (`anchor_major`) from the dense product; ldz >= rp * na is the row pitch.  The two halves are launched in the order
@@ -1261,7 +1301,20 @@ class _InterConv(torch.autograd.Function):
             ctx.W_param = weakref.ref(W_param)
             ctx.save_for_backward(W, x, idx, args.gx, rk, None, nonident, feats, None)
             return y
-        lists_ok = BACKWARD_MODE != 'dx' and _inv_lists_supported(idx, n, na, ks)
+        # at most 32 contraction indices and no gradient into the input (the first layer): nothing the inverse lists could serve -- the
+        # backward is dW alone, straight from the kept X
+        narrow = c * ks <= _hip.NARROW_CONV_MAX_CK and not ctx.needs_input_grad[0]
+        if narrow and train_ep is not None and FUSE_CONV_NORM and _hip.narrow_conv_takes(o, c * ks, p * na):
+            if FORWARD_LOG is not None:
+                FORWARD_LOG.append({'channels': (c, o), 'dense': False, 'parts': None, 'regime': 'narrow input'})
+            y, x, bn = _forward_narrow(feats, W, args, train_ep)
+            wanted = args.grad_mode and any(ctx.needs_input_grad[1:_InterConv.DIFFERENTIABLE])
+            ctx.bn, ctx.conv_args, ctx.head, ctx.layout, ctx.plan = (bn if wanted else None), args, None, 0, None
+            ctx.narrow = True
+            ctx.W_param = weakref.ref(W_param)
+            ctx.save_for_backward(W, x if wanted else None, idx, None, rk, None, None, feats, None)
+            return y
+        lists_ok = BACKWARD_MODE != 'dx' and _inv_lists_supported(idx, n, na, ks) and not narrow
         keep = needs_grad and (not lists_ok or _keep_x_hint(W_param))
         plan = _DensePlan(args, n, o, lists_ok, needs_grad, keep, folded)
         head = plan.head if needs_grad else None
@@ -1293,7 +1346,13 @@ class _InterConv(torch.autograd.Function):
         n = feats.shape[2]
         need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         g_bn_w = g_bn_b = None
-        if args.amap is not None:
+        if getattr(ctx, 'narrow', False):
+            if BACKWARD_LOG is not None:
+                BACKWARD_LOG.append({'channels': (feats.shape[1], W.shape[0]), 'support_rows': n, 'referenced_rows_max': 0,
+                                     'regime': 'narrow input', 'norm': 'in the node'})
+            gF = None
+            gW, g_bn_w, g_bn_b = _backward_narrow(gy, W, x, ctx.bn, need_w)
+        elif args.amap is not None:
             if BACKWARD_LOG is not None:
                 BACKWARD_LOG.append({'channels': (feats.shape[1], W.shape[0]), 'support_rows': n, 'referenced_rows_max': 0, 'regime': 'anchor map'})
             gF, gW = _backward_map(gy, W, feats, x, args, need_f, need_w)

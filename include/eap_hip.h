@@ -738,6 +738,29 @@ int eap_narrow_contract_dx_f32(int b, int o, int c, int64_t n, const float *W, c
 int eap_narrow_contract_dw_slabs(int64_t n);
 int eap_narrow_contract_dw_f32(int b, int o, int c, int64_t n, const float *g, const float *x, float *partial, eap_stream_t stream);
 
+/* ---- first inter conv layer + training-mode BatchNorm + leaky_relu without the conv output (csrc/narrow_conv.hip) -------- */
+/* y[b,o,n] = sum_k W[o,k] x[b,k,n] with ck = C*K <= 32 contraction indices (the 1 -> 64 layer: ck = 24; vgtk/vgtk/so3conv/modules.py:L48-55
+ * followed by `feat = relu(norm(x.feats))`, SPConvNets/utils/base_so3poseconv.py:L205-222) is recomputed from the grouped input x [b, ck, n]
+ * (reference layout, n = P*A) in every pass instead of being stored.  Every entry refuses, before any device call: ck outside 1..32, o not a
+ * multiple of 32, n not a multiple of 4 (or >= 2^25), x / gy / y (and scale / shift of the forward) not 16-byte aligned.
+ * Reductions come as per-block partials [o][b * eap_narrow_conv_segments(n)] for the caller to sum in a fixed order (deterministic). */
+int eap_narrow_conv_segments(int64_t n);
+/* partial sums of (y - pivot_o) and (y - pivot_o)^2; pivot [o] (written) = y[0, o, 0], a function of the data alone */
+int eap_narrow_conv_stats_f32(int b, int o, int ck, int64_t n, const float *W, const float *x, float *pivot, float *psum, float *psq,
+                              eap_stream_t stream);
+/* y' [b,o,n] = leaky_relu(scale[o] * y + shift[o], slope) */
+int eap_narrow_conv_bnact_fwd_f32(int b, int o, int ck, int64_t n, float slope, const float *W, const float *x, const float *scale,
+                                  const float *shift, float *y, eap_stream_t stream);
+/* partial sums of g and g * xhat as eap_bn_act_bwd_reduce_f32 leaves them, from gy = dL/dy' and the recomputed y */
+int eap_narrow_conv_bwd_reduce_f32(int b, int o, int ck, int64_t n, float slope, const float *gy, const float *x, const float *W,
+                                   const float *scale, const float *shift, const float *mean, const float *invstd, float *pg, float *pgx,
+                                   eap_stream_t stream);
+/* dW [o, ck] = sum_{b,n} gx x^T, gx = scale g - k2 - xhat k3 (eap_bn_act_bwd_apply_f32's formula) formed in registers; partial: scratch of
+ * b * eap_narrow_conv_segments(n) slabs of o * ck floats, added in slab order (no float atomics) */
+int eap_narrow_conv_bwd_dw_f32(int b, int o, int ck, int64_t n, float slope, const float *gy, const float *x, const float *W,
+                               const float *scale, const float *shift, const float *mean, const float *invstd, const float *k2,
+                               const float *k3, float *partial, float *dW, eap_stream_t stream);
+
 /* ---- heads on the backbone's [b,c,n,na] feature map ------------------------ */
 /* Anchor attention pooling, InvPPOutBlockOurs.forward (SPConvNets/utils/base_so3conv.py:L905-912):
  * conf[b,n,a] = softmax_a(logits[b,n,a] * temperature), out[b,c,n] = sum_a x[b,c,n,a] conf[b,n,a].  na % 4 == 0, <= 64.
