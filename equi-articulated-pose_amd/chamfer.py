@@ -24,8 +24,7 @@ def forward(xyz1, xyz2):
     d2 = torch.empty(b, m, dtype=xyz1.dtype, device=dev)
     i1 = torch.empty(b, n, dtype=torch.int32, device=dev)
     i2 = torch.empty(b, m, dtype=torch.int32, device=dev)
-    _hip.call('eap_chamfer_fwd_' + sfx, xyz1, b, n, m, _hip._ptr(xyz1), _hip._ptr(xyz2), _hip._ptr(d1), _hip._ptr(d2),
-              _hip._ptr(i1), _hip._ptr(i2))
+    _hip.call('eap_chamfer_fwd_' + sfx, xyz1, b, n, m, xyz1, xyz2, d1, d2, i1, i2)
     return [d1, d2, i1, i2]
 
 
@@ -49,6 +48,6 @@ def backward(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, ordered=None):
     m = xyz2.shape[1]
     g1 = torch.empty_like(xyz1)
     g2 = torch.empty_like(xyz2)
-    _hip.call('eap_chamfer_bwd_ordered_' + sfx if ordered else 'eap_chamfer_bwd_f32', xyz1, b, n, m, _hip._ptr(xyz1), _hip._ptr(xyz2),
-              _hip._ptr(idx1), _hip._ptr(idx2), _hip._ptr(grad_dist1), _hip._ptr(grad_dist2), _hip._ptr(g1), _hip._ptr(g2))
+    _hip.call('eap_chamfer_bwd_ordered_' + sfx if ordered else 'eap_chamfer_bwd_f32', xyz1, b, n, m, xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2,
+              g1, g2)
     return [g1, g2]

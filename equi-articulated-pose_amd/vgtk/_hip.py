@@ -11,6 +11,8 @@ import, and non-device tensors are rejected.
 """
 import ctypes
 import os
+import re
+import types
 import weakref
 
 import torch
@@ -25,14 +27,15 @@ if not os.path.exists(LIB_PATH):
         'This package has no CPU fallback.')
 
 lib = ctypes.CDLL(LIB_PATH)
-lib.eap_last_error.restype = ctypes.c_char_p
-lib.eap_last_kernel.restype = ctypes.c_char_p
-lib.eap_gemm_f32_reduce_workspace.restype = ctypes.c_int64
-lib.eap_so3_inter_group_bwd_workspace.restype = ctypes.c_int64
-lib.eap_inter_zpconv_fwd_workspace.restype = ctypes.c_int64
-lib.eap_inter_zpconv_bwd_workspace.restype = ctypes.c_int64
-lib.eap_inter_zpconv_bwd_hot_workspace.restype = ctypes.c_int64
-lib.eap_bn_act_segments.restype = ctypes.c_int
+
+# ---- typed prototypes, read from the header ---------------------------------------------------------
+# include/eap_hip.h is plain C over a small fixed vocabulary (stated at its top).  Every `ret eap_name(params);` in it becomes one
+# ctypes prototype, abi.<name>: the arity, the 64-bit and float positions and the 64-bit / string returns come from the declaration
+# instead of from wrappers at the call sites, and a declaration outside the vocabulary stops the import.
+
+# (the package carries a link to the header, so a copy of the package directory alone brings it along; the repository's own file otherwise)
+_HEADERS = (os.path.join(_PKG_ROOT, 'include', 'eap_hip.h'), os.path.join(os.path.dirname(_PKG_ROOT), 'include', 'eap_hip.h'))
+HEADER_PATH = next((p for p in _HEADERS if os.path.exists(p)), _HEADERS[-1])
 
 _I64 = ctypes.c_int64
 _F32 = ctypes.c_float
@@ -40,6 +43,62 @@ _F32 = ctypes.c_float
 
 def _ptr(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+class _Pointer:
+    """argtype of a pointer parameter: None (NULL), an int address, a ctypes.c_void_p, or a DEVICE tensor whose element size is the
+    pointee's (width 0, `void *`: any).  Width, not dtype: int32 views travel as `uint32_t *`, float bit patterns as `int32_t *`."""
+    width = 0
+
+    @classmethod
+    def from_param(cls, v):
+        if isinstance(v, torch.Tensor):
+            if cls.width and v.element_size() != cls.width:
+                raise RuntimeError(f'a {v.dtype} tensor ({v.element_size()} bytes per element) for a pointer to {cls.width}-byte elements')
+            if not v.is_cuda:
+                raise RuntimeError('tensor must be a CUDA(HIP) tensor')
+            return ctypes.c_void_p(v.data_ptr())
+        if isinstance(v, ctypes.c_void_p):
+            return v
+        if v is None or isinstance(v, int):
+            return ctypes.c_void_p(v)
+        raise TypeError(f'None, an address, a ctypes.c_void_p or a device tensor expected, not {type(v).__name__}')
+
+
+_POINTERS = {w: type(f'_Pointer{w}', (_Pointer,), {'width': w}) for w in (0, 1, 4, 8)}
+_POINTEES = {'void': 0, 'uint8_t': 1, 'float': 4, 'int32_t': 4, 'uint32_t': 4, 'double': 8, 'int64_t': 8, 'uint64_t': 8}
+_SCALARS = {'int': ctypes.c_int, 'int64_t': _I64, 'float': _F32, 'eap_stream_t': ctypes.c_void_p}
+_RETURNS = {'int': ctypes.c_int, 'int64_t': _I64, 'const char *': ctypes.c_char_p}
+
+
+def _argtype(name, param):
+    m = re.fullmatch(r'(const )?(\w+) ?(\*?) ?\w*', param)
+    const, base, star = m.groups() if m else (None, None, None)
+    if star and base in _POINTEES:
+        return _POINTERS[_POINTEES[base]]
+    if m and not star and not const and base in _SCALARS:
+        return _SCALARS[base]
+    raise ImportError(f'{HEADER_PATH}: {name}: parameter `{param}` is outside the vocabulary the binding accepts')
+
+
+def _bind_header():
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError(f'{HEADER_PATH} not found: the C ABI is bound from its header')
+    text = re.sub(r'/\*.*?\*/', ' ', open(HEADER_PATH).read(), flags=re.S)
+    text = re.sub(r'^\s*#.*$', '', text, flags=re.M)
+    abi = types.SimpleNamespace()
+    for ret, name, params in re.findall(r'([^;{}()]*?)\b(eap_\w+)\s*\(([^()]*)\)\s*;', text):
+        ret, params = ' '.join(ret.split()), [' '.join(p.split()) for p in params.split(',')]
+        if ret not in _RETURNS:
+            raise ImportError(f'{HEADER_PATH}: {name}: return type `{ret}` is outside the vocabulary the binding accepts')
+        argtypes = [] if params == ['void'] else [_argtype(name, p) for p in params]
+        setattr(abi, name, ctypes.CFUNCTYPE(_RETURNS[ret], *argtypes)((name, lib)))
+        if ret != 'int':                 # `lib` stays an untyped handle: only the returns a C `int` would truncate are told to it
+            getattr(lib, name).restype = _RETURNS[ret]
+    return abi
+
+
+abi = _bind_header()
 
 
 def check_input(*tensors):
@@ -62,25 +121,36 @@ def stream_of(t):
 KERNEL_TIMES = None
 
 
+def _invoke(name, args):
+    """abi.<name>(*args) with the argument count checked here (ctypes lets a surplus argument through) and a refused argument reported
+    as the RuntimeError the callers of this package expect, naming the entry and the argument's position."""
+    fn = getattr(abi, name)
+    if len(args) != len(fn.argtypes):
+        raise RuntimeError(f'{name} takes {len(fn.argtypes)} arguments (the stream last), {len(args)} given')
+    try:
+        return fn(*args)
+    except ctypes.ArgumentError as e:
+        raise RuntimeError(f'{name}: {e}') from None
+
+
 def call(name, ref_tensor, *args, tag=None):
-    """Invoke lib.<name>(*args, stream) under the device of `ref_tensor`; raise on error."""
-    fn = getattr(lib, name)
+    """Invoke abi.<name>(*args, stream) under the device of `ref_tensor`; raise on error."""
     with torch.cuda.device(ref_tensor.device):
         if KERNEL_TIMES is not None:
             stream = torch.cuda.current_stream(ref_tensor.device)
             e0 = torch.cuda.Event(enable_timing=True)
             e1 = torch.cuda.Event(enable_timing=True)
-            lib.eap_last_kernel()        # (clear)
+            abi.eap_last_kernel()        # (clear)
             e0.record(stream)
-            rc = fn(*args, stream_of(ref_tensor))
+            rc = _invoke(name, args + (stream_of(ref_tensor),))
             e1.record(stream)
             if tag is not None:          # the HIP kernel (with its template arguments) this entry just launched
-                tag = dict(tag, kernel=lib.eap_last_kernel().decode() or name)
+                tag = dict(tag, kernel=abi.eap_last_kernel().decode() or name)
             KERNEL_TIMES.append((name, tag, e0, e1))
         else:
-            rc = fn(*args, stream_of(ref_tensor))
+            rc = _invoke(name, args + (stream_of(ref_tensor),))
     if rc != 0:
-        raise RuntimeError(f'{name} failed (hip error {rc}): {lib.eap_last_error().decode()}')
+        raise RuntimeError(f'{name} failed (hip error {rc}): {abi.eap_last_error().decode()}')
 
 
 def suffix(t):
@@ -95,14 +165,11 @@ def suffix(t):
 
 # csrc/gemm_dma_f32.hip (DMA-fed three-stage ring) serves every GEMM whose operands it can take (K a multiple of 16,
 # 16-byte aligned rows); csrc/gemm_f32.hip the rest (first layer K = 24, blocked intermediates, odd shapes).
-lib.eap_gemm_dma_f32_reduce_workspace.restype = ctypes.c_int64
-lib.eap_gemm_skinny_reduce_workspace.restype = ctypes.c_int64
-lib.eap_gemm_bf16x3_reduce_workspace.restype = ctypes.c_int64
 
 
 def _dma_ok(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB):
-    return bool(lib.eap_gemm_dma_f32_supported(int(transA), int(transB), M, N, K, _ptr(A), _I64(lda), _I64(strideA),
-                                               _ptr(B), _I64(ldb), _I64(strideB)))
+    return bool(abi.eap_gemm_dma_f32_supported(int(transA), int(transB), M, N, K, A, lda, strideA,
+                                               B, ldb, strideB))
 
 
 # Contractions whose A operand is shared by the batch (the inter conv's forward contraction on the transposed
@@ -140,7 +207,7 @@ def absmax_rows(t, batch, rows, cols, ld, stride):
     if not _pieces_ok(t, cols, ld, stride):
         return None
     out = torch.empty(batch, rows, dtype=torch.int32, device=t.device)
-    call('eap_absmax_rows_f32', t, _ptr(t), batch, rows, cols, _I64(ld), _I64(stride), _ptr(out))
+    call('eap_absmax_rows_f32', t, t, batch, rows, cols, ld, stride, out)
     return out
 
 
@@ -149,7 +216,7 @@ def absmax_colgroups(t, batch, rows, cols, ld, stride, grp):
     if not _pieces_ok(t, cols, ld, stride, grp) or cols % grp:
         return None
     out = torch.empty(batch, cols // grp, dtype=torch.int32, device=t.device)
-    call('eap_absmax_colgroups_f32', t, _ptr(t), batch, rows, cols, _I64(ld), _I64(stride), grp, _ptr(out))
+    call('eap_absmax_colgroups_f32', t, t, batch, rows, cols, ld, stride, grp, out)
     return out
 
 
@@ -161,7 +228,7 @@ def so3_grouped_bound(feats, idx):
     if pm is None:
         return None
     out = torch.empty(b, idx.shape[1], dtype=torch.int32, device=feats.device)
-    call('eap_so3_grouped_bound_f32', feats, b, idx.shape[1], idx.shape[2], n, _ptr(pm), _ptr(idx), _ptr(out))
+    call('eap_so3_grouped_bound_f32', feats, b, idx.shape[1], idx.shape[2], n, pm, idx, out)
     return out
 
 
@@ -189,14 +256,13 @@ def _gemm_split(transB, M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, batch
     not qualify (nothing launched)."""
     tb = int(bool(transB))
     split = 'eap_gemm_bf16x3_f32' if tb else 'eap_gemm_bf16x3_nn_f32'
-    if not getattr(lib, split + '_supported')(M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB)):
+    if not getattr(abi, split + '_supported')(M, N, K, A, lda, B, ldb, strideB):
         return False
-    ops = (M, N, K, _ptr(A), _I64(lda), _ptr(B), _I64(ldb), _I64(strideB), _ptr(C), _I64(ldc), _I64(strideC), batch)
-    ep = (None, None, _F32(0.0), None, _I64(0)) if epilogue is None else \
-        (_ptr(epilogue[0]), _ptr(epilogue[1]), _F32(epilogue[2]), _ptr(epilogue[3]), _I64(strideC))
+    ops = (M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, batch)
+    ep = (None, None, 0.0, None, 0) if epilogue is None else (*epilogue, strideC)
     two = _planes2(tb, M, N, K, A, lda, batch, B, ldb, strideB, b_bound)
     if two is not None:
-        call('eap_gemm_f16x2_f32', C, tb, *ops, _ptr(two[0]), _ptr(two[1]), two[2], _F32(two[3]), *ep, tag=tag)
+        call('eap_gemm_f16x2_f32', C, tb, *ops, two[0], two[1], two[2], two[3], *ep, tag=tag)
     elif epilogue is None:
         call(split, C, *ops, tag=tag)
     else:
@@ -213,11 +279,10 @@ def gemm(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, stri
             _gemm_split(transB, M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, batch, b_bound, tag):
         return
     if not b_blocked and _dma_ok(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB):
-        call('eap_gemm_dma_f32', C, int(transA), int(transB), M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb),
-             _I64(strideB), _ptr(C), _I64(ldc), _I64(strideC), batch, tag=tag)
+        call('eap_gemm_dma_f32', C, int(transA), int(transB), M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch, tag=tag)
         return
-    call('eap_gemm_f32_xb' if b_blocked else 'eap_gemm_f32', C, int(transA), int(transB), M, N, K, _ptr(A), _I64(lda), _I64(strideA),
-         _ptr(B), _I64((N if transB else K) if b_blocked else ldb), _I64(strideB), _ptr(C), _I64(ldc), _I64(strideC), batch, tag=tag)
+    call('eap_gemm_f32_xb' if b_blocked else 'eap_gemm_f32', C, int(transA), int(transB), M, N, K, A, lda, strideA, B,
+         (N if transB else K) if b_blocked else ldb, strideB, C, ldc, strideC, batch, tag=tag)
 
 
 def gemm_epilogue(transB, M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, batch, scale, shift, slope, residual=None, b_bound=None):
@@ -231,23 +296,23 @@ def gemm_epilogue(transB, M, N, K, A, lda, B, ldb, strideB, C, ldc, strideC, bat
 
 def gemm_reduce(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, batch, b_blocked=False):
     tag = {'flops': 2.0 * M * N * K * batch, 'shape': ('gemm_reduce', int(transA), int(transB), M, N, K, batch)}
-    ops = (M, N, K, _ptr(A), _I64(lda), _I64(strideA), _ptr(B), _I64(ldb), _I64(strideB))
+    ops = (M, N, K, A, lda, strideA, B, ldb, strideB)
     nt = not b_blocked and not transA and transB
     lead = (int(transA), int(transB))
     # (the predicate never sees C, whose float4 stores the entry requires 16-byte aligned: checked here, so such a C falls through)
-    if SPLIT_BF16_CONTRACTION and nt and C.data_ptr() % 16 == 0 and lib.eap_gemm_bf16x3_reduce_f32_supported(*ops, _I64(ldc)):
-        name, ws_words, lead = 'eap_gemm_bf16x3_reduce_f32', lib.eap_gemm_bf16x3_reduce_workspace, ()      # ('nt' only: no transposition flags)
-    elif nt and lib.eap_gemm_skinny_reduce_f32_supported(*ops):
+    if SPLIT_BF16_CONTRACTION and nt and C.data_ptr() % 16 == 0 and abi.eap_gemm_bf16x3_reduce_f32_supported(*ops, ldc):
+        name, ws_words, lead = 'eap_gemm_bf16x3_reduce_f32', abi.eap_gemm_bf16x3_reduce_workspace, ()      # ('nt' only: no transposition flags)
+    elif nt and abi.eap_gemm_skinny_reduce_f32_supported(*ops):
         # a small output over a long contraction (the first layer's weight gradient): streaming reduction, csrc/gemm_skinny.hip
-        name, ws_words, lead = 'eap_gemm_skinny_reduce_f32', lib.eap_gemm_skinny_reduce_workspace, ()
+        name, ws_words, lead = 'eap_gemm_skinny_reduce_f32', abi.eap_gemm_skinny_reduce_workspace, ()
     elif not b_blocked and _dma_ok(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB):
-        name, ws_words = 'eap_gemm_dma_f32_reduce', lib.eap_gemm_dma_f32_reduce_workspace
+        name, ws_words = 'eap_gemm_dma_f32_reduce', abi.eap_gemm_dma_f32_reduce_workspace
     else:
-        name, ws_words = 'eap_gemm_f32_reduce_xb' if b_blocked else 'eap_gemm_f32_reduce', lib.eap_gemm_f32_reduce_workspace
+        name, ws_words = 'eap_gemm_f32_reduce_xb' if b_blocked else 'eap_gemm_f32_reduce', abi.eap_gemm_f32_reduce_workspace
         if b_blocked:
-            ops = ops[:7] + (_I64(N if transB else K),) + ops[8:]
+            ops = ops[:7] + (N if transB else K,) + ops[8:]
     ws = torch.empty(max(int(ws_words(M, N, K, batch)), 1), dtype=torch.float32, device=C.device)
-    call(name, C, *lead, *ops, _ptr(C), _I64(ldc), batch, _ptr(ws), tag=tag)
+    call(name, C, *lead, *ops, C, ldc, batch, ws, tag=tag)
 
 
 # ---- the same products stated as tensor views -----------------------------------------------------
@@ -315,7 +380,7 @@ def matmul_reduce_takes_split(A, B, out):
     kernel's own predicate (all gemm_reduce_takes_split asked), that the product is 'nt' and that out is 16-byte aligned."""
     ta, tb, M, N, K, lda, sa, ldb, sb, ldc, _, _ = _product(A, B, out, reduce=True)
     return bool(SPLIT_BF16_CONTRACTION and not ta and tb and out.data_ptr() % 16 == 0 and
-                lib.eap_gemm_bf16x3_reduce_f32_supported(M, N, K, _ptr(A), _I64(lda), _I64(sa), _ptr(B), _I64(ldb), _I64(sb), _I64(ldc)))
+                abi.eap_gemm_bf16x3_reduce_f32_supported(M, N, K, A, lda, sa, B, ldb, sb, ldc))
 
 
 def matmul_epilogue(A, B, out, scale, shift, slope, residual=None, b_bound=None):
@@ -340,8 +405,7 @@ def so3_prep(q_xyz, s_xyz, idx, q_pose, s_pose, anchors, identity_anchor):
     nn = idx.shape[2]
     gx = torch.empty(b, p, nn, 4, dtype=torch.float32, device=q_xyz.device)
     nonident = torch.empty(b, dtype=torch.int32, device=q_xyz.device)
-    call('eap_so3_prep_f32', gx, b, p, n, nn, anchors.shape[0], _ptr(q_xyz), _ptr(s_xyz), _ptr(idx),
-         _ptr(q_pose), _ptr(s_pose), _ptr(anchors), int(identity_anchor), _ptr(gx), _ptr(nonident))
+    call('eap_so3_prep_f32', gx, b, p, n, nn, anchors.shape[0], q_xyz, s_xyz, idx, q_pose, s_pose, anchors, int(identity_anchor), gx, nonident)
     return gx, nonident
 
 
@@ -349,7 +413,7 @@ def so3_inter_weights(gx, rk, sigma):
     b, p, nn, _ = gx.shape
     na, ks, _ = rk.shape
     w = torch.empty(b, p, na, ks, nn, dtype=torch.float32, device=gx.device)
-    call('eap_so3_inter_weights_f32', w, b, p, nn, na, ks, _F32(sigma), _ptr(gx), _ptr(rk), _ptr(w))
+    call('eap_so3_inter_weights_f32', w, b, p, nn, na, ks, sigma, gx, rk, w)
     return w
 
 
@@ -357,11 +421,10 @@ def so3_anchor_perm(gx, mult):
     b, p, nn, _ = gx.shape
     na = mult.shape[0]
     perm = torch.empty(b, p, nn, na, dtype=torch.int64, device=gx.device)
-    call('eap_so3_anchor_perm', gx, b, p, nn, na, _ptr(gx), _ptr(mult), _ptr(perm))
+    call('eap_so3_anchor_perm', gx, b, p, nn, na, gx, mult, perm)
     return perm
 
 
-lib.eap_so3_inter_group_bwd_map_workspace.restype = ctypes.c_int64
 
 
 def so3_anchor_map(idx, q_pose, s_pose, anchors):
@@ -374,8 +437,7 @@ def so3_anchor_map(idx, q_pose, s_pose, anchors):
         raise RuntimeError('so3_anchor_map: poses must be [b,p,4,4] (query) and [b,n,4,4] (support)')
     amap = torch.empty(b, p, nn, na, dtype=torch.uint8, device=idx.device)
     nontrivial = torch.empty(b, dtype=torch.int32, device=idx.device)
-    call('eap_so3_anchor_map_f32', amap, b, p, s_pose.shape[1], nn, na, _ptr(idx), _ptr(q_pose), _ptr(s_pose), _ptr(anchors), _ptr(amap),
-         _ptr(nontrivial))
+    call('eap_so3_anchor_map_f32', amap, b, p, s_pose.shape[1], nn, na, idx, q_pose, s_pose, anchors, amap, nontrivial)
     return amap, nontrivial
 
 
@@ -391,8 +453,8 @@ def so3_inter_group_fwd_map(feats, idx, gx, rk, amap, sigma):
     ks = rk.shape[1]
     _check_map(amap, idx, na)
     out = torch.empty(b, c, ks, p, na, dtype=torch.float32, device=feats.device)
-    call('eap_so3_inter_group_fwd_map_f32', out, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(feats), _ptr(idx), _ptr(gx), _ptr(rk), _ptr(amap),
-         _ptr(out), tag={'flops': 2.0 * b * c * ks * p * nn * na, 'shape': ('group_fwd_map', b, c, p, nn, na, ks)})
+    call('eap_so3_inter_group_fwd_map_f32', out, b, c, p, n, nn, na, ks, sigma, feats, idx, gx, rk, amap, out,
+         tag={'flops': 2.0 * b * c * ks * p * nn * na, 'shape': ('group_fwd_map', b, c, p, nn, na, ks)})
     return out
 
 
@@ -402,21 +464,20 @@ def so3_inter_group_bwd_map(gout, idx, gx, rk, amap, sigma, n):
     nn = idx.shape[2]
     _check_map(amap, idx, na)
     gfeats = torch.empty(b, c, n, na, dtype=torch.float32, device=gout.device)
-    ws = torch.empty(max(1, int(lib.eap_so3_inter_group_bwd_map_workspace(b, c, p, n, na))), dtype=torch.float32, device=gout.device)
-    call('eap_so3_inter_group_bwd_map_f32', gfeats, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(gout), _ptr(idx), _ptr(gx), _ptr(rk), _ptr(amap),
-         _ptr(gfeats), _ptr(ws))
+    ws = torch.empty(max(1, int(abi.eap_so3_inter_group_bwd_map_workspace(b, c, p, n, na))), dtype=torch.float32, device=gout.device)
+    call('eap_so3_inter_group_bwd_map_f32', gfeats, b, c, p, n, nn, na, ks, sigma, gout, idx, gx, rk, amap, gfeats, ws)
     return gfeats
 
 
 def so3_inter_group_fwd_can_block(c, n, na, ks, has_mult, has_flag):
-    return bool(lib.eap_so3_inter_group_fwd_can_block(c, n, na, ks, int(has_mult), int(has_flag)))
+    return bool(abi.eap_so3_inter_group_fwd_can_block(c, n, na, ks, int(has_mult), int(has_flag)))
 
 
 _TP_COLUMNS = {}
 
 
 def so3_group_fwd_tp_takes(c, na, ks):
-    return bool(lib.eap_so3_group_fwd_tp_takes(int(c), int(na), int(ks)))
+    return bool(abi.eap_so3_group_fwd_tp_takes(int(c), int(na), int(ks)))
 
 
 def so3_group_fwd_tp_columns(c, ks, device):
@@ -427,8 +488,8 @@ def so3_group_fwd_tp_columns(c, ks, device):
     if hit is None:
         import numpy as np
         perm = np.empty(c * ks, np.int32)
-        if lib.eap_so3_group_fwd_tp_columns(int(c), int(ks), perm.ctypes.data_as(ctypes.c_void_p)) != 0:
-            raise RuntimeError(lib.eap_last_error().decode())
+        if abi.eap_so3_group_fwd_tp_columns(int(c), int(ks), perm.ctypes.data_as(ctypes.c_void_p)) != 0:
+            raise RuntimeError(abi.eap_last_error().decode())
         hit = _TP_COLUMNS[key] = torch.from_numpy(perm.astype(np.int64)).to(device)
     return hit
 
@@ -449,21 +510,18 @@ def so3_inter_group_fwd(feats, idx, gx, rk, mult, sigma, nonident=None, blocked=
         # clouds with anchor permutations on the two-tile kernel (csrc/so3_inter_lists2.hip, PERM): their features with a coset-major
         # anchor axis, the per-entry words of (idx, gx) prepared once; clouds whose flag is 0 cost three empty launches
         feats_c = torch.empty_like(feats)
-        call('eap_anchor_reorder_clouds_f32', feats, b, _I64(c * n), na, _ptr(feats), _ptr(coset[0]), _ptr(nonident), _ptr(feats_c))
+        call('eap_anchor_reorder_clouds_f32', feats, b, c * n, na, feats, coset[0], nonident, feats_c)
         ent_pc, ent_gx2 = so3_perm_entries(idx.view(b, p * nn), gx.view(b, p * nn, 4), coset[1], None, 0, na, n, nonident)
-        call('eap_so3_inter_group_fwd_perm2_t_f32', out, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(feats), _ptr(feats_c), _ptr(idx), _ptr(gx),
-             _ptr(ent_pc), _ptr(ent_gx2), _ptr(rk), _ptr(coset[0]), _ptr(nonident), int(bool(store_order)), _ptr(out),
-             tag=tag('group_fwd_perm2'))
+        call('eap_so3_inter_group_fwd_perm2_t_f32', out, b, c, p, n, nn, na, ks, sigma, feats, feats_c, idx, gx, ent_pc, ent_gx2, rk, coset[0],
+             nonident, int(bool(store_order)), out, tag=tag('group_fwd_perm2'))
         return out
     if store_order:
         if mult is not None or int(blocked) != 2:
             raise RuntimeError('store-order columns: transposed layout, clouds without permutation (or the coset tables for the flagged ones)')
-        call('eap_so3_inter_group_fwd_tp_f32', out, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(feats), _ptr(idx), _ptr(gx), _ptr(rk), _ptr(out),
-             tag=tag('group_fwd_tp'))
+        call('eap_so3_inter_group_fwd_tp_f32', out, b, c, p, n, nn, na, ks, sigma, feats, idx, gx, rk, out, tag=tag('group_fwd_tp'))
         return out
-    call({0: 'eap_so3_inter_group_fwd_f32', 1: 'eap_so3_inter_group_fwd_xb_f32', 2: 'eap_so3_inter_group_fwd_t_f32'}[int(blocked)], out, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(feats), _ptr(idx),
-         _ptr(gx), _ptr(rk), _ptr(mult), _ptr(nonident), _ptr(out),
-         tag=tag('group_fwd'))
+    call({0: 'eap_so3_inter_group_fwd_f32', 1: 'eap_so3_inter_group_fwd_xb_f32', 2: 'eap_so3_inter_group_fwd_t_f32'}[int(blocked)], out, b, c, p, n,
+         nn, na, ks, sigma, feats, idx, gx, rk, mult, nonident, out, tag=tag('group_fwd'))
     return out
 
 
@@ -475,13 +533,11 @@ def so3_inter_group_bwd(gout, idx, gx, rk, mult, sigma, n, identity_anchor=0):
     nn = idx.shape[2]
     gfeats = torch.empty(b, c, n, na, dtype=torch.float32, device=gout.device)
     if ks <= 24 and na % 4 == 0 and not FORCE_ATOMIC_BWD:
-        ws = torch.empty(int(lib.eap_so3_inter_group_bwd_workspace(b, c, p, n, na)), dtype=torch.float32,
+        ws = torch.empty(int(abi.eap_so3_inter_group_bwd_workspace(b, c, p, n, na)), dtype=torch.float32,
                          device=gout.device)
-        call('eap_so3_inter_group_bwd_slab_f32', gfeats, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(gout), _ptr(idx),
-             _ptr(gx), _ptr(rk), _ptr(mult), int(identity_anchor), _ptr(gfeats), _ptr(ws))
+        call('eap_so3_inter_group_bwd_slab_f32', gfeats, b, c, p, n, nn, na, ks, sigma, gout, idx, gx, rk, mult, int(identity_anchor), gfeats, ws)
         return gfeats
-    call('eap_so3_inter_group_bwd_f32', gfeats, b, c, p, n, nn, na, ks, _F32(sigma), _ptr(gout), _ptr(idx),
-         _ptr(gx), _ptr(rk), _ptr(mult), _ptr(gfeats))
+    call('eap_so3_inter_group_bwd_f32', gfeats, b, c, p, n, nn, na, ks, sigma, gout, idx, gx, rk, mult, gfeats)
     return gfeats
 
 
@@ -489,14 +545,14 @@ def so3_intra_group_fwd(feats, intra_idx):
     b, c, p, na = feats.shape
     t = intra_idx.shape[1]
     out = torch.empty(b, c, t, p, na, dtype=torch.float32, device=feats.device)
-    call('eap_so3_intra_group_fwd_f32', out, b, c, p, na, t, _ptr(feats), _ptr(intra_idx), _ptr(out))
+    call('eap_so3_intra_group_fwd_f32', out, b, c, p, na, t, feats, intra_idx, out)
     return out
 
 
 def so3_intra_group_bwd(gout, intra_idx):
     b, c, t, p, na = gout.shape
     gfeats = torch.empty(b, c, p, na, dtype=torch.float32, device=gout.device)
-    call('eap_so3_intra_group_bwd_f32', gfeats, b, c, p, na, t, _ptr(gout), _ptr(intra_idx), _ptr(gfeats))
+    call('eap_so3_intra_group_bwd_f32', gfeats, b, c, p, na, t, gout, intra_idx, gfeats)
     return gfeats
 
 
@@ -510,15 +566,15 @@ def so3_inter_group_inv(gy, rows, off, cnt, ent_p, ent_gx, rk, multinv, sigma, n
     if multinv is not None and coset is not None:
         if na % 8 == 4:          # the kernel's DMA loader copies rows as they are: re-order the anchor axis once (csrc/so3_inter_inv.hip)
             gyc = torch.empty_like(gy)
-            call('eap_anchor_reorder_f32', gy, _I64(b * o * p), na, _ptr(gy), _ptr(coset[0]), _ptr(gyc))
+            call('eap_anchor_reorder_f32', gy, b * o * p, na, gy, coset[0], gyc)
             gy = gyc
-        call('eap_so3_inter_group_inv_coset_f32', z, b, o, p, nn, na, ks, rcap, _F32(sigma), _ptr(gy), _ptr(rows), _ptr(off),
-             _ptr(cnt), _ptr(ent_p), _ptr(ent_gx), _ptr(rk), _ptr(multinv), _ptr(anchors), int(identity_anchor), _ptr(coset[0]), _ptr(coset[1]),
-             _ptr(z), tag={'flops': 2.0 * b * o * ks * p * nn * na, 'shape': ('group_inv_coset', b, o, p, nn, na, ks, rcap)})
+        call('eap_so3_inter_group_inv_coset_f32', z, b, o, p, nn, na, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, multinv, anchors,
+             int(identity_anchor), coset[0], coset[1], z, tag={'flops': 2.0 * b * o * ks * p * nn * na, 'shape': ('group_inv_coset', b, o, p, nn, na,
+             ks, rcap)})
         return z
-    call('eap_so3_inter_group_inv_f32', z, b, o, p, nn, na, ks, rcap, _F32(sigma), _ptr(gy), _ptr(rows), _ptr(off),
-         _ptr(cnt), _ptr(ent_p), _ptr(ent_gx), _ptr(rk), _ptr(multinv), _ptr(anchors if multinv is not None else None), int(identity_anchor), _ptr(z),
-         tag={'flops': 2.0 * b * o * ks * p * nn * na, 'shape': ('group_inv', b, o, p, nn, na, ks, rcap)})
+    call('eap_so3_inter_group_inv_f32', z, b, o, p, nn, na, ks, rcap, sigma, gy, rows, off, cnt, ent_p, ent_gx, rk, multinv,
+         anchors if multinv is not None else None, int(identity_anchor), z, tag={'flops': 2.0 * b * o * ks * p * nn * na, 'shape': ('group_inv', b, o,
+         p, nn, na, ks, rcap)})
     return z
 
 
@@ -527,12 +583,12 @@ def anchor_reorder(t, order):
     t = t.contiguous()
     na = t.shape[-1]
     out = torch.empty_like(t)
-    call('eap_anchor_reorder_f32', t, _I64(t.numel() // na), na, _ptr(t), _ptr(order), _ptr(out))
+    call('eap_anchor_reorder_f32', t, t.numel() // na, na, t, order, out)
     return out
 
 
 def so3_group_perm_lists2_takes(channels, na, ks, n_support):
-    return bool(lib.eap_so3_group_perm_lists2_takes(int(channels), int(na), int(ks), int(n_support)))
+    return bool(abi.eap_so3_group_perm_lists2_takes(int(channels), int(na), int(ks), int(n_support)))
 
 
 def so3_perm_entries(ent_p, ent_gx, code, anchors, identity_anchor, na, n_support, nonident=None):
@@ -541,8 +597,8 @@ def so3_perm_entries(ent_p, ent_gx, code, anchors, identity_anchor, na, n_suppor
     ent_pc = torch.empty(b, per, 4, 4, dtype=torch.int32, device=ent_p.device)
     ent_gx2 = torch.empty(b, per, 4, dtype=torch.float32, device=ent_p.device)
     anchors = anchors.contiguous() if anchors is not None else None
-    call('eap_so3_perm_entries_f32', ent_p, b, per, int(na), int(n_support), _ptr(ent_p), _ptr(ent_gx), _ptr(code),
-         _ptr(anchors), int(identity_anchor), _ptr(nonident), _ptr(ent_pc), _ptr(ent_gx2))
+    call('eap_so3_perm_entries_f32', ent_p, b, per, int(na), int(n_support), ent_p, ent_gx, code, anchors, int(identity_anchor), nonident, ent_pc,
+         ent_gx2)
     return ent_pc, ent_gx2
 
 
@@ -551,8 +607,7 @@ def so3_inter_group_inv_perm2(gy_c, rows, off, cnt, ent_pc, ent_gx2, rk, order, 
     b, o, p, na = gy_c.shape
     rcap, ks = rows.shape[1], rk.shape[1]
     z = torch.empty(b, o, ks, rcap, na, dtype=torch.float32, device=gy_c.device)
-    call('eap_so3_inter_group_inv_perm2_f32', z, b, o, p, nn, na, ks, rcap, _F32(sigma), _ptr(gy_c), _ptr(rows), _ptr(off), _ptr(cnt),
-         _ptr(ent_pc), _ptr(ent_gx2), _ptr(rk), _ptr(order), _ptr(z),
+    call('eap_so3_inter_group_inv_perm2_f32', z, b, o, p, nn, na, ks, rcap, sigma, gy_c, rows, off, cnt, ent_pc, ent_gx2, rk, order, z,
          tag={'flops': 2.0 * b * o * ks * p * nn * na, 'shape': ('group_inv_perm2', b, o, p, nn, na, ks, rcap)})
     return z
 
@@ -564,7 +619,7 @@ def inv_lists_rows(idx, n):
     counts = torch.empty(b, n, dtype=torch.int32, device=dev)
     rows, off, cnt = torch.empty_like(counts), torch.empty_like(counts), torch.empty_like(counts)
     n_rows = torch.empty(b, dtype=torch.int32, device=dev)
-    call('eap_inv_lists_rows', idx, b, p, n, nn, _ptr(idx), _ptr(counts), _ptr(rows), _ptr(off), _ptr(cnt), _ptr(n_rows))
+    call('eap_inv_lists_rows', idx, b, p, n, nn, idx, counts, rows, off, cnt, n_rows)
     return rows, off, cnt, n_rows
 
 
@@ -574,7 +629,7 @@ def inv_lists_fill(idx, gx, rows, off, rcap):
     n = rows.shape[1]
     ent_p = torch.empty(b, p * nn, dtype=torch.int32, device=idx.device)
     ent_gx = torch.empty(b, p * nn, 4, dtype=torch.float32, device=idx.device)
-    call('eap_inv_lists_fill', idx, b, p, n, nn, int(rcap), _ptr(idx), _ptr(gx), _ptr(rows), _ptr(off), _ptr(ent_p), _ptr(ent_gx))
+    call('eap_inv_lists_fill', idx, b, p, n, nn, int(rcap), idx, gx, rows, off, ent_p, ent_gx)
     return ent_p, ent_gx
 
 
@@ -582,7 +637,7 @@ def rows_gather(src, rows, rcap):
     """src [b,c,n,na], rows int32 [b,>=rcap] -> [b,c,rcap,na] (zeros for rows < 0)."""
     b, c, n, na = src.shape
     dst = torch.empty(b, c, rcap, na, dtype=torch.float32, device=src.device)
-    call('eap_rows_gather_f32', src, b, c, n, na, int(rcap), rows.stride(0), _ptr(rows), _ptr(src), _ptr(dst))
+    call('eap_rows_gather_f32', src, b, c, n, na, int(rcap), rows.stride(0), rows, src, dst)
     return dst
 
 
@@ -590,21 +645,20 @@ def rows_scatter(src, rows, n):
     """src [b,c,rcap,na] -> [b,c,n,na], zero except the rows named by `rows`."""
     b, c, rcap, na = src.shape
     dst = torch.empty(b, c, n, na, dtype=torch.float32, device=src.device)
-    call('eap_rows_scatter_f32', src, b, c, n, na, int(rcap), rows.stride(0), _ptr(rows), _ptr(src), _ptr(dst))
+    call('eap_rows_scatter_f32', src, b, c, n, na, int(rcap), rows.stride(0), rows, src, dst)
     return dst
 
 
 # ---- block-layer epilogue (csrc/bn_act.hip) -------------------------------------------------------
 
 # ---- the inter conv re-associated over its referenced rows as a dense product (csrc/so3_dense.hip) ----------------------
-lib.eap_so3_dense_mask_words.restype = ctypes.c_int64
 
 
 def so3_dense_supported(p, na, ks, rp, o):
-    return bool(lib.eap_so3_dense_supported(int(p), int(na), int(ks), int(rp), int(o)))
+    return bool(abi.eap_so3_dense_supported(int(p), int(na), int(ks), int(rp), int(o)))
 
 
-DENSE_MAX_ROWS = int(lib.eap_so3_dense_max_rows())        # 1024: the wide tables (32 membership words per point, int64 keys)
+DENSE_MAX_ROWS = int(abi.eap_so3_dense_max_rows())        # 1024: the wide tables (32 membership words per point, int64 keys)
 DENSE_NARROW_ROWS = 512                                   # up to here the 16-word tables and the int32 key (include/eap_hip.h)
 
 
@@ -627,7 +681,7 @@ def so3_dense_member(idx, rows, n_rows, n):
     flags = torch.empty(b, dtype=torch.int32, device=dev)
     slot_of = torch.empty(b, n, dtype=torch.int32, device=dev)
     call('eap_so3_dense_member_wide' if wide else 'eap_so3_dense_member', idx, b, p, n, nn, min(DENSE_MAX_ROWS if wide else DENSE_NARROW_ROWS, n),
-         rows.stride(0), _ptr(idx), _ptr(rows), _ptr(n_rows), _ptr(slot_of), _ptr(memb), _ptr(flags))
+         rows.stride(0), idx, rows, n_rows, slot_of, memb, flags)
     return memb, flags
 
 
@@ -647,7 +701,6 @@ def so3_dense_narrow(memb, rp):
 # pass writes Y through it.  SORT_DENSE_POINTS = False: index order and every k-step, as round 5 (A/B runs, tests).
 SORT_DENSE_POINTS = True
 SKIP_DENSE_STEPS = True
-lib.eap_so3_dense_steps_words.restype = ctypes.c_int64
 
 
 class DenseGeometry:
@@ -672,7 +725,7 @@ class DenseGeometry:
         if SORT_DENSE_POINTS if sort is None else sort:
             # (32-word tables: one bit per group g < 64, an int64 key)
             keys = torch.empty(b, p, dtype=torch.int64 if _dense_wide(memb) else torch.int32, device=dev)
-            call('eap_so3_dense_point_keys_wide' if _dense_wide(memb) else 'eap_so3_dense_point_keys', memb, b, p, _ptr(memb), _ptr(keys))
+            call('eap_so3_dense_point_keys_wide' if _dense_wide(memb) else 'eap_so3_dense_point_keys', memb, b, p, memb, keys)
             order = torch.sort(keys, dim=1, stable=True).indices                               # int64 [b,p]: column j of the product is point order[b, j]
             q_xyz = q_xyz.gather(2, order[:, None, :].expand(b, 3, p)).contiguous()
             memb = memb.gather(1, order[:, :, None].expand(b, p, memb.shape[2])).contiguous()
@@ -686,16 +739,16 @@ class DenseGeometry:
         self.kr = torch.empty(b, na, kd_pad, 4, dtype=torch.float32, device=dev)
         if row_rot is not None and (row_rot.dtype != torch.float32 or not row_rot.is_contiguous() or row_rot.numel() != b * rows.stride(0) * 9):
             raise RuntimeError('DenseGeometry: row_rot must be a contiguous float32 [b, rows.stride(0), 3, 3]')
-        call('eap_so3_dense_tables_f32', memb, b, p, n, na, ks, self.rp, rows.stride(0), _F32(sigma), _ptr(q_xyz), _ptr(s_xyz), _ptr(rows),
-             _ptr(rk), _ptr(row_rot), _ptr(self.centre), _ptr(self.pt), _ptr(self.kr))
+        call('eap_so3_dense_tables_f32', memb, b, p, n, na, ks, self.rp, rows.stride(0), sigma, q_xyz, s_xyz, rows, rk, row_rot, self.centre, self.pt,
+             self.kr)
         self._masks, self._steps, self._composed = {}, {}, {}
 
     def mask(self, direction):
         m = self._masks.get(direction)
         if m is None:
-            words = int(lib.eap_so3_dense_mask_words(self.b, self.p, self.ks, self.rp, int(direction)))
+            words = int(abi.eap_so3_dense_mask_words(self.b, self.p, self.ks, self.rp, int(direction)))
             m = torch.empty(words, dtype=torch.int64, device=self.memb.device)
-            call('eap_so3_dense_masks_wide' if self.wide else 'eap_so3_dense_masks', m, self.b, self.p, self.ks, self.rp, int(direction), _ptr(self.memb), _ptr(m))
+            call('eap_so3_dense_masks_wide' if self.wide else 'eap_so3_dense_masks', m, self.b, self.p, self.ks, self.rp, int(direction), self.memb, m)
             self._masks[direction] = m
         return m
 
@@ -708,11 +761,11 @@ class DenseGeometry:
             kd = (self.ks * self.rp + 31) // 32 * 32
             blocks_n = ((self.p if direction else self.ks * self.rp) + 255) // 256
             k_steps = (kd if direction else self.p) // 32
-            words = int(lib.eap_so3_dense_steps_words(self.b, self.p, self.ks, self.rp, int(direction)))
+            words = int(abi.eap_so3_dense_steps_words(self.b, self.p, self.ks, self.rp, int(direction)))
             assert words == self.b * blocks_n * (k_steps + 1)
             st = torch.empty(self.b, blocks_n, k_steps + 1, dtype=torch.int32, device=self.memb.device)
-            call('eap_so3_dense_steps_wide' if self.wide else 'eap_so3_dense_steps', st, self.b, self.p, self.ks, self.rp, int(direction), 1, _ptr(self.n_rows),
-                 _ptr(self.mask(direction)), _ptr(st))
+            call('eap_so3_dense_steps_wide' if self.wide else 'eap_so3_dense_steps', st, self.b, self.p, self.ks, self.rp, int(direction), 1,
+                 self.n_rows, self.mask(direction), st)
             self._steps[direction] = st
         return self._steps[direction]
 
@@ -744,8 +797,7 @@ def so3_dense_split(src, seg=0, seg_pitch=0, shape=None, mapped=False, n_rows=No
         seg_pitch, l = l * na, colmap.shape[1]
     scale = torch.empty(2, b, na, m, dtype=torch.float32, device=src.device)      # [0]: [b,na,m]; [1]: the same numbers as [b,m,na]
     planes = torch.empty(b * na * m * ((l + 31) // 32 * 32), dtype=torch.int32, device=src.device)       # 4 bytes per element
-    call('eap_so3_dense_split_f32', src, b, m, l, na, int(seg), _I64(seg_pitch), int(bool(mapped)), _ptr(n_rows), _ptr(rowmax), _ptr(colmap), _ptr(src), _ptr(scale),
-         _ptr(planes))
+    call('eap_so3_dense_split_f32', src, b, m, l, na, int(seg), seg_pitch, int(bool(mapped)), n_rows, rowmax, colmap, src, scale, planes)
     return scale, planes
 
 
@@ -771,10 +823,9 @@ def _dense_executed_flops(geo, o, p, direction):
 def _dense_product(direction, geo, b, o, p, ld, scale, planes, out, flops):
     """One launch of the product kernel over p columns with the stored operand (scale, planes): direction 0 -> Z [b,o,ks,ld] (the backward;
     row pitch ld), 1 -> Yt [b,na,o,p] (the forward; ld 0).  flops: what the launch stands for algorithmically (bench.py).  -> out"""
-    call('eap_so3_dense_product_steps_f32', out, direction, b, o, p, geo.na, geo.ks, geo.rp, _I64(ld), _F32(geo.sigma), _ptr(geo.n_rows), _ptr(planes),
-         _ptr(scale), _ptr(geo.pt), _ptr(geo.kr), _ptr(geo.mask(direction)), _ptr(geo.steps(direction)), _ptr(out),
-         tag={'flops': flops, 'executed_f16_flops': _dense_executed_flops(geo, o, p, direction),
-              'shape': ('so3_dense', direction, b, o, p, geo.na, geo.ks, geo.rp)})
+    call('eap_so3_dense_product_steps_f32', out, direction, b, o, p, geo.na, geo.ks, geo.rp, ld, geo.sigma, geo.n_rows, planes, scale, geo.pt, geo.kr,
+         geo.mask(direction), geo.steps(direction), out, tag={'flops': flops, 'executed_f16_flops': _dense_executed_flops(geo, o, p, direction),
+         'shape': ('so3_dense', direction, b, o, p, geo.na, geo.ks, geo.rp)})
     return out
 
 
@@ -800,7 +851,7 @@ def so3_dense_gplanes(fc4, W3, geo):
     magnitude: too large a bound costs dynamic range only."""
     b, c, rp, na = fc4.shape
     o = W3.shape[0] // geo.ks
-    if not GPLANES or not lib.eap_so3_dense_gplanes_supported(o, c, na, geo.ks, rp):
+    if not GPLANES or not abi.eap_so3_dense_gplanes_supported(o, c, na, geo.ks, rp):
         return None
     ft = fc4.permute(0, 3, 2, 1).contiguous()                                       # [b,na,rp,c]
     # |G[o,(k,r),a]| <= max_k sum_c |W[o,c,k]| x max_{c,r} |F[c,r,a]|: two reductions over small tensors (the tighter sum_c |W| max_r |F_c|
@@ -810,7 +861,7 @@ def so3_dense_gplanes(fc4, W3, geo):
     bound = (fm[:, :, None] * (wsum * 1.0001)[None, None, :]).contiguous()          # [b,na,o]
     scale = torch.empty(2, b, na, o, dtype=torch.float32, device=fc4.device)
     planes = torch.empty(b * na * o * ((geo.ks * rp + 31) // 32 * 32), dtype=torch.int32, device=fc4.device)
-    call('eap_so3_dense_gplanes_f32', fc4, b, o, c, na, geo.ks, rp, _ptr(W3), _ptr(ft), _ptr(geo.n_rows), _ptr(bound), _ptr(scale), _ptr(planes),
+    call('eap_so3_dense_gplanes_f32', fc4, b, o, c, na, geo.ks, rp, W3, ft, geo.n_rows, bound, scale, planes,
          tag={'flops': 0.0, 'shape': ('so3_dense_gplanes', b, o, c, na, geo.ks, rp)})      # (write-bound operand preparation: not priced as matrix work)
     return scale, planes
 
@@ -829,7 +880,7 @@ def so3_dense_fwd(g, geo, p, c=0, ldg=None, out=None, col_map=None, operand=None
     if col_map is not None:
         if out is None or col_map.dtype != torch.int32 or tuple(col_map.shape) != (b, p) or not col_map.is_contiguous() or not out.is_contiguous():
             raise RuntimeError('so3_dense_fwd: col_map must be a contiguous int32 [b,p] and come with a contiguous out')
-        call('eap_so3_dense_untranspose_map_f32', yt, b, o, p, na, out.shape[2], _ptr(geo.columns(col_map)), _ptr(yt), _ptr(out))
+        call('eap_so3_dense_untranspose_map_f32', yt, b, o, p, na, out.shape[2], geo.columns(col_map), yt, out)
         return out
     y = torch.empty(b, o, p, na, dtype=torch.float32, device=yt.device)
     # the re-ordering pass also leaves the channel moments a BatchNorm right behind this layer starts with (its own pass otherwise)
@@ -837,9 +888,9 @@ def so3_dense_fwd(g, geo, p, c=0, ldg=None, out=None, col_map=None, operand=None
     ps = torch.empty(o, b * chunks, dtype=torch.float32, device=yt.device)
     pq = torch.empty_like(ps)
     if geo.order is not None:                                     # columns in the geometry's point order: written through it
-        call('eap_so3_dense_untranspose_map_stats_f32', yt, b, o, p, na, p, _ptr(geo.order), _ptr(geo.pivot_pos), _ptr(yt), _ptr(y), _ptr(ps), _ptr(pq))
+        call('eap_so3_dense_untranspose_map_stats_f32', yt, b, o, p, na, p, geo.order, geo.pivot_pos, yt, y, ps, pq)
     else:
-        call('eap_so3_dense_untranspose_f32', yt, b, o, p, na, _ptr(yt), _ptr(y), _ptr(ps), _ptr(pq))
+        call('eap_so3_dense_untranspose_f32', yt, b, o, p, na, yt, y, ps, pq)
     leave_stats_hint(y, (ps, pq))
     return y
 
@@ -870,10 +921,10 @@ def so3_dense_fwd_bnact(g, geo, p, c, ldg, norm_moments, operand=None, o=None, a
     else:
         # moments of every channel over (cloud, anchor, point): Yt is [b na][o][p] for the statistics kernel; the pivot is its own first element
         ps, pq = _partials(yt, b * na, o, p)
-        call('eap_bn_stats_f32', yt, b * na, o, _I64(p), _ptr(yt), _ptr(ps), _ptr(pq))
+        call('eap_bn_stats_f32', yt, b * na, o, p, yt, ps, pq)
         bn_scale, bn_shift, slope = norm_moments(ps.sum(1, dtype=torch.float64), pq.sum(1, dtype=torch.float64), yt[0, 0, :, 0].double(), b * na * p)
     y = torch.empty(b, o, p, na, dtype=torch.float32, device=yt.device)
-    call('eap_so3_dense_untranspose_bnact_f32', yt, b, o, p, na, p, _ptr(geo.order), _ptr(yt), _ptr(bn_scale), _ptr(bn_shift), _F32(slope), _ptr(y))
+    call('eap_so3_dense_untranspose_bnact_f32', yt, b, o, p, na, p, geo.order, yt, bn_scale, bn_shift, slope, y)
     return y
 
 
@@ -882,12 +933,12 @@ def bn_act_bwd_reduce_fromy(gy, y, beta, inv_gamma, slope):
     (csrc/bn_act.hip bn_act_bwd_reduce_fromy_kernel)."""
     b, c, p, na = y.shape
     n = p * na
-    nblk = int(lib.eap_bn_act_fromy_blocks(_I64(n), na))
+    nblk = int(abi.eap_bn_act_fromy_blocks(n, na))
     pg = torch.empty(c, b * nblk, dtype=torch.float32, device=y.device)
     pgx = torch.empty_like(pg)
     gmax = torch.empty(b, c, na, dtype=torch.int32, device=y.device)
     xmax = torch.empty_like(gmax)
-    call('eap_bn_act_bwd_reduce_fromy_f32', y, b, c, _I64(n), na, _F32(slope), _ptr(gy), _ptr(y), _ptr(beta), _ptr(inv_gamma), _ptr(pg), _ptr(pgx), _ptr(gmax), _ptr(xmax))
+    call('eap_bn_act_bwd_reduce_fromy_f32', y, b, c, n, na, slope, gy, y, beta, inv_gamma, pg, pgx, gmax, xmax)
     return pg.sum(1, dtype=torch.float64), pgx.sum(1, dtype=torch.float64), gmax.view(torch.float32), xmax.view(torch.float32)
 
 
@@ -901,14 +952,13 @@ def so3_dense_bwd_bn(gy, yact, geo, ldz, coef, rowbound, slope):
     l = p if colmap is None else colmap.shape[1]
     scale = torch.empty(2, b, na, o, dtype=torch.float32, device=gy.device)
     planes = torch.empty(b * na * o * ((l + 31) // 32 * 32), dtype=torch.int32, device=gy.device)
-    call('eap_so3_dense_split_bn_f32', gy, b, o, l, p, na, _ptr(rowbound.view(torch.int32)), _ptr(colmap), _ptr(gy), _ptr(yact), _ptr(coef), _F32(slope), _ptr(scale),
-         _ptr(planes))
+    call('eap_so3_dense_split_bn_f32', gy, b, o, l, p, na, rowbound.view(torch.int32), colmap, gy, yact, coef, slope, scale, planes)
     z = torch.empty(b, o, geo.ks, ldz, dtype=torch.float32, device=gy.device)
     return _dense_product(0, geo, b, o, l, ldz, scale, planes, z, 2.0 * b * o * l * na * geo.ks * geo.nn)
 
 
 def _partials(x, b, c, n):
-    nseg = int(lib.eap_bn_act_segments(_I64(n)))
+    nseg = int(abi.eap_bn_act_segments(n))
     return (torch.empty(c, b * nseg, dtype=torch.float32, device=x.device),
             torch.empty(c, b * nseg, dtype=torch.float32, device=x.device))
 
@@ -948,23 +998,22 @@ def bn_stats(x, b, c, n):
     if hint is not None and hint[0].shape[0] == c:
         return hint[0].sum(1, dtype=torch.float64), hint[1].sum(1, dtype=torch.float64)
     ps, pq = _partials(x, b, c, n)
-    call('eap_bn_stats_f32', x, b, c, _I64(n), _ptr(x), _ptr(ps), _ptr(pq))
+    call('eap_bn_stats_f32', x, b, c, n, x, ps, pq)
     return ps.sum(1, dtype=torch.float64), pq.sum(1, dtype=torch.float64)
 
 
 def bn_act_fwd(x, b, c, n, scale, shift, slope, residual=None):
     y = torch.empty_like(x)
     if residual is None:
-        call('eap_bn_act_fwd_f32', x, b, c, _I64(n), _F32(slope), _ptr(x), _ptr(scale), _ptr(shift), _ptr(y))
+        call('eap_bn_act_fwd_f32', x, b, c, n, slope, x, scale, shift, y)
     else:
-        call('eap_bn_act_add_fwd_f32', x, b, c, _I64(n), _F32(slope), _ptr(x), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y))
+        call('eap_bn_act_add_fwd_f32', x, b, c, n, slope, x, scale, shift, residual, y)
     return y
 
 
 def bn_act_bwd_reduce(gy, x, b, c, n, scale, shift, mean, invstd, slope):
     pg, pgx = _partials(x, b, c, n)
-    call('eap_bn_act_bwd_reduce_f32', x, b, c, _I64(n), _F32(slope), _ptr(gy), _ptr(x), _ptr(scale), _ptr(shift),
-         _ptr(mean), _ptr(invstd), _ptr(pg), _ptr(pgx))
+    call('eap_bn_act_bwd_reduce_f32', x, b, c, n, slope, gy, x, scale, shift, mean, invstd, pg, pgx)
     return pg.sum(1, dtype=torch.float64), pgx.sum(1, dtype=torch.float64)
 
 
@@ -995,12 +1044,10 @@ def bn_act_bwd_apply(gy, x, b, c, n, scale, shift, mean, invstd, k2, k3, slope):
         # [b, c, points, anchors] at a width the dense backward product takes: the same pass also leaves the row maxima its
         # stored-operand split needs (csrc/bn_act.hip bn_act_bwd_apply_rowmax_kernel)
         rowmax = torch.empty(b, c, x.shape[3], dtype=torch.int32, device=x.device)
-        call('eap_bn_act_bwd_apply_rowmax_f32', x, b, c, _I64(n), int(x.shape[3]), _F32(slope), _ptr(gy), _ptr(x), _ptr(scale), _ptr(shift),
-             _ptr(mean), _ptr(invstd), _ptr(k2), _ptr(k3), _ptr(gx), _ptr(rowmax))
+        call('eap_bn_act_bwd_apply_rowmax_f32', x, b, c, n, int(x.shape[3]), slope, gy, x, scale, shift, mean, invstd, k2, k3, gx, rowmax)
         leave_rowmax_hint(gx, rowmax)
         return gx
-    call('eap_bn_act_bwd_apply_f32', x, b, c, _I64(n), _F32(slope), _ptr(gy), _ptr(x), _ptr(scale), _ptr(shift),
-         _ptr(mean), _ptr(invstd), _ptr(k2), _ptr(k3), _ptr(gx))
+    call('eap_bn_act_bwd_apply_f32', x, b, c, n, slope, gy, x, scale, shift, mean, invstd, k2, k3, gx)
     return gx
 
 
@@ -1015,7 +1062,7 @@ def narrow_conv_takes(o, ck, n):
 
 
 def _narrow_partials(x, b, o, n):
-    nseg = int(lib.eap_narrow_conv_segments(_I64(n)))
+    nseg = int(abi.eap_narrow_conv_segments(n))
     return (torch.empty(o, b * nseg, dtype=torch.float32, device=x.device),
             torch.empty(o, b * nseg, dtype=torch.float32, device=x.device))
 
@@ -1027,7 +1074,7 @@ def narrow_conv_stats(W, x):
     o = W.shape[0]
     ps, pq = _narrow_partials(x, b, o, n)
     pivot = torch.empty(o, dtype=torch.float32, device=x.device)
-    call('eap_narrow_conv_stats_f32', x, b, o, ck, _I64(n), _ptr(W), _ptr(x), _ptr(pivot), _ptr(ps), _ptr(pq))
+    call('eap_narrow_conv_stats_f32', x, b, o, ck, n, W, x, pivot, ps, pq)
     return ps.sum(1, dtype=torch.float64), pq.sum(1, dtype=torch.float64), pivot.double()
 
 
@@ -1037,7 +1084,7 @@ def narrow_conv_bnact_fwd(W, x, scale, shift, slope):
     b, ck, n = x.shape
     o = W.shape[0]
     y = torch.empty(b, o, n, dtype=torch.float32, device=x.device)
-    call('eap_narrow_conv_bnact_fwd_f32', x, b, o, ck, _I64(n), _F32(slope), _ptr(W), _ptr(x), _ptr(scale), _ptr(shift), _ptr(y))
+    call('eap_narrow_conv_bnact_fwd_f32', x, b, o, ck, n, slope, W, x, scale, shift, y)
     return y
 
 
@@ -1047,8 +1094,7 @@ def narrow_conv_bwd_reduce(gy, x, W, scale, shift, mean, invstd, slope):
     b, ck, n = x.shape
     o = W.shape[0]
     pg, pgx = _narrow_partials(x, b, o, n)
-    call('eap_narrow_conv_bwd_reduce_f32', x, b, o, ck, _I64(n), _F32(slope), _ptr(gy), _ptr(x), _ptr(W), _ptr(scale), _ptr(shift),
-         _ptr(mean), _ptr(invstd), _ptr(pg), _ptr(pgx))
+    call('eap_narrow_conv_bwd_reduce_f32', x, b, o, ck, n, slope, gy, x, W, scale, shift, mean, invstd, pg, pgx)
     return pg.sum(1, dtype=torch.float64), pgx.sum(1, dtype=torch.float64)
 
 
@@ -1057,11 +1103,10 @@ def narrow_conv_bwd_dw(gy, x, W, scale, shift, mean, invstd, k2, k3, slope):
     check_input(gy, x, W, scale, shift, mean, invstd, k2, k3)
     b, ck, n = x.shape
     o = W.shape[0]
-    nseg = int(lib.eap_narrow_conv_segments(_I64(n)))
+    nseg = int(abi.eap_narrow_conv_segments(n))
     partial = torch.empty(b * nseg, o, ck, dtype=torch.float32, device=x.device)
     dW = torch.empty(o, ck, dtype=torch.float32, device=x.device)
-    call('eap_narrow_conv_bwd_dw_f32', x, b, o, ck, _I64(n), _F32(slope), _ptr(gy), _ptr(x), _ptr(W), _ptr(scale), _ptr(shift),
-         _ptr(mean), _ptr(invstd), _ptr(k2), _ptr(k3), _ptr(partial), _ptr(dW))
+    call('eap_narrow_conv_bwd_dw_f32', x, b, o, ck, n, slope, gy, x, W, scale, shift, mean, invstd, k2, k3, partial, dW)
     return dW
 
 
@@ -1070,27 +1115,25 @@ def narrow_conv_bwd_dw(gy, x, W, scale, shift, mean, invstd, k2, k3, slope):
 def bn_stats_masked(x, b, c, n, na, mask):
     """-> (sum, sumsq) of mask * (x - pivot) per (cloud, channel), float64 [b, c] (pivot = x[0, c, 0])."""
     ps, pq = _partials(x, b, c, n)
-    call('eap_bn_stats_masked_f32', x, b, c, _I64(n), na, _ptr(x), _ptr(mask), _ptr(ps), _ptr(pq))
+    call('eap_bn_stats_masked_f32', x, b, c, n, na, x, mask, ps, pq)
     return ps.view(c, b, -1).sum(2, dtype=torch.float64).t(), pq.view(c, b, -1).sum(2, dtype=torch.float64).t()
 
 
 def bn_act_cloud_fwd(x, b, c, n, scale, shift, slope):
     y = torch.empty_like(x)
-    call('eap_bn_act_cloud_fwd_f32', x, b, c, _I64(n), _F32(slope), _ptr(x), _ptr(scale), _ptr(shift), _ptr(y))
+    call('eap_bn_act_cloud_fwd_f32', x, b, c, n, slope, x, scale, shift, y)
     return y
 
 
 def bn_act_cloud_bwd_reduce(gy, x, b, c, n, scale, shift, mean, invstd, slope):
     pg, pgx = _partials(x, b, c, n)
-    call('eap_bn_act_cloud_bwd_reduce_f32', x, b, c, _I64(n), _F32(slope), _ptr(gy), _ptr(x), _ptr(scale), _ptr(shift),
-         _ptr(mean), _ptr(invstd), _ptr(pg), _ptr(pgx))
+    call('eap_bn_act_cloud_bwd_reduce_f32', x, b, c, n, slope, gy, x, scale, shift, mean, invstd, pg, pgx)
     return pg.view(c, b, -1).sum(2, dtype=torch.float64).t(), pgx.view(c, b, -1).sum(2, dtype=torch.float64).t()
 
 
 def bn_act_cloud_bwd_apply(gy, x, b, c, n, na, scale, shift, mean, invstd, k2, k3, mask, slope):
     gx = torch.empty_like(x)
-    call('eap_bn_act_cloud_bwd_apply_f32', x, b, c, _I64(n), na, _F32(slope), _ptr(gy), _ptr(x), _ptr(scale), _ptr(shift),
-         _ptr(mean), _ptr(invstd), _ptr(k2), _ptr(k3), _ptr(mask), _ptr(gx))
+    call('eap_bn_act_cloud_bwd_apply_f32', x, b, c, n, na, slope, gy, x, scale, shift, mean, invstd, k2, k3, mask, gx)
     return gx
 
 
@@ -1099,15 +1142,13 @@ def so3_intra_conv(feats, W, intra_idx32):
     b, c, p, na = feats.shape
     o, nt = W.shape[0], intra_idx32.shape[1]
     out = torch.empty(b, o, p, na, dtype=torch.float32, device=feats.device)
-    split = SPLIT_BF16_CONTRACTION and W.data_ptr() % 16 == 0 and lib.eap_so3_intra_conv_bf16x3_f32_supported(b, o, c, p, na, nt)
+    split = SPLIT_BF16_CONTRACTION and W.data_ptr() % 16 == 0 and abi.eap_so3_intra_conv_bf16x3_f32_supported(b, o, c, p, na, nt)
     tag = {'flops': 2.0 * b * o * c * nt * p * na, 'shape': ('intra_conv', b, o, c, p, na, nt)}
     if split and SPLIT_PLANES == 2 and feats.data_ptr() % 16 == 0:
         abs_w = absmax_rows(W, 1, o, c * nt, c * nt, 0)
         abs_f = absmax_colgroups(feats, b, c, p * na, p * na, c * p * na, na) if na % 4 == 0 else None
         if abs_w is not None and abs_f is not None:
-            call('eap_so3_intra_conv_f16x2_f32', out, b, o, c, p, na, nt, _ptr(W), _ptr(feats), _ptr(intra_idx32), _ptr(out), _ptr(abs_w),
-                 _ptr(abs_f), tag=tag)
+            call('eap_so3_intra_conv_f16x2_f32', out, b, o, c, p, na, nt, W, feats, intra_idx32, out, abs_w, abs_f, tag=tag)
             return out
-    call('eap_so3_intra_conv_bf16x3_f32' if split else 'eap_so3_intra_conv_f32', out, b, o, c, p, na, nt, _ptr(W), _ptr(feats),
-         _ptr(intra_idx32), _ptr(out), tag=tag)
+    call('eap_so3_intra_conv_bf16x3_f32' if split else 'eap_so3_intra_conv_f32', out, b, o, c, p, na, nt, W, feats, intra_idx32, out, tag=tag)
     return out

@@ -13,7 +13,7 @@ def gather_points_forward(pts, idx):
     b, c, n = pts.shape
     m = idx.shape[1]
     out = torch.empty(b, c, m, dtype=torch.float32, device=pts.device)
-    _hip.call('eap_gather_points_fwd_' + _hip.suffix(pts), out, b, c, n, m, _hip._ptr(pts), _hip._ptr(idx), _hip._ptr(out))
+    _hip.call('eap_gather_points_fwd_' + _hip.suffix(pts), out, b, c, n, m, pts, idx, out)
     return out
 
 
@@ -24,6 +24,5 @@ def gather_points_backward(grad_out, idx, npoint):
         raise RuntimeError('gather_points_backward: idx must be int32')
     b, c, m = grad_out.shape
     out = torch.empty(b, c, npoint, dtype=grad_out.dtype, device=grad_out.device)
-    _hip.call('eap_gather_points_bwd_' + _hip.suffix(grad_out), out, b, c, int(npoint), m,
-              _hip._ptr(grad_out), _hip._ptr(idx), _hip._ptr(out))
+    _hip.call('eap_gather_points_bwd_' + _hip.suffix(grad_out), out, b, c, int(npoint), m, grad_out, idx, out)
     return out

@@ -1,11 +1,8 @@
 """vgtk.cuda.grouping -- replaces the pybind module of vgtk/vgtk/cuda/grouping_cuda.cpp."""
-import ctypes
-
 import torch
 
 from .. import _hip
 
-_F32 = ctypes.c_float
 
 
 def _same_dtype(op, **tensors):
@@ -24,8 +21,7 @@ def ball_query(new_xyz, xyz, radius, nsample):
     b, _, m = new_xyz.shape
     n = xyz.shape[2]
     idx = torch.empty(b, m, nsample, dtype=torch.int32, device=xyz.device)
-    _hip.call('eap_ball_query_' + _hip.suffix(xyz), xyz, b, n, m, _F32(radius), int(nsample),
-              _hip._ptr(new_xyz), _hip._ptr(xyz), _hip._ptr(idx))
+    _hip.call('eap_ball_query_' + _hip.suffix(xyz), xyz, b, n, m, radius, int(nsample), new_xyz, xyz, idx)
     return idx
 
 
@@ -36,7 +32,7 @@ def furthest_point_sampling(xyz, m):
     b, _, n = xyz.shape
     idx = torch.empty(b, m, dtype=torch.int32, device=xyz.device)
     temp = torch.empty(b, n, dtype=xyz.dtype, device=xyz.device)
-    _hip.call('eap_furthest_point_sampling_' + sfx, xyz, b, n, int(m), _hip._ptr(xyz), _hip._ptr(temp), _hip._ptr(idx))
+    _hip.call('eap_furthest_point_sampling_' + sfx, xyz, b, n, int(m), xyz, temp, idx)
     return idx
 
 
@@ -48,8 +44,7 @@ def anchor_query(sample_idx, grouped_idx, grouped_xyz, anchors, kernel_pts, nq):
     b, _, np_, nn = grouped_xyz.shape
     na, ks = anchors.shape[0], kernel_pts.shape[0]
     w = torch.empty(b, np_, na, ks, nn, dtype=grouped_xyz.dtype, device=grouped_xyz.device)
-    _hip.call('eap_anchor_query_' + sfx, w, b, np_, nn, na, ks, _hip._ptr(grouped_xyz), _hip._ptr(anchors),
-              _hip._ptr(kernel_pts), _hip._ptr(w))
+    _hip.call('eap_anchor_query_' + sfx, w, b, np_, nn, na, ks, grouped_xyz, anchors, kernel_pts, w)
     return [w]
 
 
@@ -63,6 +58,5 @@ def initial_anchor_query(centers, xyz, kernel_pts, radius, sigma):
     ks, na, _ = kernel_pts.shape
     w = torch.empty(b, ks, nc, na, dtype=centers.dtype, device=centers.device)
     cnt = torch.empty_like(w)
-    _hip.call('eap_initial_anchor_query_' + sfx, w, b, nc, m, na, ks, _F32(radius), _F32(sigma),
-              _hip._ptr(centers), _hip._ptr(xyz), _hip._ptr(kernel_pts), _hip._ptr(w), _hip._ptr(cnt))
+    _hip.call('eap_initial_anchor_query_' + sfx, w, b, nc, m, na, ks, radius, sigma, centers, xyz, kernel_pts, w, cnt)
     return [w, cnt]

@@ -27,13 +27,11 @@ def inter_zpconv_forward(idx, w, feats):
     out = torch.empty(b, c, ks, np_, na, dtype=feats.dtype, device=feats.device)
     if feats.dtype == torch.float32:
         # scratch for the device-side index check + the per-point neighbour lists (csrc/zpconv_mfma.hip)
-        nbytes = int(_hip.lib.eap_inter_zpconv_fwd_workspace(b, np_, ann))
+        nbytes = int(_hip.abi.eap_inter_zpconv_fwd_workspace(b, np_, ann))
         ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=feats.device)
-        _hip.call('eap_inter_zpconv_fwd_ws_f32', out, b, np_, nq, na, ks, ann, c,
-                  _hip._ptr(idx), _hip._ptr(w), _hip._ptr(feats), _hip._ptr(out), _hip._ptr(ws))
+        _hip.call('eap_inter_zpconv_fwd_ws_f32', out, b, np_, nq, na, ks, ann, c, idx, w, feats, out, ws)
         return out
-    _hip.call('eap_inter_zpconv_fwd_' + _hip.suffix(feats), out, b, np_, nq, na, ks, ann, c,
-              _hip._ptr(idx), _hip._ptr(w), _hip._ptr(feats), _hip._ptr(out))
+    _hip.call('eap_inter_zpconv_fwd_' + _hip.suffix(feats), out, b, np_, nq, na, ks, ann, c, idx, w, feats, out)
     return out
 
 
@@ -61,8 +59,7 @@ def inter_zpconv_backward(idx, w, grad, npoint):
                 run = [i]
             return out
         return _backward_with_products(idx, w, grad, int(npoint), out)
-    _hip.call('eap_inter_zpconv_bwd_' + _hip.suffix(grad), out, b, np_, int(npoint), na, ks, ann, c,
-              _hip._ptr(idx), _hip._ptr(w), _hip._ptr(grad), _hip._ptr(out))
+    _hip.call('eap_inter_zpconv_bwd_' + _hip.suffix(grad), out, b, np_, int(npoint), na, ks, ann, c, idx, w, grad, out)
     return out
 
 
@@ -108,7 +105,7 @@ def _backward_on_chip(idx, w, grad, out):
     _check_pending_verdicts()
     b, np_, na, ks, ann = idx.shape
     c, nq = grad.shape[1], out.shape[2]
-    nbytes = int(_hip.lib.eap_inter_zpconv_bwd_hot_workspace(b, np_, nq, na, ks, ann, c)) if ON_CHIP_BACKWARD else 0
+    nbytes = int(_hip.abi.eap_inter_zpconv_bwd_hot_workspace(b, np_, nq, na, ks, ann, c)) if ON_CHIP_BACKWARD else 0
     if nbytes <= 0 or any(t.data_ptr() % 16 for t in (idx, w, grad, out)):
         return list(range(b))
     key = (_verdict_key(idx), c, nq)
@@ -118,8 +115,7 @@ def _backward_on_chip(idx, w, grad, out):
         return list(known)                                   # nothing for the on-chip kernel here (every cloud goes to the product pipeline: correct whatever the index holds)
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=grad.device)
     status = torch.empty(b, dtype=torch.int32, device=grad.device)
-    _hip.call('eap_inter_zpconv_bwd_hot_f32', out, b, np_, nq, na, ks, ann, c, _hip._ptr(idx), _hip._ptr(w), _hip._ptr(grad),
-              _hip._ptr(out), _hip._ptr(ws), _hip._ptr(status))
+    _hip.call('eap_inter_zpconv_bwd_hot_f32', out, b, np_, nq, na, ks, ann, c, idx, w, grad, out, ws, status)
     if known is not None:
         # same index, same shapes: the same clouds as last time, no host read now -- the status travels to pinned memory behind the
         # kernel and is compared at the next call
@@ -146,23 +142,22 @@ def _backward_with_products(idx, w, grad, npoint, out=None):
     if out is None:
         out = torch.empty(b, c, npoint, na, dtype=grad.dtype, device=grad.device)
     # atomics-free path (csrc/zpconv_bwd.hip): scratch for the per-(point, neighbour) products, a few clouds at a time
-    per_cloud = int(_hip.lib.eap_inter_zpconv_bwd_workspace(1, np_, int(npoint), na, ann, c))
+    per_cloud = int(_hip.abi.eap_inter_zpconv_bwd_workspace(1, np_, int(npoint), na, ann, c))
     step = min(b, BWD_WORKSPACE_BYTES // max(per_cloud, 1))
     ws = None
     if step >= 1:
         try:
-            ws = torch.empty((int(_hip.lib.eap_inter_zpconv_bwd_workspace(step, np_, int(npoint), na, ann, c)) + 3) // 4,
+            ws = torch.empty((int(_hip.abi.eap_inter_zpconv_bwd_workspace(step, np_, int(npoint), na, ann, c)) + 3) // 4,
                              dtype=torch.int32, device=grad.device)
         except torch.cuda.OutOfMemoryError:
             ws = None
     if ws is None:
-        _hip.call('eap_inter_zpconv_bwd_f32', out, b, np_, int(npoint), na, ks, ann, c,
-                  _hip._ptr(idx), _hip._ptr(w), _hip._ptr(grad), _hip._ptr(out))
+        _hip.call('eap_inter_zpconv_bwd_f32', out, b, np_, int(npoint), na, ks, ann, c, idx, w, grad, out)
         return out
     for b0 in range(0, b, step):
         nb = min(step, b - b0)
-        _hip.call('eap_inter_zpconv_bwd_ws_f32', out, nb, np_, int(npoint), na, ks, ann, c, _hip._ptr(idx[b0:b0 + nb]),
-                  _hip._ptr(w[b0:b0 + nb]), _hip._ptr(grad[b0:b0 + nb]), _hip._ptr(out[b0:b0 + nb]), _hip._ptr(ws))
+        _hip.call('eap_inter_zpconv_bwd_ws_f32', out, nb, np_, int(npoint), na, ks, ann, c, idx[b0:b0 + nb], w[b0:b0 + nb], grad[b0:b0 + nb],
+                  out[b0:b0 + nb], ws)
     return out
 
 
@@ -174,8 +169,7 @@ def intra_zpconv_forward(idx, w, feats):
     ks = w.shape[1]
     b, c, np_, na_in = feats.shape
     out = torch.empty(b, c, ks, np_, na_out, dtype=feats.dtype, device=feats.device)
-    _hip.call('eap_intra_zpconv_fwd_' + _hip.suffix(feats), out, b, np_, na_in, na_out, ks, ann, c,
-              _hip._ptr(idx), _hip._ptr(w), _hip._ptr(feats), _hip._ptr(out))
+    _hip.call('eap_intra_zpconv_fwd_' + _hip.suffix(feats), out, b, np_, na_in, na_out, ks, ann, c, idx, w, feats, out)
     return out
 
 
@@ -186,6 +180,5 @@ def intra_zpconv_backward(idx, w, grad, anchor_in):
     ks = w.shape[1]
     b, c, _, np_, _ = grad.shape
     out = torch.empty(b, c, np_, int(anchor_in), dtype=grad.dtype, device=grad.device)
-    _hip.call('eap_intra_zpconv_bwd_' + _hip.suffix(grad), out, b, np_, int(anchor_in), na_out, ks, ann, c,
-              _hip._ptr(idx), _hip._ptr(w), _hip._ptr(grad), _hip._ptr(out))
+    _hip.call('eap_intra_zpconv_bwd_' + _hip.suffix(grad), out, b, np_, int(anchor_in), na_out, ks, ann, c, idx, w, grad, out)
     return out

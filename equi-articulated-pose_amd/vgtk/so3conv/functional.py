@@ -1450,7 +1450,7 @@ class _NarrowContract(torch.autograd.Function):
         b, c, n = x.shape
         o = W.shape[0]
         y = torch.empty(b, o, n, dtype=torch.float32, device=x.device)
-        _hip.call('eap_narrow_contract_fwd_f32', x, b, o, c, _hip._I64(n), _hip._ptr(W), _hip._ptr(x), _hip._ptr(y))
+        _hip.call('eap_narrow_contract_fwd_f32', x, b, o, c, n, W, x, y)
         ctx.save_for_backward(W, x)
         return y
 
@@ -1463,11 +1463,11 @@ class _NarrowContract(torch.autograd.Function):
         gW = gx = None
         if ctx.needs_input_grad[1]:
             gx = torch.empty_like(x)
-            _hip.call('eap_narrow_contract_dx_f32', x, b, o, c, _hip._I64(n), _hip._ptr(W), _hip._ptr(gy), _hip._ptr(gx))
+            _hip.call('eap_narrow_contract_dx_f32', x, b, o, c, n, W, gy, gx)
         if ctx.needs_input_grad[0]:
-            slabs = int(_hip.lib.eap_narrow_contract_dw_slabs(_hip._I64(n)))
+            slabs = int(_hip.abi.eap_narrow_contract_dw_slabs(n))
             part = torch.empty(slabs * b, o, c, dtype=torch.float32, device=x.device)
-            _hip.call('eap_narrow_contract_dw_f32', x, b, o, c, _hip._I64(n), _hip._ptr(gy), _hip._ptr(x), _hip._ptr(part))
+            _hip.call('eap_narrow_contract_dw_f32', x, b, o, c, n, gy, x, part)
             gW = part.sum(0, dtype=torch.float64).float()
         return gW, gx
 
@@ -1479,7 +1479,7 @@ def so3_contract(W, x, epilogue=None):
         raise RuntimeError('so3_contract: float32 only')
     if not W.is_cuda:
         raise RuntimeError('so3_contract: W must be a device tensor')
-    if epilogue is None and W.shape[0] <= 4 and _hip.lib.eap_narrow_contract_supported(x.shape[0], W.shape[0], x.shape[1], _hip._I64(x.shape[2])):
+    if epilogue is None and W.shape[0] <= 4 and _hip.abi.eap_narrow_contract_supported(x.shape[0], W.shape[0], x.shape[1], x.shape[2]):
         return _NarrowContract.apply(W, x)
     return _Contract.apply(W, x, epilogue)
 

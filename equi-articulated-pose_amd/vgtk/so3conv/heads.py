@@ -18,8 +18,6 @@ and 3), mirroring the reference classes so a maintainer can swap the import:
 
 Every 1x1 convolution over the [B,C,N,A] map (InvPPOutBlockOurs' included) is the path's contraction, every BatchNorm +
 activation after one the fused epilogue; only the regressors on pooled [B,c,A] tensors are torch layers."""
-import ctypes
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -28,7 +26,6 @@ from .. import _hip
 from . import functional as L
 from .blocks import _BNAct
 
-_F32 = ctypes.c_float
 
 
 class _AnchorAttnPool(torch.autograd.Function):
@@ -40,7 +37,7 @@ class _AnchorAttnPool(torch.autograd.Function):
         b, c, n, na = x.shape
         out = torch.empty(b, c, n, dtype=torch.float32, device=x.device)
         conf = torch.empty(b, n, na, dtype=torch.float32, device=x.device)
-        _hip.call('eap_anchor_attn_pool_fwd_f32', x, b, c, n, na, _F32(temperature), _hip._ptr(x), _hip._ptr(logits), _hip._ptr(out), _hip._ptr(conf))
+        _hip.call('eap_anchor_attn_pool_fwd_f32', x, b, c, n, na, temperature, x, logits, out, conf)
         ctx.save_for_backward(x, logits)
         ctx.temperature = temperature
         ctx.mark_non_differentiable(conf)
@@ -53,8 +50,7 @@ class _AnchorAttnPool(torch.autograd.Function):
         dx = torch.empty_like(x)
         dl = torch.empty_like(logits)
         g = g.contiguous()            # bound to a local: the buffer must outlive the enqueue
-        _hip.call('eap_anchor_attn_pool_bwd_f32', x, b, c, n, na, _F32(ctx.temperature), _hip._ptr(x), _hip._ptr(logits),
-                  _hip._ptr(g), _hip._ptr(dx), _hip._ptr(dl))
+        _hip.call('eap_anchor_attn_pool_bwd_f32', x, b, c, n, na, ctx.temperature, x, logits, g, dx, dl)
         return dx, dl, None
 
 
@@ -158,7 +154,7 @@ class _SlotMaskedMean(torch.autograd.Function):
         ns = mask.shape[1]
         inv_den = (1.0 / mask.sum(-1).clamp(min=1e-8)).contiguous()
         out = torch.empty(b, ns, c, na, dtype=torch.float32, device=x.device)
-        _hip.call('eap_slot_masked_mean_fwd_f32', x, b, ns, c, n, na, _hip._ptr(x), _hip._ptr(mask), _hip._ptr(inv_den), _hip._ptr(out))
+        _hip.call('eap_slot_masked_mean_fwd_f32', x, b, ns, c, n, na, x, mask, inv_den, out)
         ctx.save_for_backward(mask, inv_den)
         ctx.dims = (b, c, n, na, ns)
         return out
@@ -169,7 +165,7 @@ class _SlotMaskedMean(torch.autograd.Function):
         b, c, n, na, ns = ctx.dims
         dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
         g = g.contiguous()            # bound to a local: the buffer must outlive the enqueue
-        _hip.call('eap_slot_masked_mean_bwd_f32', g, b, ns, c, n, na, _hip._ptr(g), _hip._ptr(mask), _hip._ptr(inv_den), _hip._ptr(dx))
+        _hip.call('eap_slot_masked_mean_bwd_f32', g, b, ns, c, n, na, g, mask, inv_den, dx)
         return dx, None
 
 
@@ -182,7 +178,7 @@ class _MaskedMax(torch.autograd.Function):
         b, c, n, na = x.shape
         out = torch.empty(b, c, na, dtype=torch.float32, device=x.device)
         arg = torch.empty(b, c, na, dtype=torch.int32, device=x.device)
-        _hip.call('eap_masked_max_fwd_f32', x, b, c, n, na, _hip._ptr(x), _hip._ptr(mask), _hip._ptr(out), _hip._ptr(arg))
+        _hip.call('eap_masked_max_fwd_f32', x, b, c, n, na, x, mask, out, arg)
         ctx.save_for_backward(arg, mask)
         ctx.dims = (b, c, n, na)
         return out
@@ -193,7 +189,7 @@ class _MaskedMax(torch.autograd.Function):
         b, c, n, na = ctx.dims
         g = g.contiguous()
         dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
-        _hip.call('eap_masked_max_bwd_f32', g, b, c, n, na, _hip._ptr(g), _hip._ptr(arg), _hip._ptr(mask), _hip._ptr(dx))
+        _hip.call('eap_masked_max_bwd_f32', g, b, c, n, na, g, arg, mask, dx)
         return dx, None
 
 

@@ -18,6 +18,15 @@
  *     check (eap_last_error() returns a message).  The reference only printf()s launch errors
  *     (vgtk/vgtk/cuda/zpconv_cuda_kernel.cu:L232-234); this ABI reports them.
  *   - *_f32 / *_f64: the reference dispatches AT_DISPATCH_FLOATING_TYPES for its native ops.
+ *
+ * Vocabulary.  The Python package reads THIS FILE at import and builds one typed ctypes prototype per `ret eap_name(params);` below
+ * (equi-articulated-pose_amd/vgtk/_hip.py, `abi`), so a declaration is plain C over these types and nothing else:
+ *   returns      int, int64_t, const char *
+ *   scalars      int, int64_t, float
+ *   pointers     [const] float / double / int32_t / uint32_t / int64_t / uint64_t / uint8_t / void *
+ *   the stream   eap_stream_t
+ * with `(void)` for no parameters, no macros, no function pointers, no arrays.  Anything else makes the import fail (ImportError naming
+ * the entry and the parameter): extend the table in _hip.py together with the header, never the header alone.
  */
 #ifndef EAP_HIP_H
 #define EAP_HIP_H

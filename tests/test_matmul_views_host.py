@@ -34,8 +34,9 @@ class Recorder:
         self._hip, self.calls = _hip, []
         for name in ('gemm', 'gemm_reduce', 'gemm_epilogue'):
             monkeypatch.setattr(_hip, name, self._recorder(name, inspect.signature(getattr(_hip, name))))
-        # (the predicate behind matmul_reduce_takes_split: a host function of the library, recorded with its ctypes arguments unwrapped)
-        monkeypatch.setattr(_hip.lib, 'eap_gemm_bf16x3_reduce_f32_supported', self._predicate, raising=False)
+        # (the predicate behind matmul_reduce_takes_split: a host function of the library, looked up in the typed prototypes; recorded with any
+        # ctypes arguments unwrapped)
+        monkeypatch.setattr(_hip.abi, 'eap_gemm_bf16x3_reduce_f32_supported', self._predicate)
         self.predicate_answer = 1
 
     def _recorder(self, name, sig):
