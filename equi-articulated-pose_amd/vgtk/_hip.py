@@ -469,6 +469,78 @@ def so3_inter_group_bwd_map(gout, idx, gx, rk, amap, sigma, n):
     return gfeats
 
 
+# ---- the `use_2d` variant with really permuted residual indices (csrc/so3_inter_res.hip) ----------
+
+RESIDUAL_IDENTITY_BYTE = 0xE4        # field z = z
+
+
+def residual_index_pack(fields):
+    """rotated_anchor_idx [...,4] with values 0..3 (any integer dtype, host or device) -> uint8 [...]: field z in bits 2z, 2z+1, the byte
+    eap_so3_residual_index_f32 writes and the `use_2d` grouping kernels read"""
+    if fields.shape[-1] != 4 or fields.dtype.is_floating_point or bool(((fields < 0) | (fields > 3)).any()):
+        raise RuntimeError('residual index: integers 0..3 in a last dimension of 4')
+    f = fields.to(torch.int32)
+    return (f[..., 0] | (f[..., 1] << 2) | (f[..., 2] << 4) | (f[..., 3] << 6)).to(torch.uint8)
+
+
+def residual_index_unpack(packed):
+    """uint8 [...] -> int64 [...,4]: the inverse of residual_index_pack (what torch.argmax returns in the reference)"""
+    if packed.dtype != torch.uint8:
+        raise RuntimeError('residual index: uint8 bytes expected')
+    v = packed.to(torch.int64)
+    return torch.stack([(v >> (2 * z)) & 3 for z in range(4)], dim=-1)
+
+
+def so3_residual_index(idx, q_pose, s_pose, res):
+    """The per-entry residual index of the `use_2d` conv (so3conv/functional.py:L1934-1938): idx int32 [b,p,nn], q_pose [b,p,4,4],
+    s_pose [b,n,4,4], res [4,3,3] -> (shift uint8 [b,p,nn], see residual_index_unpack; nontrivial int32 [b])."""
+    check_input(idx, q_pose, s_pose, res)
+    b, p, nn = idx.shape
+    if tuple(q_pose.shape) != (b, p, 4, 4) or s_pose.dim() != 4 or s_pose.shape[0] != b or tuple(s_pose.shape[2:]) != (4, 4):
+        raise RuntimeError('so3_residual_index: poses must be [b,p,4,4] (query) and [b,n,4,4] (support)')
+    if tuple(res.shape) != (4, 3, 3) or idx.dtype != torch.int32 or any(t.dtype != torch.float32 for t in (q_pose, s_pose, res)):
+        raise RuntimeError('so3_residual_index: int32 idx, float32 poses, float32 res [4,3,3]')
+    shift = torch.empty(b, p, nn, dtype=torch.uint8, device=idx.device)
+    nontrivial = torch.empty(b, dtype=torch.int32, device=idx.device)
+    call('eap_so3_residual_index_f32', shift, b, p, s_pose.shape[1], nn, idx, q_pose, s_pose, res, shift, nontrivial)
+    return shift, nontrivial
+
+
+def _check_res(feats_like, idx, gx, rk, shift, na4):
+    check_input(feats_like, idx, gx, rk, shift)
+    if na4 % 4 != 0 or tuple(rk.shape) != (na4, rk.shape[1], 3):
+        raise RuntimeError('use_2d grouping: na x 4 anchors, rk [na*4,ks,3]')
+    if shift.dtype != torch.uint8 or tuple(shift.shape) != tuple(idx.shape) or idx.dtype != torch.int32:
+        raise RuntimeError('use_2d grouping: idx int32 [b,p,nn] and the residual index uint8 [b,p,nn]')
+    if tuple(gx.shape) != tuple(idx.shape) + (4,) or any(t.dtype != torch.float32 for t in (feats_like, gx, rk)):
+        raise RuntimeError('use_2d grouping: float32 tensors, gx [b,p,nn,4]')
+
+
+def so3_inter_group_fwd_res(feats, idx, gx, rk, shift, sigma):
+    """feats [b,c,n,na*4] -> X [b,c,ks,p,na*4] (reference layout): the gather through the per-entry residual index, any byte
+    (csrc/so3_inter_res.hip)"""
+    b, c, n, na4 = feats.shape
+    p, nn = idx.shape[1], idx.shape[2]
+    ks = rk.shape[1]
+    _check_res(feats, idx, gx, rk, shift, na4)
+    out = torch.empty(b, c, ks, p, na4, dtype=torch.float32, device=feats.device)
+    call('eap_so3_inter_group_fwd_res_f32', out, b, c, p, n, nn, na4 // 4, ks, sigma, feats, idx, gx, rk, shift, out,
+         tag={'flops': 2.0 * b * c * ks * p * nn * na4, 'shape': ('group_fwd_res', b, c, p, nn, na4, ks)})
+    return out
+
+
+def so3_inter_group_bwd_res(gout, idx, gx, rk, shift, sigma, n):
+    """gout [b,c,ks,p,na*4] -> gfeats [b,c,n,na*4] through the per-entry residual index; no float atomics (csrc/so3_inter_res.hip)"""
+    b, c, ks, p, na4 = gout.shape
+    nn = idx.shape[2]
+    _check_res(gout, idx, gx, rk, shift, na4)
+    gfeats = torch.empty(b, c, n, na4, dtype=torch.float32, device=gout.device)
+    ws = torch.empty(max(1, int(abi.eap_so3_inter_group_bwd_res_workspace(b, c, p, n, na4 // 4))), dtype=torch.float32, device=gout.device)
+    call('eap_so3_inter_group_bwd_res_f32', gfeats, b, c, p, n, nn, na4 // 4, ks, sigma, gout, idx, gx, rk, shift, gfeats, ws,
+         tag={'flops': 2.0 * b * c * ks * p * nn * na4, 'shape': ('group_bwd_res', b, c, p, nn, na4, ks)})
+    return gfeats
+
+
 def so3_inter_group_fwd_can_block(c, n, na, ks, has_mult, has_flag):
     return bool(abi.eap_so3_inter_group_fwd_can_block(c, n, na, ks, int(has_mult), int(has_flag)))
 

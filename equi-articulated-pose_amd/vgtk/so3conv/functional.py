@@ -329,27 +329,32 @@ class _InterGroup(torch.autograd.Function):
     """new_feats[b,c,k,p,a] = sum_n feats[b,c,idx_n,perm_n(a)] w(p,a,k,n)  (functional.py:L1221-1261)."""
 
     @staticmethod
-    def forward(ctx, feats, idx, gx, rk, mult, sigma, ident=0, nonident=None, amap=None):
-        # (amap: the per-entry anchor map of a set that is not a group, see _anchor_map -- perm_n(a) = amap[b,p,n,a], no table)
+    def forward(ctx, feats, idx, gx, rk, mult, sigma, ident=0, nonident=None, amap=None, shift=None):
+        # (amap: the per-entry anchor map of a set that is not a group, see _anchor_map -- perm_n(a) = amap[b,p,n,a], no table;
+        # shift: the per-entry residual index of the `use_2d` variant, see _conv_2d -- feats [b,c,n,na*4], perm_n(a, z) = (a, shift_z))
         feats = feats.contiguous()
         ctx.ident = ident
-        ctx.save_for_backward(idx, gx, rk, mult if mult is not None else torch.empty(0), amap)
+        ctx.save_for_backward(idx, gx, rk, mult if mult is not None else torch.empty(0), amap, shift)
         ctx.has_mult = mult is not None
         ctx.sigma = sigma
         ctx.n = feats.shape[2]
+        if shift is not None:
+            return _hip.so3_inter_group_fwd_res(feats, idx, gx, rk, shift, sigma)
         if amap is not None:
             return _hip.so3_inter_group_fwd_map(feats, idx, gx, rk, amap, sigma)
         return _hip.so3_inter_group_fwd(feats, idx, gx, rk, mult, sigma, nonident)
 
     @staticmethod
     def backward(ctx, gout):
-        idx, gx, rk, mult, amap = ctx.saved_tensors
-        if amap is not None:
+        idx, gx, rk, mult, amap, shift = ctx.saved_tensors
+        if shift is not None:
+            g = _hip.so3_inter_group_bwd_res(gout.contiguous(), idx, gx, rk, shift, ctx.sigma, ctx.n)
+        elif amap is not None:
             g = _hip.so3_inter_group_bwd_map(gout.contiguous(), idx, gx, rk, amap, ctx.sigma, ctx.n)
         else:
             g = _hip.so3_inter_group_bwd(gout.contiguous(), idx, gx, rk, mult if ctx.has_mult else None,
                                          ctx.sigma, ctx.n, ctx.ident)
-        return g, None, None, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None, None, None
 
 
 class _IntraGroup(torch.autograd.Function):
@@ -884,10 +889,13 @@ def _dense_forward(feats, W, rows, geo, p):
 class _InterConvArgs:
     """The inputs of _InterConv that carry no gradient, as one record, made where the conv is called."""
 
-    def __init__(self, idx, gx, rk, mult, sigma, ident, nonident=None, anchors=None, epilogue=None, geometry=None, amap=None):
+    def __init__(self, idx, gx, rk, mult, sigma, ident, nonident=None, anchors=None, epilogue=None, geometry=None, amap=None, shift=None):
         self.idx, self.gx, self.rk, self.mult, self.sigma, self.ident, self.nonident = idx, gx, rk, mult, float(sigma), ident, nonident
         # amap uint8 [b,p,nn,na]: the per-entry anchor map of an anchor set that is not a group (_anchor_map) -- the 'anchor map' regime
         self.amap = amap
+        # shift uint8 [b,p,nn]: the per-entry residual index of the `use_2d` variant, really permuted (_conv_2d) -- the 'residual map'
+        # regime: feats [b,c,n,na*4], rk [na*4,ks,3]
+        self.shift = shift
         self.anchors = anchors.detach().contiguous() if (anchors is not None and mult is not None) else None   # the rotations `mult` was built from
         # epilogue: a FoldedEpilogue or a TrainEpilogue;
         # geometry = (q_xyz, xyz, q_rot, rot): what the dense product over the referenced rows is built from (csrc/so3_dense.hip)
@@ -1017,6 +1025,47 @@ def _forward_map(feats, W, args, keep, folded):
         _contract_into(W, x, y[b0:b1].view(b1 - b0, o, p * na), 0, folded, b0)
         x = x if keep else None
     return y, x
+
+
+def _forward_res(feats, W, args, keep, folded):
+    """The forward of the 'residual map' regime (the `use_2d` variant with really permuted residual indices): grouping through the per-entry
+    byte (csrc/so3_inter_res.hip) into the reference layout -- all four residual planes at once -- then the contraction -> (y [b,o,p,na*4], x):
+    x = the intermediate when it is kept for the backward's dW = dY X^T (keep), else None -- X_CHUNK_CLOUDS clouds at a time then."""
+    idx, gx, rk, shift = args.idx, args.gx, args.rk, args.shift
+    b, na4 = feats.shape[0], feats.shape[3]
+    p, o = idx.shape[1], W.shape[0]
+    y = torch.empty(b, o, p, na4, dtype=torch.float32, device=feats.device)
+    step = max(1, b if keep else X_CHUNK_CLOUDS)
+    x = None
+    for b0 in range(0, b, step):
+        b1 = min(b, b0 + step)
+        x = _hip.so3_inter_group_fwd_res(feats[b0:b1], idx[b0:b1], gx[b0:b1], rk, shift[b0:b1], args.sigma)      # [b,c,k,p,a*4]
+        _contract_into(W, x, y[b0:b1].view(b1 - b0, o, p * na4), 0, folded, b0)
+        x = x if keep else None
+    return y, x
+
+
+def _backward_res(gy, W, feats, x, args, need_f, need_w):
+    """The backward of the 'residual map' regime: the textbook dW = dY X^T and dX = W^T dY on the GEMMs of _backward_textbook, then the
+    transposed grouping through the residual index (csrc/so3_inter_res.hip: many-to-one in the support row and, on ties, in the residual
+    plane; accumulated without float atomics) -> (gF, gW)"""
+    b, c, n, na4 = feats.shape
+    idx, gx, rk, shift = args.idx, args.gx, args.rk, args.shift
+    p, ks = idx.shape[1], rk.shape[1]
+    o, ck, pa = W.shape[0], c * ks, p * na4
+    gF = gW = None
+    if need_w:
+        if x is None:
+            x = _hip.so3_inter_group_fwd_res(feats, idx, gx, rk, shift, args.sigma)
+        gW = torch.empty_like(W)          # sum_b gy_b x_b^T
+        _hip.matmul_reduce(gy.view(b, o, pa), x.view(b, ck, pa).transpose(1, 2), gW)
+        x = None
+    if need_f:
+        gx_ = torch.empty(b, ck, pa, dtype=torch.float32, device=gy.device)      # W^T gy
+        Wt = W.t().contiguous()
+        _hip.matmul(Wt, gy.view(b, o, pa), gx_)
+        gF = _hip.so3_inter_group_bwd_res(gx_.view(b, c, ks, p, na4), idx, gx, rk, shift, args.sigma, n)
+    return gF, gW
 
 
 # ---- regime 'narrow input': C*K <= 32 contraction indices, no input gradient, training-mode norm in the node (csrc/narrow_conv.hip) ----
@@ -1292,11 +1341,13 @@ class _InterConv(torch.autograd.Function):
         folded = None if train_ep is not None else args.epilogue      # (the list kernels know nothing of a TrainEpilogue: `applied` stays False there)
         if folded is not None and (needs_grad or not folded.inference):
             raise RuntimeError('a folded epilogue is an inference-time fusion: build and use it under torch.no_grad()')
-        if args.amap is not None:
-            # an anchor set that is not a group, really permuted: the per-entry map has no inverse-list or dense form
+        if args.amap is not None or args.shift is not None:
+            # an anchor set that is not a group, really permuted ('anchor map'), or the 60 x 4 anchor axis of the `use_2d` variant with really
+            # permuted residual indices ('residual map', feats [b,c,n,na*4]): a per-entry map has no inverse-list or dense form
+            regime, fwd = ('anchor map', _forward_map) if args.shift is None else ('residual map', _forward_res)
             if FORWARD_LOG is not None:
-                FORWARD_LOG.append({'channels': (c, o), 'dense': False, 'parts': None, 'regime': 'anchor map'})
-            y, x = _forward_map(feats, W, args, needs_grad and ctx.needs_input_grad[1], folded)
+                FORWARD_LOG.append({'channels': (c, o), 'dense': False, 'parts': None, 'regime': regime})
+            y, x = fwd(feats, W, args, needs_grad and ctx.needs_input_grad[1], folded)
             ctx.bn, ctx.conv_args, ctx.head, ctx.layout, ctx.plan = None, args, None, 0, None
             ctx.W_param = weakref.ref(W_param)
             ctx.save_for_backward(W, x, idx, args.gx, rk, None, nonident, feats, None)
@@ -1352,10 +1403,11 @@ class _InterConv(torch.autograd.Function):
                                      'regime': 'narrow input', 'norm': 'in the node'})
             gF = None
             gW, g_bn_w, g_bn_b = _backward_narrow(gy, W, x, ctx.bn, need_w)
-        elif args.amap is not None:
+        elif args.amap is not None or args.shift is not None:
+            regime, bwd = ('anchor map', _backward_map) if args.shift is None else ('residual map', _backward_res)
             if BACKWARD_LOG is not None:
-                BACKWARD_LOG.append({'channels': (feats.shape[1], W.shape[0]), 'support_rows': n, 'referenced_rows_max': 0, 'regime': 'anchor map'})
-            gF, gW = _backward_map(gy, W, feats, x, args, need_f, need_w)
+                BACKWARD_LOG.append({'channels': (feats.shape[1], W.shape[0]), 'support_rows': n, 'referenced_rows_max': 0, 'regime': regime})
+            gF, gW = bwd(gy, W, feats, x, args, need_f, need_w)
         elif plan is not None and plan.parts is not None:
             gF, gW = _backward_dense_parts(gy, W, feats, head, plan.geo(), need_f, need_w)
         elif plan is not None:
@@ -1613,8 +1665,9 @@ def inter_so3conv_fused_art_mode(xyz, pose, feats, W, seg_labels, n_neighbor, an
 # (na, 4) -- every anchor times four residual rotations about the y axis
 # ------------------------------------------------------------------------------------------------
 _RES_2D = {}
-SLOW_2D_CHUNK = 64      # query points per slab of the general (really permuted) 2-D path
-FORCE_GENERAL_2D = False    # test knob: the general path even when no residual index is permuted
+SLOW_2D_CHUNK = 64      # query points per slab of the tensor form of the really permuted 2-D conv
+FORCE_GENERAL_2D = False    # test knob: the tensor form at any size, even when no residual index is permuted
+KERNEL_2D_MIN_POINTS = SLOW_2D_CHUNK + 1     # clouds of at least this many points take the 'residual map' kernels, see _conv_2d
 
 
 def _res_rot_2d(device):
@@ -1648,8 +1701,18 @@ def _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, p
     With the residual index unpermuted -- permute_modes == 0, or every entry's relative rotation closest to the identity among
     the four residual rotations (identity poses: what the shipped model feeds) -- output anchor (a, z) reads feature anchor (a, z)
     only, with the weights of rotation A_a RES_z: FOUR ordinary convolutions on the fused kernels, one per residual rotation,
-    over the anchor sets {A_a RES_z}_a (the poses still rotate the offsets).  Otherwise the reference's expression in device
-    tensor ops, a slab of SLOW_2D_CHUNK query points at a time (correct, not accelerated: the permuted 2-D case has no kernel)."""
+    over the anchor sets {A_a RES_z}_a (the poses still rotate the offsets).
+
+    With a really permuted residual index (one rotation per rigid part, one per point) -- the 'residual map' regime: the index as one
+    byte per entry (eap_so3_residual_index_f32; one host read of its per-cloud flags, as _anchor_map), the grouping through it for all
+    240 anchors at once and its transpose without float atomics (csrc/so3_inter_res.hip), ONE autograd node (_InterConv for the module,
+    _InterGroup for the functional grouping API).
+
+    KERNEL_2D_MIN_POINTS: a cloud of at most one slab (p <= SLOW_2D_CHUNK) keeps the reference's expression in device tensor ops -- there
+    it materialises everything exactly once, a few MB, and it is the form the 40-point reference-made fixture pins (the fixture's test
+    asserts that the materialised weights were asked for).  FORCE_GENERAL_2D selects that tensor form at any size, a slab of
+    SLOW_2D_CHUNK query points at a time: the comparator the tests hold the kernels against, with residual_rotation_index as the tensor
+    statement of the index."""
     _check_inputs(xyz, feats)
     b, c, p, na4 = feats.shape
     na = anchors.shape[0]
@@ -1658,11 +1721,27 @@ def _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, p
     res = _res_rot_2d(feats.device)
     tot = torch.matmul(anchors.unsqueeze(1), res.unsqueeze(0)).contiguous()                          # [na,4,3,3] = A_a RES_z (L1921)
     ball_idx = cuda_nn.ball_query(xyz, xyz, radius, n_neighbor)
-    shift = None
+    shift = packed = None
     if permute and pose is not None:
-        shift = residual_rotation_index(pose, ball_idx)
-        if not FORCE_GENERAL_2D and bool((shift == torch.arange(4, device=shift.device)).all()):
-            shift = None
+        if FORCE_GENERAL_2D or p < KERNEL_2D_MIN_POINTS:
+            shift = residual_rotation_index(pose, ball_idx)
+            if not FORCE_GENERAL_2D and bool((shift == torch.arange(4, device=shift.device)).all()):
+                shift = None
+        else:
+            rot = pose.contiguous()
+            if rot.shape[-2:] != (4, 4) or rot.dtype != torch.float32:
+                raise RuntimeError('so3conv: pose must be float32 [b,p,4,4]')
+            packed, nontrivial = _hip.so3_residual_index(ball_idx, rot, rot, res)
+            if int(nontrivial.max()) == 0:            # (one host read) unpermuted: the four fused convolutions below
+                packed = None
+    if packed is not None:
+        rk = rotated_kernels(tot.view(na4, 3, 3), kernels)                                           # [na*4,ks,3]
+        gx, _ = _hip.so3_prep(xyz, xyz, ball_idx, rot, rot, anchors.contiguous(), 0)                  # rotated offsets (L1859-1862)
+        if contract:
+            y = _InterConv.apply(feats, W, None, None, _InterConvArgs(ball_idx, gx, rk, None, sigma, 0, shift=packed))
+        else:
+            y = _InterGroup.apply(feats, ball_idx, gx, rk, None, float(sigma), 0, None, None, packed)
+        return ball_idx, InterWeights(gx, rk, sigma), y
     f5 = feats.contiguous().view(b, c, p, na, 4)
     if shift is None:
         outs = []
@@ -1679,7 +1758,7 @@ def _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, p
         gx, _ = _hip.so3_prep(xyz, xyz, ball_idx, None if pose is None else pose.contiguous(), None if pose is None else pose.contiguous(),
                               anchors.contiguous(), 0)
         return ball_idx, InterWeights(gx, rk, sigma), y
-    # the general case: really permuted residual indices
+    # the tensor form of the really permuted case (small clouds, FORCE_GENERAL_2D)
     rk = rotated_kernels(tot.view(na4, 3, 3), kernels)                                               # [na*4,ks,3]
     rot = pose.contiguous()
     gx, _ = _hip.so3_prep(xyz, xyz, ball_idx, rot, rot, anchors.contiguous(), 0)                      # rotated offsets (L1859-1862)

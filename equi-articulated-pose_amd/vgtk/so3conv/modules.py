@@ -119,7 +119,8 @@ class InterSO3PoseConv(InterSO3Conv):
         if self.use_2d:
             # anchor axis (60, 4) = anchors x residual rotations about y (functional.py:L1718-2130; scripts/train/eyeglasses.sh):
             # four ordinary convolutions on the fused kernels while the residual index is unpermuted (identity poses), the
-            # reference's expression in device tensor ops otherwise
+            # 'residual map' kernels (csrc/so3_inter_res.hip) when poses really permute it; clouds of at most
+            # L.SLOW_2D_CHUNK points keep the reference's expression in device tensor ops
             if inter_idx is None and self.stride > 1:
                 raise NotImplementedError('use_2d with stride > 1 (the reference forces stride 1 for this configuration)')
             w, feats = L.inter_so3conv_fused_2d(x.xyz, x.pose, x.feats, self.basic_conv.W, self.n_neighbor, self.anchors, self.kernels,

@@ -259,6 +259,37 @@ int eap_so3_inter_group_bwd_map_f32(int b, int c, int p, int n, int nn, int na, 
                                     const float *gout, const int32_t *idx, const float *gx, const float *rk,
                                     const uint8_t *amap, float *gfeats, float *workspace, eap_stream_t stream);
 
+/* ---- the `use_2d` variant with really permuted residual indices (so3conv/functional.py:L1718-2130; csrc/so3_inter_res.hip) ---- */
+
+/* so3_residual_index: rotated_anchor_idx of so3conv/functional.py:L1934-1938, one byte per entry.
+ * idx int32 [b,p,nn], q_pose [b,p,4,4], s_pose [b,n,4,4], res [4,3,3] (the four residual rotations about y, L1921)
+ *  -> shift uint8 [b,p,nn]: field z (bits 2z, 2z+1) = argmax_j tr(R_rel^T RES_z RES_j^T) with R_rel = R_p R_idx^T, compared with a
+ *     strict >, so the lowest j wins a tie (torch.argmax); the four fields are a cyclic shift only where no trace ties;
+ *     nontrivial int32 [b] = 1 for clouds where some entry's byte is not the identity byte 0xE4 (field z = z); zeroed by the call. */
+int eap_so3_residual_index_f32(int b, int p, int n, int nn, const int32_t *idx, const float *q_pose,
+                               const float *s_pose, const float *res, uint8_t *shift, int32_t *nontrivial,
+                               eap_stream_t stream);
+
+/* so3_inter_group_fwd_res: so3conv/functional.py:L1944-1957 (shadow row, gather of the neighbours, gather of the residual plane through
+ * the index) and L2124 (the weighted sum) without the [b,p,nn,na,4,c] and [b,p,na,4,ks,nn] tensors,
+ * out[b,c,k,p,a,z] = sum_n w(p,(a,z),k,n) feats[b,c,idx_n,a,shift_z(b,p,n)].
+ * feats [b,c,n,na,4], idx int32 [b,p,nn] (an index >= n names the shadow row: skipped), gx float4 [b,p,nn] from so3_prep,
+ * rk [na*4,ks,3] = A_a RES_z kappa_k, shift uint8 [b,p,nn] (ANY byte: many-to-one maps included) -> out [b,c,ks,p,na*4] (the
+ * reference layout).  na <= 64, ks <= 32; feats and out 16-byte aligned. */
+int eap_so3_inter_group_fwd_res_f32(int b, int c, int p, int n, int nn, int na, int ks, float sigma,
+                                    const float *feats, const int32_t *idx, const float *gx, const float *rk,
+                                    const uint8_t *shift, float *out, eap_stream_t stream);
+
+/* so3_inter_group_bwd_res: the transpose of the above w.r.t. feats (autograd of so3conv/functional.py:L1944-1957 + L2124),
+ * gfeats[b,c,q,a,s] = sum_{(p,n): idx = q} sum_{z: shift_z = s} sum_k w(p,(a,z),k,n) gout[b,c,k,p,a,z].
+ * Many-to-one in q (and, on ties, in s): private slabs in `workspace` (eap_so3_inter_group_bwd_res_workspace floats, zeroed by the
+ * call) accumulated in a fixed order and reduced by a second kernel -- no float atomics, bit-identical run to run, lists that name
+ * a row twice included.  Same limits; gout and gfeats 16-byte aligned. */
+int64_t eap_so3_inter_group_bwd_res_workspace(int b, int c, int p, int n, int na);
+int eap_so3_inter_group_bwd_res_f32(int b, int c, int p, int n, int nn, int na, int ks, float sigma,
+                                    const float *gout, const int32_t *idx, const float *gx, const float *rk,
+                                    const uint8_t *shift, float *gfeats, float *workspace, eap_stream_t stream);
+
 /* Which entry-list grouping kernel serves eap_so3_inter_group_fwd*_f32 / eap_so3_inter_group_inv*_f32 when no anchor
  * permutation is in play: 2 (default) = the fp32-MFMA kernel with two channel tiles per wave where the channel count fills
  * 64-channel blocks (csrc/so3_inter_lists2.hip), 1 = always the one-tile fp32-MFMA kernel (csrc/so3_inter_lists.hip);
