@@ -12,6 +12,7 @@ import, and non-device tensors are rejected.
 import ctypes
 import os
 import re
+import struct
 import types
 import weakref
 
@@ -799,10 +800,13 @@ class DenseGeometry:
             keys = torch.empty(b, p, dtype=torch.int64 if _dense_wide(memb) else torch.int32, device=dev)
             call('eap_so3_dense_point_keys_wide' if _dense_wide(memb) else 'eap_so3_dense_point_keys', memb, b, p, memb, keys)
             order = torch.sort(keys, dim=1, stable=True).indices                               # int64 [b,p]: column j of the product is point order[b, j]
-            q_xyz = q_xyz.gather(2, order[:, None, :].expand(b, 3, p)).contiguous()
-            memb = memb.gather(1, order[:, :, None].expand(b, p, memb.shape[2])).contiguous()
-            self.order = order.to(torch.int32).contiguous()
-            self.pivot_pos = (order[0] == 0).to(torch.int32).argmax().to(torch.int32).view(1)   # the column of cloud 0 that is point 0
+            if NATIVE_NORM_GLUE and q_xyz.dtype == torch.float32 and tuple(q_xyz.shape) == (b, 3, p):
+                self.order, memb, q_xyz, self.pivot_pos = so3_dense_point_order(order.contiguous(), memb, q_xyz.contiguous())
+            else:
+                q_xyz = q_xyz.gather(2, order[:, None, :].expand(b, 3, p)).contiguous()
+                memb = memb.gather(1, order[:, :, None].expand(b, p, memb.shape[2])).contiguous()
+                self.order = order.to(torch.int32).contiguous()
+                self.pivot_pos = (order[0] == 0).to(torch.int32).argmax().to(torch.int32).view(1)   # the column of cloud 0 that is point 0
         self.b, self.p, self.na, self.ks, self.rp, self.nn, self.memb, self.sigma = b, p, na, ks, int(rp), int(nn), memb, float(sigma)
         self.n_rows = n_rows                      # int32 [b] or None: the products stop at every cloud's own rows (include/eap_hip.h)
         p_pad, kd_pad = (p + 31) // 32 * 32, (ks * self.rp + 31) // 32 * 32
@@ -928,9 +932,12 @@ def so3_dense_gplanes(fc4, W3, geo):
     ft = fc4.permute(0, 3, 2, 1).contiguous()                                       # [b,na,rp,c]
     # |G[o,(k,r),a]| <= max_k sum_c |W[o,c,k]| x max_{c,r} |F[c,r,a]|: two reductions over small tensors (the tighter sum_c |W| max_r |F_c|
     # is a matrix product whose launch path cost more host time than it saved range)
-    wsum = W3.abs().sum(1).view(o, geo.ks).amax(1)                                  # [o]
-    fm = fc4.abs().amax((1, 2))                                                     # [b,na]
-    bound = (fm[:, :, None] * (wsum * 1.0001)[None, None, :]).contiguous()          # [b,na,o]
+    if NATIVE_NORM_GLUE:
+        bound = so3_dense_gplanes_bound(W3, fc4, geo.ks)
+    else:
+        wsum = W3.abs().sum(1).view(o, geo.ks).amax(1)                                  # [o]
+        fm = fc4.abs().amax((1, 2))                                                     # [b,na]
+        bound = (fm[:, :, None] * (wsum * 1.0001)[None, None, :]).contiguous()          # [b,na,o]
     scale = torch.empty(2, b, na, o, dtype=torch.float32, device=fc4.device)
     planes = torch.empty(b * na * o * ((geo.ks * rp + 31) // 32 * 32), dtype=torch.int32, device=fc4.device)
     call('eap_so3_dense_gplanes_f32', fc4, b, o, c, na, geo.ks, rp, W3, ft, geo.n_rows, bound, scale, planes,
@@ -939,6 +946,89 @@ def so3_dense_gplanes(fc4, W3, geo):
 
 
 GPLANES = True      # False: G by a GEMM + the split pass, as round 5 (tests)
+
+
+# ---- the per-channel bookkeeping of the conv + norm nodes, one launch per site (csrc/norm_fold.hip) ----------------------
+# The arithmetic between the big kernels of a node (partial sums -> moments -> the affine map and the running statistics; the backward's
+# coefficients and bounds; the bound of the forward's operand; what follows the sort of the query points) in the library instead of as
+# 10 - 35 tensor expressions per site.  False: the tensor expressions (tests, A/B runs).  They also remain where an all-reduce stands
+# between the sums and the coefficients (SyncBatchNorm) and for tensors that are not on the device.
+NATIVE_NORM_GLUE = True
+
+
+def _f64_bits(x):
+    """a float64 scalar as the int64 with its bit pattern (the header's vocabulary has no double)"""
+    return struct.unpack('<q', struct.pack('<d', float(x)))[0]
+
+
+def norm_fold_train(ps, pq, pivot, count, gamma, beta, eps, momentum, running_mean, running_var):
+    """ps, pq float32 [o, parts] (partial sums of y - pivot and its square), pivot a float32 view of o elements, a fixed stride apart ->
+    scale, shift float32 [o], mean, invstd float64 [o], a copy of beta and inv_gamma float32 [o]; the running statistics (or None, None) are
+    updated in place (vgtk.so3conv.blocks: batch_moments, update_running_stats, affine_from_moments)"""
+    check_input(ps, pq, gamma, beta, running_mean, running_var)
+    o, parts = ps.shape
+    if pivot.dim() != 1 or pivot.shape[0] != o or pivot.dtype != torch.float32 or not pivot.is_cuda:
+        raise RuntimeError('norm_fold_train: pivot must be a float32 device vector (any stride) of one element per channel')
+    dev = ps.device
+    scale, shift, beta_copy, inv_gamma = (torch.empty(o, dtype=torch.float32, device=dev) for _ in range(4))
+    mean, invstd = (torch.empty(o, dtype=torch.float64, device=dev) for _ in range(2))
+    call('eap_norm_fold_train_f32', ps, o, parts, max(int(pivot.stride(0)), 1), int(count), _f64_bits(eps), _f64_bits(momentum), ps, pq, pivot, gamma,
+         beta, running_mean, running_var, scale, shift, mean, invstd, beta_copy, inv_gamma)
+    return scale, shift, mean, invstd, beta_copy, inv_gamma
+
+
+def norm_fold_bwd(pg, pgx, k1, count, beta=None, inv_gamma=None, gmax=None, xmax=None):
+    """pg, pgx float32 [o, parts] (partial sums of g and g xhat), k1 = the forward's scale -> (d gamma, d beta, k2, k3) float32 [o]; with beta,
+    inv_gamma [o] and the row maxima gmax, xmax [b,o,na] (the dense node) also coef [5,o], bound [b,o,na] and colmax [b,na]"""
+    check_input(pg, pgx, k1, beta, inv_gamma, gmax, xmax)
+    o, parts = pg.shape
+    dev = pg.device
+    dgamma, dbeta, k2, k3 = (torch.empty(o, dtype=torch.float32, device=dev) for _ in range(4))
+    if gmax is None:
+        call('eap_norm_fold_bwd_f32', pg, o, parts, 0, 0, int(count), pg, pgx, k1, None, None, None, None, dgamma, dbeta, k2, k3, None, None, None)
+        return dgamma, dbeta, k2, k3
+    b, _, na = gmax.shape
+    coef = torch.empty(5, o, dtype=torch.float32, device=dev)
+    bound = torch.empty(b, o, na, dtype=torch.float32, device=dev)
+    colmax = torch.empty(b, na, dtype=torch.float32, device=dev)
+    call('eap_norm_fold_bwd_f32', pg, o, parts, b, na, int(count), pg, pgx, k1, beta, inv_gamma, gmax, xmax, dgamma, dbeta, k2, k3, coef, bound, colmax)
+    return dgamma, dbeta, k2, k3, coef, bound, colmax
+
+
+def so3_dense_zbound(colmax, cnt, n_rows, rp, p, ldz):
+    """-> words float32 [b, ldz / 4]: the bound on Z's columns, four to a word, from colmax [b,na] and the number of points that list every row
+    (cnt int32 [b, >= rp], counted up to n_rows [b] and clamped to 0 .. p)"""
+    b, na = colmax.shape
+    if cnt.dtype != torch.int32 or n_rows.dtype != torch.int32 or cnt.stride(1) != 1 or not n_rows.is_contiguous():
+        raise RuntimeError('so3_dense_zbound: cnt and n_rows must be int32, the rows of cnt contiguous')
+    words = torch.empty(b, ldz // 4, dtype=torch.float32, device=colmax.device)
+    call('eap_so3_dense_zbound_f32', colmax, b, na, int(rp), int(p), int(ldz), cnt.stride(0), colmax, cnt, n_rows, words)
+    return words
+
+
+def so3_dense_gplanes_bound(W3, fc4, ks):
+    """-> bound float32 [b,na,o] = max_{c,r} |fc4| x (max_k sum_c |W3| x 1.0001), fc4 [b,c,rp,na], W3 [o ks, c]"""
+    check_input(W3, fc4)
+    b, c, rp, na = fc4.shape
+    o = W3.shape[0] // ks
+    dev = fc4.device
+    fpart = torch.empty(b, c, na, dtype=torch.float32, device=dev)
+    wsum = torch.empty(o, dtype=torch.float32, device=dev)
+    bound = torch.empty(b, na, o, dtype=torch.float32, device=dev)
+    call('eap_so3_dense_gplanes_bound_f32', fc4, b, o, c, na, int(ks), rp, W3, fc4, fpart, wsum, bound)
+    return bound
+
+
+def so3_dense_point_order(order, memb, q_xyz):
+    """order int64 [b,p] (the indices of a sort), memb int32 [b,p,16 or 32], q_xyz float32 [b,3,p] -> (order as int32, memb and q_xyz gathered
+    through it, pivot_pos int32 [1]: the column of cloud 0 that is point 0)"""
+    check_input(order, memb, q_xyz)
+    b, p = order.shape
+    order32 = torch.empty(b, p, dtype=torch.int32, device=order.device)
+    memb_out, xyz_out = torch.empty_like(memb), torch.empty_like(q_xyz)
+    pivot_pos = torch.empty(1, dtype=torch.int32, device=order.device)
+    call('eap_so3_dense_point_order', order, b, p, memb.shape[2], order, memb, q_xyz, order32, memb_out, xyz_out, pivot_pos)
+    return order32, memb_out, xyz_out, pivot_pos
 
 
 def so3_dense_fwd(g, geo, p, c=0, ldg=None, out=None, col_map=None, operand=None, o=None):
@@ -981,11 +1071,12 @@ def _dense_fwd_yt(g, geo, p, c, ldg, operand, o):
     return _dense_product(1, geo, b, o, p, 0, scale, planes, yt, 2.0 * b * c * geo.ks * na * (p * geo.nn + o * p - o * geo.rp))
 
 
-def so3_dense_fwd_bnact(g, geo, p, c, ldg, norm_moments, operand=None, o=None, affine=None):
+def so3_dense_fwd_bnact(g, geo, p, c, ldg, norm_moments, operand=None, o=None, affine=None, partials=False):
     """The dense forward with the training-mode BatchNorm + leaky_relu behind it applied by the re-ordering pass (the conv + BatchNorm
     node of vgtk/so3conv/functional.py): product -> Yt; statistics pass over Yt; norm_moments(s1, s2, pivot, count) -> (scale, shift, slope)
     per channel (float32 [o]); y' = leaky(scale y + shift) written through the geometry's point order.  affine = (scale, shift, slope)
-    instead of norm_moments: an inference-mode norm folded into one per-channel map (FoldedEpilogue), no statistics pass.  -> y' [b,o,p,na]"""
+    instead of norm_moments: an inference-mode norm folded into one per-channel map (FoldedEpilogue), no statistics pass.  partials:
+    norm_moments takes the partial sums float32 [o, parts] and the pivot as a float32 view of Yt (eap_norm_fold_train_f32 sums them).  -> y' [b,o,p,na]"""
     yt = _dense_fwd_yt(g, geo, p, c, ldg, operand, o)
     b, na, o = yt.shape[0], geo.na, yt.shape[2]
     if affine is not None:
@@ -994,15 +1085,18 @@ def so3_dense_fwd_bnact(g, geo, p, c, ldg, norm_moments, operand=None, o=None, a
         # moments of every channel over (cloud, anchor, point): Yt is [b na][o][p] for the statistics kernel; the pivot is its own first element
         ps, pq = _partials(yt, b * na, o, p)
         call('eap_bn_stats_f32', yt, b * na, o, p, yt, ps, pq)
-        bn_scale, bn_shift, slope = norm_moments(ps.sum(1, dtype=torch.float64), pq.sum(1, dtype=torch.float64), yt[0, 0, :, 0].double(), b * na * p)
+        if partials:
+            bn_scale, bn_shift, slope = norm_moments(ps, pq, yt[0, 0, :, 0], b * na * p)
+        else:
+            bn_scale, bn_shift, slope = norm_moments(ps.sum(1, dtype=torch.float64), pq.sum(1, dtype=torch.float64), yt[0, 0, :, 0].double(), b * na * p)
     y = torch.empty(b, o, p, na, dtype=torch.float32, device=yt.device)
     call('eap_so3_dense_untranspose_bnact_f32', yt, b, o, p, na, p, geo.order, yt, bn_scale, bn_shift, slope, y)
     return y
 
 
-def bn_act_bwd_reduce_fromy(gy, y, beta, inv_gamma, slope):
+def bn_act_bwd_reduce_fromy(gy, y, beta, inv_gamma, slope, partials=False):
     """gy, y [b,c,p,na] (y = the layer's activated output) -> (sum g, sum g xhat) float64 [c] and the per-row maxima gmax, xmax float32 [b,c,na]
-    (csrc/bn_act.hip bn_act_bwd_reduce_fromy_kernel)."""
+    (csrc/bn_act.hip bn_act_bwd_reduce_fromy_kernel).  partials: the two sums as the kernel leaves them, float32 [c, parts], for norm_fold_bwd."""
     b, c, p, na = y.shape
     n = p * na
     nblk = int(abi.eap_bn_act_fromy_blocks(n, na))
@@ -1011,6 +1105,8 @@ def bn_act_bwd_reduce_fromy(gy, y, beta, inv_gamma, slope):
     gmax = torch.empty(b, c, na, dtype=torch.int32, device=y.device)
     xmax = torch.empty_like(gmax)
     call('eap_bn_act_bwd_reduce_fromy_f32', y, b, c, n, na, slope, gy, y, beta, inv_gamma, pg, pgx, gmax, xmax)
+    if partials:
+        return pg, pgx, gmax.view(torch.float32), xmax.view(torch.float32)
     return pg.sum(1, dtype=torch.float64), pgx.sum(1, dtype=torch.float64), gmax.view(torch.float32), xmax.view(torch.float32)
 
 
@@ -1139,14 +1235,17 @@ def _narrow_partials(x, b, o, n):
             torch.empty(o, b * nseg, dtype=torch.float32, device=x.device))
 
 
-def narrow_conv_stats(W, x):
-    """-> (sum, sumsq) of y - pivot per channel (float64 [o]) and pivot (float64 [o]) for y = W x, which is not written"""
+def narrow_conv_stats(W, x, partials=False):
+    """-> (sum, sumsq) of y - pivot per channel (float64 [o]) and pivot (float64 [o]) for y = W x, which is not written; partials: the sums as
+    the kernel leaves them, float32 [o, parts], and the pivot in float32, for norm_fold_train"""
     check_input(W, x)
     b, ck, n = x.shape
     o = W.shape[0]
     ps, pq = _narrow_partials(x, b, o, n)
     pivot = torch.empty(o, dtype=torch.float32, device=x.device)
     call('eap_narrow_conv_stats_f32', x, b, o, ck, n, W, x, pivot, ps, pq)
+    if partials:
+        return ps, pq, pivot
     return ps.sum(1, dtype=torch.float64), pq.sum(1, dtype=torch.float64), pivot.double()
 
 
@@ -1160,13 +1259,15 @@ def narrow_conv_bnact_fwd(W, x, scale, shift, slope):
     return y
 
 
-def narrow_conv_bwd_reduce(gy, x, W, scale, shift, mean, invstd, slope):
-    """-> sum(g), sum(g xhat) per channel, float64 [o]"""
+def narrow_conv_bwd_reduce(gy, x, W, scale, shift, mean, invstd, slope, partials=False):
+    """-> sum(g), sum(g xhat) per channel, float64 [o]; partials: as the kernel leaves them, float32 [o, parts], for norm_fold_bwd"""
     check_input(gy, x, W, scale, shift, mean, invstd)
     b, ck, n = x.shape
     o = W.shape[0]
     pg, pgx = _narrow_partials(x, b, o, n)
     call('eap_narrow_conv_bwd_reduce_f32', x, b, o, ck, n, slope, gy, x, W, scale, shift, mean, invstd, pg, pgx)
+    if partials:
+        return pg, pgx
     return pg.sum(1, dtype=torch.float64), pgx.sum(1, dtype=torch.float64)
 
 

@@ -627,6 +627,25 @@ class TrainEpilogue:
         self.saved = (scale, norm.bias.detach().float().clone(), inv_gamma.contiguous(), total)
         return scale.contiguous(), shift.contiguous(), float(norm.negative_slope)
 
+    def takes_partials(self, t):
+        """the moments of `t`'s node come from moments_from_partials: the switch is on, the tensors are on the device, and no exchange stands
+        between the sums and the coefficients (SyncBatchNorm over several ranks keeps the tensor expressions of `moments`)"""
+        from .blocks import _syncing
+        norm = self.norm
+        return bool(_hip.NATIVE_NORM_GLUE and t.is_cuda and not _syncing(norm.sync) and norm.weight.dtype == torch.float32
+                    and norm.bias.dtype == torch.float32 and (norm.running_mean is None or norm.running_mean.dtype == torch.float32))
+
+    def moments_from_partials(self, ps, pq, pivot, count):
+        """`moments` from the partial sums float32 [o, parts] as the statistics kernels leave them and a float32 pivot (any stride), in one
+        launch (csrc/norm_fold.hip: the same float64 arithmetic; the partials are summed there).  Same results, same self.stats / self.saved."""
+        norm = self.norm
+        running = (None, None) if norm.running_mean is None else (norm.running_mean, norm.running_var)
+        scale, shift, mean, invstd, beta, inv_gamma = _hip.norm_fold_train(ps, pq, pivot, count, norm.weight.detach().contiguous(),
+                                                                          norm.bias.detach().contiguous(), norm.eps, norm.momentum, *running)
+        self.stats = (mean, invstd)
+        self.saved = (scale, beta, inv_gamma, count)
+        return scale, shift, float(norm.negative_slope)
+
 
 def _contract_into(W, x, y, layout, epilogue=None, b0=0, x_bound=None):
     """y[b,o,pa] = W . x for the intermediate in one of its three layouts (epilogue: see FoldedEpilogue; b0 = first
@@ -967,15 +986,17 @@ def _forward_dense(feats, W, plan, p, train_ep, folded):
     if plan.parts is not None:
         return _dense_forward_parts(feats, W, rows, geo, p), None
     moments = affine = None
+    partials = False
     if train_ep is not None:
-        ep, moments = train_ep, train_ep.moments
+        partials = train_ep.takes_partials(feats)
+        ep, moments = train_ep, (train_ep.moments_from_partials if partials else train_ep.moments)
     elif folded is not None and folded.residual is None:
         # an inference-mode norm folded into one per-channel map: applied by the re-ordering pass too
         ep, affine = folded, (folded.scale, folded.shift, folded.slope)
     else:
         return _dense_forward(feats, W, rows, geo, p), None
     g, ldg, operand = _dense_operand(feats, W, rows, geo)
-    y = _hip.so3_dense_fwd_bnact(g, geo, p, feats.shape[1], ldg, moments, operand=operand, o=W.shape[0], affine=affine)
+    y = _hip.so3_dense_fwd_bnact(g, geo, p, feats.shape[1], ldg, moments, operand=operand, o=W.shape[0], affine=affine, partials=partials)
     ep.applied = True
     return y, (None if train_ep is None else train_ep.saved + (float(train_ep.norm.negative_slope), bool(train_ep.norm.sync)))
 
@@ -1080,12 +1101,22 @@ def _forward_narrow(feats, W, args, train_ep):
     b, c, _, na = feats.shape
     p, ks, o = idx.shape[1], rk.shape[1], W.shape[0]
     x = _hip.so3_inter_group_fwd(feats, idx, args.gx, rk, args.mult, args.sigma, args.nonident).view(b, c * ks, p * na)
-    s1, s2, pivot = _hip.narrow_conv_stats(W, x)
-    scale, shift, slope = train_ep.moments(s1, s2, pivot, b * p * na)
+    if train_ep.takes_partials(x):
+        scale, shift, slope = train_ep.moments_from_partials(*_hip.narrow_conv_stats(W, x, partials=True), b * p * na)
+    else:
+        s1, s2, pivot = _hip.narrow_conv_stats(W, x)
+        scale, shift, slope = train_ep.moments(s1, s2, pivot, b * p * na)
     y = _hip.narrow_conv_bnact_fwd(W, x, scale, shift, slope).view(b, o, p, na)
     train_ep.applied = True
     mean, invstd = train_ep.stats
     return y, x, (scale, shift, mean.float(), invstd.float(), train_ep.saved[3], slope, bool(train_ep.norm.sync))
+
+
+def _native_norm_bwd(gy, count, sync):
+    """the backward's per-channel sums and coefficients come from csrc/norm_fold.hip (see _hip.NATIVE_NORM_GLUE): not when the sums of several
+    ranks are exchanged first (the element count is then a tensor too)"""
+    from .blocks import _syncing
+    return bool(_hip.NATIVE_NORM_GLUE and gy.is_cuda and isinstance(count, int) and not _syncing(sync))
 
 
 def _backward_narrow(gy, W, x, bn, need_w):
@@ -1095,6 +1126,10 @@ def _backward_narrow(gy, W, x, bn, need_w):
     scale, shift, mean, invstd, count, slope, sync = bn
     b, o = gy.shape[0], gy.shape[1]
     gy = gy.view(b, o, -1)
+    if _native_norm_bwd(gy, count, sync):
+        # sums, d gamma, d beta, k2 and k3 in one launch (csrc/norm_fold.hip)
+        g_bn_w, g_bn_b, k2, k3 = _hip.norm_fold_bwd(*_hip.narrow_conv_bwd_reduce(gy, x, W, scale, shift, mean, invstd, slope, partials=True), scale, count)
+        return (_hip.narrow_conv_bwd_dw(gy, x, W, scale, shift, mean, invstd, k2, k3, slope) if need_w else None), g_bn_w, g_bn_b
     sg, sgx = _hip.narrow_conv_bwd_reduce(gy, x, W, scale, shift, mean, invstd, slope)
     gW = None
     if need_w:
@@ -1167,15 +1202,24 @@ def _backward_dense(gy, W, feats, head, geo, bn, yact, need_f, need_w):
         # formed inside the split of the product's stored operand
         k1, beta, inv_gamma, count, slope, sync = bn
         from .blocks import all_reduce_sums
-        sg, sgx, gmax, xmax = _hip.bn_act_bwd_reduce_fromy(gy, yact, beta, inv_gamma, slope)
-        g_bn_w, g_bn_b = sgx.float(), sg.float()
-        tg, tgx = all_reduce_sums(sg, sgx, sync=sync)                        # whole-batch means (SyncBatchNorm backward)
-        k2 = (k1.double() * tg / count).float()
-        k3 = (k1.double() * tgx / count).float()
-        coef = torch.stack([k1, k2, k3, beta, inv_gamma]).contiguous()      # [5, o]
-        bound = (k1.abs()[None, :, None] * gmax + k2.abs()[None, :, None] + k3.abs()[None, :, None] * xmax).contiguous()
+        native = _native_norm_bwd(gy, count, sync)
+        if native:
+            # the sums, the coefficients and the bounds in one entry (csrc/norm_fold.hip); colmax [b,na] = bound.amax(1)
+            pg, pgx, gmax, xmax = _hip.bn_act_bwd_reduce_fromy(gy, yact, beta, inv_gamma, slope, partials=True)
+            g_bn_w, g_bn_b, _, _, coef, bound, colmax = _hip.norm_fold_bwd(pg, pgx, k1, count, beta, inv_gamma, gmax, xmax)
+        else:
+            sg, sgx, gmax, xmax = _hip.bn_act_bwd_reduce_fromy(gy, yact, beta, inv_gamma, slope)
+            g_bn_w, g_bn_b = sgx.float(), sg.float()
+            tg, tgx = all_reduce_sums(sg, sgx, sync=sync)                        # whole-batch means (SyncBatchNorm backward)
+            k2 = (k1.double() * tg / count).float()
+            k3 = (k1.double() * tgx / count).float()
+            coef = torch.stack([k1, k2, k3, beta, inv_gamma]).contiguous()      # [5, o]
+            bound = (k1.abs()[None, :, None] * gmax + k2.abs()[None, :, None] + k3.abs()[None, :, None] * xmax).contiguous()
         z = _hip.so3_dense_bwd_bn(gy, yact, geo, ldz, coef, bound, slope)
-        if ldz % 4 == 0 and rp % 4 == 0:
+        if ldz % 4 == 0 and rp % 4 == 0 and native:
+            # (the same bound as below in one launch: eap_so3_dense_zbound_f32)
+            z_bound = (_hip.so3_dense_zbound(colmax, head.cnt, head.n_rows, rp, p, ldz).view(torch.int32), 4, 1.0)
+        elif ldz % 4 == 0 and rp % 4 == 0:
             # a bound on Z's columns for the feature-gradient GEMM below (it then runs with two fp16 planes per operand instead of
             # three bf16 planes, without a pass over Z): |Z[o,k,(a,r)]| = |sum_p gx[o,p,a] w| <= max_o bound[o,a] x (points listing row r)
             live = torch.arange(rp, device=gy.device)[None, :] < head.n_rows[:, None]                      # (slots past a cloud's rows: zero columns)

@@ -801,6 +801,41 @@ int eap_narrow_conv_bwd_dw_f32(int b, int o, int ck, int64_t n, float slope, con
                                const float *scale, const float *shift, const float *mean, const float *invstd, const float *k2,
                                const float *k3, float *partial, float *dW, eap_stream_t stream);
 
+/* ---- the per-channel bookkeeping of the conv + BatchNorm + leaky_relu nodes (csrc/norm_fold.hip) ------------------------ */
+/* Between the big kernels of a node stand a few thousand float64 operations on [o], [b,o,na] and [b,p] tensors; written as tensor expressions
+ * they are 10 - 35 launches per site.  Each entry below is that arithmetic in one launch (two where a reduction follows a reduction), operation
+ * for operation; sums over partials are taken in float64 by one wave per channel in a fixed order (lane l adds partials l, l + 64, ..., then a
+ * fixed tree): deterministic.  Every entry refuses a null pointer, a non-positive size and a size beyond the launch limits before it launches
+ * (hipErrorInvalidValue, the condition in eap_last_error()).  float64 scalars travel as their bit patterns (`*_bits`): the vocabulary has no double.
+ *
+ * eap_norm_fold_train_f32 replaces TrainEpilogue.moments without an exchange (batch_moments, update_running_stats, affine_from_moments of
+ * vgtk/so3conv/blocks.py = nn.BatchNorm2d's training forward, SPConvNets/utils/base_so3poseconv.py:L214-221): ps, pq float [o, parts] partial sums
+ * of (y - pivot) and its square, pivot[ch * pivot_stride], count elements per channel, gamma, beta [o] -> scale, shift float [o]
+ * (y' = scale y + shift), mean, invstd double [o], beta_copy, inv_gamma float [o] (0 where gamma == 0); running_mean / running_var float [o]
+ * updated in place with the unbiased variance (both null: none kept). */
+int eap_norm_fold_train_f32(int o, int parts, int64_t pivot_stride, int64_t count, int64_t eps_bits, int64_t momentum_bits, const float *ps,
+                            const float *pq, const float *pivot, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                            float *scale, float *shift, double *mean, double *invstd, float *beta_copy, float *inv_gamma, eap_stream_t stream);
+/* replaces the sums and coefficients at the top of _backward_dense / _backward_narrow (vgtk/so3conv/functional.py): pg, pgx float [o, parts] partial
+ * sums of g and g xhat, k1 [o] the forward's scale -> dgamma = sum g xhat, dbeta = sum g, k2 = k1 sum g / count, k3 = k1 sum g xhat / count (float [o]).
+ * The dense node also hands beta, inv_gamma [o] and the row maxima gmax, xmax float [b,o,na] and gets coef float [5,o] = k1, k2, k3, beta, inv_gamma,
+ * bound [b,o,na] = |k1| gmax + |k2| + |k3| xmax and colmax [b,na] = max over o of bound (a second launch); the narrow node passes these seven null. */
+int eap_norm_fold_bwd_f32(int o, int parts, int b, int na, int64_t count, const float *pg, const float *pgx, const float *k1, const float *beta,
+                          const float *inv_gamma, const float *gmax, const float *xmax, float *dgamma, float *dbeta, float *k2, float *k3, float *coef,
+                          float *bound, float *colmax, eap_stream_t stream);
+/* replaces the z_bound block of _backward_dense: words float [b, ldz / 4], word (a rp + r) / 4 = the largest of its four columns'
+ * colmax[b,a] * clamp(cnt[b,r], 0, p) (cnt int32, rows cnt_stride apart; 0 for r >= n_rows[b]), zero from na rp / 4 on.  rp % 4 == 0, ldz % 4 == 0. */
+int eap_so3_dense_zbound_f32(int b, int na, int rp, int p, int ldz, int64_t cnt_stride, const float *colmax, const int32_t *cnt,
+                             const int32_t *n_rows, float *words, eap_stream_t stream);
+/* replaces the reductions in front of eap_so3_dense_gplanes_f32: bound float [b,na,o] = max_{c,r} |fc4[b,c,r,a]| x (max_k sum_c |W3[(o,k),c]| x 1.0001)
+ * from W3 [o ks, c] and fc4 [b,c,rp,na]; fpart float [b,c,na] and wsum float [o] are scratch (written).  na <= 128.  Two launches. */
+int eap_so3_dense_gplanes_bound_f32(int b, int o, int c, int na, int ks, int rp, const float *W3, const float *fc4, float *fpart, float *wsum,
+                                    float *bound, eap_stream_t stream);
+/* replaces what DenseGeometry did behind its sort: order int64 [b,p] (a permutation per cloud), memb [b,p,words] (words = 16 or 32, 16-byte aligned),
+ * q_xyz float [b,3,p] -> order32 int32 [b,p], memb_out and xyz_out gathered through it, pivot_pos int32 [1] = the j with order[0,j] == 0 */
+int eap_so3_dense_point_order(int b, int p, int words, const int64_t *order, const uint32_t *memb, const float *q_xyz, int32_t *order32,
+                              uint32_t *memb_out, float *xyz_out, int32_t *pivot_pos, eap_stream_t stream);
+
 /* ---- heads on the backbone's [b,c,n,na] feature map ------------------------ */
 /* Anchor attention pooling, InvPPOutBlockOurs.forward (SPConvNets/utils/base_so3conv.py:L905-912):
  * conf[b,n,a] = softmax_a(logits[b,n,a] * temperature), out[b,c,n] = sum_a x[b,c,n,a] conf[b,n,a].  na % 4 == 0, <= 64.
