@@ -428,12 +428,18 @@ def _inv_lists_supported(idx, n_sup, na, ks):
 _SIDE_STREAMS = {}      # the inverse neighbour lists are built beside the forward's grouping / contraction kernels
 
 
-def _side_stream(dev):
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+def _side_stream(dev, second=False):
+    """the device's side stream; second: another one, for work that can run beside the side stream's own (_ListHead's look at a norm)"""
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), second)
     st = _SIDE_STREAMS.get(key)
     if st is None:
         st = _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
     return st
+
+
+def _norm_ill(weight, bias):
+    """-> int32 scalar tensor: 1 if a channel has gamma != 0 and |beta| > NORM_IN_NODE_MAX_RATIO |gamma| (exact: the ratio is a power of two)"""
+    return ((bias.abs() > NORM_IN_NODE_MAX_RATIO * weight.abs()) & (weight != 0)).any().to(torch.int32)
 
 
 class _ListHead:
@@ -443,7 +449,7 @@ class _ListHead:
     cloud; whether any cloud carries non-identity relative rotations; whether any cloud cannot take the dense product).
     Built in the forward, read in the backward: by then the copy has long landed, so nothing stalls."""
 
-    def __init__(self, idx, n_sup, nonident, gx=None, prefill=False, dense_probe=None):
+    def __init__(self, idx, n_sup, nonident, gx=None, prefill=False, dense_probe=None, norm=None):
         """prefill (with gx): also the second half (csrc/inv_lists.hip fill: the entries of every referenced row) right away,
         for all rows -- the launch needs no host value that way.  Everything runs on a SIDE stream: these
         are small latency-bound kernels (0.3 + 0.45 ms per layer) that nothing in the forward waits for, and the grouping and
@@ -451,7 +457,9 @@ class _ListHead:
         dense_probe = (rotation blocks or None, ...): also the membership bits of the dense product (csrc/so3_dense.hip) and
         whether every cloud can take it (no list names a row twice, at most min(n_sup, 1024) referenced rows, every given pose rotation
         EXACTLY the identity -- the dense operand has no rotation in it).  The row count is not known on the host yet, so a support of
-        more than 512 rows is probed with the 32-word table (vgtk._hip.so3_dense_member); decide() narrows it once the count is known."""
+        more than 512 rows is probed with the 32-word table (vgtk._hip.so3_dense_member); decide() narrows it once the count is known.
+        norm = the BatchNormLeakyReLU of a TrainEpilogue that may join the node: whether one of its channels is too ill-conditioned for the
+        backward from the output (NORM_IN_NODE_MAX_RATIO) is decided here on the device and travels in the same copy (norm_ill())."""
         dev = idx.device
         main = torch.cuda.current_stream(dev)
         side = _side_stream(dev)
@@ -460,6 +468,15 @@ class _ListHead:
         for t in (idx, gx, nonident) + tuple(x[1] if isinstance(x, tuple) else x for x in (dense_probe or ())):
             if t is not None:
                 t.record_stream(side)                     # (read on the side stream: the allocator must not recycle them under it)
+        ill = None
+        if norm is not None:
+            # a handful of one-block kernels over the [o] parameters, on a stream of their own: they run beside the list kernels below, which
+            # take far longer, so the copy the forward waits for arrives no later than without them
+            second = _side_stream(dev, True)
+            second.wait_stream(main)                      # (the optimizer's update of the parameters ran on the main stream)
+            with torch.cuda.stream(second):
+                ill = _norm_ill(norm.weight.detach(), norm.bias.detach())
+            ill.record_stream(side)
         with torch.cuda.stream(side):
             self.rows, self.off, self.cnt, self.n_rows = _hip.inv_lists_rows(idx, n_sup)
             flag = nonident.max() if nonident is not None else torch.ones((), dtype=torch.int32, device=dev)
@@ -483,8 +500,14 @@ class _ListHead:
             if self.memb is not None:
                 touched = ((self.memb & 0xffff) != 0).sum((1, 2)) + ((self.memb & -65536) != 0).sum((1, 2))       # [b]
                 groups16 = (touched.max().to(torch.float32) * (16.0 / max(idx.shape[1], 1))).to(torch.int32)
-            stats = torch.stack([self.n_rows.max().to(torch.int32), flag.to(torch.int32), dense_bad.to(torch.int32), groups16])
-            self.host = torch.empty(4, dtype=torch.int32, pin_memory=True)
+            stats = [self.n_rows.max().to(torch.int32), flag.to(torch.int32), dense_bad.to(torch.int32), groups16]
+            if ill is not None:
+                # (the forward waits for this copy on the host before it goes on: no later in-place update of the parameters can overtake
+                # the read above)
+                side.wait_stream(second)
+                stats.append(ill)
+            stats = torch.stack(stats)
+            self.host = torch.empty(stats.shape[0], dtype=torch.int32, pin_memory=True)
             self.host.copy_(stats, non_blocking=True)
             self.entries = _hip.inv_lists_fill(idx, gx, self.rows, self.off, n_sup) if (prefill and gx is not None) else None
             self.event = torch.cuda.Event()
@@ -520,8 +543,16 @@ class _ListHead:
     def decide(self):
         """-> (rcap, any_nonident) as Python values."""
         self._settle()
-        rcap, flag, _, _ = self.host.tolist()
+        rcap, flag = self.host[:2].tolist()
         return int(rcap), bool(flag)
+
+    def norm_ill(self):
+        """a channel of the `norm` given to __init__ has gamma != 0 and |beta| > NORM_IN_NODE_MAX_RATIO |gamma| (False without a norm);
+        blocks on the host like decide() -- the forward has waited for that copy already when it asks"""
+        if self.host.shape[0] <= 4:
+            return False
+        self._settle()
+        return int(self.host[4]) != 0
 
     def groups_touched(self):
         """mean number of 16-row groups a point's list touches (the largest per-cloud mean); blocks on the host like decide()"""
@@ -603,7 +634,14 @@ class TrainEpilogue:
     A conv with at most 32 contraction indices C*K whose input needs no gradient (the first layer) takes the norm into its node too, regime
     'narrow input' (_forward_narrow): it keeps the grouped input X and recomputes the conv output from it in every pass.
     Otherwise (list kernels, posed parts, ...) `applied` stays False and the caller runs the norm module as a pass of its own.
-    A channel whose gamma is exactly 0 has a constant output: its input gradient is exactly 0 either way, its d gamma is reported as 0."""
+    A channel whose gamma is exactly 0 has a constant output: its input gradient is exactly 0 either way, its d gamma is reported as 0.
+    Conditioning: the recovery (pre - beta) / gamma is a float32 subtraction of two numbers of size |beta| that leaves one of size
+    |gamma xhat|, so xhat comes back with an absolute error of up to 8 x 2^-24 (|xhat| + |beta / gamma| + |mean| invstd) per channel, and
+    d gamma, d beta and gx with the sums of it (tests/test_fused_norm_host.py derives the bound, tests/test_gpu_conv_norm_conditioning.py
+    holds the kernels and the node to it channel by channel).  A layer with a channel that has gamma != 0 and |beta| >
+    NORM_IN_NODE_MAX_RATIO |gamma| (128) therefore does NOT take the norm into the dense node: `applied` stays False.  The flag is formed
+    on the device beside _ListHead's host words and arrives in the copy the forward waits for anyway; gamma = 0 does not raise it.  The
+    'narrow input' node recomputes xhat from X and is free of the effect."""
 
     def __init__(self, norm):
         self.norm = norm
@@ -704,6 +742,11 @@ DENSE_MAX_GROUPS_WIDE = 16.0
 DENSE_FWD_NARROW = True
 # a training-mode BatchNorm + leaky_relu behind a conv whose forward runs the dense product joins the conv's node (TrainEpilogue)
 FUSE_CONV_NORM = True
+# ... unless one of its channels has gamma != 0 and |beta| > NORM_IN_NODE_MAX_RATIO |gamma|.  The node's backward recovers xhat from the
+# OUTPUT, (pre - beta) / gamma in float32: an absolute error of up to 8 x 2^-24 (|xhat| + |beta / gamma| + |mean| invstd), typically a
+# quarter of that (derived and emulated in tests/test_fused_norm_host.py).  At 128 the typical loss 2 x 2^-24 (max |xhat| + 128) ~ 1.6e-5
+# reaches the 2e-5 the suite grants d gamma / d beta anywhere; the separate module normalises the stored conv output and has no such term.
+NORM_IN_NODE_MAX_RATIO = 128.0
 
 
 def _dense_rows(rcap, n):
@@ -929,8 +972,9 @@ class _DensePlan:
     taken), forward = the forward runs it too (else the backward alone), parts = the _PoseParts when it runs once per rigid part, probed = the
     batch was probed for it; head = the _ListHead of the neighbour lists (None when neither the probe nor a backward needs one)."""
 
-    def __init__(self, args, n, o, lists_ok, needs_grad, keep, folded):
-        # (folded: the FoldedEpilogue of an inference call or None)
+    def __init__(self, args, n, o, lists_ok, needs_grad, keep, folded, norm=None):
+        # (folded: the FoldedEpilogue of an inference call or None; norm: the module of a TrainEpilogue that joins the node if the forward
+        # runs the product -- the probe then also looks at its conditioning, _ListHead.norm_ill)
         # whether the batch can take the product is known on the host once the lists' first half has run -- one host wait per layer,
         # only for layers whose width fills the dense kernel's blocks
         idx, geometry = args.idx, args.geometry
@@ -959,7 +1003,8 @@ class _DensePlan:
         # they run beside it; the entries too when the previous backward of this layer took the lists
         self.head = None
         if (lists_ok and needs_grad) or probe is not None:
-            self.head = _ListHead(idx, n, args.nonident, args.gx, prefill=(not keep) and probe is None, dense_probe=probe)
+            self.head = _ListHead(idx, n, args.nonident, args.gx, prefill=(not keep) and probe is None, dense_probe=probe,
+                                  norm=norm if probe is not None else None)
         self.probed = probe is not None
         self.rp, self.forward = _dense_wanted(self.head, o, p, na, ks, nn, n) if self.probed else (0, False)
 
@@ -1411,7 +1456,7 @@ class _InterConv(torch.autograd.Function):
             return y
         lists_ok = BACKWARD_MODE != 'dx' and _inv_lists_supported(idx, n, na, ks) and not narrow
         keep = needs_grad and (not lists_ok or _keep_x_hint(W_param))
-        plan = _DensePlan(args, n, o, lists_ok, needs_grad, keep, folded)
+        plan = _DensePlan(args, n, o, lists_ok, needs_grad, keep, folded, train_ep.norm if (train_ep is not None and FUSE_CONV_NORM) else None)
         head = plan.head if needs_grad else None
         if FORWARD_LOG is not None:
             FORWARD_LOG.append({'channels': (c, o), 'dense': bool(plan.forward), 'parts': None if plan.parts is None else plan.parts.n})
@@ -1419,7 +1464,9 @@ class _InterConv(torch.autograd.Function):
             # (a frozen conv under a trainable norm -- gradients wanted for the norm's parameters only -- keeps the separate module:
             # the node's backward is the conv's dense backward)
             bn_only = args.grad_mode and not needs_grad and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
-            y, ctx.bn = _forward_dense(feats, W, plan, p, train_ep if (FUSE_CONV_NORM and not bn_only) else None, folded)
+            # (a norm with a channel past NORM_IN_NODE_MAX_RATIO keeps the separate module too: its backward has the stored input)
+            join = FUSE_CONV_NORM and not bn_only and train_ep is not None and not plan.head.norm_ill()
+            y, ctx.bn = _forward_dense(feats, W, plan, p, train_ep if join else None, folded)
             x, layout = None, 0
         else:
             fill = head is not None and plan.probed and not keep and plan.rp == 0

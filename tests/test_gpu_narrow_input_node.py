@@ -133,6 +133,48 @@ def test_node_against_separate_modules_and_float64(dev, monkeypatch, P, O, kerne
     assert float(a[2][5]) == float(a[2][5]) and torch.isfinite(a[1]).all()      # the gamma = 0 channel: finite everywhere
 
 
+def test_node_per_channel_over_the_conditioning_table(dev, monkeypatch):
+    """The first case with the (gamma, beta) table of tests/test_fused_norm_host.py over the channels -- |beta / gamma| up to 3e4 -- channel by
+    channel against float64.  This regime recomputes xhat from X and never from y', so it must meet the bounds of that file with r = 0: the
+    narrow-input node is free of the effect the dense node is guarded against (tests/test_gpu_conv_norm_conditioning.py), and its layer
+    stays in the node whatever beta / gamma is.  What the recomputed conv output adds -- a 24-term float32 dot product, 24u sum |W||X| at
+    the most -- is charged to the kink only; the sums' bounds stay 8u."""
+    import test_fused_norm_host as H
+    import vgtk.so3conv.functional as L
+    P, O, kernel_size, slope, rotated = CASES[0]
+    xyz, pose, feats, W, _, _, gy = _inputs(dev, P, O, 24, rotated, 7 + P + O)
+    pairs = torch.tensor([H.TABLE[i % 11] for i in range(O)], dtype=torch.float32, device=dev)
+    gamma, beta = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+    monkeypatch.setattr(L, 'FUSE_CONV_NORM', True)
+    conv, norm = _modules(dev, O, kernel_size, slope, W, gamma, beta)
+    res, blog, flog, _ = _step(conv, norm, xyz, pose, feats, gy)
+    assert len(blog) == 1 and blog[0]['regime'] == 'narrow input' and blog[0].get('norm') == 'in the node', blog
+    x = L._inter_group(xyz, pose, feats, NN, conv.anchors, conv.kernels, conv.radius, conv.sigma, True)[2]
+    x = x.reshape(B, -1, x.shape[3] * x.shape[4]).double().cpu()                                          # [b,ck,n]
+    W64, g64, b64 = W.double().cpu(), gamma.double().cpu(), beta.double().cpu()
+    y = torch.einsum('ok,bkn->bon', W64, x)
+    mean, var = y.mean((0, 2)), y.var((0, 2), unbiased=False)
+    invstd = torch.rsqrt(var + norm.eps)
+    xhat = (y - mean[None, :, None]) * invstd[None, :, None]
+    count = y.shape[0] * y.shape[2]
+    yrun = res[0].flatten(2).cpu()
+    ref = H.float64_reference(y, g64, b64, gy.flatten(2).cpu(), slope, eps=norm.eps, pos=yrun > 0)
+    differ = (yrun > 0) != (ref['pre'] > 0)
+    kink = (4 * H.U * (g64.abs()[None, :, None] * (xhat.abs() + (mean.abs() * invstd)[None, :, None]) + b64.abs()[None, :, None])
+            + 24 * H.U * (g64.abs() * invstd)[None, :, None] * torch.einsum('ok,bkn->bon', W64.abs(), x.abs()))
+    assert bool((ref['pre'].abs()[differ] <= kink[differ]).all()), int(differ.sum())
+    bd = H.bounds(ref, xhat, g64, b64, mean, invstd, count, r_cap=0.0)
+    ry = H.ratio((yrun.double() - ref['y']).abs(), (1e-5 * ref['y'].abs().amax((0, 2)))[None, :, None].expand_as(ref['y']))
+    rg = H.ratio((res[2].double().cpu() - ref['dgamma']).abs(), bd['dgamma'])
+    rb = H.ratio((res[3].double().cpu() - ref['dbeta']).abs(), bd['dbeta'])
+    dW64 = torch.einsum('bon,bkn->ok', ref['gx'], x)
+    dWb = torch.einsum('bon,bkn->ok', bd['gx'], x.abs())
+    rW = ((res[1].double().cpu() - dW64).abs() / (5e-5 * float(dW64.abs().max()) + dWb)).amax(1)
+    print(f'narrow input over the table ({int(differ.sum())} elements at the kink): largest error / bound per channel  y\' {float(ry.max()):.3f}  '
+          f'dgamma {float(rg.max()):.3f}  dbeta {float(rb.max()):.3f}  dW {float(rW.max()):.3f}')
+    assert float(ry.max()) <= 1.0 and float(rg.max()) <= 1.0 and float(rb.max()) <= 1.0 and float(rW.max()) <= 1.0
+
+
 def test_two_identical_steps_are_bit_equal(dev):
     xyz, pose, feats, W, gamma, beta, gy = _inputs(dev, 52, 64, 24, True, 19)
     res = []
