@@ -32,7 +32,9 @@
 //   1  B_z[K, N] row-major ("NN"): the pointwise contractions `so3_contract` (every 1 x 1 conv of the blocks and heads over
 //      [b, C, P*A]); a piece = four dword loads from four k-rows, lanes along n (256 contiguous bytes per request)
 //   2  implicit intra-SO(3) gather: B[(c, t), (p, a)] = F_z[c, p, idx[a, t]] (so3conv/functional.py:L2553-2602), the 60 x 12
-//      table in LDS; a piece = the four taps t0..t0+3 of one channel, four dword loads inside the point's 240-byte row
+//      table in LDS; a piece = the four taps t0..t0+3 of one channel, four dword loads inside the point's 240-byte row.
+//      With nr residuals per anchor, innermost (IntraSO3Conv2D, so3conv/functional.py:L2606-2627, nr = 4): column (p, a, r) reads
+//      F_z[c, p, idx[a, t], r] -- the same four loads inside the point's 960-byte row, the table in steps of nr floats
 #include "common.h"
 #include "device_prims.h"
 #include <algorithm>
@@ -55,6 +57,7 @@ struct Args {
     float *C; long long ldc, sC;
     int tiles_m, tiles_n;
     const int *tbl; int na;             // BMODE 2: gather table [na][TAPS], anchors per point
+    int nr;                             // BMODE 2: residuals per anchor, innermost (1: the plain anchor axis; 4: IntraSO3Conv2D)
     const unsigned *Apre;               // APRE: A split once by presplit_kernel, [M][K/4] pieces of 32 bytes (h0 h1 m0 m1 | l0 l1 - -)
     long long sA; int slabs, kslab;     // batch-reduce form (BMODE 0): z = item * slabs + slab; both operands start at k = slab * kslab
     // row epilogue (the block layer's inference-mode BatchNorm + leaky_relu (+ skip sum) folded into the contraction,
@@ -181,9 +184,10 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
     for (int u = 0; u < NPO; ++u) {
         const int n = min(n0 + RG * u, g.N - RG) + rqb;
         if constexpr (BMODE == 2) {
-            const int pt = n / g.na;
-            colB[u] = (unsigned)(pt * g.na) * 4u;
-            tapB[u] = (unsigned)(n - pt * g.na) * (TAPS * 4u);
+            // column n = (point, anchor, residual): the residual stays with the column, the anchor picks the table row
+            const int per = g.na * g.nr, pt = n / per, an = (n - pt * per) / g.nr;
+            colB[u] = (unsigned)(n - an * g.nr) * 4u;
+            tapB[u] = (unsigned)an * (TAPS * 4u);
         } else {
             colB[u] = (unsigned)n * 4u; tapB[u] = 0;
         }
@@ -196,7 +200,7 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
     const unsigned wr_off = wr_of(rq, c4), wr_offB = wr_of(rqb, c4b);
     const unsigned char *tbl = smem + 3 * STAGE_BYTES;
     if constexpr (BMODE == 2) {
-        for (int i = t; i < g.na * TAPS; i += NT) reinterpret_cast<int *>(smem + 3 * STAGE_BYTES)[i] = g.tbl[i] * 4;   // byte offsets
+        for (int i = t; i < g.na * TAPS; i += NT) reinterpret_cast<int *>(smem + 3 * STAGE_BYTES)[i] = g.tbl[i] * 4 * g.nr;   // byte offsets of the anchor's nr residuals
         __syncthreads();
     }
     const int nk = (g.slabs > 1 ? g.kslab : g.K) / BK;
@@ -591,13 +595,15 @@ int launch_split(Args &g, long long batch, hipStream_t stream, const char *who) 
         if (pre) kern = tall ? gemm_bf16x3_kernel<4, WAVES_N, BMODE, true> : gemm_bf16x3_kernel<2, WAVES_N, BMODE, true>;
         else kern = tall ? gemm_bf16x3_kernel<4, WAVES_N, BMODE, false> : gemm_bf16x3_kernel<2, WAVES_N, BMODE, false>;
     }
-    static const char *names[3][2] = {{"gemm_bf16x3_kernel<2, 4>", "gemm_bf16x3_kernel<4, 4>"},
+    static const char *names[4][2] = {{"gemm_bf16x3_kernel<2, 4>", "gemm_bf16x3_kernel<4, 4>"},
                                       {"gemm_bf16x3_kernel<2, 4, nn>", "gemm_bf16x3_kernel<4, 4, nn>"},
-                                      {"gemm_bf16x3_kernel<2, 4, gather>", "gemm_bf16x3_kernel<4, 4, gather>"}};
-    static const char *names2[3][2] = {{"gemm_f16x2_kernel<2, 4>", "gemm_f16x2_kernel<4, 4>"},
+                                      {"gemm_bf16x3_kernel<2, 4, gather>", "gemm_bf16x3_kernel<4, 4, gather>"},
+                                      {"gemm_bf16x3_kernel<2, 4, gather 2d>", "gemm_bf16x3_kernel<4, 4, gather 2d>"}};
+    static const char *names2[4][2] = {{"gemm_f16x2_kernel<2, 4>", "gemm_f16x2_kernel<4, 4>"},
                                        {"gemm_f16x2_kernel<2, 4, nn>", "gemm_f16x2_kernel<4, 4, nn>"},
-                                       {"gemm_f16x2_kernel<2, 4, gather>", "gemm_f16x2_kernel<4, 4, gather>"}};
-    eap::set_kernel((PL == 2 ? names2 : names)[BMODE][tall ? 1 : 0]);
+                                       {"gemm_f16x2_kernel<2, 4, gather>", "gemm_f16x2_kernel<4, 4, gather>"},
+                                       {"gemm_f16x2_kernel<2, 4, gather 2d>", "gemm_f16x2_kernel<4, 4, gather 2d>"}};
+    eap::set_kernel((PL == 2 ? names2 : names)[BMODE + (BMODE == 2 && g.nr > 1)][tall ? 1 : 0]);
     return eap::run_kernel(who, kern, (long long)g.tiles_m * g.tiles_n, batch, 1, dim3(128 * WAVES_N), shmem, stream, g);
 }
 
@@ -762,7 +768,7 @@ extern "C" int eap_so3_intra_conv_f16x2_f32(int b, int o, int c, int p, int na, 
     g.A = W; g.lda = (long long)c * nt;
     g.B = feats; g.ldb = pa; g.sB = (long long)c * pa;
     g.C = out; g.ldc = pa; g.sC = (long long)o * pa;
-    g.tbl = intra_idx; g.na = na;
+    g.tbl = intra_idx; g.na = na; g.nr = 1;
     g.absA = reinterpret_cast<const unsigned *>(abs_w); g.absB = reinterpret_cast<const unsigned *>(abs_f); g.multB = 1.0f;
     g.grpB = na; g.sAbsB = p;
     return launch_split<2, 2>(g, b, eap::S(stream), "so3_intra_conv_f16x2_f32");
@@ -785,8 +791,64 @@ extern "C" int eap_so3_intra_conv_bf16x3_f32(int b, int o, int c, int p, int na,
     g.A = W; g.lda = (long long)c * nt;
     g.B = feats; g.ldb = pa; g.sB = (long long)c * pa;
     g.C = out; g.ldc = pa; g.sC = (long long)o * pa;
-    g.tbl = intra_idx; g.na = na;
+    g.tbl = intra_idx; g.na = na; g.nr = 1;
     return launch_split<2>(g, b, eap::S(stream), "so3_intra_conv_bf16x3_f32");
+}
+
+// ---- the intra conv on the (na, nr = 4) anchor axis of IntraSO3Conv2D (so3conv/functional.py:L2606-2627 + modules.py:L48-55):
+// out[b,o,p,a,r] = sum_{c,t} W[o, c*12 + t] feats[b,c,p,idx[a,t],r] -- the 1-D entries above with p*na*nr columns, the residual
+// carried by the column and the table row by the anchor
+extern "C" int eap_so3_intra_conv2d_split_supported(int b, int o, int c, int p, int na, int nr, int nt) {
+    if (nt != TAPS || nr != 4 || na <= 0 || na > 64 || (long long)p * na * nr >= (1ll << 29)) return 0;
+    return tile_dims_ok(o, p * na * nr, c * nt) ? 1 : 0;
+}
+
+namespace {
+
+// what both 2-D split entries say before a pointer is touched: the limits first (named), then the tile shapes
+int intra2d_refusal(int b, int o, int c, int p, int na, int nr, int nt, const float *W, const char *who) {
+    char buf[192];
+    if (nr != 4 || na > 64 || nt != TAPS)
+        snprintf(buf, sizeof(buf), "%s: nr = 4 residuals per anchor, at most 64 anchors and nt = 12 taps on the split kernel", who);
+    else if (!eap_so3_intra_conv2d_split_supported(b, o, c, p, na, nr, nt) || (reinterpret_cast<uintptr_t>(W) & 15))
+        snprintf(buf, sizeof(buf), "%s: unsupported shape (ask eap_so3_intra_conv2d_split_supported)", who);
+    else
+        return 0;
+    return eap::bad_arg(buf);
+}
+
+void intra2d_args(Args &g, int o, int c, int p, int na, int nr, int nt, const float *W, const float *feats, const int32_t *intra_idx, float *out) {
+    const long long pa = (long long)p * na * nr;
+    g.M = o; g.N = (int)pa; g.K = c * nt;
+    g.A = W; g.lda = (long long)c * nt;
+    g.B = feats; g.ldb = pa; g.sB = (long long)c * pa;
+    g.C = out; g.ldc = pa; g.sC = (long long)o * pa;
+    g.tbl = intra_idx; g.na = na; g.nr = nr;
+}
+
+}  // namespace
+
+extern "C" int eap_so3_intra_conv2d_bf16x3_f32(int b, int o, int c, int p, int na, int nr, int nt, const float *W, const float *feats,
+                                               const int32_t *intra_idx, float *out, eap_stream_t stream) {
+    if (b <= 0 || o <= 0 || p <= 0 || na <= 0) return 0;
+    if (int e = intra2d_refusal(b, o, c, p, na, nr, nt, W, "so3_intra_conv2d_bf16x3_f32")) return e;
+    Args g{};
+    intra2d_args(g, o, c, p, na, nr, nt, W, feats, intra_idx, out);
+    return launch_split<2>(g, b, eap::S(stream), "so3_intra_conv2d_bf16x3_f32");
+}
+
+// two fp16 planes: abs_w [o] = eap_absmax_rows_f32 of W, abs_f [b][p] = the features' per-point maxima (eap_absmax_colgroups_f32
+// over [b][c][p*na*nr] with groups of na*nr: a column gathers 12 quads of its point)
+extern "C" int eap_so3_intra_conv2d_f16x2_f32(int b, int o, int c, int p, int na, int nr, int nt, const float *W, const float *feats,
+                                              const int32_t *intra_idx, float *out, const int32_t *abs_w, const int32_t *abs_f, eap_stream_t stream) {
+    if (b <= 0 || o <= 0 || p <= 0 || na <= 0) return 0;
+    if (int e = intra2d_refusal(b, o, c, p, na, nr, nt, W, "so3_intra_conv2d_f16x2_f32")) return e;
+    if (!abs_w || !abs_f) return eap::bad_arg("so3_intra_conv2d_f16x2_f32: the operand magnitudes are required (eap_absmax_rows_f32 / _colgroups_f32)");
+    Args g{};
+    intra2d_args(g, o, c, p, na, nr, nt, W, feats, intra_idx, out);
+    g.absA = reinterpret_cast<const unsigned *>(abs_w); g.absB = reinterpret_cast<const unsigned *>(abs_f); g.multB = 1.0f;
+    g.grpB = na * nr; g.sAbsB = p;
+    return launch_split<2, 2>(g, b, eap::S(stream), "so3_intra_conv2d_f16x2_f32");
 }
 
 // ---- batch-reduce form: C[M,N] = sum_z A_z[M,K] B_z[N,K]^T (the weight gradient of the pointwise contraction: dW = sum over

@@ -42,6 +42,9 @@ struct GemmArgs {
     // (channel, kernel point) rows, position x along P*A) at  (x >> 2) * bblk * 4 + r * 4 + (x & 3)
     // -- the layout the grouping kernels can write with coalesced stores (csrc/so3_inter_lists.hip)
     long long bblk;
+    // GATHER == 2, the (anchor, residual) axis of IntraSO3Conv2D: column n = (point p = n / gna, anchor a = n % gna / 4, residual
+    // r = n % 4), the table has gna / 4 rows  ->  B[c*ldb + p*gna + 4*gidx[a*gnt + t] + r]: a thread's 4 columns are one 16-byte quad
+    int gquad;
 };
 
 // Load 4 consecutive elements along the contiguous dimension `x` of a row-major [rows][cols]
@@ -65,7 +68,7 @@ __device__ __forceinline__ float4 load4(const float *__restrict__ base, long lon
 }
 
 // NWM x NWN waves per block, every wave owns a WTM x 64 tile (WTM = 64, or 32 for the small-M variant)
-template <int NWM, int NWN, int WTM, bool TA, bool TB, bool VEC, bool GATHER = false>
+template <int NWM, int NWN, int WTM, bool TA, bool TB, bool VEC, int GATHER = 0>
 __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN >= 16 ? 4 : 2)) void gemm_f32_kernel(GemmArgs g) {
     constexpr int BM = WTM * NWM, BN = 64 * NWN, NT = 64 * NWM * NWN;
     __shared__ Smem<BM, BN> sm;
@@ -102,10 +105,10 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN >= 16 ? 4 : 2)) void gem
 
     float4 ra[A_V4], rb[B_V4];
 
-    // implicit intra conv: this thread's 4 B columns are 4 consecutive anchors of one point
+    // implicit intra conv: this thread's 4 B columns are 4 consecutive anchors of one point (GATHER == 2: the 4 residuals of one anchor)
     int g_pcol = 0, g_a0 = 0;
     if (GATHER) {
-        for (int i = t; i < g.gna * g.gnt; i += NT) s_gi[i] = g.gidx[i];
+        for (int i = t; i < (GATHER == 2 ? g.gna / 4 : g.gna) * g.gnt; i += NT) s_gi[i] = g.gidx[i];
         const int n = n0 + (t % (BN / 4)) * 4;
         g_pcol = n / g.gna * g.gna;
         g_a0 = n - g_pcol;
@@ -131,8 +134,14 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN >= 16 ? 4 : 2)) void gem
                 if (k < kend && n < g.N) {                  // N = P*A is a multiple of 4: all four columns valid
                     const int ci = k / g.gnt, tt = k - ci * g.gnt;
                     const float *row = B + (long long)ci * g.ldb + g_pcol;
-                    v.x = row[s_gi[(g_a0 + 0) * g.gnt + tt]]; v.y = row[s_gi[(g_a0 + 1) * g.gnt + tt]];
-                    v.z = row[s_gi[(g_a0 + 2) * g.gnt + tt]]; v.w = row[s_gi[(g_a0 + 3) * g.gnt + tt]];
+                    if (GATHER == 2) {          // the four residuals of anchor g_a0 / 4: one quad of the point's row
+                        const float *quad = row + 4 * s_gi[(g_a0 >> 2) * g.gnt + tt];
+                        if (VEC) v = *reinterpret_cast<const float4 *>(quad);
+                        else { v.x = quad[0]; v.y = quad[1]; v.z = quad[2]; v.w = quad[3]; }
+                    } else {
+                        v.x = row[s_gi[(g_a0 + 0) * g.gnt + tt]]; v.y = row[s_gi[(g_a0 + 1) * g.gnt + tt]];
+                        v.z = row[s_gi[(g_a0 + 2) * g.gnt + tt]]; v.w = row[s_gi[(g_a0 + 3) * g.gnt + tt]];
+                    }
                 }
                 rb[u] = v;
             } else if (!TB) {   // B [K,N]: n contiguous
@@ -261,8 +270,10 @@ int launch(bool ta, bool tb, const GemmArgs &g, long long zcount, hipStream_t s)
     const bool vec = aligned16(g.A) && aligned16(g.B) && g.lda % 4 == 0 && g.ldb % 4 == 0 &&
                      g.sA % 4 == 0 && g.sB % 4 == 0;
     void (*kern)(GemmArgs);
-    if (g.gidx)   // implicit intra conv: A = W [M,K] row-major, B gathered
-        kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, false, false, true, true> : gemm_f32_kernel<NWM, NWN, WTM, false, false, false, true>;
+    if (g.gidx && g.gquad)   // implicit intra conv on the (anchor, residual) axis: A = W [M,K] row-major, B gathered by quads
+        kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, false, false, true, 2> : gemm_f32_kernel<NWM, NWN, WTM, false, false, false, 2>;
+    else if (g.gidx)   // implicit intra conv: A = W [M,K] row-major, B gathered
+        kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, false, false, true, 1> : gemm_f32_kernel<NWM, NWN, WTM, false, false, false, 1>;
     else if (!ta && !tb) kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, false, false, true> : gemm_f32_kernel<NWM, NWN, WTM, false, false, false>;
     else if (ta && !tb) kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, true, false, true> : gemm_f32_kernel<NWM, NWN, WTM, true, false, false>;
     else if (!ta && tb) kern = vec ? gemm_f32_kernel<NWM, NWN, WTM, false, true, true> : gemm_f32_kernel<NWM, NWN, WTM, false, true, false>;
@@ -328,6 +339,21 @@ extern "C" int eap_so3_intra_conv_f32(int b, int o, int c, int p, int na, int nt
     GemmArgs g{o, N, K, W, K, 0, feats, (long long)N, (long long)c * N, out, (long long)N, (long long)o * N, 1,
                (K + BK - 1) / BK * BK, 0, 0, intra_idx, na, nt, 0};
     if (g.kchunk == 0) g.kchunk = BK;
+    return run(false, false, g, b, eap::S(stream));
+}
+
+// The same on the (na, nr = 4) anchor axis of IntraSO3Conv2D: out[b,o,p,a,r] = sum_{c,t} W[o, c*T + t] * feats[b, c, p, intra_idx[a,t], r]
+// (so3conv/functional.py:L2606-2627 + modules.py:L48-55); the four columns a thread loads are the four residuals of one anchor.
+extern "C" int eap_so3_intra_conv2d_f32(int b, int o, int c, int p, int na, int nr, int nt, const float *W, const float *feats,
+                                        const int32_t *intra_idx, float *out, eap_stream_t stream) {
+    if (b <= 0 || o <= 0 || p <= 0 || na <= 0) return 0;
+    if (nr != 4 || na > 64 || nt > 16 || nt < 0) return eap::bad_arg("so3_intra_conv2d: nr = 4 residuals per anchor, at most 64 anchors and 16 taps");
+    if ((long long)p * na * nr >= (1ll << 31) || (long long)c * nt >= (1ll << 31)) return eap::bad_arg("so3_intra_conv2d: p*na*nr and c*nt below 2^31");
+    const int K = c * nt, N = p * na * nr;
+    GemmArgs g{o, N, K, W, K, 0, feats, (long long)N, (long long)c * N, out, (long long)N, (long long)o * N, 1,
+               (K + BK - 1) / BK * BK, 0, 0, intra_idx, na * nr, nt, 0, 1};
+    if (g.kchunk == 0) g.kchunk = BK;
+    eap::set_kernel("gemm_f32_kernel<GATHER quad>");
     return run(false, false, g, b, eap::S(stream));
 }
 

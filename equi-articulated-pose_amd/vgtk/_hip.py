@@ -629,6 +629,37 @@ def so3_intra_group_bwd(gout, intra_idx):
     return gfeats
 
 
+def _quads(t):
+    """`t` contiguous with its first element on a 16-byte boundary (the 2-D grouping kernels move an anchor's four residuals as one
+    quad): `t` itself where it already is, else a copy."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def _residuals(tot, na):
+    """residuals per anchor of an anchor axis of `tot` = na * nr entries, the residual innermost"""
+    if na <= 0 or tot % na:
+        raise RuntimeError(f'an anchor axis of {tot} entries is not (na = {na}) x residuals')
+    return tot // na
+
+
+def so3_intra_group2d_fwd(feats, intra_idx):
+    """feats [b,c,p,na*nr], intra_idx int32 [na,t] -> [b,c,t,p,na*nr] = feats[b,c,p,intra_idx[a,t],r], the residual r innermost."""
+    b, c, p, tot = feats.shape
+    na, t = intra_idx.shape
+    out = torch.empty(b, c, t, p, tot, dtype=torch.float32, device=feats.device)
+    call('eap_so3_intra_group2d_fwd_f32', out, b, c, p, na, _residuals(tot, na), t, _quads(feats), intra_idx, out)
+    return out
+
+
+def so3_intra_group2d_bwd(gout, intra_idx):
+    b, c, t, p, tot = gout.shape
+    na = intra_idx.shape[0]
+    gfeats = torch.empty(b, c, p, tot, dtype=torch.float32, device=gout.device)
+    call('eap_so3_intra_group2d_bwd_f32', gfeats, b, c, p, na, _residuals(tot, na), t, _quads(gout), intra_idx, gfeats)
+    return gfeats
+
+
 def so3_inter_group_inv(gy, rows, off, cnt, ent_p, ent_gx, rk, multinv, sigma, nn, identity_anchor=0, anchors=None, coset=None):
     """gy [b,o,p,na] + inverse neighbour lists -> z [b,o,ks,rcap,na] (see include/eap_hip.h).  coset = (order, code) of
     `multinv` (vgtk.so3conv.functional._coset_tables): the permuted clouds' operand is kept coset-major in LDS."""
@@ -1324,4 +1355,23 @@ def so3_intra_conv(feats, W, intra_idx32):
             call('eap_so3_intra_conv_f16x2_f32', out, b, o, c, p, na, nt, W, feats, intra_idx32, out, abs_w, abs_f, tag=tag)
             return out
     call('eap_so3_intra_conv_bf16x3_f32' if split else 'eap_so3_intra_conv_f32', out, b, o, c, p, na, nt, W, feats, intra_idx32, out, tag=tag)
+    return out
+
+
+def so3_intra_conv2d(feats, W, intra_idx32):
+    """so3_intra_conv on the (na, nr) anchor axis of IntraSO3Conv2D, the residual innermost: feats [b,c,p,na*nr], W [o, c*nt], intra_idx
+    int32 [na,nt] -> [b,o,p,na*nr] = sum_{c,t} W[o, c*nt + t] feats[b,c,p,intra_idx[a,t],r]."""
+    b, c, p, tot = feats.shape
+    na, nt = intra_idx32.shape
+    o, nr = W.shape[0], _residuals(tot, na)
+    out = torch.empty(b, o, p, tot, dtype=torch.float32, device=feats.device)
+    split = SPLIT_BF16_CONTRACTION and W.data_ptr() % 16 == 0 and abi.eap_so3_intra_conv2d_split_supported(b, o, c, p, na, nr, nt)
+    tag = {'flops': 2.0 * b * o * c * nt * p * tot, 'shape': ('intra_conv2d', b, o, c, p, na, nr, nt)}
+    if split and SPLIT_PLANES == 2 and feats.data_ptr() % 16 == 0:
+        abs_w = absmax_rows(W, 1, o, c * nt, c * nt, 0)
+        abs_f = absmax_colgroups(feats, b, c, p * tot, p * tot, c * p * tot, tot)
+        if abs_w is not None and abs_f is not None:
+            call('eap_so3_intra_conv2d_f16x2_f32', out, b, o, c, p, na, nr, nt, W, feats, intra_idx32, out, abs_w, abs_f, tag=tag)
+            return out
+    call('eap_so3_intra_conv2d_bf16x3_f32' if split else 'eap_so3_intra_conv2d_f32', out, b, o, c, p, na, nr, nt, W, feats, intra_idx32, out, tag=tag)
     return out

@@ -371,6 +371,20 @@ class _IntraGroup(torch.autograd.Function):
         return _hip.so3_intra_group_bwd(gout.contiguous(), intra_idx32), None
 
 
+class _IntraGroup2D(torch.autograd.Function):
+    """out[b,c,t,p,(a,r)] = feats[b,c,p,(intra_idx[a,t],r)]  (functional.py:L2606-2627): one kernel each way."""
+
+    @staticmethod
+    def forward(ctx, feats, intra_idx32):
+        ctx.save_for_backward(intra_idx32)
+        return _hip.so3_intra_group2d_fwd(feats.contiguous(), intra_idx32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        intra_idx32, = ctx.saved_tensors
+        return _hip.so3_intra_group2d_bwd(gout.contiguous(), intra_idx32), None
+
+
 class _Contract(torch.autograd.Function):
     """y[b,o,pa] = W[o,ck] x[b,ck,pa] on the matrix cores (BasicSO3Conv, modules.py:L48-55)."""
 
@@ -1526,6 +1540,22 @@ class _InterConv(torch.autograd.Function):
 INTRA_DW_SLICE = 64      # channels whose 12-tap gather is materialised at a time for the intra weight gradient
 
 
+def _intra_inverse_table(idx32):
+    """inv[idx[a,t], t] = a: every column idx[:, t] is a permutation of the anchors"""
+    na, nt = idx32.shape
+    inv = torch.empty_like(idx32)
+    inv.scatter_(0, idx32.long(), torch.arange(na, device=idx32.device, dtype=torch.int32)[:, None].expand(na, nt).contiguous())
+    return inv.contiguous()
+
+
+def _intra_kernels(feats, idx32):
+    """(implicit conv, grouping) launchers for the features' anchor axis: the table's rows, or rows x residuals with the residual
+    innermost (IntraSO3Conv2D, functional.py:L2606-2627), where the kernels move an anchor's residuals as one 16-byte quad"""
+    if feats.shape[3] == idx32.shape[0]:
+        return _hip.so3_intra_conv, _hip.so3_intra_group_fwd
+    return _hip.so3_intra_conv2d, _hip.so3_intra_group2d_fwd
+
+
 class _IntraConv(torch.autograd.Function):
     """Intra SO(3) conv  y[b,o,p,a] = sum_{c,t} W[o, c*T + t] F[b,c,p,idx[a,t]]  (functional.py:L2553-2602 +
     modules.py:L48-55) WITHOUT the [B,C,T,P,A] gathered tensor (48 GB at C = 512, B = 8) in either direction:
@@ -1535,35 +1565,39 @@ class _IntraConv(torch.autograd.Function):
                 table inv[a', t];
       dW        sum_{b,p,a} dY[b,o,p,a] F[b,c,p,idx[a,t]]: the gather is materialised for INTRA_DW_SLICE channels at
                 a time (eap_so3_intra_group_fwd) and contracted by the k-split reduce GEMM (3 GB of scratch instead
-                of 48)."""
+                of 48).
+    The (60, 4) anchor axis of IntraSO3Conv2D, y[b,o,p,a,r] = sum_{c,t} W[o, c*T + t] F[b,c,p,idx[a,t],r] (functional.py:L2606-2627; the
+    gathered tensor would be 193 GB), takes the same three steps on the quad kernels (_intra_kernels), with as many channels per dW slice
+    as keep its bytes: 16 of 240 entries for 64 of 60."""
 
     @staticmethod
     def forward(ctx, feats, W, idx32):
         feats, W = feats.contiguous(), W.contiguous()
         ctx.save_for_backward(feats, W, idx32)
-        return _hip.so3_intra_conv(feats, W, idx32)
+        return _intra_kernels(feats, idx32)[0](feats, W, idx32)
 
     @staticmethod
     def backward(ctx, gy):
         feats, W, idx32 = ctx.saved_tensors
         gy = gy.contiguous()
-        b, c, p, na = feats.shape
-        o, nt = W.shape[0], idx32.shape[1]
+        b, c, p, tot = feats.shape
+        o, (na, nt) = W.shape[0], idx32.shape
+        conv, group = _intra_kernels(feats, idx32)
         gF = gW = None
         if ctx.needs_input_grad[0]:
-            inv = torch.empty_like(idx32)                                         # inv[idx[a,t], t] = a
-            inv.scatter_(0, idx32.long(), torch.arange(na, device=idx32.device, dtype=torch.int32)[:, None].expand(na, nt).contiguous())
             W2 = W.view(o, c, nt).permute(1, 0, 2).reshape(c, o * nt).contiguous()
-            gF = _hip.so3_intra_conv(gy, W2, inv.contiguous())
+            gF = conv(gy, W2, _intra_inverse_table(idx32))
         if ctx.needs_input_grad[1]:
             gW = torch.empty(o, c, nt, dtype=torch.float32, device=gy.device)
-            pa = p * na
-            for c0 in range(0, c, INTRA_DW_SLICE):
-                c1 = min(c, c0 + INTRA_DW_SLICE)
-                g = _hip.so3_intra_group_fwd(feats[:, c0:c1].contiguous(), idx32)       # [b, cs, nt, p, na]
+            pa = p * tot
+            step = max(1, INTRA_DW_SLICE * na // tot)
+            for c0 in range(0, c, step):
+                c1 = min(c, c0 + step)
+                g = group(feats[:, c0:c1].contiguous(), idx32)                          # [b, cs, nt, p, tot]
                 d = torch.empty(o, (c1 - c0) * nt, dtype=torch.float32, device=gy.device)
                 _hip.matmul_reduce(gy.view(b, o, pa), g.view(b, (c1 - c0) * nt, pa).transpose(1, 2), d)
                 gW[:, c0:c1] = d.view(o, c1 - c0, nt)
+                del g, d                                                                # one slice of scratch at a time, not two
             gW = gW.view(o, c * nt)
         return gF, gW, None
 
@@ -1572,6 +1606,15 @@ def intra_so3conv(feats, W, intra_idx):
     """feats [b,c,p,na], W [o, c*T], intra_idx [na,T] -> [b,o,p,na]; what IntraSO3Conv.forward runs."""
     if feats.dtype != torch.float32 or not feats.is_cuda:
         raise RuntimeError('intra_so3conv: float32 device tensors only')
+    return _IntraConv.apply(feats, W, intra_idx.to(torch.int32).contiguous())
+
+
+def intra_so3conv2d(feats, W, intra_idx):
+    """feats [b,c,p,na*4], W [o, c*T], intra_idx [na,T] -> [b,o,p,na*4], the residual innermost; what IntraSO3Conv2D.forward runs."""
+    if feats.dtype != torch.float32 or not feats.is_cuda:
+        raise RuntimeError('intra_so3conv2d: float32 device tensors only')
+    if feats.shape[3] != 4 * intra_idx.shape[0]:
+        raise RuntimeError(f'intra_so3conv2d: an anchor axis of {feats.shape[3]} entries is not {intra_idx.shape[0]} anchors x 4 residuals')
     return _IntraConv.apply(feats, W, intra_idx.to(torch.int32).contiguous())
 
 
@@ -1953,8 +1996,11 @@ def intra_so3conv_grouping(intra_idx, feature):
 
 def intra_so3conv_grouping_2D(intra_idx, feature):
     """The 2-D variant (functional.py:L2606-2628): the anchor axis is (na, 4); the 12-tap gather acts on na.
-    feature [nb,c,np,na*4] -> [nb,c,pnn,np,na*4].  Index plumbing only (a view + one gather)."""
+    feature [nb,c,np,na*4] -> [nb,c,pnn,np,na*4].  float32 device tensors: one kernel each way (_IntraGroup2D); anything else: the
+    reference's tensor expression (a view + one gather)."""
     nb, c_in, nq, tot_na = feature.shape
+    if feature.is_cuda and feature.dtype == torch.float32:
+        return _IntraGroup2D.apply(feature, intra_idx.to(torch.int32).contiguous())
     f = feature.contiguous().view(nb, c_in, nq, -1, 4)
     na = f.size(-2)
     _, pnn = intra_idx.shape

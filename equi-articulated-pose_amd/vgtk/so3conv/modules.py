@@ -177,7 +177,13 @@ class IntraSO3Conv2D(IntraSO3Conv):
     buffers, the 12-tap gather acts on the 60-axis."""
 
     def forward(self, x):
-        out = self.basic_conv(L.intra_so3conv_grouping_2D(self.intra_idx, x.feats))
+        feats = x.feats
+        if feats.is_cuda and feats.dtype == torch.float32 and feats.shape[3] == 4 * self.intra_idx.shape[0]:
+            # implicit GEMM in both directions, an anchor's four residuals gathered as one 16-byte quad: the [B,C,12,P,240] tensor
+            # (193 GB at C = 512, B = 8, P = 4096) is never written (L._IntraConv on the quad kernels)
+            out = L.intra_so3conv2d(feats, self.basic_conv.W, self.intra_idx)
+        else:
+            out = self.basic_conv(L.intra_so3conv_grouping_2D(self.intra_idx, feats))
         return SphericalPointCloud(x.xyz, out, self.anchors)
 
 

@@ -680,6 +680,35 @@ int eap_gemm_f32_reduce_xb(int transA, int transB, int M, int N, int K, const fl
 int eap_so3_intra_conv_f32(int b, int o, int c, int p, int na, int nt, const float *W, const float *feats,
                            const int32_t *intra_idx, float *out, eap_stream_t stream);
 
+/* ---- SO(3) intra convolution on the (na, nr) anchor axis of `use_2d` ------------------------------------------
+ * IntraSO3Conv2D (so3conv/modules.py:L350-373): the anchor axis is na icosahedral anchors times nr in-plane residual rotations, the
+ * residual innermost, and the 12-tap gather acts on the na-axis alone (intra_so3conv_grouping_2D, so3conv/functional.py:L2606-2627).
+ * Limits of every entry below: nr = 4 (the residuals of one anchor are one 16-byte quad), na <= 64, nt <= 16 (nt = 12 on the split
+ * kernel); anything else returns hipErrorInvalidValue before a pointer is touched; an empty problem returns 0. */
+
+/* so3_intra_group2d_fwd: intra_so3conv_grouping_2D, so3conv/functional.py:L2606-2627.
+ * feats [b,c,p,na,nr], intra_idx int32 [na,t] -> out [b,c,t,p,na,nr] = feats[b,c,p,intra_idx[a,t],r]; feats and out 16-byte aligned. */
+int eap_so3_intra_group2d_fwd_f32(int b, int c, int p, int na, int nr, int t, const float *feats, const int32_t *intra_idx, float *out,
+                                  eap_stream_t stream);
+/* transpose: gout [b,c,t,p,na,nr] -> gfeats [b,c,p,na,nr], every element the sum of the quads that read it, in table order
+ * (no float atomics: bit-identical run to run). */
+int eap_so3_intra_group2d_bwd_f32(int b, int c, int p, int na, int nr, int t, const float *gout, const int32_t *intra_idx, float *gfeats,
+                                  eap_stream_t stream);
+/* The layer as an implicit GEMM (no [b,c,t,p,na,nr] gathered tensor):
+ * out[b,o,p,a,r] = sum_{c,t} W[o, c*nt + t] * feats[b, c, p, intra_idx[a*nt + t], r]
+ * (so3conv/functional.py:L2606-2627 intra_so3conv_grouping_2D + so3conv/modules.py:L48-55 BasicSO3Conv).
+ * W [o, c*nt], feats [b,c,p,na,nr], intra_idx int32 [na,nt], out [b,o,p,na,nr]. */
+int eap_so3_intra_conv2d_f32(int b, int o, int c, int p, int na, int nr, int nt, const float *W, const float *feats,
+                             const int32_t *intra_idx, float *out, eap_stream_t stream);
+/* the same on the split kernel (nt = 12; o and p*na*nr multiples of 128; c*nt a multiple of 16; W 16-byte aligned), three bf16 planes or
+ * two fp16 planes: abs_w [o] = eap_absmax_rows_f32 of W, abs_f [b][p] = eap_absmax_colgroups_f32 of feats [b][c][p*na*nr] in groups of
+ * na*nr (a column gathers 12 quads of its point). */
+int eap_so3_intra_conv2d_split_supported(int b, int o, int c, int p, int na, int nr, int nt);
+int eap_so3_intra_conv2d_bf16x3_f32(int b, int o, int c, int p, int na, int nr, int nt, const float *W, const float *feats,
+                                    const int32_t *intra_idx, float *out, eap_stream_t stream);
+int eap_so3_intra_conv2d_f16x2_f32(int b, int o, int c, int p, int na, int nr, int nt, const float *W, const float *feats,
+                                   const int32_t *intra_idx, float *out, const int32_t *abs_w, const int32_t *abs_f, eap_stream_t stream);
+
 /* ---- chamfer distance (extensions/chamfer_dist) ------------------------------------------- */
 
 /* chamfer.forward: chamfer_cuda.cpp:L22-25, chamfer.cu:L15-171.
