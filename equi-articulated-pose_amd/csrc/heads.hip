@@ -6,6 +6,8 @@
 //   slot-masked point mean     the pose head's masked averages over the points of every slot at once
 //        (SPConvNets/models/model_utils.py:L470-472 + L484 / L549-552, called once per slot by
 //        ...pn_38_multi_stage.py:L695-1015):   out[b,s,c,a] = sum_n m[b,s,n] x[b,c,n,a] / max(sum_n m[b,s,n], 1e-8)
+//   norm + act + point mean    the last unary layer of InvOutBlockOursWithMask and the point average behind it
+//        (SPConvNets/utils/base_so3conv.py:L1076-1107):   out[b,c,a] = inv_den[b] sum_p w[b,p] leaky(x[b,c,p,a] scale[b,c] + shift[b,c])
 //
 // Mapping: 16 lanes per point (15 anchor quads of a 60-anchor row + one idle lane), 4 consecutive points per
 // wave: one 16-byte load per lane covers 960 contiguous bytes of x; reductions over the anchors are 4 shuffle
@@ -199,6 +201,152 @@ __global__ __launch_bounds__(256) void masked_max_bwd_kernel(int c, int n, int n
     }
 }
 
+// ---- BatchNorm2d + leaky_relu + weighted point mean in one pass: the last unary layer of InvOutBlockOursWithMask and the point
+// average behind it (SPConvNets/utils/base_so3conv.py:L1076-1107; between that ReLU and the average the reference's pointnet stage
+// is linear, so the average moves in front of it and the activated [b,c,n,a] map is never needed):
+//     out[b,c,a] = inv_den[b] sum_p w[b,p] leaky(x[b,c,p,a] scale[b,c] + shift[b,c])
+// block = (channel, cloud); lane = (point group of 4, anchor quad) as above.  A lane takes PM_UNROLL points per loop trip into as
+// many accumulators (independent loads in flight, fp32 chains of n / 64 terms); accumulators, point groups and waves are folded in a
+// fixed order: bit-identical run to run.  Points past n re-read point n - 1 with weight 0.
+constexpr int PM_UNROLL = 4;
+constexpr int PM_PARTS = 16;            // partial sums per (cloud, channel) the backward reduction leaves: 4 waves x 4 point groups
+constexpr int PM_APPLY_PTS = 512;       // points per block of the backward apply
+
+__device__ __forceinline__ float leaky(float pre, float slope) { return pre > 0.f ? pre : pre * slope; }
+
+__global__ __launch_bounds__(256) void bn_act_mean_fwd_kernel(int c, int n, int na, float slope, const float *__restrict__ x,
+                                                              const float *__restrict__ scale, const float *__restrict__ shift,
+                                                              const float *__restrict__ w, const float *__restrict__ inv_den,
+                                                              float *__restrict__ out) {
+    __shared__ float4 s_part[16][16];                         // [wave * 4 + point group][quad]
+    const int ci = blockIdx.x, bi = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane >> 4, quad = lane & 15, nq = na >> 2;
+    const size_t si = (size_t)bi * c + ci;
+    const float sc = scale[si], sh = shift[si];
+    const float *xp = x + si * n * na + 4 * min(quad, nq - 1);
+    const float *wp = w + (size_t)bi * n;
+    float4 acc[PM_UNROLL];
+#pragma unroll
+    for (int u = 0; u < PM_UNROLL; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int p0 = wave * 4 + grp; p0 < n; p0 += 16 * PM_UNROLL) {
+        float4 v[PM_UNROLL];
+        float wv[PM_UNROLL];
+#pragma unroll
+        for (int u = 0; u < PM_UNROLL; ++u) {
+            const int p = p0 + 16 * u, pc = min(p, n - 1);
+            v[u] = *reinterpret_cast<const float4 *>(xp + (size_t)pc * na);
+            wv[u] = p < n ? wp[pc] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < PM_UNROLL; ++u) {
+            acc[u].x = fmaf(wv[u], leaky(fmaf(v[u].x, sc, sh), slope), acc[u].x);
+            acc[u].y = fmaf(wv[u], leaky(fmaf(v[u].y, sc, sh), slope), acc[u].y);
+            acc[u].z = fmaf(wv[u], leaky(fmaf(v[u].z, sc, sh), slope), acc[u].z);
+            acc[u].w = fmaf(wv[u], leaky(fmaf(v[u].w, sc, sh), slope), acc[u].w);
+        }
+    }
+    s_part[wave * 4 + grp][quad] = make_float4((acc[0].x + acc[1].x) + (acc[2].x + acc[3].x), (acc[0].y + acc[1].y) + (acc[2].y + acc[3].y),
+                                               (acc[0].z + acc[1].z) + (acc[2].z + acc[3].z), (acc[0].w + acc[1].w) + (acc[2].w + acc[3].w));
+    __syncthreads();
+    if (threadIdx.x < nq) {
+        const int q = threadIdx.x;
+        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int j = 0; j < 16; ++j) { const float4 u = s_part[j][q]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
+        const float d = inv_den[bi];
+        *reinterpret_cast<float4 *>(out + si * na + 4 * q) = make_float4(t.x * d, t.y * d, t.z * d, t.w * d);
+    }
+}
+
+// backward, reduction pass: with gg = (pre > 0 ? 1 : slope) w[b,p] inv_den[b] g[b,c,a] (the gradient the unfused composition would
+// broadcast to [b,c,n,a] and read back), the sums of gg and gg xhat over the points and anchors of a (cloud, channel) row as PM_PARTS
+// partials [b][c][wave * 4 + point group], for the caller to add in float64
+__global__ __launch_bounds__(256) void bn_act_mean_bwd_reduce_kernel(int c, int n, int na, float slope, const float *__restrict__ g,
+                                                                     const float *__restrict__ x, const float *__restrict__ scale,
+                                                                     const float *__restrict__ shift, const float *__restrict__ mean,
+                                                                     const float *__restrict__ invstd, const float *__restrict__ w,
+                                                                     const float *__restrict__ inv_den, float *__restrict__ pg,
+                                                                     float *__restrict__ pgx) {
+    const int ci = blockIdx.x, bi = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane >> 4, quad = lane & 15, nq = na >> 2;
+    const size_t si = (size_t)bi * c + ci;
+    const float sc = scale[si], sh = shift[si], mu = mean[si], is = invstd[si], d = inv_den[bi];
+    float4 gq = *reinterpret_cast<const float4 *>(g + si * na + 4 * min(quad, nq - 1));
+    gq = make_float4(gq.x * d, gq.y * d, gq.z * d, gq.w * d);
+    const float *xp = x + si * n * na + 4 * min(quad, nq - 1);
+    const float *wp = w + (size_t)bi * n;
+    float s[PM_UNROLL], q[PM_UNROLL];
+#pragma unroll
+    for (int u = 0; u < PM_UNROLL; ++u) s[u] = q[u] = 0.f;
+    for (int p0 = wave * 4 + grp; p0 < n; p0 += 16 * PM_UNROLL) {
+        float4 v[PM_UNROLL];
+        float wv[PM_UNROLL];
+#pragma unroll
+        for (int u = 0; u < PM_UNROLL; ++u) {
+            const int p = p0 + 16 * u, pc = min(p, n - 1);
+            v[u] = *reinterpret_cast<const float4 *>(xp + (size_t)pc * na);
+            wv[u] = p < n ? wp[pc] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < PM_UNROLL; ++u) {
+            const float g0 = (fmaf(v[u].x, sc, sh) > 0.f ? gq.x : gq.x * slope) * wv[u], g1 = (fmaf(v[u].y, sc, sh) > 0.f ? gq.y : gq.y * slope) * wv[u];
+            const float g2 = (fmaf(v[u].z, sc, sh) > 0.f ? gq.z : gq.z * slope) * wv[u], g3 = (fmaf(v[u].w, sc, sh) > 0.f ? gq.w : gq.w * slope) * wv[u];
+            s[u] += (g0 + g1) + (g2 + g3);
+            q[u] += (g0 * ((v[u].x - mu) * is) + g1 * ((v[u].y - mu) * is)) + (g2 * ((v[u].z - mu) * is) + g3 * ((v[u].w - mu) * is));
+        }
+    }
+    const bool live = quad < nq;                              // an idle lane re-read the last quad
+    const float ts = group16_sum(live ? (s[0] + s[1]) + (s[2] + s[3]) : 0.f), tq = group16_sum(live ? (q[0] + q[1]) + (q[2] + q[3]) : 0.f);
+    if (quad == 0) {
+        pg[si * PM_PARTS + wave * 4 + grp] = ts;
+        pgx[si * PM_PARTS + wave * 4 + grp] = tq;
+    }
+}
+
+// backward, apply pass: gx = scale gg - stat_mask (k2 + xhat k3), the formula of bn_act_bwd_apply_kernel<CLOUD> (csrc/bn_act.hip) on the gradient
+// formed in registers.  block = (channel, cloud, PM_APPLY_PTS points)
+__global__ __launch_bounds__(256) void bn_act_mean_bwd_apply_kernel(int c, int n, int na, float slope, const float *__restrict__ g,
+                                                                    const float *__restrict__ x, const float *__restrict__ scale,
+                                                                    const float *__restrict__ shift, const float *__restrict__ mean,
+                                                                    const float *__restrict__ invstd, const float *__restrict__ k2,
+                                                                    const float *__restrict__ k3, const float *__restrict__ w,
+                                                                    const float *__restrict__ inv_den, const float *__restrict__ stat_mask,
+                                                                    float *__restrict__ gx) {
+    const int ci = blockIdx.x, bi = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane >> 4, quad = lane & 15, nq = na >> 2;
+    if (quad >= nq) return;
+    const size_t si = (size_t)bi * c + ci;
+    const float sc = scale[si], sh = shift[si], mu = mean[si], is = invstd[si], c2 = k2[si], c3 = k3[si], d = inv_den[bi];
+    float4 gq = *reinterpret_cast<const float4 *>(g + si * na + 4 * quad);
+    gq = make_float4(gq.x * d, gq.y * d, gq.z * d, gq.w * d);
+    const float *xp = x + si * n * na + 4 * quad;
+    float *op = gx + si * n * na + 4 * quad;
+    const float *wp = w + (size_t)bi * n;
+    const float *mp = stat_mask ? stat_mask + (size_t)bi * n : nullptr;
+    const int first = blockIdx.z * PM_APPLY_PTS, last = min(n, first + PM_APPLY_PTS);
+    auto one = [&](float gv, float xv, float wv, float m) {
+        const float gg = (fmaf(xv, sc, sh) > 0.f ? gv : gv * slope) * wv;
+        return fmaf(-m, fmaf((xv - mu) * is, c3, c2), gg * sc);
+    };
+    for (int p = first + wave * 4 + grp; p < last; p += 16) {
+        const float4 v = *reinterpret_cast<const float4 *>(xp + (size_t)p * na);
+        const float wv = wp[p], m = mp ? mp[p] : 1.f;
+        *reinterpret_cast<float4 *>(op + (size_t)p * na) = make_float4(one(gq.x, v.x, wv, m), one(gq.y, v.y, wv, m), one(gq.z, v.z, wv, m), one(gq.w, v.w, wv, m));
+    }
+}
+
+inline int point_mean_dims(const char *who, int na, const void *p0, const void *p1, const void *p2) {
+    char buf[200];
+    if (na <= 0 || na > 64 || (na & 3) != 0) {
+        snprintf(buf, sizeof(buf), "%s: anchors must be a multiple of 4, at most 64", who);
+        return eap::bad_arg(buf);
+    }
+    if (((reinterpret_cast<uintptr_t>(p0) | reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2)) & 15) != 0) {
+        snprintf(buf, sizeof(buf), "%s: the [b,c,n,na] and [b,c,na] tensors must be 16-byte aligned", who);
+        return eap::bad_arg(buf);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int eap_anchor_attn_pool_fwd_f32(int b, int c, int n, int na, float temperature, const float *x, const float *logits,
@@ -246,4 +394,36 @@ extern "C" int eap_masked_max_bwd_f32(int b, int c, int n, int na, const float *
     if (b <= 0 || c <= 0 || n <= 0) return 0;
     if (na <= 0 || na > 64 || (na & 3) != 0) return eap::bad_arg("masked_max: anchors must be a multiple of 4, at most 64");
     return eap::run_kernel("masked_max_bwd", masked_max_bwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, g, arg, mask, dx);
+}
+
+// ---- BatchNorm2d + leaky_relu + weighted point mean (InvOutBlockOursWithMask, SPConvNets/utils/base_so3conv.py:L1076-1107) ----
+extern "C" int eap_bn_act_cloud_mean_parts(int n) { return n > 0 ? PM_PARTS : 0; }
+
+extern "C" int eap_bn_act_cloud_mean_fwd_f32(int b, int c, int n, int na, float slope, const float *x, const float *scale, const float *shift,
+                                             const float *w, const float *inv_den, float *out, eap_stream_t stream) {
+    if (b <= 0 || c <= 0) return 0;
+    if (n <= 0) return eap::bad_arg("bn_act_cloud_mean_fwd: no points");
+    if (int e = point_mean_dims("bn_act_cloud_mean_fwd", na, x, out, nullptr)) return e;
+    return eap::run_kernel("bn_act_cloud_mean_fwd", bn_act_mean_fwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, slope, x, scale, shift, w,
+                           inv_den, out);
+}
+
+extern "C" int eap_bn_act_cloud_mean_bwd_reduce_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
+                                                    const float *shift, const float *mean, const float *invstd, const float *w,
+                                                    const float *inv_den, float *pg, float *pgx, eap_stream_t stream) {
+    if (b <= 0 || c <= 0) return 0;
+    if (n <= 0) return eap::bad_arg("bn_act_cloud_mean_bwd_reduce: no points");
+    if (int e = point_mean_dims("bn_act_cloud_mean_bwd_reduce", na, x, g, nullptr)) return e;
+    return eap::run_kernel("bn_act_cloud_mean_bwd_reduce", bn_act_mean_bwd_reduce_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, slope, g, x,
+                           scale, shift, mean, invstd, w, inv_den, pg, pgx);
+}
+
+extern "C" int eap_bn_act_cloud_mean_bwd_apply_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
+                                                   const float *shift, const float *mean, const float *invstd, const float *k2, const float *k3,
+                                                   const float *w, const float *inv_den, const float *stat_mask, float *gx, eap_stream_t stream) {
+    if (b <= 0 || c <= 0) return 0;
+    if (n <= 0) return eap::bad_arg("bn_act_cloud_mean_bwd_apply: no points");
+    if (int e = point_mean_dims("bn_act_cloud_mean_bwd_apply", na, x, g, gx)) return e;
+    return eap::run_kernel("bn_act_cloud_mean_bwd_apply", bn_act_mean_bwd_apply_kernel, c, b, eap::cdiv(n, PM_APPLY_PTS), dim3(256), 0, eap::S(stream), c,
+                           n, na, slope, g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, gx);
 }

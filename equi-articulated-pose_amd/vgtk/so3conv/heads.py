@@ -15,6 +15,10 @@ and 3), mirroring the reference classes so a maintainer can swap the import:
                            regressors and the masked translation average stay torch ops.
 
   pose_head_over_subsets   the model's per-cloud loop around that head (...pn_38_multi_stage.py:L706-830) as one call per slot
+  InvOutBlockOursWithMask  SPConvNets/utils/base_so3conv.py:L1013-1150 with its PointnetSO3ConvOurs (L1153-1205), the per-slot
+                           shape-code head: the last unary layer's BatchNorm + ReLU and the point mean are one HIP pass
+                           (csrc/heads.hip), the embed layer runs on the means
+  inv_head_over_subsets, inv_heads_over_slot_groups   the model's per-cloud / per-slot loops around that head, batched
 
 Every 1x1 convolution over the [B,C,N,A] map (InvPPOutBlockOurs' included) is the path's contraction, every BatchNorm +
 activation after one the fused epilogue; only the regressors on pooled [B,c,A] tensors are torch layers."""
@@ -714,4 +718,349 @@ def pose_head_over_slot_groups(heads, feats, xyz, labels, anchors, use_offset=Tr
         sub_feats = _GatherPoints.apply(feats, rows)
         sub_xyz = torch.gather(xyz, 2, sel.unsqueeze(1).expand(-1, xyz.shape[1], -1)).contiguous()
         outs.append(pose_head_over_subsets(head, sub_feats, sub_xyz, member, anchors, use_offset))
+    return outs
+
+
+# ---- the per-slot shape-code head: InvOutBlockOursWithMask + PointnetSO3ConvOurs (base_so3conv.py:L1013-1205) ----------------------
+# Between the ReLU of the head's last unary layer and the average over the points the reference is linear (a mask, a concatenation
+# with the rotated coordinates, the 1x1 `embed`), so with point weights w_p of sum 1
+#     mean_p embed([h_p ; A^T x_p]) = W_f (mean_p h_p) + W_x A^T (mean_p x_p) + bias
+# and the only work left on the [B,c,N,A] map is BatchNorm2d + ReLU + the weighted point mean, one fused pass (csrc/heads.hip,
+# the eap_bn_act_cloud_mean_* entries): neither the activated map, the (c+3)-channel concatenation nor the embed output exists.
+
+class _NormActPointMean(torch.autograd.Function):
+    """out[b,c,a] = inv_den[b] sum_p w[b,p] leaky(BatchNorm2d(y + bias))[b,c,p,a]: y [B,C,P,A] the raw contraction output, w [B,P] point
+    weights and inv_den [B] (data).  stat_mask [B,P] (0/1): training statistics per cloud over its members, as _SubsetBNAct takes them
+    (B momentum updates of the running statistics in cloud order, in closed form); None: the statistics of the whole batch, as
+    nn.BatchNorm2d takes them.  The conv bias rides in the mean (gradient exactly zero in training mode).  Saved for the backward:
+    y and [B,C] vectors; the backward is a reduction pass and an apply pass over y."""
+
+    @staticmethod
+    def forward(ctx, y, bias, w, inv_den, stat_mask, weight, beta, running_mean, running_var, training, momentum, eps, slope):
+        y = L._aligned16(y)
+        b, c, p, na = y.shape
+        n = p * na
+        if training:
+            pivot = y.view(b, c, n)[0, :, 0].double().view(1, c)
+            if stat_mask is not None:
+                cnt = (stat_mask.sum(1, dtype=torch.float64) * na).view(b, 1)           # member points x anchors
+                s1, s2 = _hip.bn_stats_masked(y, b, c, n, na, stat_mask)                # of y - pivot, [b, c] float64
+            else:
+                cnt = torch.full((1, 1), float(b * n), dtype=torch.float64, device=y.device)
+                s1, s2 = (s.view(1, c) for s in _hip.bn_stats(y, b, c, n))
+            d = s1 / cnt
+            var = (s2 / cnt - d * d).clamp_min(0.0)                                     # biased, as BatchNorm normalises with
+            mean = d + pivot                                                            # of y (without the bias)
+            with torch.no_grad():
+                full = (mean + bias.double().view(1, c)) if bias is not None else mean
+                unb = var * (cnt / (cnt - 1.0).clamp_min(1.0))
+                r = mean.shape[0]                                                       # r sequential updates in closed form
+                keep = (1.0 - momentum) ** torch.arange(r - 1, -1, -1, device=y.device, dtype=torch.float64).view(r, 1)
+                running_mean.mul_((1.0 - momentum) ** r).add_((momentum * (keep * full).sum(0)).to(running_mean.dtype))
+                running_var.mul_((1.0 - momentum) ** r).add_((momentum * (keep * unb).sum(0)).to(running_var.dtype))
+        else:
+            mean = (running_mean.double() - (bias.double() if bias is not None else 0.0)).view(1, c)
+            var = running_var.double().view(1, c)
+        invstd = torch.rsqrt(var + eps)
+        scale64 = weight.double().view(1, c) * invstd
+        scale = scale64.expand(b, c).float().contiguous()
+        shift = (beta.double().view(1, c) - mean * scale64).expand(b, c).float().contiguous()
+        out = _hip.bn_act_cloud_mean_fwd(y, scale, shift, w, inv_den, slope)
+        ctx.save_for_backward(y, scale, shift, mean.expand(b, c).float().contiguous(), invstd.expand(b, c).float().contiguous(), w, inv_den,
+                              stat_mask)
+        ctx.training, ctx.slope, ctx.has_bias = training, slope, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y, scale, shift, mean, invstd, w, inv_den, stat_mask = ctx.saved_tensors
+        b, c, p, na = y.shape
+        g = L._aligned16(g)
+        sg, sgx = _hip.bn_act_cloud_mean_bwd_reduce(g, y, scale, shift, mean, invstd, w, inv_den, ctx.slope)     # [b, c] float64
+        g_y = None
+        if ctx.needs_input_grad[0]:
+            if ctx.training and stat_mask is not None:
+                cnt = (stat_mask.sum(1, dtype=torch.float64) * na).view(b, 1)
+                k2 = (scale.double() * sg / cnt).float().contiguous()
+                k3 = (scale.double() * sgx / cnt).float().contiguous()
+            elif ctx.training:
+                cnt = float(b * p * na)
+                k2 = (scale.double() * sg.sum(0, keepdim=True) / cnt).float().contiguous()
+                k3 = (scale.double() * sgx.sum(0, keepdim=True) / cnt).float().contiguous()
+            else:
+                k2 = torch.zeros_like(scale)
+                k3 = torch.zeros_like(scale)
+            g_y = _hip.bn_act_cloud_mean_bwd_apply(g, y, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, ctx.slope)
+        g_bias = None
+        if ctx.has_bias:           # absorbed by the batch mean in training mode; in eval mode it shifts the pre-activation like beta does
+            g_bias = torch.zeros(c, dtype=torch.float32, device=g.device) if ctx.training else (sg * scale.double()).sum(0).float()
+        return g_y, g_bias, None, None, None, sgx.sum(0).float(), sg.sum(0).float(), None, None, None, None, None, None
+
+
+def _norm_act_point_mean(y, bias, w, inv_den, stat_mask, bn, slope=0.0):
+    """inv_den sum_p w act(bn(y + bias)) -> [B,c,A]; y [B,c,P,A] raw contraction output, w [B,P], inv_den [B], stat_mask [B,P] or None
+    (see _NormActPointMean); anchor counts the 16-byte kernels do not take run the same expressions as device tensor ops."""
+    if bn.momentum is None or not bn.track_running_stats:
+        raise NotImplementedError('InvOutBlockOursWithMask: BatchNorm with running statistics and a momentum only')
+    b, c = y.shape[:2]
+    w, inv_den = w.to(torch.float32).contiguous(), inv_den.to(torch.float32).contiguous()
+    if not _anchor_rows_vectorise(y.shape[3]):
+        if stat_mask is not None:
+            if bn.training:
+                bn.num_batches_tracked.add_(b)
+            z = _subset_batchnorm_act_torch(y, bias, stat_mask, bn, slope)
+        else:
+            z = bn(y + bias.view(1, c, 1, 1) if bias is not None else y)
+            z = F.leaky_relu(z, slope) if slope else F.relu(z)
+        return torch.einsum('bcpa,bp->bca', z, w) * inv_den.view(b, 1, 1)
+    if bn.training:
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(b if stat_mask is not None else 1)
+    return _NormActPointMean.apply(y, bias, w, inv_den, None if stat_mask is None else stat_mask.to(torch.float32).contiguous(), bn.weight, bn.bias,
+                                   bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps, slope)
+
+
+def _weighted_point_mean(h, w, inv_den):
+    """inv_den[b] sum_p w[b,p] h[b,c,p,a] of a map that exists (one pass: slot_masked_mean with its own denominator undone)"""
+    b, _, n, _ = h.shape
+    return slot_masked_mean(h, w.view(b, 1, n))[:, 0] * (w.sum(1).clamp(min=1e-8) * inv_den).view(b, 1, 1)
+
+
+def _batchnorm1d_per_cloud(bn, x):
+    """nn.BatchNorm1d on x [B,c,A] as B batch-1 calls: training statistics per cloud over its A anchors, the running statistics
+    updated B times in cloud order."""
+    if not bn.training:
+        return bn(x)
+    if bn.momentum is None or not bn.track_running_stats:
+        raise NotImplementedError('inv_head_over_subsets: BatchNorm with running statistics and a momentum only')
+    b, c, a = x.shape
+    mean, var = x.mean(2), x.var(2, unbiased=False)
+    with torch.no_grad():
+        unb = var * (a / max(a - 1, 1))
+        for i in range(b):
+            bn.running_mean.mul_(1.0 - bn.momentum).add_(mean[i], alpha=bn.momentum)
+            bn.running_var.mul_(1.0 - bn.momentum).add_(unb[i], alpha=bn.momentum)
+        bn.num_batches_tracked.add_(b)
+    return (x - mean.unsqueeze(2)) * torch.rsqrt(var.unsqueeze(2) + bn.eps) * bn.weight.view(1, c, 1) + bn.bias.view(1, c, 1)
+
+
+def inv_head_tail(head, pooled, xyz_mean=None, bias_weight=None, per_cloud=False, point_map=None):
+    """What InvOutBlockOursWithMask does behind the point average (base_so3conv.py:L1099-1150), on pooled [B,c,A] = the weighted point
+    mean of the last unary layer's activation.  Pure torch on small tensors (no native call: runs on any device):
+      use_pointnet: `embed` on the means, W_f pooled + W_x A^T xyz_mean + bias_weight * bias (xyz_mean [B,3]: the weighted mean of the
+        coordinates the embed layer would see, None = exactly zero, the centred plain mean; bias_weight [B]: the sum of the point
+        weights, None = 1), then BatchNorm1d + ReLU (per_cloud: statistics per cloud, as B batch-1 calls);
+      the mode pooling over the anchors.
+    -> the reference's return values: ([pooled features [B,c,A],] code [B,c], logits [B,A]); point_map stands for the per-point map the
+    reference hands out in the last place when the pooling is not 'attention'."""
+    x_out = pooled
+    if head.use_pointnet:
+        pn = head.pointnet
+        c, na = pooled.shape[1], pooled.shape[2]
+        W = pn.embed.weight.view(pn.dim_out, c + 3)
+        bias = pn.embed.bias.view(1, -1, 1)
+        x_out = torch.einsum('oc,bca->boa', W[:, :c], pooled) + (bias if bias_weight is None else bias * bias_weight.view(-1, 1, 1))
+        if xyz_mean is not None:
+            if na == 1:
+                coords = xyz_mean.unsqueeze(-1)
+            else:
+                anchors = pn.anchors if na == pn.anchors.size(0) else pn.tot_anchors.to(pooled.device)
+                coords = torch.einsum('aji,bj->bia', anchors, xyz_mean)
+            x_out = x_out + torch.einsum('oi,bia->boa', W[:, c:], coords)
+        bn = head.norm[len(head.linear)]
+        x_out = F.relu(_batchnorm1d_per_cloud(bn, x_out) if per_cloud else bn(x_out))
+    x_out_points_pooling = x_out.clone()
+    out_feat = point_map
+    if head.pooling_method == 'mean':
+        x_out = x_out.mean(dim=2)
+    elif head.pooling_method == 'debug':
+        x_out = x_out[..., 0].mean(2)
+    elif head.pooling_method == 'max':
+        x_out = x_out.max(2)[0]
+    elif head.pooling_method == 'sel_mode':
+        x_out = x_out[..., head.sel_mode]
+    elif head.pooling_method.startswith('attention'):
+        out_feat = head.attention_layer(x_out)                      # [B,1,A]
+        confidence = F.softmax(out_feat * head.temperature, dim=2)
+        x_out = (x_out * confidence).sum(-1)
+    else:
+        raise NotImplementedError(f"Pooling mode {head.pooling_method} is not implemented!")
+    if out_feat is None:
+        raise RuntimeError("InvOutBlockOursWithMask: without the pointnet stage only 'attention' pooling defines the head's last return value "
+                           '(the reference fails on an unbound name there)')
+    if head.return_point_pooling_feature:
+        return x_out_points_pooling, x_out, out_feat.squeeze(1)
+    return x_out, out_feat.squeeze(1)
+
+
+class PointnetSO3ConvOurs(nn.Module):
+    """base_so3conv.py:L1153-1205: 1x1 conv over [feats ; A^T xyz] (xyz centred unless use_abs_pos), max over the points unless
+    return_raw.  Same constructor, sub-module `embed`, buffer `anchors`; the 240 products with the four in-plane turns are the plain
+    attribute tot_anchors, as in the reference.  The concatenation is never built: the feature half of the weights is the path's
+    contraction, the three coordinate channels a rank-3 term added to it."""
+
+    def __init__(self, dim_in, dim_out, kanchor=60, return_raw=False, use_abs_pos=False):
+        super(PointnetSO3ConvOurs, self).__init__()
+        self.register_buffer('anchors', torch.from_numpy(L.get_anchors(kanchor)))
+        self.dim_in = dim_in + 3
+        self.dim_out = dim_out
+        self.return_raw = return_raw
+        self.use_abs_pos = use_abs_pos
+        self.plane_anchors = L.get_2D_res_anchors()
+        self.tot_anchors = torch.matmul(self.anchors.unsqueeze(1), self.plane_anchors.to(self.anchors.dtype).unsqueeze(0)).contiguous().view(
+            self.anchors.size(0) * self.plane_anchors.size(0), 3, 3).contiguous()
+        self.embed = nn.Conv2d(self.dim_in, self.dim_out, 1)
+
+    def forward(self, x):
+        xyz, feats = x.xyz, x.feats
+        if not feats.is_cuda or feats.dtype != torch.float32:
+            raise RuntimeError('PointnetSO3ConvOurs: float32 CUDA(HIP) tensors only (no CPU fallback)')
+        b, c, n, na = feats.shape
+        if not self.use_abs_pos:
+            xyz = xyz - xyz.mean(2, keepdim=True)
+        W = self.embed.weight.view(self.dim_out, c + 3)
+        y = L.so3_contract(W[:, :c], feats.reshape(b, c, n * na)).view(b, self.dim_out, n, na)
+        if na == 1:
+            coords = xyz.unsqueeze(-1)
+        else:
+            anchors = self.anchors if na == self.anchors.size(0) else self.tot_anchors.to(feats.device)
+            coords = torch.einsum('aji,bjn->bina', anchors, xyz)
+        y = y + torch.einsum('oi,bina->bona', W[:, c:], coords) + self.embed.bias.view(1, -1, 1, 1)
+        return y if self.return_raw else torch.max(y, 2)[0]
+
+
+class InvOutBlockOursWithMask(nn.Module):
+    """The head that turns a slot's points into the invariant code the shape decoders read (base_so3conv.py:L1013-1150; the model's
+    slot_outblock / abs_slot_outblock / pair_slot_outblock / whole_shp_outblock / glb_outblock): 1x1-conv MLP over [B,C,N,A], the
+    pointnet embed, the (soft-mask weighted) mean over the points, BatchNorm1d + ReLU, pooling over the anchors.  Constructor
+    parameters, sub-module names (state_dict keys) and return values are the reference's.  The last unary layer's norm + ReLU and the
+    point mean are one fused pass and the embed layer runs on the means (see _NormActPointMean, inv_head_tail); in the centred case the
+    mean of x - mean(x), rounding noise in the reference, is taken as exactly zero.  soft_mask is treated as data."""
+
+    def __init__(self, params, norm=None, pooling_method='max', use_pointnet=True, sel_mode=None, use_abs_pos=False,
+                 return_point_pooling_feature=False):
+        super(InvOutBlockOursWithMask, self).__init__()
+        c_in = params['dim_in']
+        mlp = params['mlp']
+        na = params['kanchor']
+        self.outDim = params['k']
+        self.linear = nn.ModuleList()
+        self.norm = nn.ModuleList()
+        self.use_pointnet = use_pointnet
+        self.sel_mode = sel_mode
+        self.use_abs_pos = use_abs_pos
+        self.return_point_pooling_feature = return_point_pooling_feature
+        for c in mlp:
+            self.linear.append(nn.Conv2d(c_in, c, 1))
+            self.norm.append(nn.BatchNorm2d(c))
+            c_in = c
+        self.pooling_method = pooling_method if self.sel_mode is None else 'sel_mode'
+        if self.pooling_method == 'attention':
+            self.temperature = params['temperature']
+            self.attention_layer = nn.Conv1d(c_in, 1, 1)
+        if self.use_pointnet:
+            self.pointnet = PointnetSO3ConvOurs(c_in, c_in, na, return_raw=True, use_abs_pos=self.use_abs_pos)
+            self.norm.append(nn.BatchNorm1d(c_in))
+
+    def _needs_point_map(self):
+        """with the pointnet stage and a pooling other than 'attention' the reference's last return value is the per-point map itself"""
+        return self.use_pointnet and not self.pooling_method.startswith('attention')
+
+    def _pooled(self, feats, w, inv_den, stat_mask):
+        """-> inv_den sum_p w relu(norm(linear(...)))[.., p, :] of the unary stack, [B,c,A]; stat_mask: per-cloud statistics over members"""
+        nl = len(self.linear)
+        if nl == 0:
+            return _weighted_point_mean(feats.contiguous(), w, inv_den)
+        if stat_mask is None:
+            h = _unary_stack(feats, self.linear[:nl - 1], self.norm[:nl - 1])
+        else:
+            h = _masked_unary_stack(feats, stat_mask, self.linear[:nl - 1], self.norm[:nl - 1])
+        b, c, n, a = h.shape
+        last = self.linear[nl - 1]
+        y = L.so3_contract(last.weight.view(last.out_channels, c), h.reshape(b, c, n * a)).view(b, last.out_channels, n, a)
+        return _norm_act_point_mean(y, last.bias, w, inv_den, stat_mask, self.norm[nl - 1])
+
+    def forward(self, x, mask, label=None, soft_mask=None):
+        feats, xyz = x.feats, x.xyz
+        if not feats.is_cuda or feats.dtype != torch.float32:
+            raise RuntimeError('InvOutBlockOursWithMask: float32 CUDA(HIP) tensors only (no CPU fallback)')
+        if soft_mask is not None and soft_mask.requires_grad:
+            raise RuntimeError('InvOutBlockOursWithMask: the soft mask is treated as data (no gradient reaches it); detach it')
+        b, _, n, _ = feats.shape
+        ones = torch.ones(b, n, dtype=torch.float32, device=feats.device)
+        if mask is not None:
+            feats = feats * mask.unsqueeze(1).unsqueeze(-1)
+            if xyz is not None:
+                xyz = xyz * mask.unsqueeze(1)
+        behind = ones if mask is None else mask.detach().to(torch.float32)            # the mask behind the stack
+        if soft_mask is None:
+            inv_den = torch.full((b,), 1.0 / n, dtype=torch.float32, device=feats.device)
+        else:
+            inv_den = 1.0 / soft_mask.to(torch.float32).sum(1).clamp(min=1e-8)
+        xyz_mean = bias_weight = point_map = None
+        if not self.use_pointnet:
+            pooled = self._pooled(feats, behind, inv_den, None)                         # (the soft mask is the denominator only)
+        else:
+            over = ones if soft_mask is None else soft_mask.to(torch.float32)           # the weights of the average behind `embed`
+            if self._needs_point_map():
+                point_map = _unary_stack(feats, self.linear, self.norm[:len(self.linear)])
+                if mask is not None:
+                    point_map = point_map * mask.unsqueeze(1).unsqueeze(-1)
+                pooled = _weighted_point_mean(point_map.contiguous(), over, inv_den)
+            else:
+                pooled = self._pooled(feats, behind * over, inv_den, None)
+            seen = xyz if self.use_abs_pos else xyz - xyz.mean(2, keepdim=True)
+            if soft_mask is not None:
+                xyz_mean = (seen * over.unsqueeze(1)).sum(2) * inv_den.view(b, 1)
+                bias_weight = over.sum(1) * inv_den
+            elif self.use_abs_pos:
+                xyz_mean = seen.mean(2)
+        return inv_head_tail(self, pooled, xyz_mean, bias_weight, False, point_map)
+
+
+def inv_head_over_subsets(head, feats, xyz, member):
+    """InvOutBlockOursWithMask on one point subset per cloud, all clouds at once -- the batched form of the model's loop
+    `for i_bz in range(bz): head(SphericalPointCloud(xyz[i_bz, :, sel], feats[i_bz, :, sel]), mask=None)` (...pn_38_multi_stage.py:L706-830,
+    calls at L765-777).  feats [B,C,P,A], xyz [B,3,P], member [B,P] in {0,1}, at least one member per cloud (all ones: the
+    pair_slot_outblock call on whole clouds) -> the head's return values with batch dimension B, equal to rounding to B batch-1 calls
+    on the gathered subsets: BatchNorm2d statistics per cloud over its members, BatchNorm1d statistics per cloud over its anchors,
+    every norm's running statistics updated B times in cloud order, num_batches_tracked += B.  Points outside the subset receive a
+    gradient of exactly zero.  A pooling other than 'attention' behind the pointnet stage returns the per-point map of every subset,
+    which has no batched form."""
+    if head._needs_point_map():
+        raise NotImplementedError("inv_head_over_subsets: behind the pointnet stage 'attention' pooling only (the others return a per-point map)")
+    if not feats.is_cuda or feats.dtype != torch.float32:
+        raise RuntimeError('inv_head_over_subsets: float32 CUDA(HIP) tensors only (no CPU fallback)')
+    mask = member.to(torch.float32).contiguous()                                     # [B, P]
+    inv_den = 1.0 / mask.sum(1)
+    pooled = head._pooled(feats, mask, inv_den, mask)
+    xyz_mean = None
+    if head.use_pointnet and head.use_abs_pos:
+        xyz_mean = (xyz * mask.unsqueeze(1)).sum(2) * inv_den.view(-1, 1)
+    return inv_head_tail(head, pooled, xyz_mean, None, True, None)
+
+
+def inv_heads_over_slot_groups(heads, feats, xyz, labels, groups=None):
+    """The model's loop `for slot: for cloud: slot_outblock[slot](points of the slot in the cloud)` (...pn_38_multi_stage.py:L706-830)
+    with the work of P points per cloud, not slots x P: every slot's members are compacted (slot_point_groups + one gather pass) and
+    run through inv_head_over_subsets; a slot that holds at least 90 % of some cloud takes the masked form on the full clouds, as the
+    pose heads do.  heads[s]: one module, or a sequence of modules run on the same gathered subset (slot_outblock and
+    abs_slot_outblock share the gather); groups: a slot_point_groups(labels, len(heads)) result to share (it costs one device -> host
+    read).  -> per slot the head's return values, or a list of them for a sequence.
+    A slot absent from a cloud falls back to the whole cloud, as slot_point_groups does; the reference feeds two all-zero points there
+    (...pn_38_multi_stage.py:L742-744)."""
+    outs = []
+    p = feats.shape[2]
+    groups = slot_point_groups(labels, len(heads)) if groups is None else groups
+    for s_, (head, rows) in enumerate(zip(heads, groups)):
+        several = not isinstance(head, nn.Module)
+        if rows.shape[1] * 10 >= p * 9:
+            member = labels == s_
+            sub_feats, sub_xyz, member = feats, xyz, member | (member.sum(1, keepdim=True) == 0)
+        else:
+            member = rows >= 0
+            sub_feats = _GatherPoints.apply(feats, rows)
+            sub_xyz = torch.gather(xyz, 2, rows.clamp(min=0).long().unsqueeze(1).expand(-1, xyz.shape[1], -1)).contiguous()
+        res = [inv_head_over_subsets(h, sub_feats, sub_xyz, member) for h in (head if several else [head])]
+        outs.append(res if several else res[0])
     return outs

@@ -886,6 +886,24 @@ int eap_masked_max_fwd_f32(int b, int c, int n, int na, const float *x, const fl
                            eap_stream_t stream);
 int eap_masked_max_bwd_f32(int b, int c, int n, int na, const float *g, const int32_t *arg, const float *mask, float *dx,
                            eap_stream_t stream);
+/* The last unary layer of InvOutBlockOursWithMask with the point average behind it, fused (SPConvNets/utils/base_so3conv.py:L1076-1107:
+ * `F.relu(norm(linear(x)))`, the mask, PointnetSO3ConvOurs' 1x1 `embed` -- linear, so the average moves in front of it -- and the plain or
+ * soft-mask weighted mean over the points).  x [b,c,n,na] the raw contraction output; scale, shift, mean, invstd, k2, k3 [b,c]; w [b,n] point
+ * weights (data: 0/1 membership or soft weights); inv_den [b]; na % 4 == 0, <= 64; x, out, g, gx 16-byte aligned.  Fixed summation order.
+ *   out[b,c,a] = inv_den[b] * sum_p w[b,p] * leaky_relu(x[b,c,p,a] * scale[b,c] + shift[b,c], slope);  the activated map is never written */
+int eap_bn_act_cloud_mean_fwd_f32(int b, int c, int n, int na, float slope, const float *x, const float *scale, const float *shift,
+                                  const float *w, const float *inv_den, float *out, eap_stream_t stream);
+/* (base_so3conv.py:L1076-1107, backward) with gg = (pre > 0 ? 1 : slope) * w[b,p] * inv_den[b] * g[b,c,a], never written: the sums of gg and
+ * gg * xhat over a (cloud, channel) row as eap_bn_act_cloud_mean_parts(n) partials each, pg, pgx [b, c, parts], for the caller to add in float64 */
+int eap_bn_act_cloud_mean_parts(int n);
+int eap_bn_act_cloud_mean_bwd_reduce_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
+                                         const float *shift, const float *mean, const float *invstd, const float *w, const float *inv_den,
+                                         float *pg, float *pgx, eap_stream_t stream);
+/* (base_so3conv.py:L1076-1107, backward) gx[b,c,p,a] = scale[b,c] * gg - stat_mask[b,p] * (k2[b,c] + xhat * k3[b,c]);  stat_mask [b,n] may be
+ * null (all ones) */
+int eap_bn_act_cloud_mean_bwd_apply_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
+                                        const float *shift, const float *mean, const float *invstd, const float *k2, const float *k3,
+                                        const float *w, const float *inv_den, const float *stat_mask, float *gx, eap_stream_t stream);
 
 #ifdef __cplusplus
 }
