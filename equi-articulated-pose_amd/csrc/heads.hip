@@ -144,7 +144,17 @@ __global__ __launch_bounds__(256) void slot_mean_bwd_kernel(int c, int n, int na
 // masked max over the points, the pose head's 'max' pooling on a point subset (`(x * mask).max(2)`: SO3OutBlockRWithMask /
 // SO3OutBlockRTWithMaskSep with pooling_method = 'max', SPConvNets/models/model_utils.py:L79-80, L470-484): out[b,c,a] = max_p
 // mask[b,p] * x[b,c,p,a] and the point that attains it (the lowest index among equals: deterministic).  One pass over x.
+// A product that is NaN (a NaN or mask 0 times an infinity in x, whatever the mask) is the result, as torch's max gives it, and arg the
+// lowest point with such a product: a diverged map must not pool to a finite number.  -0.0 and +0.0 are equals.
 // block = (channel, cloud); lane = (point group of 4, anchor quad); groups and waves are folded through LDS in a fixed order
+__device__ __forceinline__ bool max_takes(float a, float best) {          // within a lane's ascending chain: larger, or the first NaN
+    return a > best || (a != a && best == best);
+}
+__device__ __forceinline__ bool max_takes(float u, int k, float best, int at) {      // between chains: ... or equal at a lower point
+    const bool un = u != u, bn = best != best;
+    return (un || bn) ? (un && (!bn || k < at)) : (u > best || (u == best && k < at));
+}
+
 __global__ __launch_bounds__(256) void masked_max_fwd_kernel(int c, int n, int na, const float *__restrict__ x, const float *__restrict__ m,
                                                              float *__restrict__ out, int32_t *__restrict__ arg) {
     __shared__ float4 s_val[16][16];
@@ -159,10 +169,10 @@ __global__ __launch_bounds__(256) void masked_max_fwd_kernel(int c, int n, int n
         const float4 v = *reinterpret_cast<const float4 *>(xp + (size_t)p0 * na);
         const float w = mp[p0];
         const float a0 = w * v.x, a1 = w * v.y, a2 = w * v.z, a3 = w * v.w;
-        if (a0 > best.x) { best.x = a0; at.x = p0; }
-        if (a1 > best.y) { best.y = a1; at.y = p0; }
-        if (a2 > best.z) { best.z = a2; at.z = p0; }
-        if (a3 > best.w) { best.w = a3; at.w = p0; }
+        if (max_takes(a0, best.x)) { best.x = a0; at.x = p0; }
+        if (max_takes(a1, best.y)) { best.y = a1; at.y = p0; }
+        if (max_takes(a2, best.z)) { best.z = a2; at.z = p0; }
+        if (max_takes(a3, best.w)) { best.w = a3; at.w = p0; }
     }
     s_val[wave * 4 + grp][quad] = best;
     s_idx[wave * 4 + grp][quad] = at;
@@ -174,10 +184,10 @@ __global__ __launch_bounds__(256) void masked_max_fwd_kernel(int c, int n, int n
         for (int j = 1; j < 16; ++j) {
             const float4 u = s_val[j][q];
             const int4 k = s_idx[j][q];
-            if (u.x > bv.x || (u.x == bv.x && k.x < bi4.x)) { bv.x = u.x; bi4.x = k.x; }
-            if (u.y > bv.y || (u.y == bv.y && k.y < bi4.y)) { bv.y = u.y; bi4.y = k.y; }
-            if (u.z > bv.z || (u.z == bv.z && k.z < bi4.z)) { bv.z = u.z; bi4.z = k.z; }
-            if (u.w > bv.w || (u.w == bv.w && k.w < bi4.w)) { bv.w = u.w; bi4.w = k.w; }
+            if (max_takes(u.x, k.x, bv.x, bi4.x)) { bv.x = u.x; bi4.x = k.x; }
+            if (max_takes(u.y, k.y, bv.y, bi4.y)) { bv.y = u.y; bi4.y = k.y; }
+            if (max_takes(u.z, k.z, bv.z, bi4.z)) { bv.z = u.z; bi4.z = k.z; }
+            if (max_takes(u.w, k.w, bv.w, bi4.w)) { bv.w = u.w; bi4.w = k.w; }
         }
         *reinterpret_cast<float4 *>(out + ((size_t)bi * c + ci) * na + 4 * q) = bv;
         *reinterpret_cast<int4 *>(arg + ((size_t)bi * c + ci) * na + 4 * q) = bi4;
@@ -347,12 +357,28 @@ inline int point_mean_dims(const char *who, int na, const void *p0, const void *
     return 0;
 }
 
+// the three older pairs: anchor rows of 16-byte words (and at most MAXS slots), every tensor a kernel reads or writes by float4 / int4 on a
+// 16-byte boundary (`which` names them in the message)
+inline int head_args(const char *who, int na, int ns, const char *which, const void *p0, const void *p1, const void *p2 = nullptr,
+                     const void *p3 = nullptr) {
+    char buf[240];
+    if (na <= 0 || na > 64 || (na & 3) != 0 || ns > MAXS) {
+        snprintf(buf, sizeof(buf), "%s: anchors must be a multiple of 4, at most 64%s", who, ns > 0 ? "; at most 8 slots" : "");
+        return eap::bad_arg(buf);
+    }
+    if (((reinterpret_cast<uintptr_t>(p0) | reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2) | reinterpret_cast<uintptr_t>(p3)) & 15) != 0) {
+        snprintf(buf, sizeof(buf), "%s: %s must be 16-byte aligned", who, which);
+        return eap::bad_arg(buf);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int eap_anchor_attn_pool_fwd_f32(int b, int c, int n, int na, float temperature, const float *x, const float *logits,
                                             float *out, float *conf, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0) return eap::bad_arg("anchor_attn_pool: anchors must be a multiple of 4, at most 64");
+    if (int e = head_args("anchor_attn_pool_fwd", na, 0, "x, logits and conf", x, logits, conf)) return e;
     return eap::run_kernel("anchor_attn_pool_fwd", anchor_attn_pool_kernel<false>, eap::cdiv(n, 16), b, 1, dim3(256), 0, eap::S(stream), c, n, na, temperature, x,
                            logits, nullptr, out, conf, nullptr, nullptr);
 }
@@ -360,7 +386,7 @@ extern "C" int eap_anchor_attn_pool_fwd_f32(int b, int c, int n, int na, float t
 extern "C" int eap_anchor_attn_pool_bwd_f32(int b, int c, int n, int na, float temperature, const float *x, const float *logits,
                                             const float *g, float *dx, float *dlogits, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0) return eap::bad_arg("anchor_attn_pool: anchors must be a multiple of 4, at most 64");
+    if (int e = head_args("anchor_attn_pool_bwd", na, 0, "x, logits, dx and dlogits", x, logits, dx, dlogits)) return e;
     return eap::run_kernel("anchor_attn_pool_bwd", anchor_attn_pool_kernel<true>, eap::cdiv(n, 16), b, 1, dim3(256), 0, eap::S(stream), c, n, na, temperature, x,
                            logits, g, nullptr, nullptr, dx, dlogits);
 }
@@ -368,31 +394,29 @@ extern "C" int eap_anchor_attn_pool_bwd_f32(int b, int c, int n, int na, float t
 extern "C" int eap_slot_masked_mean_fwd_f32(int b, int ns, int c, int n, int na, const float *x, const float *mask,
                                             const float *inv_den, float *out, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0 || ns <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0 || ns > MAXS)
-        return eap::bad_arg("slot_masked_mean: anchors must be a multiple of 4, at most 64; at most 8 slots");
+    if (int e = head_args("slot_masked_mean_fwd", na, ns, "x and out", x, out)) return e;
     return eap::run_kernel("slot_masked_mean_fwd", slot_mean_fwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, ns, x, mask, inv_den, out);
 }
 
 extern "C" int eap_slot_masked_mean_bwd_f32(int b, int ns, int c, int n, int na, const float *g, const float *mask,
                                             const float *inv_den, float *dx, eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0 || ns <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0 || ns > MAXS)
-        return eap::bad_arg("slot_masked_mean: anchors must be a multiple of 4, at most 64; at most 8 slots");
+    if (int e = head_args("slot_masked_mean_bwd", na, ns, "g and dx", g, dx)) return e;
     return eap::run_kernel("slot_masked_mean_bwd", slot_mean_bwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, ns, g, mask, inv_den, dx);
 }
 
 extern "C" int eap_masked_max_fwd_f32(int b, int c, int n, int na, const float *x, const float *mask, float *out, int32_t *arg,
                                       eap_stream_t stream) {
     if (b <= 0 || c <= 0) return 0;
-    if (n <= 0) return eap::bad_arg("masked_max: no points");
-    if (na <= 0 || na > 64 || (na & 3) != 0) return eap::bad_arg("masked_max: anchors must be a multiple of 4, at most 64");
+    if (n <= 0) return eap::bad_arg("masked_max_fwd: no points");
+    if (int e = head_args("masked_max_fwd", na, 0, "x, out and arg", x, out, arg)) return e;
     return eap::run_kernel("masked_max_fwd", masked_max_fwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, x, mask, out, arg);
 }
 
 extern "C" int eap_masked_max_bwd_f32(int b, int c, int n, int na, const float *g, const int32_t *arg, const float *mask, float *dx,
                                       eap_stream_t stream) {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
-    if (na <= 0 || na > 64 || (na & 3) != 0) return eap::bad_arg("masked_max: anchors must be a multiple of 4, at most 64");
+    if (int e = head_args("masked_max_bwd", na, 0, "g, arg and dx", g, arg, dx)) return e;
     return eap::run_kernel("masked_max_bwd", masked_max_bwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, g, arg, mask, dx);
 }
 

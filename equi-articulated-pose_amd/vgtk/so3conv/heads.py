@@ -37,7 +37,7 @@ class _AnchorAttnPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, logits, temperature):
-        x, logits = x.contiguous(), logits.contiguous()
+        x, logits = L._aligned16(x), L._aligned16(logits)           # 16-byte loads along the anchor axis
         b, c, n, na = x.shape
         out = torch.empty(b, c, n, dtype=torch.float32, device=x.device)
         conf = torch.empty(b, n, na, dtype=torch.float32, device=x.device)
@@ -62,11 +62,15 @@ def anchor_attention_pool(x, logits, temperature):
     """x [b,c,n,a], logits [b,n,a] (or [b,1,n,a]) -> pooled [b,c,n], confidence [b,n,a].
     The fused pass hands the confidence out as data; when the logits carry a gradient the returned confidence is the
     (small, [b,n,a]) torch softmax instead, so a caller that feeds it to a loss (the reference's `orbit_attn == 1`
-    concatenation, ...pn_38_multi_stage.py:L612-613) gets the gradient the reference's softmax gives."""
+    concatenation, ...pn_38_multi_stage.py:L612-613) gets the gradient the reference's softmax gives.
+    Anchor counts the 16-byte rows do not take (kanchor = 1, 3: _anchor_rows_vectorise) run the same two expressions as device torch ops."""
     if x.dtype != torch.float32 or not x.is_cuda:
         raise RuntimeError('anchor_attention_pool: float32 device tensors only')
     if logits.dim() == 4:
         logits = logits.squeeze(1)
+    if not _anchor_rows_vectorise(x.shape[3]):
+        conf = torch.softmax(logits * float(temperature), dim=-1)
+        return (x * conf.unsqueeze(1)).sum(-1), conf
     out, conf = _AnchorAttnPool.apply(x, logits, float(temperature))
     if logits.requires_grad and torch.is_grad_enabled():
         conf = torch.softmax(logits * float(temperature), dim=-1)
@@ -153,7 +157,7 @@ def _anchor_rows_vectorise(na):
 class _SlotMaskedMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask):
-        x, mask = x.contiguous(), mask.contiguous()
+        x, mask = L._aligned16(x), mask.contiguous()                 # 16-byte loads along the anchor axis
         b, c, n, na = x.shape
         ns = mask.shape[1]
         inv_den = (1.0 / mask.sum(-1).clamp(min=1e-8)).contiguous()
@@ -168,7 +172,7 @@ class _SlotMaskedMean(torch.autograd.Function):
         mask, inv_den = ctx.saved_tensors
         b, c, n, na, ns = ctx.dims
         dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
-        g = g.contiguous()            # bound to a local: the buffer must outlive the enqueue
+        g = L._aligned16(g)           # bound to a local: the buffer must outlive the enqueue
         _hip.call('eap_slot_masked_mean_bwd_f32', g, b, ns, c, n, na, g, mask, inv_den, dx)
         return dx, None
 
@@ -191,7 +195,7 @@ class _MaskedMax(torch.autograd.Function):
     def backward(ctx, g):
         arg, mask = ctx.saved_tensors
         b, c, n, na = ctx.dims
-        g = g.contiguous()
+        g = L._aligned16(g)
         dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
         _hip.call('eap_masked_max_bwd_f32', g, b, c, n, na, g, arg, mask, dx)
         return dx, None

@@ -868,20 +868,27 @@ int eap_so3_dense_point_order(int b, int p, int words, const int64_t *order, con
 /* ---- heads on the backbone's [b,c,n,na] feature map ------------------------ */
 /* Anchor attention pooling, InvPPOutBlockOurs.forward (SPConvNets/utils/base_so3conv.py:L905-912):
  * conf[b,n,a] = softmax_a(logits[b,n,a] * temperature), out[b,c,n] = sum_a x[b,c,n,a] conf[b,n,a].  na % 4 == 0, <= 64.
- * Backward: dx [b,c,n,na], dlogits [b,n,na] from g [b,c,n]. */
+ * Backward: dx [b,c,n,na], dlogits [b,n,na] from g [b,c,n].
+ * x, logits, conf (may be null), dx and dlogits are moved by 16-byte words and must be 16-byte aligned (refused otherwise); out and g
+ * are not.  A logit of -inf is a masked anchor (confidence 0); NaN in x or the logits spreads to what it touches, as in torch. */
 int eap_anchor_attn_pool_fwd_f32(int b, int c, int n, int na, float temperature, const float *x, const float *logits,
                                  float *out, float *conf, eap_stream_t stream);
 int eap_anchor_attn_pool_bwd_f32(int b, int c, int n, int na, float temperature, const float *x, const float *logits,
                                  const float *g, float *dx, float *dlogits, eap_stream_t stream);
 /* Masked point averages of every slot in one pass (SO3OutBlockRTWithMaskSep, SPConvNets/models/model_utils.py:L470-484,
- * L549-552): out[b,s,c,a] = inv_den[b,s] * sum_n mask[b,s,n] x[b,c,n,a];  ns <= 8.  Backward w.r.t. x. */
+ * L549-552): out[b,s,c,a] = inv_den[b,s] * sum_n mask[b,s,n] x[b,c,n,a];  ns <= 8.  Backward w.r.t. x.
+ * x and out (forward), g and dx (backward) are moved by 16-byte words and must be 16-byte aligned (refused otherwise); mask and inv_den
+ * are not.  Sums: a NaN in x reaches every slot of its (cloud, channel, anchor), whatever the mask (0 * NaN). */
 int eap_slot_masked_mean_fwd_f32(int b, int ns, int c, int n, int na, const float *x, const float *mask,
                                  const float *inv_den, float *out, eap_stream_t stream);
 int eap_slot_masked_mean_bwd_f32(int b, int ns, int c, int n, int na, const float *g, const float *mask,
                                  const float *inv_den, float *dx, eap_stream_t stream);
 /* The pose heads' 'max' pooling on a point subset, `(x * mask).max(2)` (SPConvNets/models/model_utils.py:L79-80, L470-484):
  * out[b,c,a] = max_p mask[b,p] * x[b,c,p,a], arg[b,c,a] = the lowest point index attaining it (int32); one pass over x.
- * Backward: dx[b,c,p,a] = (p == arg[b,c,a]) * mask[b,p] * g[b,c,a], written for every point. */
+ * Backward: dx[b,c,p,a] = (p == arg[b,c,a]) * mask[b,p] * g[b,c,a], written for every point.
+ * NaN: a product mask[b,p] * x[b,c,p,a] that is NaN (member or not: 0 * NaN, 0 * inf) makes out[b,c,a] NaN, as torch's max does, and
+ * arg[b,c,a] the lowest such point; otherwise the maximum at its lowest point, -0.0 and +0.0 being equal.
+ * x, out, arg (forward), g, arg, dx (backward) are moved by 16-byte words and must be 16-byte aligned (refused otherwise); mask is not. */
 int eap_masked_max_fwd_f32(int b, int c, int n, int na, const float *x, const float *mask, float *out, int32_t *arg,
                            eap_stream_t stream);
 int eap_masked_max_bwd_f32(int b, int c, int n, int na, const float *g, const int32_t *arg, const float *mask, float *dx,
