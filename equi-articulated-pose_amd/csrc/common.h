@@ -45,6 +45,11 @@ static inline hipStream_t S(eap_stream_t s) { return (hipStream_t)s; }
 
 static inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
+// true when every pointer is 16-byte aligned: the predicate of a kernel lists exactly the operands it touches with 16-byte
+// instructions (a contiguous tensor view may start at any 4-byte offset of its storage)
+template <typename... P>
+static inline bool aligned16(const P *...p) { return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & 15) == 0; }
+
 // The launch limits, without a HIP call: every grid and block dimension >= 1, at most 1024 threads per block, gx * block.x < 2^32
 // (hip_runtime_api.h at the launch functions: "HIP does not support kernel launch with total work items defined in dimension with
 // size gridDim x blockDim >= 2^32"), gy and gz <= 65535.  -> 0 and *grid, or bad_arg with the sizes in the message.

@@ -170,17 +170,28 @@ int inter_zpconv_bwd_flagged(int b, int np, int nq, int na, int ks, int ann, int
 }
 }  // namespace eap
 
+// Every entry names the regime it chose (eap_last_kernel): zpconv_fwd_rows / zpconv_fwd_scalar / zpconv_bwd_scatter / intra_zpconv here,
+// zpconv_fwd_matrix, zpconv_bwd_products and zp_hot_kernel in their own files.
 #define EAP_INTER(NAME, T, BWD)                                                                  \
     extern "C" int NAME(int b, int np, int nq, int na, int ks, int ann, int c, const int32_t *idx, \
                         const T *w, const T *src, T *dst, eap_stream_t stream) {                 \
-        return launch_inter<T, BWD>(b, np, nq, na, ks, ann, c, idx, w, src, dst, eap::S(stream)); \
+        const int e = launch_inter<T, BWD>(b, np, nq, na, ks, ann, c, idx, w, src, dst, eap::S(stream)); \
+        if (!e) eap::set_kernel(BWD ? "zpconv_bwd_scatter" : "zpconv_fwd_scalar");              \
+        return e;                                                                                \
     }
 extern "C" int eap_inter_zpconv_fwd_f32(int b, int np, int nq, int na, int ks, int ann, int c, const int32_t *idx,
                                         const float *w, const float *src, float *dst, eap_stream_t stream) {
-    // HBM-speed path when the sizes fit (csrc/zpconv_rows.hip; it checks the index pattern itself)
-    if (b > 0 && np > 0 && eap::inter_zpconv_rows_supported(np, nq, na, ks, ann, c))
-        return eap::inter_zpconv_rows_fwd(b, np, nq, na, ks, ann, c, idx, w, src, dst, nullptr, eap::S(stream));
-    return launch_inter<float, false>(b, np, nq, na, ks, ann, c, idx, w, src, dst, eap::S(stream));
+    // HBM-speed path when the sizes fit (csrc/zpconv_rows.hip; it checks the index pattern itself).  That kernel moves idx and w
+    // as int4 / float4, feature quads as 16-byte words and writes float4 rows: all four pointers 16-byte aligned, or the kernel
+    // below (4-byte accesses only) serves the call
+    if (b > 0 && np > 0 && eap::inter_zpconv_rows_supported(np, nq, na, ks, ann, c) && eap::aligned16(idx, w, src, dst)) {
+        const int e = eap::inter_zpconv_rows_fwd(b, np, nq, na, ks, ann, c, idx, w, src, dst, nullptr, eap::S(stream));
+        if (!e) eap::set_kernel("zpconv_fwd_rows");
+        return e;
+    }
+    const int e = launch_inter<float, false>(b, np, nq, na, ks, ann, c, idx, w, src, dst, eap::S(stream));
+    if (!e) eap::set_kernel("zpconv_fwd_scalar");
+    return e;
 }
 EAP_INTER(eap_inter_zpconv_fwd_f64, double, false)
 EAP_INTER(eap_inter_zpconv_bwd_f32, float, true)
@@ -189,7 +200,9 @@ EAP_INTER(eap_inter_zpconv_bwd_f64, double, true)
 #define EAP_INTRA(NAME, T, BWD)                                                                  \
     extern "C" int NAME(int b, int np, int na_in, int na_out, int ks, int ann, int c,            \
                         const int32_t *idx, const T *w, const T *src, T *dst, eap_stream_t stream) { \
-        return launch_intra<T, BWD>(b, np, na_in, na_out, ks, ann, c, idx, w, src, dst, eap::S(stream)); \
+        const int e = launch_intra<T, BWD>(b, np, na_in, na_out, ks, ann, c, idx, w, src, dst, eap::S(stream)); \
+        if (!e) eap::set_kernel("intra_zpconv");                                                 \
+        return e;                                                                                \
     }
 EAP_INTRA(eap_intra_zpconv_fwd_f32, float, false)
 EAP_INTRA(eap_intra_zpconv_fwd_f64, double, false)

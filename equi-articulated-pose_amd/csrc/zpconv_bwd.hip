@@ -221,8 +221,9 @@ extern "C" int eap_inter_zpconv_bwd_ws_f32(int b, int np, int nq, int na, int ks
     hipStream_t s = eap::S(stream);
     const bool matrix = workspace != nullptr && eap::inter_zpconv_bwd_matrix_supported(np, nq, na, ks, ann, c) && (ann & 3) == 0 &&
                         (long long)na * ks * ann < (1ll << 31) &&
-                        ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(gfeats) |
-                          reinterpret_cast<uintptr_t>(workspace)) & 15) == 0;
+                        // 16-byte accesses: idx (int4 rows), grad (the A operand's quads), gfeats (float4 along the anchors) and the
+                        // workspace; w is read 4 bytes per lane (ld_off<float>) and may sit at any 4-byte offset
+                        eap::aligned16(idx, grad, gfeats, reinterpret_cast<const char *>(workspace));
     if (!matrix) return eap_inter_zpconv_bwd_f32(b, np, nq, na, ks, ann, c, idx, w, grad, gfeats, stream);
     const BwdWorkspace L(b, np, nq, na, ann, c);
     char *wsb = reinterpret_cast<char *>(workspace);
@@ -264,5 +265,7 @@ extern "C" int eap_inter_zpconv_bwd_ws_f32(int b, int np, int nq, int na, int ks
     e = eap::run_kernel("inter_zpconv_backward (sums)", zpconv_bwd_sum_kernel, (na + 15) / 16, nq, b, dim3(256), 0, s, c, na, nq, np, ann, rows, off, cnt,
                         reinterpret_cast<const float4 *>(ent_e), flag, T, gfeats);
     if (e) return e;
-    return eap::inter_zpconv_bwd_flagged(b, np, nq, na, ks, ann, c, idx, w, grad, gfeats, flag, s);
+    e = eap::inter_zpconv_bwd_flagged(b, np, nq, na, ks, ann, c, idx, w, grad, gfeats, flag, s);
+    if (!e) eap::set_kernel("zpconv_bwd_products");
+    return e;
 }

@@ -363,8 +363,8 @@ extern "C" int eap_inter_zpconv_bwd_hot_f32(int b, int np, int nq, int na, int k
                                             const float *grad, float *gfeats, void *workspace, int32_t *status, eap_stream_t stream) {
     if (b <= 0) return 0;
     if (!workspace || !status || !hot_supported(np, nq, na, ks, ann, c) ||
-        ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(gfeats) |
-          reinterpret_cast<uintptr_t>(workspace)) & 15) != 0)
+        // 16-byte accesses: idx (int4 rows), grad (16-byte pieces), gfeats (16-byte stores) and the workspace; w streams 4 bytes per lane
+        !eap::aligned16(idx, grad, gfeats, reinterpret_cast<const char *>(workspace)))
         return eap::bad_arg("inter_zpconv_backward (on-chip rows): shape or alignment not taken (query eap_inter_zpconv_bwd_hot_workspace first)");
     hipStream_t s = eap::S(stream);
     const HotWorkspace L(b, np, nq, na, c);

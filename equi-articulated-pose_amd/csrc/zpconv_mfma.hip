@@ -393,7 +393,9 @@ extern "C" int eap_inter_zpconv_fwd_ws_f32(int b, int np, int nq, int na, int ks
     hipStream_t s = eap::S(stream);
     const bool matrix = workspace != nullptr && eap::inter_zpconv_mfma_supported(np, nq, na, ks, ann, c) &&
                         eap::inter_zpconv_rows_supported(np, nq, na, ks, ann, c) && (long long)na * ks * ann < (1ll << 31) &&
-                        ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0;
+                        // 16-byte accesses: idx (int4 rows), w (dwordx4 per lane), the feature rows (16-byte DMA pieces), the output
+                        // rows (float4) and the lists in the workspace
+                        eap::aligned16(idx, w, src, dst, reinterpret_cast<const char *>(workspace));
     if (!matrix) return eap_inter_zpconv_fwd_f32(b, np, nq, na, ks, ann, c, idx, w, src, dst, stream);
     // The matrix kernel walks one neighbour list per point: idx0 = the first (a,k) row of every point (a 1 MB gather).  Whether
     // every other row equals it is checked by streaming the whole index once -- on the side stream, BESIDE the matrix kernel
@@ -417,5 +419,7 @@ extern "C" int eap_inter_zpconv_fwd_ws_f32(int b, int np, int nq, int na, int ks
     if (e) return e;
     e = joiner.join();
     if (e) return e;
-    return eap::inter_zpconv_rows_fwd(b, np, nq, na, ks, ann, c, idx, w, src, dst, flag, s);
+    e = eap::inter_zpconv_rows_fwd(b, np, nq, na, ks, ann, c, idx, w, src, dst, flag, s);
+    if (!e) eap::set_kernel("zpconv_fwd_matrix");
+    return e;
 }

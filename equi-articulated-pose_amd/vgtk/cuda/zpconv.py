@@ -106,7 +106,8 @@ def _backward_on_chip(idx, w, grad, out):
     b, np_, na, ks, ann = idx.shape
     c, nq = grad.shape[1], out.shape[2]
     nbytes = int(_hip.abi.eap_inter_zpconv_bwd_hot_workspace(b, np_, nq, na, ks, ann, c)) if ON_CHIP_BACKWARD else 0
-    if nbytes <= 0 or any(t.data_ptr() % 16 for t in (idx, w, grad, out)):
+    # (the kernel moves idx, grad and out as 16-byte words; w streams 4 bytes per lane and may start at any element)
+    if nbytes <= 0 or any(t.data_ptr() % 16 for t in (idx, grad, out)):
         return list(range(b))
     key = (_verdict_key(idx), c, nq)
     hit = _HOT_VERDICTS.get(key)

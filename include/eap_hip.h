@@ -110,6 +110,12 @@ int eap_gather_points_bwd_f64(int b, int c, int n, int m, const double *grad_out
 
 /* ---- zpconv (vgtk/vgtk/cuda/zpconv_cuda.cpp) ---------------------------------------------- */
 
+/* Every zpconv entry names the regime that served the call (eap_last_kernel): zpconv_fwd_matrix, zpconv_fwd_rows,
+ * zpconv_fwd_scalar, zp_hot_kernel, zpconv_bwd_products, zpconv_bwd_scatter, intra_zpconv.  Operands may sit at any
+ * element-aligned address: a kernel that moves 16-byte words is selected only when every operand it touches that way is
+ * 16-byte aligned (rows kernel: idx, w, feats, out; matrix forward: those and the workspace; product pipeline and on-chip
+ * backward: idx, grad, gfeats and the workspace -- w is read 4 bytes per lane); the scalar kernels take the rest. */
+
 /* inter_zpconv_forward: zpconv_cuda.cpp:L41-56, kernel zpconv_cuda_kernel.cu:L33-73.
  * idx,w [b,np,na,ks,ann], feats [b,c,nq,na] -> out [b,c,ks,np,na]. */
 int eap_inter_zpconv_fwd_f32(int b, int np, int nq, int na, int ks, int ann, int c,
