@@ -10,62 +10,14 @@ entries load into it; its forward equals `F.leaky_relu(bn(x), negative_slope)`.
 The arithmetic runs in csrc/bn_act.hip (no CPU / eager fallback).
 """
 import torch
-import torch.distributed as dist
 from torch import nn
 
+from vgtk.spconv import SphericalPointCloud, SphericalPointCloudPose
 
-def _syncing(sync):
-    return bool(sync) and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-
-
-def batch_moments(s1, s2, pivot, count, sync=False):
-    """Per-channel mean and biased variance from pivoted sums  s1 = sum(x - pivot), s2 = sum((x - pivot)^2)
-    over `count` elements (float64 tensors [C]).  With `sync` (the reference wraps its models in
-    nn.SyncBatchNorm for multi-GPU training, trainer_unsup_arti_align.py:L430) the raw moments of
-    all ranks are summed by ONE all-reduce of 2C+1 doubles, so every rank normalises with the
-    statistics of the whole batch.  Returns (mean, var, total_count)."""
-    if not _syncing(sync):
-        m = s1 / count
-        return pivot + m, (s2 / count - m * m).clamp_(min=0.0), count
-    raw = torch.cat([s1 + count * pivot, s2 + 2.0 * pivot * s1 + count * pivot * pivot,
-                     torch.full((1,), float(count), dtype=torch.float64, device=s1.device)])
-    dist.all_reduce(raw)
-    c = s1.numel()
-    total = raw[2 * c]
-    mean = raw[:c] / total
-    var = (raw[c:2 * c] / total - mean * mean).clamp_(min=0.0)
-    return mean, var, total
-
-
-def affine_from_moments(mean, var, weight, bias, eps):
-    """BatchNorm as one per-channel map y = scale x + shift, formed in float64 from the (float64) mean and biased variance:
-    -> (scale float32, shift float32, invstd float64)."""
-    invstd = torch.rsqrt(var + eps)
-    scale64 = weight.double() * invstd
-    return scale64.float(), (bias.double() - mean * scale64).float(), invstd
-
-
-def update_running_stats(running_mean, running_var, mean, var, count, momentum):
-    """nn.BatchNorm2d's running statistics after a training batch of `count` elements per channel (unbiased variance)."""
-    with torch.no_grad():
-        running_mean.mul_(1.0 - momentum).add_(mean.to(running_mean.dtype), alpha=momentum)
-        running_var.mul_(1.0 - momentum).add_((var * (count / (count - 1))).to(running_var.dtype), alpha=momentum)
-
-
-def all_reduce_sums(*tensors, sync=False):
-    """Sum float64 per-channel reductions over the ranks (one all-reduce); identity without sync."""
-    if not _syncing(sync):
-        return tensors
-    flat = torch.cat([t.reshape(-1) for t in tensors])
-    dist.all_reduce(flat)
-    out, o = [], 0
-    for t in tensors:
-        out.append(flat[o:o + t.numel()].view_as(t))
-        o += t.numel()
-    return tuple(out)
-
-
-from .. import _hip  # noqa: E402  (after the pure-torch helpers: they are unit-tested without the HIP library)
+from .. import _hip
+from . import norm_fold
+from .functional import FoldedEpilogue, TrainEpilogue, so3_contract
+from .norm_fold import _syncing, affine_from_moments, all_reduce_sums, batch_moments, update_running_stats  # noqa: F401  (re-exported)
 
 
 class _BNAct(torch.autograd.Function):
@@ -82,18 +34,8 @@ class _BNAct(torch.autograd.Function):
                 raise RuntimeError('BatchNormLeakyReLU: residual must have the shape of the input')
         b, c = x.shape[0], x.shape[1]
         n = x.numel() // (b * c)
-        count = b * n
-        if training:
-            pivot = x.reshape(b, c, n)[0, :, 0].double()
-            s1, s2 = _hip.bn_stats(x, b, c, n)
-            mean, var, count = batch_moments(s1, s2, pivot, count, sync)    # biased variance, as BatchNorm normalises with
-            if running_mean is not None:
-                update_running_stats(running_mean, running_var, mean if pre_bias is None else mean + pre_bias.double(), var, count, momentum)
-        else:
-            mean, var = running_mean.double(), running_var.double()
-            if pre_bias is not None:
-                mean = mean - pre_bias.double()
-        scale, shift, invstd = affine_from_moments(mean, var, weight, bias, eps)
+        sums = (*_hip.bn_stats(x, b, c, n), x.reshape(b, c, n)[0, :, 0].double(), b * n) if training else None
+        scale, shift, mean, invstd, count = norm_fold.fold(sums, weight, bias, running_mean, running_var, training, momentum, eps, pre_bias, sync)
         y = _hip.bn_act_fwd(x, b, c, n, scale, shift, slope, residual)
         ctx.has_res = residual is not None
         ctx.has_pre_bias = pre_bias is not None
@@ -109,17 +51,9 @@ class _BNAct(torch.autograd.Function):
         sg, sgx = _hip.bn_act_bwd_reduce(gy, x, b, c, n, scale, shift, mean, invstd, ctx.slope)
         g_x = None
         if ctx.needs_input_grad[0]:
-            if ctx.training:
-                tg, tgx = all_reduce_sums(sg, sgx, sync=ctx.sync)          # whole-batch means (SyncBatchNorm backward)
-                k2 = (scale.double() * tg / ctx.count).float()
-                k3 = (scale.double() * tgx / ctx.count).float()
-            else:
-                k2 = torch.zeros_like(scale)
-                k3 = torch.zeros_like(scale)
+            k2, k3 = norm_fold.backward_coefficients(scale, sg, sgx, ctx.count, ctx.training, ctx.sync)
             g_x = _hip.bn_act_bwd_apply(gy, x, b, c, n, scale, shift, mean, invstd, k2, k3, ctx.slope)
-        g_pre = None
-        if ctx.has_pre_bias:
-            g_pre = torch.zeros_like(scale) if ctx.training else (sg * scale.double()).float()
+        g_pre = norm_fold.pre_bias_grad(sg, scale, ctx.training) if ctx.has_pre_bias else None
         return g_x, sgx.float(), sg.float(), None, None, None, None, None, None, None, (gy if ctx.has_res else None), g_pre
 
 
@@ -148,11 +82,10 @@ class BatchNormLeakyReLU(nn.BatchNorm2d):
         """The layer in inference mode as one per-channel affine map + activation ("inference-mode BN
         folds into W"): leaky_relu(scale * x + shift) (+ residual), scale = gamma / sqrt(running_var + eps),
         shift = beta - (running_mean - pre_bias) * scale, computed in float64 exactly as the eval-mode forward does."""
-        from .functional import FoldedEpilogue
         if self.training:
             raise RuntimeError('BatchNormLeakyReLU.folded: training-mode statistics depend on the data; call .eval() first')
-        mean = self.running_mean.double() if pre_bias is None else self.running_mean.double() - pre_bias.detach().double()
-        scale, shift, _ = affine_from_moments(mean, self.running_var.double(), self.weight.detach(), self.bias.detach(), self.eps)
+        mean, var = norm_fold.eval_moments(self.running_mean, self.running_var, pre_bias)
+        scale, shift, _ = affine_from_moments(mean, var, self.weight.detach(), self.bias.detach(), self.eps)
         return FoldedEpilogue(scale, shift, self.negative_slope, residual)
 
 
@@ -163,8 +96,6 @@ def conv_norm_act(conv, norm, x, **conv_kwargs):
     contraction's epilogue -- the feature map is written once, no pass of its own; in training the norm joins the conv's autograd
     node where the conv runs the dense product, or where it has at most 32 contraction indices and an input without gradient (the
     first layer: regime 'narrow input'); otherwise conv and norm run as usual."""
-    from vgtk.spconv import SphericalPointCloud, SphericalPointCloudPose
-    from .functional import TrainEpilogue
     fold = not norm.training and not torch.is_grad_enabled()
     ep = norm.folded() if fold else None
     if ep is None and norm.training and isinstance(norm, BatchNormLeakyReLU) and norm.negative_slope > 0:
@@ -189,7 +120,6 @@ def pointwise_norm_act(conv1x1, norm, x, residual=None):
     """relu(norm(conv1x1(x))) (+ residual): the separable block's skip branch and sum (base_so3poseconv.py:L319-328) for an
     nn.Conv2d(c, o, 1) and a BatchNormLeakyReLU.  The conv bias always rides in the norm's mean; in inference the whole
     norm + activation + sum ride in the contraction's epilogue."""
-    from .functional import so3_contract
     b, c, n, a = x.shape
     W = conv1x1.weight.view(conv1x1.out_channels, c)
     ep = norm.folded(pre_bias=conv1x1.bias, residual=residual) if (not norm.training and not torch.is_grad_enabled()) else None

@@ -27,6 +27,7 @@ import vgtk.spconv as zpconv
 import vgtk.cuda.grouping as cuda_nn
 
 from .. import _hip
+from . import norm_fold
 
 inter_so3conv_feat_grouping = zpconv.inter_zpconv_grouping_naive
 batched_index_select = zpconv.batched_index_select
@@ -666,13 +667,10 @@ class TrainEpilogue:
     def moments(self, s1, s2, pivot, count):
         """pivoted sums of the conv output per channel -> (scale, shift, slope) of the fused pass; updates the running statistics exactly as
         vgtk.so3conv.blocks._BNAct.forward does; leaves what the backward needs in self.saved"""
-        from .blocks import affine_from_moments, batch_moments, update_running_stats
         norm = self.norm
-        mean, var, total = batch_moments(s1, s2, pivot, count, norm.sync)
-        if norm.running_mean is not None:
-            update_running_stats(norm.running_mean, norm.running_var, mean, var, total, norm.momentum)
         gamma = norm.weight.detach().double()
-        scale, shift, invstd = affine_from_moments(mean, var, gamma, norm.bias.detach(), norm.eps)
+        scale, shift, mean, invstd, total = norm_fold.fold((s1, s2, pivot, count), gamma, norm.bias.detach(), norm.running_mean, norm.running_var,
+                                                           True, norm.momentum, norm.eps, sync=norm.sync)
         self.stats = (mean, invstd)          # float64 [o]: what a node that recomputes the conv output normalises with in its backward
         inv_gamma = torch.where(gamma == 0, torch.zeros_like(gamma), 1.0 / gamma).float()
         # (copies, not views of the parameters: the backward must see the values this forward normalised with)
@@ -682,9 +680,8 @@ class TrainEpilogue:
     def takes_partials(self, t):
         """the moments of `t`'s node come from moments_from_partials: the switch is on, the tensors are on the device, and no exchange stands
         between the sums and the coefficients (SyncBatchNorm over several ranks keeps the tensor expressions of `moments`)"""
-        from .blocks import _syncing
         norm = self.norm
-        return bool(_hip.NATIVE_NORM_GLUE and t.is_cuda and not _syncing(norm.sync) and norm.weight.dtype == torch.float32
+        return bool(_hip.NATIVE_NORM_GLUE and t.is_cuda and not norm_fold._syncing(norm.sync) and norm.weight.dtype == torch.float32
                     and norm.bias.dtype == torch.float32 and (norm.running_mean is None or norm.running_mean.dtype == torch.float32))
 
     def moments_from_partials(self, ps, pq, pivot, count):
@@ -1174,14 +1171,12 @@ def _forward_narrow(feats, W, args, train_ep):
 def _native_norm_bwd(gy, count, sync):
     """the backward's per-channel sums and coefficients come from csrc/norm_fold.hip (see _hip.NATIVE_NORM_GLUE): not when the sums of several
     ranks are exchanged first (the element count is then a tensor too)"""
-    from .blocks import _syncing
-    return bool(_hip.NATIVE_NORM_GLUE and gy.is_cuda and isinstance(count, int) and not _syncing(sync))
+    return bool(_hip.NATIVE_NORM_GLUE and gy.is_cuda and isinstance(count, int) and not norm_fold._syncing(sync))
 
 
 def _backward_narrow(gy, W, x, bn, need_w):
     """-> (gW, d gamma, d beta): one reduction pass over (dL/dy', X), then dW = sum gx X^T with the gradient behind the norm formed in
     registers (vgtk.so3conv.blocks._BNAct.backward's arithmetic)"""
-    from .blocks import all_reduce_sums
     scale, shift, mean, invstd, count, slope, sync = bn
     b, o = gy.shape[0], gy.shape[1]
     gy = gy.view(b, o, -1)
@@ -1192,9 +1187,7 @@ def _backward_narrow(gy, W, x, bn, need_w):
     sg, sgx = _hip.narrow_conv_bwd_reduce(gy, x, W, scale, shift, mean, invstd, slope)
     gW = None
     if need_w:
-        tg, tgx = all_reduce_sums(sg, sgx, sync=sync)          # whole-batch means (SyncBatchNorm backward)
-        k2 = (scale.double() * tg / count).float()
-        k3 = (scale.double() * tgx / count).float()
+        k2, k3 = norm_fold.backward_coefficients(scale, sg, sgx, count, True, sync)
         gW = _hip.narrow_conv_bwd_dw(gy, x, W, scale, shift, mean, invstd, k2, k3, slope)
     return gW, sgx.float(), sg.float()
 
@@ -1260,7 +1253,6 @@ def _backward_dense(gy, W, feats, head, geo, bn, yact, need_f, need_w):
         # the BatchNorm + leaky_relu backward of the node (csrc/bn_act.hip header): one reduction pass over (dL/dy', y'), then gx is
         # formed inside the split of the product's stored operand
         k1, beta, inv_gamma, count, slope, sync = bn
-        from .blocks import all_reduce_sums
         native = _native_norm_bwd(gy, count, sync)
         if native:
             # the sums, the coefficients and the bounds in one entry (csrc/norm_fold.hip); colmax [b,na] = bound.amax(1)
@@ -1269,9 +1261,7 @@ def _backward_dense(gy, W, feats, head, geo, bn, yact, need_f, need_w):
         else:
             sg, sgx, gmax, xmax = _hip.bn_act_bwd_reduce_fromy(gy, yact, beta, inv_gamma, slope)
             g_bn_w, g_bn_b = sgx.float(), sg.float()
-            tg, tgx = all_reduce_sums(sg, sgx, sync=sync)                        # whole-batch means (SyncBatchNorm backward)
-            k2 = (k1.double() * tg / count).float()
-            k3 = (k1.double() * tgx / count).float()
+            k2, k3 = norm_fold.backward_coefficients(k1, sg, sgx, count, True, sync)
             coef = torch.stack([k1, k2, k3, beta, inv_gamma]).contiguous()      # [5, o]
             bound = (k1.abs()[None, :, None] * gmax + k2.abs()[None, :, None] + k3.abs()[None, :, None] * xmax).contiguous()
         z = _hip.so3_dense_bwd_bn(gy, yact, geo, ldz, coef, bound, slope)

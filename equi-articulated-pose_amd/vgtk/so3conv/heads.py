@@ -28,6 +28,7 @@ import torch.nn.functional as F
 
 from .. import _hip
 from . import functional as L
+from . import norm_fold
 from .blocks import _BNAct
 
 
@@ -506,29 +507,15 @@ class _SubsetBNAct(torch.autograd.Function):
         y = y.contiguous()
         b, c, p, na = y.shape
         n = p * na
+        sums = None
         if training:
             cnt = (mask.sum(1, dtype=torch.float64) * na).view(b, 1)                # member points x anchors
             pivot = y.view(b, c, n)[0, :, 0].double().view(1, c)
-            s1, s2 = _hip.bn_stats_masked(y, b, c, n, na, mask)                     # of y - pivot, [b, c] float64
-            d = s1 / cnt
-            var = (s2 / cnt - d * d).clamp_min(0.0)                                 # biased, as BatchNorm normalises with
-            mean = d + pivot                                                        # of y (without the bias)
-            with torch.no_grad():
-                full = (mean + bias.double().view(1, c)) if bias is not None else mean
-                unb = var * (cnt / (cnt - 1.0).clamp_min(1.0))
-                # B sequential updates r <- (1 - mom) r + mom v_i in closed form
-                keep = (1.0 - momentum) ** torch.arange(b - 1, -1, -1, device=y.device, dtype=torch.float64).view(b, 1)
-                running_mean.mul_((1.0 - momentum) ** b).add_((momentum * (keep * full).sum(0)).to(running_mean.dtype))
-                running_var.mul_((1.0 - momentum) ** b).add_((momentum * (keep * unb).sum(0)).to(running_var.dtype))
-        else:
-            mean = (running_mean.double() - (bias.double() if bias is not None else 0.0)).view(1, c).expand(b, c)
-            var = running_var.double().view(1, c).expand(b, c)
-        invstd = torch.rsqrt(var + eps)
-        scale64 = weight.double().view(1, c) * invstd
-        scale = scale64.float().contiguous()
-        shift = (beta.double().view(1, c) - mean * scale64).float().contiguous()
+            sums = (*_hip.bn_stats_masked(y, b, c, n, na, mask), pivot, cnt)        # of y - pivot, [b, c] float64
+        fold = norm_fold.fold(sums, weight.expand(b, c), beta, running_mean, running_var, training, momentum, eps, bias)   # (gamma per cloud: scale, shift [b, c])
+        scale, shift, mean, invstd = (t.expand(b, c).float().contiguous() for t in fold[:4])
         out = _hip.bn_act_cloud_fwd(y, b, c, n, scale, shift, slope)
-        ctx.save_for_backward(y, scale, shift, mean.float().contiguous(), invstd.float().contiguous(), mask)
+        ctx.save_for_backward(y, scale, shift, mean, invstd, mask)
         ctx.training, ctx.slope, ctx.dims, ctx.has_bias = training, slope, (b, c, n, na), bias is not None
         return out
 
@@ -540,19 +527,10 @@ class _SubsetBNAct(torch.autograd.Function):
         sg, sgx = _hip.bn_act_cloud_bwd_reduce(g, y, b, c, n, scale, shift, mean, invstd, ctx.slope)     # [b, c] float64
         g_y = None
         if ctx.needs_input_grad[0]:
-            if ctx.training:
-                cnt = (mask.sum(1, dtype=torch.float64) * na).view(b, 1)
-                k2 = (scale.double() * sg / cnt).float().contiguous()
-                k3 = (scale.double() * sgx / cnt).float().contiguous()
-            else:
-                k2 = torch.zeros_like(scale)
-                k3 = torch.zeros_like(scale)
+            cnt = (mask.sum(1, dtype=torch.float64) * na).view(b, 1) if ctx.training else None
+            k2, k3 = norm_fold.backward_coefficients(scale, sg, sgx, cnt, ctx.training)
             g_y = _hip.bn_act_cloud_bwd_apply(g, y, b, c, n, na, scale, shift, mean, invstd, k2, k3, mask, ctx.slope)
-        # the bias is absorbed by the batch mean in training mode (its gradient is exactly zero); in eval mode it shifts the
-        # pre-activation like beta does
-        g_bias = None
-        if ctx.has_bias:
-            g_bias = torch.zeros(c, dtype=torch.float32, device=g.device) if ctx.training else (sg * scale.double()).sum(0).float()
+        g_bias = norm_fold.pre_bias_grad(sg, scale, ctx.training) if ctx.has_bias else None
         return g_y, g_bias, None, sgx.sum(0).float(), sg.sum(0).float(), None, None, None, None, None, None
 
 
@@ -567,11 +545,7 @@ def _subset_batchnorm_act_torch(y, bias, mask, bn, slope):
         ym = y * m
         mean = ym.sum((2, 3)) / cnt
         var = ((ym * ym).sum((2, 3)) / cnt - mean * mean).clamp_min(0.0)
-        with torch.no_grad():
-            unb = var * (cnt / (cnt - 1.0).clamp_min(1.0))
-            for i in range(b):                                              # the loop's B momentum updates, in cloud order
-                bn.running_mean.mul_(1.0 - bn.momentum).add_(mean[i], alpha=bn.momentum)
-                bn.running_var.mul_(1.0 - bn.momentum).add_(unb[i], alpha=bn.momentum)
+        norm_fold.update_running_stats(bn.running_mean, bn.running_var, mean, var, cnt, bn.momentum)      # B updates, in cloud order
         mean, var = mean[:, :, None, None], var[:, :, None, None]
     else:
         mean, var = bn.running_mean.view(1, c, 1, 1), bn.running_var.view(1, c, 1, 1)
@@ -744,6 +718,7 @@ class _NormActPointMean(torch.autograd.Function):
         y = L._aligned16(y)
         b, c, p, na = y.shape
         n = p * na
+        sums = None
         if training:
             pivot = y.view(b, c, n)[0, :, 0].double().view(1, c)
             if stat_mask is not None:
@@ -752,26 +727,11 @@ class _NormActPointMean(torch.autograd.Function):
             else:
                 cnt = torch.full((1, 1), float(b * n), dtype=torch.float64, device=y.device)
                 s1, s2 = (s.view(1, c) for s in _hip.bn_stats(y, b, c, n))
-            d = s1 / cnt
-            var = (s2 / cnt - d * d).clamp_min(0.0)                                     # biased, as BatchNorm normalises with
-            mean = d + pivot                                                            # of y (without the bias)
-            with torch.no_grad():
-                full = (mean + bias.double().view(1, c)) if bias is not None else mean
-                unb = var * (cnt / (cnt - 1.0).clamp_min(1.0))
-                r = mean.shape[0]                                                       # r sequential updates in closed form
-                keep = (1.0 - momentum) ** torch.arange(r - 1, -1, -1, device=y.device, dtype=torch.float64).view(r, 1)
-                running_mean.mul_((1.0 - momentum) ** r).add_((momentum * (keep * full).sum(0)).to(running_mean.dtype))
-                running_var.mul_((1.0 - momentum) ** r).add_((momentum * (keep * unb).sum(0)).to(running_var.dtype))
-        else:
-            mean = (running_mean.double() - (bias.double() if bias is not None else 0.0)).view(1, c)
-            var = running_var.double().view(1, c)
-        invstd = torch.rsqrt(var + eps)
-        scale64 = weight.double().view(1, c) * invstd
-        scale = scale64.expand(b, c).float().contiguous()
-        shift = (beta.double().view(1, c) - mean * scale64).expand(b, c).float().contiguous()
+            sums = (s1, s2, pivot, cnt)
+        fold = norm_fold.fold(sums, weight.expand(b, c), beta, running_mean, running_var, training, momentum, eps, bias)   # (gamma per cloud: scale, shift [b, c])
+        scale, shift, mean, invstd = (t.expand(b, c).float().contiguous() for t in fold[:4])
         out = _hip.bn_act_cloud_mean_fwd(y, scale, shift, w, inv_den, slope)
-        ctx.save_for_backward(y, scale, shift, mean.expand(b, c).float().contiguous(), invstd.expand(b, c).float().contiguous(), w, inv_den,
-                              stat_mask)
+        ctx.save_for_backward(y, scale, shift, mean, invstd, w, inv_den, stat_mask)
         ctx.training, ctx.slope, ctx.has_bias = training, slope, bias is not None
         return out
 
@@ -783,21 +743,12 @@ class _NormActPointMean(torch.autograd.Function):
         sg, sgx = _hip.bn_act_cloud_mean_bwd_reduce(g, y, scale, shift, mean, invstd, w, inv_den, ctx.slope)     # [b, c] float64
         g_y = None
         if ctx.needs_input_grad[0]:
+            cnt = float(b * p * na)                                                     # whole batch: the sums of all clouds
             if ctx.training and stat_mask is not None:
                 cnt = (stat_mask.sum(1, dtype=torch.float64) * na).view(b, 1)
-                k2 = (scale.double() * sg / cnt).float().contiguous()
-                k3 = (scale.double() * sgx / cnt).float().contiguous()
-            elif ctx.training:
-                cnt = float(b * p * na)
-                k2 = (scale.double() * sg.sum(0, keepdim=True) / cnt).float().contiguous()
-                k3 = (scale.double() * sgx.sum(0, keepdim=True) / cnt).float().contiguous()
-            else:
-                k2 = torch.zeros_like(scale)
-                k3 = torch.zeros_like(scale)
+            k2, k3 = norm_fold.backward_coefficients(scale, sg, sgx, cnt, ctx.training)
             g_y = _hip.bn_act_cloud_mean_bwd_apply(g, y, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, ctx.slope)
-        g_bias = None
-        if ctx.has_bias:           # absorbed by the batch mean in training mode; in eval mode it shifts the pre-activation like beta does
-            g_bias = torch.zeros(c, dtype=torch.float32, device=g.device) if ctx.training else (sg * scale.double()).sum(0).float()
+        g_bias = norm_fold.pre_bias_grad(sg, scale, ctx.training) if ctx.has_bias else None
         return g_y, g_bias, None, None, None, sgx.sum(0).float(), sg.sum(0).float(), None, None, None, None, None, None
 
 
@@ -839,11 +790,8 @@ def _batchnorm1d_per_cloud(bn, x):
         raise NotImplementedError('inv_head_over_subsets: BatchNorm with running statistics and a momentum only')
     b, c, a = x.shape
     mean, var = x.mean(2), x.var(2, unbiased=False)
+    norm_fold.update_running_stats(bn.running_mean, bn.running_var, mean, var, float(a), bn.momentum)
     with torch.no_grad():
-        unb = var * (a / max(a - 1, 1))
-        for i in range(b):
-            bn.running_mean.mul_(1.0 - bn.momentum).add_(mean[i], alpha=bn.momentum)
-            bn.running_var.mul_(1.0 - bn.momentum).add_(unb[i], alpha=bn.momentum)
         bn.num_batches_tracked.add_(b)
     return (x - mean.unsqueeze(2)) * torch.rsqrt(var.unsqueeze(2) + bn.eps) * bn.weight.view(1, c, 1) + bn.bias.view(1, c, 1)
 
