@@ -1369,6 +1369,64 @@ def bn_act_cloud_mean_bwd_apply(g, x, scale, shift, mean, invstd, k2, k3, w, inv
     return gx
 
 
+# SlotAttention's per-point passes (csrc/slot_attention.hip, the eap_slot_attn_* entries): x [b,d,n] channel-major, mean / rstd [b,n] the
+# LayerNorm statistics of a point, z = (x - mean) rstd never written; u, gmsum [b,s,d]; c0, gwsum [b,s]; attn, w, gdots [b,s,n]
+
+def _slot_f32(*tensors):
+    check_input(*tensors)
+    for t in tensors:
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f'slot attention kernels take float32 tensors, not {t.dtype}')
+
+
+def slot_attn_stats(x, ln_eps):
+    """-> mean, rstd [b, n] over the d channels of every point"""
+    _slot_f32(x)
+    b, d, n = x.shape
+    mean = torch.empty(b, n, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    call('eap_slot_attn_stats_f32', x, b, d, n, ln_eps, x, mean, rstd)
+    return mean, rstd
+
+
+def slot_attn_scores_fwd(x, mean, rstd, u, c0, eps):
+    """-> attn [b, s, n] = softmax_s(z . u_s + c0_s) + eps"""
+    _slot_f32(x, mean, rstd, u, c0)
+    (b, d, n), s = x.shape, u.shape[1]
+    attn = torch.empty(b, s, n, dtype=torch.float32, device=x.device)
+    call('eap_slot_attn_scores_fwd_f32', x, b, s, d, n, eps, x, mean, rstd, u, c0, attn)
+    return attn
+
+
+def slot_attn_pool(x, mean, rstd, w):
+    """-> msum [b, s, d] = sum_n w[s,n] z[n], wsum [b, s] = sum_n w[s,n]: float32 partials per 1024 points added in float64"""
+    _slot_f32(x, mean, rstd, w)
+    (b, d, n), s = x.shape, w.shape[1]
+    parts = int(abi.eap_slot_attn_pool_parts(n))
+    psum = torch.empty(b, parts, s, d + 1, dtype=torch.float32, device=x.device)
+    call('eap_slot_attn_pool_f32', x, b, s, d, n, x, mean, rstd, w, psum)
+    total = psum[:, 0] if parts == 1 else psum.sum(1, dtype=torch.float64).float()
+    return total[..., :d], total[..., d]
+
+
+def slot_attn_scores_bwd(x, mean, rstd, attn, gmsum, gwsum, gattn, eps):
+    """-> gdots [b, s, n], the gradient of the scores, from the gradients of msum, wsum and (None allowed) attn"""
+    _slot_f32(x, mean, rstd, attn, gmsum, gwsum, gattn)
+    (b, d, n), s = x.shape, attn.shape[1]
+    gdots = torch.empty_like(attn)
+    call('eap_slot_attn_scores_bwd_f32', x, b, s, d, n, eps, x, mean, rstd, attn, gmsum, gwsum, gattn, gdots)
+    return gdots
+
+
+def slot_attn_input_grad(x, mean, rstd, rows, vecs):
+    """-> gx [b, d, n] of gz[n] = sum_j rows[j,n] vecs[j] through the LayerNorm statistics; rows [b,j,n], vecs [b,j,d], j <= 16"""
+    _slot_f32(x, mean, rstd, rows, vecs)
+    (b, d, n), j = x.shape, rows.shape[1]
+    gx = torch.empty_like(x)
+    call('eap_slot_attn_input_grad_f32', x, b, j, d, n, x, mean, rstd, rows, vecs, gx)
+    return gx
+
+
 def so3_intra_conv(feats, W, intra_idx32):
     """Implicit-GEMM intra conv forward: feats [b,c,p,na], W [o, c*nt], intra_idx int32 [na,nt] -> [b,o,p,na]."""
     b, c, p, na = feats.shape

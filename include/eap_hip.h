@@ -918,6 +918,32 @@ int eap_bn_act_cloud_mean_bwd_apply_f32(int b, int c, int n, int na, float slope
                                         const float *shift, const float *mean, const float *invstd, const float *k2, const float *k3,
                                         const float *w, const float *inv_den, const float *stat_mask, float *gx, eap_stream_t stream);
 
+/* ---- SlotAttention's per-point passes (SPConvNets/utils/slot_attention_spec_v2.py:L132-193; csrc/slot_attention.hip) -------- */
+/* The per-slot LayerNorm (L149), to_k / to_v (L153-154) and the einsums (L167, L175) are linear in z[n,:] = (x[:,n] - mean[n]) * rstd[n], the same
+ * for every slot, so the [b,s,n,d] key and value tensors are never formed.  x float [b,d,n] channel-major; mean, rstd [b,n]; any n >= 1, d >= 1,
+ * 1 <= s <= 8 (hipErrorInvalidValue otherwise, the argument named in eap_last_error(), before any device call).  16-byte words are moved where
+ * n % 4 == 0 and the per-point tensors of the entry are 16-byte aligned, scalars otherwise.  No atomics; sums in a fixed order.
+ *
+ * (L149, nn.LayerNorm's statistics) mean[b,n], rstd[b,n] = 1 / sqrt(var + ln_eps) over the d channels of a point, two passes */
+int eap_slot_attn_stats_f32(int b, int d, int n, float ln_eps, const float *x, float *mean, float *rstd, eap_stream_t stream);
+/* (L167-169) attn[b,s,n] = softmax over s of (z[n] . u[b,s,:] + c0[b,s]), + eps;  u [b,s,d], c0 [b,s] */
+int eap_slot_attn_scores_fwd_f32(int b, int s, int d, int n, float eps, const float *x, const float *mean, const float *rstd, const float *u,
+                                 const float *c0, float *attn, eap_stream_t stream);
+/* (L172-175) psum[b,part,s,d+1], part < eap_slot_attn_pool_parts(n): partial sums over 1024 points each of w[b,s,n] z[n,:] (columns 0 .. d-1) and of
+ * w[b,s,n] (column d), for the caller to add over the parts in float64.  w: attn forward; the gradient of the scores backward, whose sums are
+ * dL/du and dL/dc0 */
+int eap_slot_attn_pool_parts(int n);
+int eap_slot_attn_pool_f32(int b, int s, int d, int n, const float *x, const float *mean, const float *rstd, const float *w, float *psum,
+                           eap_stream_t stream);
+/* (L167-175, backward) gattn = gattn_in[b,s,n] (may be null) + z[n] . gmsum[b,s,:] + gwsum[b,s];  p = attn - eps;
+ * gdots[b,s,n] = p * (gattn - sum over s of p * gattn) */
+int eap_slot_attn_scores_bwd_f32(int b, int s, int d, int n, float eps, const float *x, const float *mean, const float *rstd, const float *attn,
+                                 const float *gmsum, const float *gwsum, const float *gattn, float *gdots, eap_stream_t stream);
+/* (L149, backward) gz[n,:] = sum over the j <= 16 rows of rows[b,j,n] * vecs[b,j,:] (never written);
+ * gx[b,c,n] = rstd[n] * (gz[n,c] - mean_c gz[n,:] - z[n,c] * mean_c (gz[n,:] z[n,:])) */
+int eap_slot_attn_input_grad_f32(int b, int j, int d, int n, const float *x, const float *mean, const float *rstd, const float *rows,
+                                 const float *vecs, float *gx, eap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
