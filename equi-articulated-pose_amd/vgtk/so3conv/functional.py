@@ -2006,3 +2006,121 @@ def anchor_permutation_index(xyz, pose, n_neighbor, anchors, radius):
         return _hip.so3_anchor_map(ball_idx, pose.contiguous(), pose.contiguous(), anchors.contiguous())[0].long()
     gx, _ = _hip.so3_prep(xyz, xyz, ball_idx, pose.contiguous(), pose.contiguous(), anchors.contiguous(), ident)
     return _hip.so3_anchor_perm(gx, mult)
+
+
+# ------------------------------------------------------------------------------------------------
+# PointnetSO3Conv: the 1x1 embed fused with the max over the points (csrc/pointnet_max.hip)
+# ------------------------------------------------------------------------------------------------
+# modules.py:L393-413: embed([feats ; A_a^T (xyz - centre)]).max over the points.  The coordinate channels are a rank-3 term
+# (v[o,a,:] = A_a W_x[o,:], a [O,na,3] table), the max is taken inside the product: neither the (c+3)-channel concatenation nor the
+# [b,o,n,na] map exists in either direction; the one dense tensor is the gradient to the features, which autograd requires.
+
+POINTNET_MAX_CHANNELS = 2048           # output channels the backward kernel's tables hold (include/eap_hip.h)
+
+
+def pointnet_max_takes(feats, dim_out):
+    """Do the kernels take these features?  float32 device [b,c,n,na], na a multiple of 4 and at most 64 (the rule of the head kernels,
+    heads._anchor_rows_vectorise), at most POINTNET_MAX_CHANNELS output channels, no empty dimension."""
+    return (feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 4 and min(feats.shape) > 0 and feats.shape[3] % 4 == 0
+            and feats.shape[3] <= 64 and 0 < dim_out <= POINTNET_MAX_CHANNELS)
+
+
+def _pointnet_centre(xyz, member):
+    """[b,3]: the mean of every cloud's points, of its members under a mask (what the batch-1 call on the gathered subset subtracts)"""
+    if member is None:
+        return xyz.mean(2)
+    return (xyz * member.unsqueeze(1)).sum(2) / member.sum(1, keepdim=True).clamp(min=1.0)
+
+
+class _PointnetMax(torch.autograd.Function):
+    """feats [b,c,n,na], xyz [b,3,n], weight [o,c+3(,1,1)], bias [o] or None, anchors [na,3,3], member [b,n] float 0/1 or None -> [b,o,na].
+    Saved: feats, xyz, weight, arg (and the two small data tensors, anchors and member)."""
+
+    @staticmethod
+    def forward(ctx, feats, xyz, weight, bias, anchors, member):
+        feats, xyz, anchors = feats.contiguous(), xyz.contiguous(), anchors.contiguous()
+        b, c, n, na = feats.shape
+        o = weight.shape[0]
+        W = weight.contiguous().view(o, c + 3)
+        centre = _pointnet_centre(xyz, member).contiguous()
+        v = torch.einsum('aji,oi->oaj', anchors, W[:, c:]).contiguous()                      # [o, na, 3]: A_a W_x[o, :]
+        wt = W[:, :c].t().contiguous()                                                       # [c, o]: W_f, output channels contiguous
+        parts = int(_hip.abi.eap_pointnet_max_parts(n))
+        pval = torch.empty(b, parts, o, na, dtype=torch.float32, device=feats.device)
+        parg = torch.empty(b, parts, o, na, dtype=torch.int32, device=feats.device)
+        out = torch.empty(b, o, na, dtype=torch.float32, device=feats.device)
+        arg = torch.empty(b, o, na, dtype=torch.int32, device=feats.device)
+        bias_c = None if bias is None else bias.contiguous()
+        _hip.call('eap_pointnet_max_fwd_f32', feats, b, c, o, n, na, feats, xyz, centre, member, wt, v, bias_c, pval, parg, out, arg,
+                  tag={'flops': 2.0 * b * o * c * n * na, 'shape': ('pointnet_max', b, c, o, n, na)})
+        ctx.save_for_backward(feats, xyz, weight, anchors, member, arg)
+        ctx.has_bias = bias is not None
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, g, _):
+        feats, xyz, weight, anchors, member, arg = ctx.saved_tensors
+        b, c, n, na = feats.shape
+        o = weight.shape[0]
+        W = weight.contiguous().view(o, c + 3)
+        g = g.contiguous()
+        d_feats = d_xyz = d_weight = d_bias = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            d_feats = torch.zeros_like(feats) if ctx.needs_input_grad[0] else None
+            d_coords = torch.zeros(b, 3, n, na, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[1] else None
+            _hip.call('eap_pointnet_max_bwd_data_f32', g, b, c, o, n, na, g, arg, W, c + 3, d_feats, d_coords)
+            if d_coords is not None:
+                d_xc = torch.einsum('aji,bina->bjn', anchors, d_coords)                      # gradient of xyz - centre
+                total = d_xc.sum(2, keepdim=True)
+                d_xyz = d_xc - total / n if member is None else d_xc - member.unsqueeze(1) * (total / member.sum(1).clamp(min=1.0).view(b, 1, 1))
+        if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
+            centre = _pointnet_centre(xyz, member).contiguous()
+            dwp = torch.empty(b, o, c + 4, dtype=torch.float32, device=g.device)
+            _hip.call('eap_pointnet_max_bwd_weight_f32', g, b, c, o, n, na, g, arg, feats, xyz, centre, anchors, dwp)
+            total = dwp.sum(0, dtype=torch.float64)                                          # the clouds, in float64
+            if ctx.needs_input_grad[2]:
+                d_weight = total[:, :c + 3].float().reshape(weight.shape)
+            if ctx.has_bias and ctx.needs_input_grad[3]:
+                d_bias = total[:, c + 3].float()
+        return d_feats, d_xyz, d_weight, d_bias, None, None
+
+
+def _pointnet_max_torch(feats, xyz, weight, bias, anchors, member):
+    """the same expression as device tensor ops, for anchor counts the kernels do not take (kanchor = 1, 3)"""
+    b, c, n, na = feats.shape
+    W = weight.reshape(weight.shape[0], c + 3)
+    xc = xyz - _pointnet_centre(xyz, member).unsqueeze(2)
+    coords = xc.unsqueeze(-1) if na == 1 else torch.einsum('aji,bjn->bina', anchors, xc)
+    y = torch.einsum('oc,bcna->bona', W[:, :c], feats) + torch.einsum('oi,bina->bona', W[:, c:], coords)
+    if bias is not None:
+        y = y + bias.view(1, -1, 1, 1)
+    if member is not None:
+        y = y.masked_fill(member.view(b, 1, n, 1) == 0, float('-inf'))
+    return y.max(2)[0]
+
+
+def pointnet_max(feats, xyz, weight, bias, anchors, member=None, return_arg=False):
+    """PointnetSO3Conv's embed + max over the points (modules.py:L393-413) without the concatenation and without the [b,o,n,na] map:
+    feats [b,c,n,na], xyz [b,3,n], weight = embed.weight [o,c+3] (or [o,c+3,1,1]), bias [o] or None, anchors [na,3,3] -> [b,o,na].
+    member [b,n] (0/1, treated as data; None: every point): the max runs over the members, and the coordinates are centred on the members'
+    mean -- what a batch-1 call on the gathered subset computes; non-members receive no gradient.  Gradients reach feats, xyz, weight
+    and bias.  return_arg: also the int32 [b,o,na] point that attains every maximum (the lowest of equals)."""
+    tensors = [t for t in (feats, xyz, weight, bias, anchors, member) if t is not None]
+    if any(not t.is_cuda for t in tensors):
+        raise RuntimeError('pointnet_max: device tensors only (no CPU fallback)')
+    if any(t.dtype != torch.float32 for t in (feats, xyz, weight, anchors)) or (bias is not None and bias.dtype != torch.float32):
+        raise RuntimeError('pointnet_max: float32 only')
+    b, c, n, na = feats.shape
+    if tuple(xyz.shape) != (b, 3, n) or weight.numel() != weight.shape[0] * (c + 3) or tuple(anchors.shape) != (na, 3, 3) or \
+            (member is not None and tuple(member.shape) != (b, n)) or (bias is not None and bias.numel() != weight.shape[0]):
+        raise RuntimeError(f'pointnet_max: feats {tuple(feats.shape)}, xyz {tuple(xyz.shape)}, weight {tuple(weight.shape)}, anchors '
+                           f'{tuple(anchors.shape)} do not agree ([b,c,n,na], [b,3,n], [o,c+3], [na,3,3], member [b,n])')
+    if member is not None:
+        member = (member != 0).to(torch.float32).contiguous()
+    if not pointnet_max_takes(feats, weight.shape[0]):
+        if return_arg:
+            raise RuntimeError('pointnet_max: return_arg needs an anchor count the kernels take (a multiple of 4, at most 64)')
+        return _pointnet_max_torch(feats, xyz, weight, bias, anchors, member)
+    out, arg = _PointnetMax.apply(feats, xyz, weight, bias, anchors, member)
+    return (out, arg) if return_arg else out

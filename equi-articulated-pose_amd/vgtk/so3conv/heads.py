@@ -587,9 +587,9 @@ def pose_head_over_subsets(head, feats, xyz, member, anchors, use_offset=True):
     feats [B,C,P,A], xyz [B,3,P], member [B,P] in {0,1} (at least one point per cloud), anchors [A,3,3] or [B,A,3,3]
     -> the head's output dictionary with batch dimension B; identical (to rounding) to B separate batch-1 calls on the
     gathered subsets, BatchNorm statistics and running-statistic updates included (tests/test_gpu_lists_and_modules.py).
-    Supported configuration: pooling 'mean' or 'max', no global_scalar."""
-    if head.pooling_method not in ('mean', 'max') or head.global_scalar:
-        raise NotImplementedError('pose_head_over_subsets: mean / max pooling without the global scalar only')
+    Supported configuration: pooling 'mean', 'max' or 'pointnet', no global_scalar."""
+    if head.pooling_method not in ('mean', 'max', 'pointnet') or head.global_scalar:
+        raise NotImplementedError('pose_head_over_subsets: mean / max / pointnet pooling without the global scalar only')
     import math
     b, _, n, na = feats.shape
     mask = member.to(feats.dtype).contiguous()                              # [B, P]
@@ -599,6 +599,10 @@ def pose_head_over_subsets(head, feats, xyz, member, anchors, use_offset=True):
     def pool(f):
         if head.pooling_method == 'max':
             return masked_max(f, mask)                                     # [B, c, A]: one pass over f (csrc/heads.hip)
+        if head.pooling_method == 'pointnet':
+            # the head's PointnetSO3Conv on every cloud's members, centred on their mean: embed fused with the max (csrc/pointnet_max.hip)
+            pn = head.pointnet
+            return L.pointnet_max(f, xyz, pn.embed.weight, pn.embed.bias, pn.anchors, mask)
         return slot_masked_mean(f, mask.view(b, 1, n))[:, 0]
 
     x_out = pool(_masked_unary_stack(feats, mask, head.linear, head.norm))                       # [B, c, A]

@@ -188,8 +188,10 @@ class IntraSO3Conv2D(IntraSO3Conv):
 
 
 class PointnetSO3Conv(nn.Module):
-    """Equivariant pointnet aggregation (modules.py:L376-412): 1x1 conv over [feats ; A^T xyz]
-    then max over points.  Dense torch layers (out of the HIP scope, SURVEY.md section 2 #12)."""
+    """Equivariant pointnet aggregation (modules.py:L376-412): 1x1 conv over [feats ; A^T xyz] then max over points.  float32
+    device features on an anchor count the kernels take (a multiple of 4, at most 64): the embed fused with the max, neither the
+    concatenation nor the [b,o,n,na] map exists (L.pointnet_max, csrc/pointnet_max.hip); with return_raw the concatenation-free
+    form of PointnetSO3ConvOurs.  Host tensors, float64 and kanchor = 1, 3 keep the reference's dense expression."""
 
     def __init__(self, dim_in, dim_out, kanchor=60, return_raw=False):
         super().__init__()
@@ -201,6 +203,16 @@ class PointnetSO3Conv(nn.Module):
         """x.xyz [b,3,n], x.feats [b,c,n,na] -> [b,dim_out,na] (or the per-point map with return_raw): every anchor sees
         the centred coordinates in ITS frame, A_a^T (x - mean), stacked under the features; a shared 1x1 layer; max over
         the points."""
+        feats, xyz = x.feats, x.xyz
+        if L.pointnet_max_takes(feats, self.dim_out) and xyz.is_cuda and xyz.dtype == torch.float32 and feats.shape[3] == self.anchors.shape[0]:
+            if not self.return_raw:
+                return L.pointnet_max(feats, xyz, self.embed.weight, self.embed.bias, self.anchors)
+            b, c, n, na = feats.shape
+            W = self.embed.weight.view(self.dim_out, c + 3)
+            y = L.so3_contract(W[:, :c], feats.reshape(b, c, n * na)).view(b, self.dim_out, n, na)
+            coords = torch.einsum('aji,bjn->bina', self.anchors, xyz - xyz.mean(2, keepdim=True))
+            y = y + torch.einsum('oi,bina->bona', W[:, c:], coords)
+            return y if self.embed.bias is None else y + self.embed.bias.view(1, -1, 1, 1)
         centred = x.xyz - x.xyz.mean(dim=2, keepdim=True)                               # [b,3,n]
         if x.feats.shape[3] == 1:
             coords = centred.unsqueeze(-1)                                              # one frame: the identity

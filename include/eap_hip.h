@@ -944,6 +944,33 @@ int eap_slot_attn_scores_bwd_f32(int b, int s, int d, int n, float eps, const fl
 int eap_slot_attn_input_grad_f32(int b, int j, int d, int n, const float *x, const float *mean, const float *rstd, const float *rows,
                                  const float *vecs, float *gx, eap_stream_t stream);
 
+/* ---- PointnetSO3Conv / PointnetSO3PoseConv: the 1x1 embed fused with the max over the points (csrc/pointnet_max.hip) -------- */
+/* (vgtk/vgtk/so3conv/modules.py:L393-413) With W = embed.weight [o, c+3], W_f = W[:, :c], W_x = W[:, c:], the two small tables the caller makes
+ * of it, wt [c,o] = W_f transposed (a half-wave reads 32 consecutive output channels) and v[o,na,3] = A_a W_x[o,:], and xc = xyz - centre[b]:  y[b,o,n,a] = sum_c W_f[o,c] feats[b,c,n,a] + v[o,a,:] . xc[b,:,n] + bias[o]   (never written),
+ *   out[b,o,a] = max of y over the points with member[b,n] != 0,   arg[b,o,a] = the lowest such point attaining it (int32).
+ * feats float [b,c,n,na], xyz [b,3,n], centre [b,3], member [b,n] (0 / 1; null: every point), bias [o] (null: none); na % 4 == 0, <= 64; o <= 2048.
+ * A point that is no member never wins; a cloud without a member gives -inf and arg -1.  NaN as eap_masked_max_fwd_f32: a member's y that is NaN
+ * makes out NaN and arg the lowest such point; -0.0 and +0.0 are equal.  Products on the fp32 MFMA, fp32 accumulation in ascending c; the points
+ * are cut into eap_pointnet_max_parts(n) groups whose partial results pval, parg [b, parts, o, na] (workspace, written and read by the entry) are
+ * folded in ascending order: no atomics, bit-identical run to run.  Every operand is moved by 4-byte words: any element-aligned address is taken.
+ * Sizes first (c, o, n <= 0, na: hipErrorInvalidValue with the operand named), then null pointers, before anything is queued; b <= 0
+ * returns 0 without touching a pointer. */
+int eap_pointnet_max_parts(int n);
+int eap_pointnet_max_fwd_f32(int b, int c, int o, int n, int na, const float *feats, const float *xyz, const float *centre, const float *member,
+                             const float *wt, const float *v, const float *bias, float *pval, int32_t *parg, float *out, int32_t *arg,
+                             eap_stream_t stream);
+/* (modules.py:L393-413, backward to the features and coordinates) from g [b,o,na] and arg: per (cloud, anchor) the channels are grouped by their
+ * point and each group is summed in ascending o:  dfeats[b,cc,n,a] = sum_{o: arg[b,o,a] = n} W[o,cc] g[b,o,a] for cc < c, and the same sum over
+ * column c + i of W into dcoords[b,i,n,a] (the gradient of A_a^T xc, i < 3).  Only the named points are written: the caller zero-fills dfeats
+ * [b,c,n,na] and dcoords [b,3,n,na]; one of the two may be null (not wanted).  arg outside [0, n) is skipped.  ldw >= c + 3. */
+int eap_pointnet_max_bwd_data_f32(int b, int c, int o, int n, int na, const float *g, const int32_t *arg, const float *w, int ldw, float *dfeats,
+                                  float *dcoords, eap_stream_t stream);
+/* (modules.py:L393-413, backward to embed.weight and embed.bias) dwp[b,o,:] float [b, o, c+4] = sum over the anchors, ascending, of
+ * g[b,o,a] * [feats[b,:,p,a] ; A_a^T xc[b,:,p] ; 1] at p = arg[b,o,a]: columns 0 .. c+2 the weight gradient, column c+3 the bias gradient, one
+ * partial per cloud for the caller to add in float64.  anchors float [na,3,3]. */
+int eap_pointnet_max_bwd_weight_f32(int b, int c, int o, int n, int na, const float *g, const int32_t *arg, const float *feats, const float *xyz,
+                                    const float *centre, const float *anchors, float *dwp, eap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
