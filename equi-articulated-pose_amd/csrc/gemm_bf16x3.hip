@@ -141,8 +141,13 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
     const long long item_of_z = item;
     const long long kbeg = g.slabs > 1 ? (long long)(z - item * g.slabs) * g.kslab : 0;
     const float *A = g.A + item * g.sA + kbeg;
-    const float *B = g.B + item * g.sB + (BMODE == 0 ? kbeg : 0);
-    float *C = g.C + (long long)z * g.sC;
+    // (BMODE 1, split K: the slab's k-rows of the row-major operand; its partial goes to slab-major scratch [slab][item][M, ldc])
+    const float *B = g.B + item * g.sB + (BMODE == 0 ? kbeg : BMODE == 1 ? kbeg * g.ldb : 0);
+    long long zc = z;
+    if constexpr (BMODE == 1) {
+        if (g.slabs > 1) zc = (long long)(z - item * g.slabs) * (gridDim.y / g.slabs) + item;
+    }
+    float *C = g.C + zc * g.sC;
 
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -165,7 +170,8 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
     constexpr int PRE_PIECE = PL == 3 ? 32 : 16;     // PL = 2: piece (row, k / 4) = 16 bytes (h0 h1 l0 l1)
     const long long pre_pitch = (long long)(g.K / 4) * PRE_PIECE;
 #pragma unroll
-    for (int u = 0; u < NPA; ++u) preA[u] = reinterpret_cast<const unsigned char *>(g.Apre) + (long long)min(m0 + RG * u, g.M - RG) * pre_pitch;
+    for (int u = 0; u < NPA; ++u)
+        preA[u] = reinterpret_cast<const unsigned char *>(g.Apre) + (long long)min(m0 + RG * u, g.M - RG) * pre_pitch + (kbeg / 4) * PRE_PIECE;
     const unsigned offP = (unsigned)((long long)rq * pre_pitch + PRE_PIECE * c4);
     // PL = 2: the operand scales (powers of two: every product below is exact) and what undoes them in the epilogue
     // PL = 2: the scales of the operand rows this thread stages (powers of two: every product below is exact); a workgroup's
@@ -557,7 +563,7 @@ int launch_split(Args &g, long long batch, hipStream_t stream, const char *who) 
     // pays from a few thousand k-tiles per workgroup column upwards (+2.7 % on the deepest layer's contraction; on the 1-2 ms
     // pointwise contractions the extra launch and the allocation cost more than the saved vector work:
     // tools/split_modes_timing.py); the test switch value 2 forces it for every shape
-    bool pre = g.sA == 0 && g.slabs <= 1 && (g_presplit == 2 || (g_presplit == 1 && g.K >= 1024));
+    bool pre = g.sA == 0 && (g.slabs <= 1 || BMODE == 1) && (g_presplit == 2 || (g_presplit == 1 && g.K >= 1024));
     void *scratch = nullptr;
     if (pre) {
         const long long pieces = (long long)g.M * (g.K / 4);
@@ -907,4 +913,98 @@ extern "C" int eap_gemm_bf16x3_reduce_f32(int M, int N, int K, const float *A, i
     const long long mn4 = (long long)M * N / 4;
     return eap::run_kernel("gemm_bf16x3_reduce_f32 (sum of the partials)", split_reduce_kernel, eap::cdiv(mn4, 256), 1, 1, dim3(256), 0, eap::S(stream), mn4,
                            batch * slabs, reinterpret_cast<const f32x4 *>(workspace), C, N, (long long)ldc);
+}
+
+// ---- split-K form of the two-plane 'nn' product: C_z[M,N] = A[M,K] B_z[K,N] with ONE row tile (M = 128) and a long contraction -----
+// The feature gradient of the dense layers (dF = W2 Z: M = 128, K = o ks up to 12288, N = the padded row axis) has 34 x 8 = 272
+// workgroups of 768 k-tiles each on 256 CUs with one workgroup per CU: a second round of 16 workgroups while 240 CUs idle.  Here the
+// contraction is cut into `slabs` runs of whole k-tiles; (item, slab) pairs are the z of the kernel above, every pair writes its own
+// [M,N] partial to workspace [slab][item][M,N], and split_reduce_kernel sums the slabs in slab order (no atomics: bit-identical from
+// run to run).  The operand scales are powers of two, so taking them off each partial is exact; the summation order over k differs
+// from the one-slab kernel's, which is what slabs = 1 runs (no workspace).
+namespace {
+
+int device_cus() {
+    static std::atomic<int> seen[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
+    const bool slot = dev >= 0 && dev < 64;
+    int n = slot ? seen[dev].load(std::memory_order_relaxed) : 0;
+    if (n > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) { (void)hipGetLastError(); n = 256; }
+    if (slot) seen[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
+
+constexpr int SPLITK_MIN_TILES = 16;      // k-tiles per slab at least: the loads run four k-tiles ahead, a shorter slab is mostly prologue
+constexpr int SPLITK_MAX_SLABS = 64;
+
+inline bool splitk_slabs_ok(int K, int slabs) {
+    return slabs >= 1 && slabs <= SPLITK_MAX_SLABS && (K / BK) % slabs == 0 && (slabs == 1 || K / BK / slabs >= SPLITK_MIN_TILES);
+}
+
+}  // namespace
+
+// the slab count the launcher picks: the smallest admissible one (a divisor of the K / 16 k-tiles that leaves slabs of at least 16) with
+// tiles x batch x slabs >= 4 rounds of the device's CUs, else the largest admissible one; 1 outside the shape class (M = 128, K >= 1024).
+// cus <= 0: the current device's (256 without one)
+extern "C" int eap_gemm_f16x2_splitk_slabs(int M, int N, int K, int batch, int cus) {
+    if (M != 128 || N <= 0 || batch <= 0 || K < 64 * BK || (K % BK) != 0) return 1;
+    if (cus <= 0) cus = device_cus();
+    const long long tiles = (long long)((N + BN - 1) / BN) * batch;
+    const long long want = (4ll * cus + tiles - 1) / tiles;
+    int best = 1;
+    for (int s = 1; s <= SPLITK_MAX_SLABS; ++s) {
+        if (!splitk_slabs_ok(K, s)) continue;
+        best = s;
+        if (s >= want) break;
+    }
+    // One workgroup per CU: a launch takes rounds x (k-tiles per workgroup).  The partials cost a write and a read of slabs x the
+    // output, and every workgroup its prologue and epilogue again: a split that does not cut the rounds' k-tiles by a quarter does not
+    // pay (measured on the 64 -> 128 layer, 544 workgroups of 192 k-tiles: two slabs model 0.83 and ran 492.6 -> 477.9 us + 31 us of sum)
+    const long long kt = K / BK;
+    const long long one = ((tiles + cus - 1) / cus) * kt, cut = ((tiles * best + cus - 1) / cus) * (kt / best);
+    return 4 * cut <= 3 * one ? best : 1;
+}
+
+// floats of workspace eap_gemm_f16x2_splitk_f32 needs (none for one slab)
+extern "C" int64_t eap_gemm_f16x2_splitk_workspace(int M, int N, int batch, int slabs) {
+    if (M <= 0 || N <= 0 || batch <= 0 || slabs <= 1) return 0;
+    return (int64_t)M * N * batch * slabs;
+}
+
+// operands as eap_gemm_f16x2_f32 with trans_b = 0 and no epilogue; slabs = 0: eap_gemm_f16x2_splitk_slabs; more than one slab needs the
+// items of C back to back (strideC = M ldc), C and the workspace 16-byte aligned, ldc a multiple of 4
+extern "C" int eap_gemm_f16x2_splitk_f32(int M, int N, int K, const float *A, int64_t lda, const float *B, int64_t ldb, int64_t strideB,
+                                         float *C, int64_t ldc, int64_t strideC, int batch, const int32_t *abs_a, const int32_t *abs_b, int grp_b,
+                                         float mult_b, int slabs, float *workspace, int64_t workspace_floats, eap_stream_t stream) {
+    if (M <= 0 || N <= 0 || batch <= 0) return eap::bad_arg("gemm_f16x2_splitk_f32: M, N and batch must be positive");
+    if (!A || !B || !C) return eap::bad_arg("gemm_f16x2_splitk_f32: A, B and C are required");
+    if (!abs_a || !abs_b || !(mult_b > 0.f) || grp_b <= 0 || (N % grp_b) != 0)
+        return eap::bad_arg("gemm_f16x2_splitk_f32: the operand magnitudes are required (eap_absmax_rows_f32 / _colgroups_f32), column groups dividing N");
+    if (M != 128 || !eap_gemm_bf16x3_nn_f32_supported(M, N, K, A, lda, B, ldb, strideB))
+        return eap::bad_arg("gemm_f16x2_splitk_f32: one 128-row tile of operands eap_gemm_bf16x3_nn_f32_supported takes");
+    if (slabs == 0) slabs = eap_gemm_f16x2_splitk_slabs(M, N, K, batch, 0);
+    if (!splitk_slabs_ok(K, slabs))
+        return eap::bad_arg("gemm_f16x2_splitk_f32: the slab count must divide the K / 16 k-tiles into slabs of at least 16 (at most 64 slabs)");
+    if ((long long)batch * slabs > 65535) return eap::bad_arg("gemm_f16x2_splitk_f32: batch x slabs exceeds 65535");
+    Args g{};
+    g.M = M; g.N = N; g.K = K;
+    g.A = A; g.lda = lda;
+    g.B = B; g.ldb = ldb; g.sB = strideB;
+    g.C = C; g.ldc = ldc; g.sC = strideC;
+    g.absA = reinterpret_cast<const unsigned *>(abs_a); g.absB = reinterpret_cast<const unsigned *>(abs_b); g.multB = mult_b;
+    g.grpB = grp_b; g.sAbsB = N / grp_b;
+    if (slabs == 1) return launch_split<1, 2>(g, batch, eap::S(stream), "gemm_f16x2_splitk_f32");
+    if (strideC != (int64_t)M * ldc || (ldc & 3) || ldc < N || !eap::aligned16(C, workspace))
+        return eap::bad_arg("gemm_f16x2_splitk_f32: more than one slab needs strideC = M ldc, ldc a multiple of 4, C and the workspace 16-byte aligned");
+    if (!workspace || workspace_floats < eap_gemm_f16x2_splitk_workspace(M, N, batch, slabs))
+        return eap::bad_arg("gemm_f16x2_splitk_f32: the workspace is too small (ask eap_gemm_f16x2_splitk_workspace)");
+    g.C = workspace; g.ldc = N; g.sC = (long long)M * N;
+    g.slabs = slabs; g.kslab = K / slabs;
+    if (int e = launch_split<1, 2>(g, (long long)batch * slabs, eap::S(stream), "gemm_f16x2_splitk_f32")) return e;
+    // the batch's rows as one [batch M, N] matrix at pitch ldc
+    const long long mn4 = (long long)batch * M * N / 4;
+    return eap::run_kernel("gemm_f16x2_splitk_f32 (sum of the slabs)", split_reduce_kernel, eap::cdiv(mn4, 256), 1, 1, dim3(256), 0, eap::S(stream), mn4, slabs,
+                           reinterpret_cast<const f32x4 *>(workspace), C, N, (long long)ldc);
 }

@@ -2,9 +2,9 @@
 //
 // Replaces the reference's grouping extension (vgtk/vgtk/cuda/grouping_cuda.cpp L71-86,
 // kernels grouping_cuda_kernel.cu L68-113).  The reference runs ONE block per cloud with a
-// thread striding over the queries; here every query point gets its own lane, the support
-// cloud streams through LDS in tiles (each support point is a wave-wide broadcast read) and a
-// block retires as soon as all of its 64 queries have found `nsample` neighbours -- with the
+// thread striding over the queries; here every query point gets a group of 16 lanes, the support
+// cloud streams through LDS in tiles (a group tests 16 consecutive support points per step) and a
+// block retires as soon as all of its 32 queries have found `nsample` neighbours -- with the
 // large radii of the deeper layers (first-nsample-in-index-order semantics) that is after the
 // first tile.
 //
@@ -17,7 +17,9 @@
 
 namespace {
 
-constexpr int BQ_THREADS = 64;
+constexpr int BQ_LANES = 16;                           // lanes that share one query point's scan
+constexpr int BQ_THREADS = 512;
+constexpr int BQ_QUERIES = BQ_THREADS / BQ_LANES;       // query points per block
 constexpr int BQ_TILE = 1024;
 
 // One rounding per operation in the operands' own type, never contracted (this file is built with -ffp-contract=off):
@@ -47,6 +49,12 @@ __device__ __forceinline__ T d2_exact(T ax, T ay, T az, T bx, T by, T bz) {
     return sq3(sub_rn(ax, bx), sub_rn(ay, by), sub_rn(az, bz));
 }
 
+// A query point is scanned by a group of BQ_LANES consecutive lanes: lane l of the group tests candidate t0 + l, the
+// group's slice of the wave's ballot ranks the hits (lower candidate = lower slot: ascending index order, as the serial scan)
+// and the hits of one point land in its one row of idx.  The four groups of a wave walk the tile in step (one LDS address
+// per candidate, broadcast to the groups), a wave leaves a tile when its four lists are full, a block the cloud when all are.
+// With the first layer's small radius a list never fills and the scan is the whole cloud: 4096 / BQ_LANES steps per lane
+// instead of 4096, on BQ_LANES times as many waves.
 template <typename T>
 __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(
     int n, int m, T radius2, int nsample, const T *__restrict__ new_xyz,
@@ -57,13 +65,14 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(
     new_xyz += (size_t)bi * 3 * m;
     idx += (size_t)bi * m * nsample;
 
-    const int j = blockIdx.x * BQ_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63, gl = lane & (BQ_LANES - 1), gsh = lane & ~(BQ_LANES - 1);
+    const int j = blockIdx.x * BQ_QUERIES + threadIdx.x / BQ_LANES;
     const bool live = j < m;
     T qx = 0, qy = 0, qz = 0;
     if (live) { qx = new_xyz[j]; qy = new_xyz[m + j]; qz = new_xyz[2 * m + j]; }
     int32_t *out = idx + (size_t)(live ? j : 0) * nsample;
 
-    int cnt = live ? 0 : nsample;
+    int cnt = live ? 0 : nsample;          // the same in every lane of a group
     for (int k0 = 0; k0 < n; k0 += BQ_TILE) {
         const int len = min(BQ_TILE, n - k0);
         __syncthreads();
@@ -73,23 +82,32 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(
             tile[2][t] = xyz[2 * n + k0 + t];
         }
         __syncthreads();
-        for (int t = 0; t < len && cnt < nsample; ++t) {
+        for (int t0 = 0; t0 < len; t0 += BQ_LANES) {             // wave-uniform trip count
+            if (__ballot(cnt < nsample) == 0ull) break;
+            const int t = min(t0 + gl, len - 1);
             const T d2 = d2_exact(qx, qy, qz, tile[0][t], tile[1][t], tile[2][t]);
-            if (d2 < radius2) { out[cnt] = k0 + t; ++cnt; }
+            const bool hit = t0 + gl < len && cnt < nsample && d2 < radius2;
+            const unsigned mine = (unsigned)(__ballot(hit) >> gsh) & ((1u << BQ_LANES) - 1u);
+            const int slot = cnt + __popc(mine & ((1u << gl) - 1u));
+            if (hit && slot < nsample) out[slot] = k0 + t;
+            cnt = min(nsample, cnt + __popc(mine));
         }
         if (__syncthreads_and(cnt >= nsample)) break;
     }
-    if (!live) return;
     // grouping_cuda_kernel.cu:L100-105: cyclic repeat-padding only when cnt < nsample-1; with
     // exactly nsample-1 hits the last slot keeps the host wrapper's zero initialisation.
+    // The repeats read back what other lanes of the group stored: out[t] = out[t - cnt] = ... = out[t % cnt].
+    __threadfence_block();
+    __syncthreads();
+    if (!live) return;
     if (cnt < nsample - 1) {
         if (cnt == 0) {
-            for (int t = 0; t < nsample; ++t) out[t] = 0;
+            for (int t = gl; t < nsample; t += BQ_LANES) out[t] = 0;
         } else {
-            for (int t = cnt; t < nsample; ++t) out[t] = out[t - cnt];
+            for (int t = cnt + gl; t < nsample; t += BQ_LANES) out[t] = out[t % cnt];
         }
     } else if (cnt == nsample - 1) {
-        out[nsample - 1] = 0;
+        if (gl == 0) out[nsample - 1] = 0;
     }
 }
 
@@ -99,7 +117,7 @@ int launch_ball_query(int b, int n, int m, float radius, int nsample, const T *n
     if (b <= 0 || m <= 0 || nsample <= 0) return 0;
     if (n <= 0) return eap::bad_arg("ball_query: empty support cloud");
     const T r2 = (T)(radius * radius);  // float product first, grouping_cuda_kernel.cu:L82
-    return eap::run_kernel("ball_query", ball_query_kernel<T>, eap::cdiv(m, BQ_THREADS), b, 1, dim3(BQ_THREADS), 0, s, n, m, r2, nsample, new_xyz, xyz, idx);
+    return eap::run_kernel("ball_query", ball_query_kernel<T>, eap::cdiv(m, BQ_QUERIES), b, 1, dim3(BQ_THREADS), 0, s, n, m, r2, nsample, new_xyz, xyz, idx);
 }
 
 

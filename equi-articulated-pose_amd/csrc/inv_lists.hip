@@ -7,8 +7,8 @@
 // and one blocking host read per layer; here it is three small kernels and no host round trip:
 //
 //   eap_inv_lists_rows   counts[b,q] (LDS histogram per block, integer atomics), then per cloud a bitonic
-//                        sort of (count, q) -- referenced rows first, longest list first, ties by index --
-//                        and an exclusive scan:  rows / cnt / off [b,n], n_rows [b]
+//                        sort of (count, q) over the referenced rows only (compacted first) -- longest list
+//                        first, ties by index -- and an exclusive scan:  rows / cnt / off [b,n], n_rows [b]
 //   eap_inv_lists_fill   one workgroup per (cloud, referenced row): stream the cloud's idx (1 MB, L2
 //                        resident), keep the matches in order (ballot + mbcnt ranks), write ent_p / ent_gx
 //
@@ -20,6 +20,7 @@ namespace {
 
 constexpr int RT = 1024;      // threads of the per-cloud sort block
 constexpr int MAXN = 16384;   // support points per cloud the LDS sort holds (128 KB of 8-byte keys)
+constexpr int SORT_COMPACT = 2048;   // up to this many referenced rows the sort covers only them, not all n support rows
 
 __global__ __launch_bounds__(256) void inv_count_kernel(int per_cloud, int n, const int32_t *__restrict__ idx,
                                                         int32_t *__restrict__ counts) {
@@ -44,18 +45,29 @@ __global__ __launch_bounds__(256) void inv_count_kernel(int per_cloud, int n, co
 __global__ __launch_bounds__(RT) void inv_rows_kernel(int n, int n2, const int32_t *__restrict__ counts,
                                                       int32_t *__restrict__ rows, int32_t *__restrict__ off,
                                                       int32_t *__restrict__ cnt, int32_t *__restrict__ n_rows) {
-    extern __shared__ unsigned long long s_key[];           // [n2]; then reused for the scan
+    extern __shared__ unsigned long long s_key[];           // [n2]
     __shared__ int s_part[RT];
+    __shared__ int s_rows;
     const int bi = blockIdx.x, t = threadIdx.x;
-    for (int i = t; i < n2; i += RT) {
-        const unsigned c = i < n ? (unsigned)counts[(size_t)bi * n + i] : 0u;
-        s_key[i] = c ? (((unsigned long long)c << 32) | (0xFFFFFFFFu - (unsigned)i)) : 0ull;
+    if (t == 0) s_rows = 0;
+    __syncthreads();
+    // the keys of the referenced rows, compacted to the front in any order (the keys are distinct: the sort below puts them in
+    // one order whatever this one was)
+    for (int i = t; i < n; i += RT) {
+        const unsigned c = (unsigned)counts[(size_t)bi * n + i];
+        if (c) s_key[atomicAdd(&s_rows, 1)] = ((unsigned long long)c << 32) | (0xFFFFFFFFu - (unsigned)i);
     }
     __syncthreads();
+    const int nref = s_rows;
+    // sorted range: the power of two that holds the referenced rows (typically 128-512 of 4096); the whole range past SORT_COMPACT
+    int m2 = n2;
+    if (nref <= SORT_COMPACT) { m2 = 64; while (m2 < nref) m2 <<= 1; }
+    for (int i = nref + t; i < m2; i += RT) s_key[i] = 0ull;
+    __syncthreads();
     // bitonic sort, descending
-    for (int k = 2; k <= n2; k <<= 1) {
+    for (int k = 2; k <= m2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = t; i < n2; i += RT) {
+            for (int i = t; i < m2; i += RT) {
                 const int l = i ^ j;
                 if (l > i) {
                     const unsigned long long a = s_key[i], b = s_key[l];
@@ -67,11 +79,11 @@ __global__ __launch_bounds__(RT) void inv_rows_kernel(int n, int n2, const int32
         }
     }
     // exclusive scan of the counts in sorted order: thread t owns the consecutive slots [t*per, (t+1)*per)
-    const int per = n2 / RT > 0 ? n2 / RT : 1;
-    int local = 0, nz = 0;
+    const int per = m2 / RT > 0 ? m2 / RT : 1;
+    int local = 0;
     for (int u = 0; u < per; ++u) {
         const int i = t * per + u;
-        if (i < n2) { const unsigned c = (unsigned)(s_key[i] >> 32); local += (int)c; nz += c != 0; }
+        if (i < m2) local += (int)(unsigned)(s_key[i] >> 32);
     }
     s_part[t] = local;
     __syncthreads();
@@ -84,7 +96,7 @@ __global__ __launch_bounds__(RT) void inv_rows_kernel(int n, int n2, const int32
     int run = s_part[t] - local;
     for (int u = 0; u < per; ++u) {
         const int i = t * per + u;
-        if (i < n) {
+        if (i < n && i < m2) {
             const unsigned long long key = s_key[i];
             const unsigned c = (unsigned)(key >> 32);
             rows[(size_t)bi * n + i] = c ? (int)(0xFFFFFFFFu - (unsigned)key) : -1;
@@ -93,15 +105,14 @@ __global__ __launch_bounds__(RT) void inv_rows_kernel(int n, int n2, const int32
             run += (int)c;
         }
     }
-    // number of referenced rows
-    __syncthreads();
-    s_part[t] = nz;
-    __syncthreads();
-    for (int d = RT / 2; d > 0; d >>= 1) {
-        if (t < d) s_part[t] += s_part[t + d];
-        __syncthreads();
+    // past the sorted range no row is referenced: the offsets hold the total
+    const int total = s_part[RT - 1];
+    for (int i = m2 + t; i < n; i += RT) {
+        rows[(size_t)bi * n + i] = -1;
+        cnt[(size_t)bi * n + i] = 0;
+        off[(size_t)bi * n + i] = total;
     }
-    if (t == 0) n_rows[bi] = s_part[0];
+    if (t == 0) n_rows[bi] = nref;
 }
 
 // one workgroup (4 waves) per (referenced row slot, cloud); wave w scans the w-th quarter of the cloud's

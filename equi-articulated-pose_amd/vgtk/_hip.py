@@ -364,9 +364,35 @@ def _product(A, B, out, reduce=False):
     return ta, tb, M, N, K, lda, sa, ldb, sb, ldc, sc, batch
 
 
+# One 128-row tile and a long contraction (the dense layers' feature gradient dF = W2 Z: 34 column tiles x 8 clouds = 272 workgroups of
+# 768 k-tiles on 256 CUs) runs with its contraction cut into slabs (eap_gemm_f16x2_splitk_f32).  False: one slab, as `gemm` runs it.
+SPLIT_K_ONE_ROW_TILE = True
+
+
+def _matmul_split_k(M, N, K, A, lda, B, ldb, sb, out, ldc, sc, batch, b_bound):
+    """the two-plane 'nn' product of the shape class M = 128, K >= 16 * 64 over several k-slabs -> False when the product is not of that
+    class, the launcher would take one slab or the operands do not qualify (nothing launched)"""
+    if not (SPLIT_K_ONE_ROW_TILE and SPLIT_BF16_CONTRACTION and M == 128 and K >= 16 * 64 and out.is_cuda and sc == M * ldc and ldc % 4 == 0
+            and out.data_ptr() % 16 == 0 and abi.eap_gemm_bf16x3_nn_f32_supported(M, N, K, A, lda, B, ldb, sb)):
+        return False
+    slabs = abi.eap_gemm_f16x2_splitk_slabs(M, N, K, batch, 0)
+    if slabs <= 1:
+        return False
+    two = _planes2(0, M, N, K, A, lda, batch, B, ldb, sb, b_bound)
+    if two is None:
+        return False
+    floats = int(abi.eap_gemm_f16x2_splitk_workspace(M, N, batch, slabs))
+    work = torch.empty(floats, dtype=torch.float32, device=out.device)
+    tag = {'flops': 2.0 * M * N * K * batch, 'shape': ('gemm', 0, 0, M, N, K, batch)}
+    call('eap_gemm_f16x2_splitk_f32', out, M, N, K, A, lda, B, ldb, sb, out, ldc, sc, batch, two[0], two[1], two[2], two[3], slabs, work, floats, tag=tag)
+    return True
+
+
 def matmul(A, B, out, b_bound=None):
     """out_z = A_z B_z: `gemm` with its numbers taken from the views (b_bound: see gemm)."""
     ta, tb, M, N, K, lda, sa, ldb, sb, ldc, sc, batch = _product(A, B, out)
+    if not ta and not tb and (sa == 0 or batch == 1) and _matmul_split_k(M, N, K, A, lda, B, ldb, sb, out, ldc, sc, batch, b_bound):
+        return
     gemm(ta, tb, M, N, K, A, lda, sa, B, ldb, sb, out, ldc, sc, batch, b_bound=b_bound)
 
 
@@ -795,6 +821,39 @@ def so3_dense_narrow(memb, rp):
     if _dense_wide(memb) and rp <= DENSE_NARROW_ROWS:
         return memb[:, :, :16].contiguous()
     return memb
+
+
+# The words the list head's host decisions read (rows, non-identity flag, dense_bad, groups16, norm_ill) from ONE entry
+# (csrc/list_probe.hip) instead of about thirty tensor-op launches per layer while the forward waits.  False: the tensor expressions
+# (tests, A/B runs); they also remain for pose tensors and norm parameters the entry does not read (so3_dense_probe_takes).
+NATIVE_LIST_PROBE = True
+
+
+def _probe_f32(t, last):
+    return (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape[-2:]) == last and t.data_ptr() % 16 == 0
+            and t.numel() > 0)
+
+
+def so3_dense_probe_takes(poses, rot_cloud, norm_w, norm_b):
+    """the operands eap_so3_dense_probe reads as they are: float32, contiguous, 16-byte aligned pose tensors [.., 4, 4] (at most two),
+    a [b,3,3] per-cloud rotation, float32 norm parameters"""
+    return bool(NATIVE_LIST_PROBE and len(poses) <= 2 and all(_probe_f32(t, (4, 4)) for t in poses)
+                and (rot_cloud is None or (_probe_f32(rot_cloud, (3, 3)) and rot_cloud.dim() == 3))
+                and all(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1) for t in (norm_w, norm_b)))
+
+
+def so3_dense_probe(p, n_rows, nonident, dflags, memb, poses, rot_cloud, norm_w, norm_b, ratio):
+    """-> int32 [5] on the device: max n_rows, max nonident (1 without), dense_bad, groups16, norm_ill (include/eap_hip.h); no host sync.
+    memb / dflags: so3_dense_member's, or None for a head without the dense probe."""
+    b = n_rows.shape[0]
+    dev = n_rows.device
+    check_input(n_rows, nonident, dflags, memb)
+    work = torch.empty(int(abi.eap_so3_dense_probe_workspace(b)), dtype=torch.int32, device=dev)
+    out = torch.empty(5, dtype=torch.int32, device=dev)
+    rot = [(t, t.numel() // 16) for t in poses] + [(None, 0)] * (2 - len(poses))
+    call('eap_so3_dense_probe', n_rows, b, int(p), 0 if memb is None else memb.shape[2], n_rows, nonident, dflags, memb, rot[0][0], rot[0][1],
+         rot[1][0], rot[1][1], rot_cloud, norm_w, norm_b, 0 if norm_w is None else norm_w.shape[0], float(ratio), work, out)
+    return out
 
 
 # Occupancy-sorted query points (round 6): a cloud's query points are handed to the dense product sorted by WHICH 16-row groups of the

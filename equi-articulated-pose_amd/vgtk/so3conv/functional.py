@@ -484,6 +484,22 @@ class _ListHead:
             if t is not None:
                 t.record_stream(side)                     # (read on the side stream: the allocator must not recycle them under it)
         ill = None
+        poses = tuple(r for r in (dense_probe or ()) if r is not None and not isinstance(r, tuple))
+        clouds = tuple(r[1] for r in (dense_probe or ()) if isinstance(r, tuple))
+        norm_wb = (None, None) if norm is None else (norm.weight.detach(), norm.bias.detach())
+        if len(clouds) <= 1 and _hip.so3_dense_probe_takes(poses, clouds[0] if clouds else None, *norm_wb):
+            # the host's words from one entry (csrc/list_probe.hip); the tensor expressions below say what they are
+            with torch.cuda.stream(side):
+                self.rows, self.off, self.cnt, self.n_rows = _hip.inv_lists_rows(idx, n_sup)
+                dflags = None
+                if dense_probe is not None:
+                    self.memb, dflags = _hip.so3_dense_member(idx, self.rows, self.n_rows, n_sup)
+                stats = _hip.so3_dense_probe(idx.shape[1], self.n_rows, nonident, dflags, self.memb, poses, clouds[0] if clouds else None,
+                                             *norm_wb, NORM_IN_NODE_MAX_RATIO)
+                if norm is None:
+                    stats = stats[:4]
+                self._finish(stats, idx, gx, n_sup, prefill, side, main)
+            return
         if norm is not None:
             # a handful of one-block kernels over the [o] parameters, on a stream of their own: they run beside the list kernels below, which
             # take far longer, so the copy the forward waits for arrives no later than without them
@@ -521,12 +537,15 @@ class _ListHead:
                 # the read above)
                 side.wait_stream(second)
                 stats.append(ill)
-            stats = torch.stack(stats)
-            self.host = torch.empty(stats.shape[0], dtype=torch.int32, pin_memory=True)
-            self.host.copy_(stats, non_blocking=True)
-            self.entries = _hip.inv_lists_fill(idx, gx, self.rows, self.off, n_sup) if (prefill and gx is not None) else None
-            self.event = torch.cuda.Event()
-            self.event.record(side)
+            self._finish(torch.stack(stats), idx, gx, n_sup, prefill, side, main)
+
+    def _finish(self, stats, idx, gx, n_sup, prefill, side, main):
+        """(under the side stream) the copy of the words to the host, the second half of the lists where asked for, the event"""
+        self.host = torch.empty(stats.shape[0], dtype=torch.int32, pin_memory=True)
+        self.host.copy_(stats, non_blocking=True)
+        self.entries = _hip.inv_lists_fill(idx, gx, self.rows, self.off, n_sup) if (prefill and gx is not None) else None
+        self.event = torch.cuda.Event()
+        self.event.record(side)
         for t in (self.rows, self.off, self.cnt, self.n_rows, self.memb) + (self.entries or ()):      # allocated under the side stream, used (and freed) under the main one
             if t is not None:
                 t.record_stream(main)

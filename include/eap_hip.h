@@ -516,6 +516,19 @@ int eap_so3_dense_point_keys_wide(int b, int p, const uint32_t *memb, int64_t *k
 int eap_so3_dense_masks_wide(int b, int p, int ks, int rp, int dir, const uint32_t *memb, uint64_t *mask, eap_stream_t stream);
 int eap_so3_dense_steps_wide(int b, int p, int ks, int rp, int dir, int skip, const int32_t *n_rows, const uint64_t *mask, int32_t *steps,
                              eap_stream_t stream);
+/* The five words the host reads before it picks a layer's kernels (csrc/list_probe.hip), after eap_inv_lists_rows and
+ * eap_so3_dense_member[_wide]:
+ *   out[0] = max_b n_rows[b];  out[1] = max_b nonident[b] (1 when nonident is null);
+ *   out[2] = max_b dflags[b] (1 when memb and dflags are null) + 1 per given pose tensor rot_a / rot_b [blocks,4,4] with a 3x3 block that
+ *            is not exactly the identity + 1 when rot_cloud [b,3,3] has max |R R^T - I| > 1e-6 in float64;
+ *   out[3] = (int32)(float(max_b #{non-zero 16-bit halves of memb[b]}) * float(16 / p)), memb uint32 [b,p,words], words 16 or 32 (0 without);
+ *   out[4] = 1 when a channel has norm_w != 0 and |norm_b| > ratio |norm_w| (0 when norm_w and norm_b are null).
+ * work: int32 [eap_so3_dense_probe_workspace(b)] scratch.  memb and the pose tensors 16-byte aligned. */
+int64_t eap_so3_dense_probe_workspace(int b);
+int eap_so3_dense_probe(int b, int p, int words, const int32_t *n_rows, const int32_t *nonident, const int32_t *dflags,
+                        const uint32_t *memb, const float *rot_a, int64_t blocks_a, const float *rot_b, int64_t blocks_b,
+                        const float *rot_cloud, const float *norm_w, const float *norm_b, int channels, float ratio,
+                        int32_t *work, int32_t *out, eap_stream_t stream);
 
 /* ---- SO(3) intra convolution -------------------------------------------------------------- */
 
@@ -627,6 +640,20 @@ int eap_gemm_f16x2_f32(int trans_b, int M, int N, int K, const float *A, int64_t
                        float *C, int64_t ldc, int64_t strideC, int batch, const int32_t *abs_a, const int32_t *abs_b, int grp_b, float mult_b,
                        const float *scale, const float *shift, float slope, const float *residual, int64_t strideRes,
                        eap_stream_t stream);
+/* eap_gemm_f16x2_f32 with trans_b = 0 and no epilogue for ONE 128-row tile and a long contraction (M = 128, K >= 1024: the dense layers'
+ * feature gradient), the contraction cut into `slabs` runs of whole k-tiles so that (item, slab) pairs fill the device: every pair
+ * writes an [M,N] partial to workspace [slab][item][M,N], the partials are summed in slab order (no atomics, bit-identical from run to
+ * run; a summation order other than the one-slab kernel's).  slabs = 1 is eap_gemm_f16x2_f32 bit for bit and needs no workspace.
+ *   eap_gemm_f16x2_splitk_slabs      the count the entry picks for slabs = 0: the smallest divisor of K / 16 leaving slabs of >= 16 k-tiles
+ *                                    with column tiles x batch x slabs >= 4 x cus (cus <= 0: the current device's CUs), at most 64 -- and 1
+ *                                    unless that cuts rounds x k-tiles per workgroup (one workgroup per CU) by a quarter at least
+ *   eap_gemm_f16x2_splitk_workspace  floats of workspace for a slab count (0 for one slab)
+ * More than one slab: strideC = M ldc, ldc % 4 == 0, C and workspace 16-byte aligned. */
+int eap_gemm_f16x2_splitk_slabs(int M, int N, int K, int batch, int cus);
+int64_t eap_gemm_f16x2_splitk_workspace(int M, int N, int batch, int slabs);
+int eap_gemm_f16x2_splitk_f32(int M, int N, int K, const float *A, int64_t lda, const float *B, int64_t ldb, int64_t strideB,
+                              float *C, int64_t ldc, int64_t strideC, int batch, const int32_t *abs_a, const int32_t *abs_b, int grp_b,
+                              float mult_b, int slabs, float *workspace, int64_t workspace_floats, eap_stream_t stream);
 int eap_so3_intra_conv_f16x2_f32(int b, int o, int c, int p, int na, int nt, const float *W, const float *feats,
                                  const int32_t *intra_idx, float *out, const int32_t *abs_w, const int32_t *abs_f, eap_stream_t stream);
 
