@@ -4,6 +4,8 @@ and 3), mirroring the reference classes so a maintainer can swap the import:
   InvPPOutBlockOurs        SPConvNets/utils/base_so3conv.py:L842-917 (same constructor parameters, sub-module
                            names `linear.i`, `norm.i`, `attention_layer`, same outputs); the attention pooling
                            over the 60 anchors runs in one HIP pass (csrc/heads.hip)
+  InvPPOutBlock2DOurs      SPConvNets/utils/base_so3conv.py:L921-1008, the same head over the 60 x 4 anchors of a `use_2d` map: the
+                           attention pooling over all 240 is one HIP pass (csrc/heads_wide.hip)
   orbit_selection          ...pn_38_multi_stage.py:L1381-1399: distance -> arg-min orbit per slot
   slot_masked_mean         the masked per-slot point averages of SO3OutBlockRTWithMaskSep
                            (SPConvNets/models/model_utils.py:L470-484, L549-552) for ALL slots in one pass
@@ -59,20 +61,55 @@ class _AnchorAttnPool(torch.autograd.Function):
         return dx, dl, None
 
 
+class _AnchorAttnPoolWide(torch.autograd.Function):
+    """_AnchorAttnPool for anchor rows of 68 to 256 floats (the 240 anchors of a `use_2d` map): one wavefront per point
+    (csrc/heads_wide.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, logits, temperature):
+        x, logits = L._aligned16(x), L._aligned16(logits)           # 16-byte loads along the anchor axis
+        b, c, n, na = x.shape
+        out = torch.empty(b, c, n, dtype=torch.float32, device=x.device)
+        conf = torch.empty(b, n, na, dtype=torch.float32, device=x.device)
+        _hip.call('eap_anchor_attn_pool_wide_fwd_f32', x, b, c, n, na, temperature, x, logits, out, conf)
+        ctx.save_for_backward(x, logits)
+        ctx.temperature = temperature
+        ctx.mark_non_differentiable(conf)
+        return out, conf
+
+    @staticmethod
+    def backward(ctx, g, _gconf):
+        x, logits = ctx.saved_tensors
+        b, c, n, na = x.shape
+        dx = torch.empty_like(x)
+        dl = torch.empty_like(logits)
+        g = g.contiguous()            # bound to a local: the buffer must outlive the enqueue
+        _hip.call('eap_anchor_attn_pool_wide_bwd_f32', x, b, c, n, na, ctx.temperature, x, logits, g, dx, dl)
+        return dx, dl, None
+
+
+def _anchor_attention_pool_torch(x, logits, temperature):
+    conf = torch.softmax(logits * float(temperature), dim=-1)
+    return (x * conf.unsqueeze(1)).sum(-1), conf
+
+
 def anchor_attention_pool(x, logits, temperature):
     """x [b,c,n,a], logits [b,n,a] (or [b,1,n,a]) -> pooled [b,c,n], confidence [b,n,a].
     The fused pass hands the confidence out as data; when the logits carry a gradient the returned confidence is the
     (small, [b,n,a]) torch softmax instead, so a caller that feeds it to a loss (the reference's `orbit_attn == 1`
     concatenation, ...pn_38_multi_stage.py:L612-613) gets the gradient the reference's softmax gives.
-    Anchor counts the 16-byte rows do not take (kanchor = 1, 3: _anchor_rows_vectorise) run the same two expressions as device torch ops."""
+    Up to 64 anchors: csrc/heads.hip (_anchor_rows_vectorise); 68 to 256, the 240 of a `use_2d` map: csrc/heads_wide.hip
+    (_anchor_rows_wide).  Anchor counts neither takes (kanchor = 1, 3, more than 256) run the same two expressions as device torch ops."""
     if x.dtype != torch.float32 or not x.is_cuda:
         raise RuntimeError('anchor_attention_pool: float32 device tensors only')
     if logits.dim() == 4:
         logits = logits.squeeze(1)
-    if not _anchor_rows_vectorise(x.shape[3]):
-        conf = torch.softmax(logits * float(temperature), dim=-1)
-        return (x * conf.unsqueeze(1)).sum(-1), conf
-    out, conf = _AnchorAttnPool.apply(x, logits, float(temperature))
+    if _anchor_rows_wide(x.shape[3]):
+        out, conf = _AnchorAttnPoolWide.apply(x, logits, float(temperature))
+    elif not _anchor_rows_vectorise(x.shape[3]):
+        return _anchor_attention_pool_torch(x, logits, temperature)
+    else:
+        out, conf = _AnchorAttnPool.apply(x, logits, float(temperature))
     if logits.requires_grad and torch.is_grad_enabled():
         conf = torch.softmax(logits * float(temperature), dim=-1)
     return out, conf
@@ -120,6 +157,54 @@ class InvPPOutBlockOurs(nn.Module):
         raise NotImplementedError(f"Pooling mode {self.pooling_method} is not implemented!")
 
 
+class InvPPOutBlock2DOurs(nn.Module):
+    """Per-point invariant head of the `use_2d` models: 1x1-conv MLP over [B,C,N,na*4] (na space anchors x 4 plane anchors), then
+    pooling over the (na, 4) view of the anchor axis (base_so3conv.py:L921-1008; same constructor parameters, attributes and
+    sub-module names).  A fixed `sel_mode` picks one space anchor and pools its 4 plane anchors by attention."""
+
+    def __init__(self, params, norm=None, pooling_method='max', sel_mode=None):
+        super(InvPPOutBlock2DOurs, self).__init__()
+        c_in = params['dim_in']
+        mlp = params['mlp']
+        self.outDim = params['k']
+        self.na = params['kanchor']
+        self.linear = nn.ModuleList()
+        self.norm = nn.ModuleList()
+        self.sel_mode = sel_mode
+        for c in mlp:
+            self.linear.append(nn.Conv2d(c_in, c, 1))
+            self.norm.append(nn.BatchNorm2d(c))
+            c_in = c
+        self.pooling_method = pooling_method if self.sel_mode is None else 'sel_mode'
+        if self.pooling_method == 'attention' or self.sel_mode is not None:
+            self.temperature = params['temperature']
+            self.attention_layer = nn.Conv2d(c_in, 1, 1)
+
+    def forward(self, x, label=None, sel_mode_new=None):
+        if sel_mode_new is not None:
+            # L983-985 hands a [B,4,C,N] selection to attention_layer = Conv2d(c_in, 1, 1): a channel mismatch unless c_in == 4
+            raise NotImplementedError('InvPPOutBlock2DOurs: sel_mode_new (base_so3conv.py:L983-985) cannot run in the reference either: '
+                                      'its selection puts the 4 plane anchors on the channel axis of the attention layer')
+        if not x.feats.is_cuda:
+            raise RuntimeError('InvPPOutBlock2DOurs: tensor must be a CUDA(HIP) tensor (no CPU fallback)')
+        x_out = _unary_stack(x.feats, self.linear, self.norm)      # contraction GEMM + fused BatchNorm / ReLU epilogue
+        bz, dim, n, tot_na = x_out.shape
+        planes = x_out.reshape(bz, dim, n, self.na, -1)               # [b,c,n,na,4]: the plane anchors are the 16-byte quads of a row
+        if self.pooling_method == 'mean':
+            return planes.mean(dim=-1).mean(dim=-1)
+        if self.pooling_method == 'debug':
+            return planes[..., 0].mean(2)
+        if self.pooling_method == 'max':
+            return planes.max(-1)[0].max(-1)[0]                     # plane anchors first, then space anchors
+        if self.sel_mode is not None:
+            quad = planes[..., self.sel_mode, :].contiguous()       # [b,c,n,4]: one quad of every row
+            return anchor_attention_pool(quad, _conv1x1(self.attention_layer, quad), self.temperature)[0]
+        if self.pooling_method.startswith('attention'):
+            out_feat = _conv1x1(self.attention_layer, x_out)        # [b,1,n,na*4]: softmax over all of them (csrc/heads_wide.hip)
+            return anchor_attention_pool(x_out, out_feat, self.temperature)
+        raise NotImplementedError(f"Pooling mode {self.pooling_method} is not implemented!")
+
+
 def orbit_selection(minn_dist_ori_to_recon, minn_dist_recon_to_ori, slot_single_cd=0, slot_single_mode=0):
     """...pn_38_multi_stage.py:L1381-1399 on the [B,S,A] distances of
     extensions.chamfer_dist.orbit_reconstruction_distances: -> (distance [B,S] or [B], orbit index [B,S])."""
@@ -153,6 +238,13 @@ def _anchor_rows_vectorise(na):
     axis and keep a point's anchors in one wavefront: anchor counts that are a multiple of 4, at most 64 (12, 20, 60 ...).
     Other counts (kanchor = 1, 3) take the same expressions as device torch ops."""
     return na % 4 == 0 and 0 < na <= 64
+
+
+def _anchor_rows_wide(na):
+    """The wide twins of the three oldest head kernels (csrc/heads_wide.hip) give a point's anchor row a whole wavefront, one 16-byte
+    word per lane: anchor counts that are a multiple of 4 past the 64 of _anchor_rows_vectorise, at most 256 -- the 60 x 4 = 240 anchors
+    of a `use_2d` feature map."""
+    return na % 4 == 0 and 64 < na <= 256
 
 
 class _SlotMaskedMean(torch.autograd.Function):
@@ -202,13 +294,73 @@ class _MaskedMax(torch.autograd.Function):
         return dx, None
 
 
+class _SlotMaskedMeanWide(torch.autograd.Function):
+    """_SlotMaskedMean for anchor rows of 68 to 256 floats (csrc/heads_wide.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, mask):
+        x, mask = L._aligned16(x), mask.contiguous()                 # 16-byte loads along the anchor axis
+        b, c, n, na = x.shape
+        ns = mask.shape[1]
+        inv_den = (1.0 / mask.sum(-1).clamp(min=1e-8)).contiguous()
+        out = torch.empty(b, ns, c, na, dtype=torch.float32, device=x.device)
+        _hip.call('eap_slot_masked_mean_wide_fwd_f32', x, b, ns, c, n, na, x, mask, inv_den, out)
+        ctx.save_for_backward(mask, inv_den)
+        ctx.dims = (b, c, n, na, ns)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mask, inv_den = ctx.saved_tensors
+        b, c, n, na, ns = ctx.dims
+        dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
+        g = L._aligned16(g)           # bound to a local: the buffer must outlive the enqueue
+        _hip.call('eap_slot_masked_mean_wide_bwd_f32', g, b, ns, c, n, na, g, mask, inv_den, dx)
+        return dx, None
+
+
+class _MaskedMaxWide(torch.autograd.Function):
+    """_MaskedMax for anchor rows of 68 to 256 floats (csrc/heads_wide.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, mask):
+        x, mask = L._aligned16(x), mask.contiguous()                 # 16-byte loads along the anchor axis
+        b, c, n, na = x.shape
+        out = torch.empty(b, c, na, dtype=torch.float32, device=x.device)
+        arg = torch.empty(b, c, na, dtype=torch.int32, device=x.device)
+        _hip.call('eap_masked_max_wide_fwd_f32', x, b, c, n, na, x, mask, out, arg)
+        ctx.save_for_backward(arg, mask)
+        ctx.dims = (b, c, n, na)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        arg, mask = ctx.saved_tensors
+        b, c, n, na = ctx.dims
+        g = L._aligned16(g)
+        dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
+        _hip.call('eap_masked_max_wide_bwd_f32', g, b, c, n, na, g, arg, mask, dx)
+        return dx, None
+
+
+def _masked_max_torch(x, mask):
+    return (x * mask.to(x.dtype).view(x.shape[0], 1, x.shape[2], 1)).max(2)[0]
+
+
+def _slot_masked_mean_torch(x, mask):
+    m = mask.to(torch.float32)
+    return torch.einsum('bcna,bsn->bsca', x, m) / m.sum(-1).clamp(min=1e-8)[:, :, None, None]
+
+
 def masked_max(x, mask):
     """x [b,c,n,a], mask [b,n] (0/1, treated as data) -> [b,c,a] = (x * mask[:, None, :, None]).max(2)[0]: the pose heads' 'max'
-    pooling over a point subset without the masked copy of x."""
+    pooling over a point subset without the masked copy of x (up to 64 anchors csrc/heads.hip, 68 to 256 csrc/heads_wide.hip)."""
     if x.dtype != torch.float32 or not x.is_cuda:
         raise RuntimeError('masked_max: float32 device tensors only')
+    if _anchor_rows_wide(x.shape[3]):
+        return _MaskedMaxWide.apply(x, mask.to(torch.float32))
     if not _anchor_rows_vectorise(x.shape[3]):
-        return (x * mask.to(x.dtype).view(x.shape[0], 1, x.shape[2], 1)).max(2)[0]
+        return _masked_max_torch(x, mask)
     return _MaskedMax.apply(x, mask.to(torch.float32))
 
 
@@ -216,15 +368,16 @@ def slot_masked_mean(x, mask):
     """x [b,c,n,a], mask [b,s,n] (hard or soft slot weights, treated as data) ->
     [b,s,c,a] = sum_n mask x / clamp(sum_n mask, 1e-8): the masked point averages the pose head takes slot by slot
     (model_utils.py:L470-484 `x_out * mask` then `.mean(2)`-style pooling, L549-552 for the translations), for all
-    slots (at most 8) in one pass over x."""
+    slots (at most 8) in one pass over x (up to 64 anchors csrc/heads.hip, 68 to 256 csrc/heads_wide.hip)."""
     if x.dtype != torch.float32 or not x.is_cuda:
         raise RuntimeError('slot_masked_mean: float32 device tensors only')
     if mask.requires_grad:
         raise RuntimeError('slot_masked_mean: the slot weights are treated as data (no gradient reaches them); detach the mask or '
                            'use torch ops for a differentiable soft mask')
+    if mask.shape[1] <= 8 and _anchor_rows_wide(x.shape[3]):
+        return _SlotMaskedMeanWide.apply(x, mask.to(torch.float32))
     if not _anchor_rows_vectorise(x.shape[3]) or mask.shape[1] > 8:
-        m = mask.to(torch.float32)
-        return torch.einsum('bcna,bsn->bsca', x, m) / m.sum(-1).clamp(min=1e-8)[:, :, None, None]
+        return _slot_masked_mean_torch(x, mask)
     return _SlotMaskedMean.apply(x, mask.to(torch.float32))
 
 

@@ -926,6 +926,28 @@ int eap_masked_max_fwd_f32(int b, int c, int n, int na, const float *x, const fl
                            eap_stream_t stream);
 int eap_masked_max_bwd_f32(int b, int c, int n, int na, const float *g, const int32_t *arg, const float *mask, float *dx,
                            eap_stream_t stream);
+/* The same three pairs for wide anchor rows (csrc/heads_wide.hip): na % 4 == 0, 4 <= na <= 256 -- the 60 x 4 = 240 anchors of a `use_2d`
+ * feature map.  Parameter lists, definitions, NaN / -inf / tie rules and alignment demands are those of the entries without _wide above;
+ * one wavefront owns a point's anchor row (lane = 16-byte quad), the anchor reductions are 6 shuffle steps, the point sums of the slot
+ * mean are chains of ceil(n / 4) fused multiply-adds folded over 4 waves in a fixed order.  No atomics, bit-identical run to run.  Other
+ * anchor counts are refused ("multiple of 4, at most 256"), as are more than 8 slots and a 16-byte operand off its boundary.
+ * Anchor attention pooling over the na * 4 anchors, InvPPOutBlock2DOurs.forward (SPConvNets/utils/base_so3conv.py:L994-1001), and
+ * InvPPOutBlockOurs.forward (L905-912) on a `use_2d` map: */
+int eap_anchor_attn_pool_wide_fwd_f32(int b, int c, int n, int na, float temperature, const float *x, const float *logits,
+                                      float *out, float *conf, eap_stream_t stream);
+int eap_anchor_attn_pool_wide_bwd_f32(int b, int c, int n, int na, float temperature, const float *x, const float *logits,
+                                      const float *g, float *dx, float *dlogits, eap_stream_t stream);
+/* Masked point averages of every slot, SO3OutBlockRTWithMaskSep (SPConvNets/models/model_utils.py:L470-484, L549-552): */
+int eap_slot_masked_mean_wide_fwd_f32(int b, int ns, int c, int n, int na, const float *x, const float *mask,
+                                      const float *inv_den, float *out, eap_stream_t stream);
+int eap_slot_masked_mean_wide_bwd_f32(int b, int ns, int c, int n, int na, const float *g, const float *mask,
+                                      const float *inv_den, float *dx, eap_stream_t stream);
+/* The pose heads' 'max' pooling on a point subset (SPConvNets/models/model_utils.py:L79-80, L470-484); n <= 0 is refused forward, as by
+ * eap_masked_max_fwd_f32: */
+int eap_masked_max_wide_fwd_f32(int b, int c, int n, int na, const float *x, const float *mask, float *out, int32_t *arg,
+                                eap_stream_t stream);
+int eap_masked_max_wide_bwd_f32(int b, int c, int n, int na, const float *g, const int32_t *arg, const float *mask, float *dx,
+                                eap_stream_t stream);
 /* The last unary layer of InvOutBlockOursWithMask with the point average behind it, fused (SPConvNets/utils/base_so3conv.py:L1076-1107:
  * `F.relu(norm(linear(x)))`, the mask, PointnetSO3ConvOurs' 1x1 `embed` -- linear, so the average moves in front of it -- and the plain or
  * soft-mask weighted mean over the points).  x [b,c,n,na] the raw contraction output; scale, shift, mean, invstd, k2, k3 [b,c]; w [b,n] point
