@@ -7,7 +7,10 @@
 // Mapping: ONE WAVEFRONT owns one point's anchor row; lane l holds the 16-byte quad l of up to 64 (at 240 anchors lanes 60-63
 // idle): one load instruction covers the row's 960 contiguous bytes.  Reductions over the anchors are 6 shuffle steps over the
 // wave.  HBM-bound: x is read once forward; the backward reads x or g once and writes dx once.  No atomics; every sum has a fixed
-// order, so results are bit-identical run to run.
+// order, so results are bit-identical run to run.  Behind them the wide twin of the fused BatchNorm + leaky_relu + point mean of
+// csrc/heads.hip (eap_bn_act_cloud_mean_wide_*), on the same mapping.
+#include <initializer_list>
+
 #include "common.h"
 
 namespace {
@@ -23,7 +26,7 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-constexpr int WAVES = 4;    // per block, all six kernels
+constexpr int WAVES = 4;    // per block, every kernel here
 
 // the wave's index in its block as a value the compiler knows to be the same in every lane: what a wave reads per POINT (a mask weight, a
 // channel's gradient) then comes through the scalar cache instead of 64 lanes fetching one address
@@ -246,6 +249,139 @@ __global__ __launch_bounds__(256) void masked_max_wide_bwd_kernel(int c, int n, 
     }
 }
 
+// ---- BatchNorm2d + leaky_relu + weighted point mean in one pass (bn_act_mean_*_kernel of csrc/heads.hip, whose lanes are (point group of
+// 4, anchor quad of 16) and stop at 64 anchors): the last unary layer of InvOutBlockOursWithMask and the point average behind it on a
+// `use_2d` map (SPConvNets/utils/base_so3conv.py:L1076-1107; PointnetSO3ConvOurs keeps tot_anchors [240,3,3] for it, L1173-1176, L1196):
+//     out[b,c,a] = inv_den[b] sum_p w[b,p] leaky(x[b,c,p,a] scale[b,c] + shift[b,c])
+// block = (channel, cloud); wave w takes the points w, w + 4, ... in ascending order, PMW_ROWS rows per loop trip into as many accumulators
+// (independent loads in flight, fp32 chains of ceil(n / 16) terms); accumulators (a tree) and waves (through LDS, in wave order) are folded
+// in a fixed order: bit-identical run to run.  Points past n re-read point n - 1 with weight 0.  What a wave reads per point (w, stat_mask)
+// and per block (scale ... inv_den) has a wave-uniform address and comes through the scalar cache.
+constexpr int PMW_ROWS = 4;
+constexpr int PMW_PARTS = WAVES;        // partial sums per (cloud, channel) the backward reduction leaves: one per wave
+constexpr int PMW_APPLY_PTS = 512;      // points per block of the backward apply
+
+__device__ __forceinline__ float leaky(float pre, float slope) { return pre > 0.f ? pre : pre * slope; }
+
+__global__ __launch_bounds__(256) void bn_act_mean_wide_fwd_kernel(int c, int n, int na, float slope, const float *__restrict__ x,
+                                                                   const float *__restrict__ scale, const float *__restrict__ shift,
+                                                                   const float *__restrict__ w, const float *__restrict__ inv_den,
+                                                                   float *__restrict__ out) {
+    __shared__ float4 s_part[WAVES][64];                      // [wave][quad]
+    const int ci = blockIdx.x, bi = blockIdx.y, lane = threadIdx.x & 63, wave = wave_index(), nq = na >> 2;
+    const size_t si = (size_t)bi * c + ci;
+    const float sc = scale[si], sh = shift[si];
+    const float *xp = x + si * n * na + 4 * min(lane, nq - 1);    // an idle lane re-reads the last quad
+    const float *wp = w + (size_t)bi * n;
+    float4 acc[PMW_ROWS];
+#pragma unroll
+    for (int u = 0; u < PMW_ROWS; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int p0 = wave; p0 < n; p0 += WAVES * PMW_ROWS) {
+        float4 v[PMW_ROWS];
+        float wv[PMW_ROWS];
+#pragma unroll
+        for (int u = 0; u < PMW_ROWS; ++u) {
+            const int p = p0 + WAVES * u, pc = min(p, n - 1);
+            v[u] = *reinterpret_cast<const float4 *>(xp + (size_t)pc * na);
+            wv[u] = p < n ? wp[pc] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < PMW_ROWS; ++u) {
+            acc[u].x = fmaf(wv[u], leaky(fmaf(v[u].x, sc, sh), slope), acc[u].x);
+            acc[u].y = fmaf(wv[u], leaky(fmaf(v[u].y, sc, sh), slope), acc[u].y);
+            acc[u].z = fmaf(wv[u], leaky(fmaf(v[u].z, sc, sh), slope), acc[u].z);
+            acc[u].w = fmaf(wv[u], leaky(fmaf(v[u].w, sc, sh), slope), acc[u].w);
+        }
+    }
+    s_part[wave][lane] = make_float4((acc[0].x + acc[1].x) + (acc[2].x + acc[3].x), (acc[0].y + acc[1].y) + (acc[2].y + acc[3].y),
+                                     (acc[0].z + acc[1].z) + (acc[2].z + acc[3].z), (acc[0].w + acc[1].w) + (acc[2].w + acc[3].w));
+    __syncthreads();
+    if (threadIdx.x < nq) {
+        const int q = threadIdx.x;
+        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int j = 0; j < WAVES; ++j) { const float4 u = s_part[j][q]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
+        const float d = inv_den[bi];
+        *reinterpret_cast<float4 *>(out + si * na + 4 * q) = make_float4(t.x * d, t.y * d, t.z * d, t.w * d);
+    }
+}
+
+// backward, reduction pass: with gg = (pre > 0 ? 1 : slope) w[b,p] inv_den[b] g[b,c,a] formed in registers, the sums of gg and gg xhat
+// over the points and anchors of a (cloud, channel) row as PMW_PARTS partials [b][c][wave], for the caller to add in float64: per trip a
+// lane adds its four anchors (a tree) to the row's accumulator; behind the loop the accumulators are folded (a tree) and the wave summed
+__global__ __launch_bounds__(256) void bn_act_mean_wide_bwd_reduce_kernel(int c, int n, int na, float slope, const float *__restrict__ g,
+                                                                          const float *__restrict__ x, const float *__restrict__ scale,
+                                                                          const float *__restrict__ shift, const float *__restrict__ mean,
+                                                                          const float *__restrict__ invstd, const float *__restrict__ w,
+                                                                          const float *__restrict__ inv_den, float *__restrict__ pg,
+                                                                          float *__restrict__ pgx) {
+    const int ci = blockIdx.x, bi = blockIdx.y, lane = threadIdx.x & 63, wave = wave_index(), nq = na >> 2;
+    const int quad = min(lane, nq - 1);
+    const size_t si = (size_t)bi * c + ci;
+    const float sc = scale[si], sh = shift[si], mu = mean[si], is = invstd[si], d = inv_den[bi];
+    float4 gq = *reinterpret_cast<const float4 *>(g + si * na + 4 * quad);
+    gq = make_float4(gq.x * d, gq.y * d, gq.z * d, gq.w * d);
+    const float *xp = x + si * n * na + 4 * quad;
+    const float *wp = w + (size_t)bi * n;
+    float s[PMW_ROWS], q[PMW_ROWS];
+#pragma unroll
+    for (int u = 0; u < PMW_ROWS; ++u) s[u] = q[u] = 0.f;
+    for (int p0 = wave; p0 < n; p0 += WAVES * PMW_ROWS) {
+        float4 v[PMW_ROWS];
+        float wv[PMW_ROWS];
+#pragma unroll
+        for (int u = 0; u < PMW_ROWS; ++u) {
+            const int p = p0 + WAVES * u, pc = min(p, n - 1);
+            v[u] = *reinterpret_cast<const float4 *>(xp + (size_t)pc * na);
+            wv[u] = p < n ? wp[pc] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < PMW_ROWS; ++u) {
+            const float g0 = (fmaf(v[u].x, sc, sh) > 0.f ? gq.x : gq.x * slope) * wv[u], g1 = (fmaf(v[u].y, sc, sh) > 0.f ? gq.y : gq.y * slope) * wv[u];
+            const float g2 = (fmaf(v[u].z, sc, sh) > 0.f ? gq.z : gq.z * slope) * wv[u], g3 = (fmaf(v[u].w, sc, sh) > 0.f ? gq.w : gq.w * slope) * wv[u];
+            s[u] += (g0 + g1) + (g2 + g3);
+            q[u] += (g0 * ((v[u].x - mu) * is) + g1 * ((v[u].y - mu) * is)) + (g2 * ((v[u].z - mu) * is) + g3 * ((v[u].w - mu) * is));
+        }
+    }
+    const bool live = lane < nq;                              // an idle lane re-read the last quad
+    const float ts = wave_sum(live ? (s[0] + s[1]) + (s[2] + s[3]) : 0.f), tq = wave_sum(live ? (q[0] + q[1]) + (q[2] + q[3]) : 0.f);
+    if (lane == 0) {
+        pg[si * PMW_PARTS + wave] = ts;
+        pgx[si * PMW_PARTS + wave] = tq;
+    }
+}
+
+// backward, apply pass: gx = scale gg - stat_mask (k2 + xhat k3), the formula of bn_act_mean_bwd_apply_kernel (csrc/heads.hip).
+// block = (channel, cloud, PMW_APPLY_PTS points); no reduction
+__global__ __launch_bounds__(256) void bn_act_mean_wide_bwd_apply_kernel(int c, int n, int na, float slope, const float *__restrict__ g,
+                                                                         const float *__restrict__ x, const float *__restrict__ scale,
+                                                                         const float *__restrict__ shift, const float *__restrict__ mean,
+                                                                         const float *__restrict__ invstd, const float *__restrict__ k2,
+                                                                         const float *__restrict__ k3, const float *__restrict__ w,
+                                                                         const float *__restrict__ inv_den, const float *__restrict__ stat_mask,
+                                                                         float *__restrict__ gx) {
+    const int ci = blockIdx.x, bi = blockIdx.y, lane = threadIdx.x & 63, wave = wave_index(), nq = na >> 2;
+    if (lane >= nq) return;
+    const size_t si = (size_t)bi * c + ci;
+    const float sc = scale[si], sh = shift[si], mu = mean[si], is = invstd[si], c2 = k2[si], c3 = k3[si], d = inv_den[bi];
+    float4 gq = *reinterpret_cast<const float4 *>(g + si * na + 4 * lane);
+    gq = make_float4(gq.x * d, gq.y * d, gq.z * d, gq.w * d);
+    const float *xp = x + si * n * na + 4 * lane;
+    float *op = gx + si * n * na + 4 * lane;
+    const float *wp = w + (size_t)bi * n;
+    const float *mp = stat_mask ? stat_mask + (size_t)bi * n : nullptr;
+    const int first = blockIdx.z * PMW_APPLY_PTS, last = min(n, first + PMW_APPLY_PTS);
+    auto one = [&](float gv, float xv, float wv, float m) {
+        const float gg = (fmaf(xv, sc, sh) > 0.f ? gv : gv * slope) * wv;
+        return fmaf(-m, fmaf((xv - mu) * is, c3, c2), gg * sc);
+    };
+#pragma unroll 4
+    for (int p = first + wave; p < last; p += WAVES) {
+        const float4 v = *reinterpret_cast<const float4 *>(xp + (size_t)p * na);
+        const float wv = wp[p], m = mp ? mp[p] : 1.f;
+        *reinterpret_cast<float4 *>(op + (size_t)p * na) = make_float4(one(gq.x, v.x, wv, m), one(gq.y, v.y, wv, m), one(gq.z, v.z, wv, m), one(gq.w, v.w, wv, m));
+    }
+}
+
 // anchor rows of 1 to 64 16-byte words (and at most MAXS slots), every tensor a kernel reads or writes by float4 / int4 on a 16-byte
 // boundary (`which` names them in the message): the message form of head_args (csrc/heads.hip)
 inline int wide_args(const char *who, int na, int ns, const char *which, const void *p0, const void *p1, const void *p2 = nullptr,
@@ -257,6 +393,26 @@ inline int wide_args(const char *who, int na, int ns, const char *which, const v
     }
     if (((reinterpret_cast<uintptr_t>(p0) | reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2) | reinterpret_cast<uintptr_t>(p3)) & 15) != 0) {
         snprintf(buf, sizeof(buf), "%s: %s must be 16-byte aligned", who, which);
+        return eap::bad_arg(buf);
+    }
+    return 0;
+}
+
+// the fused norm + point mean: the anchor rule, then the operands every kernel of the entry reads (`required`: one of them null is named
+// a refusal, not a fault), then the 16-byte rule on the [b,c,n,na] and [b,c,na] tensors
+inline int wide_mean_args(const char *who, int na, std::initializer_list<const void *> required, const void *p0, const void *p1, const void *p2) {
+    char buf[240];
+    if (na <= 0 || na > 256 || (na & 3) != 0) {
+        snprintf(buf, sizeof(buf), "%s: anchors must be a multiple of 4, at most 256", who);
+        return eap::bad_arg(buf);
+    }
+    for (const void *p : required)
+        if (!p) {
+            snprintf(buf, sizeof(buf), "%s: a required pointer is null", who);
+            return eap::bad_arg(buf);
+        }
+    if (((reinterpret_cast<uintptr_t>(p0) | reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2)) & 15) != 0) {
+        snprintf(buf, sizeof(buf), "%s: the [b,c,n,na] and [b,c,na] tensors must be 16-byte aligned", who);
         return eap::bad_arg(buf);
     }
     return 0;
@@ -307,4 +463,36 @@ extern "C" int eap_masked_max_wide_bwd_f32(int b, int c, int n, int na, const fl
     if (b <= 0 || c <= 0 || n <= 0) return 0;
     if (int e = wide_args("masked_max_wide_bwd", na, 0, "g, arg and dx", g, arg, dx)) return e;
     return eap::run_kernel("masked_max_wide_bwd", masked_max_wide_bwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, g, arg, mask, dx);
+}
+
+// ---- BatchNorm2d + leaky_relu + weighted point mean on wide anchor rows (InvOutBlockOursWithMask, SPConvNets/utils/base_so3conv.py:L1076-1107) ----
+extern "C" int eap_bn_act_cloud_mean_wide_parts(int n) { return n > 0 ? PMW_PARTS : 0; }
+
+extern "C" int eap_bn_act_cloud_mean_wide_fwd_f32(int b, int c, int n, int na, float slope, const float *x, const float *scale, const float *shift,
+                                                  const float *w, const float *inv_den, float *out, eap_stream_t stream) {
+    if (b <= 0 || c <= 0) return 0;
+    if (n <= 0) return eap::bad_arg("bn_act_cloud_mean_wide_fwd: no points");
+    if (int e = wide_mean_args("bn_act_cloud_mean_wide_fwd", na, {x, scale, shift, w, inv_den, out}, x, out, nullptr)) return e;
+    return eap::run_kernel("bn_act_cloud_mean_wide_fwd", bn_act_mean_wide_fwd_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, slope, x, scale,
+                           shift, w, inv_den, out);
+}
+
+extern "C" int eap_bn_act_cloud_mean_wide_bwd_reduce_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
+                                                         const float *shift, const float *mean, const float *invstd, const float *w,
+                                                         const float *inv_den, float *pg, float *pgx, eap_stream_t stream) {
+    if (b <= 0 || c <= 0) return 0;
+    if (n <= 0) return eap::bad_arg("bn_act_cloud_mean_wide_bwd_reduce: no points");
+    if (int e = wide_mean_args("bn_act_cloud_mean_wide_bwd_reduce", na, {g, x, scale, shift, mean, invstd, w, inv_den, pg, pgx}, x, g, nullptr)) return e;
+    return eap::run_kernel("bn_act_cloud_mean_wide_bwd_reduce", bn_act_mean_wide_bwd_reduce_kernel, c, b, 1, dim3(256), 0, eap::S(stream), c, n, na, slope,
+                           g, x, scale, shift, mean, invstd, w, inv_den, pg, pgx);
+}
+
+extern "C" int eap_bn_act_cloud_mean_wide_bwd_apply_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
+                                                        const float *shift, const float *mean, const float *invstd, const float *k2, const float *k3,
+                                                        const float *w, const float *inv_den, const float *stat_mask, float *gx, eap_stream_t stream) {
+    if (b <= 0 || c <= 0) return 0;
+    if (n <= 0) return eap::bad_arg("bn_act_cloud_mean_wide_bwd_apply: no points");
+    if (int e = wide_mean_args("bn_act_cloud_mean_wide_bwd_apply", na, {g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, gx}, x, g, gx)) return e;
+    return eap::run_kernel("bn_act_cloud_mean_wide_bwd_apply", bn_act_mean_wide_bwd_apply_kernel, c, b, eap::cdiv(n, PMW_APPLY_PTS), dim3(256), 0,
+                           eap::S(stream), c, n, na, slope, g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, gx);
 }

@@ -1428,6 +1428,33 @@ def bn_act_cloud_mean_bwd_apply(g, x, scale, shift, mean, invstd, k2, k3, w, inv
     return gx
 
 
+# the same three for anchor rows of up to 256 floats, the 240 of a `use_2d` map (csrc/heads_wide.hip, the eap_bn_act_cloud_mean_wide_* entries)
+
+def bn_act_cloud_mean_wide_fwd(x, scale, shift, w, inv_den, slope):
+    """-> [b, c, na] = inv_den sum_p w leaky(x scale + shift)"""
+    b, c, p, na = x.shape
+    out = torch.empty(b, c, na, dtype=torch.float32, device=x.device)
+    call('eap_bn_act_cloud_mean_wide_fwd_f32', x, b, c, p, na, slope, x, scale, shift, w, inv_den, out)
+    return out
+
+
+def bn_act_cloud_mean_wide_bwd_reduce(g, x, scale, shift, mean, invstd, w, inv_den, slope):
+    """-> sum(gg), sum(gg xhat) per (cloud, channel), float64 [b, c]"""
+    b, c, p, na = x.shape
+    parts = int(abi.eap_bn_act_cloud_mean_wide_parts(p))
+    pg = torch.empty(b, c, parts, dtype=torch.float32, device=x.device)
+    pgx = torch.empty_like(pg)
+    call('eap_bn_act_cloud_mean_wide_bwd_reduce_f32', x, b, c, p, na, slope, g, x, scale, shift, mean, invstd, w, inv_den, pg, pgx)
+    return pg.sum(2, dtype=torch.float64), pgx.sum(2, dtype=torch.float64)
+
+
+def bn_act_cloud_mean_wide_bwd_apply(g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, slope):
+    b, c, p, na = x.shape
+    gx = torch.empty_like(x)
+    call('eap_bn_act_cloud_mean_wide_bwd_apply_f32', x, b, c, p, na, slope, g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, gx)
+    return gx
+
+
 # SlotAttention's per-point passes (csrc/slot_attention.hip, the eap_slot_attn_* entries): x [b,d,n] channel-major, mean / rstd [b,n] the
 # LayerNorm statistics of a point, z = (x - mean) rstd never written; u, gmsum [b,s,d]; c0, gwsum [b,s]; attn, w, gdots [b,s,n]
 

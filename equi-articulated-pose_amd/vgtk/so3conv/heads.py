@@ -19,7 +19,7 @@ and 3), mirroring the reference classes so a maintainer can swap the import:
   pose_head_over_subsets   the model's per-cloud loop around that head (...pn_38_multi_stage.py:L706-830) as one call per slot
   InvOutBlockOursWithMask  SPConvNets/utils/base_so3conv.py:L1013-1150 with its PointnetSO3ConvOurs (L1153-1205), the per-slot
                            shape-code head: the last unary layer's BatchNorm + ReLU and the point mean are one HIP pass
-                           (csrc/heads.hip), the embed layer runs on the means
+                           (csrc/heads.hip; on the 240 anchors of a `use_2d` map csrc/heads_wide.hip), the embed layer runs on the means
   inv_head_over_subsets, inv_heads_over_slot_groups   the model's per-cloud / per-slot loops around that head, batched
 
 Every 1x1 convolution over the [B,C,N,A] map (InvPPOutBlockOurs' included) is the path's contraction, every BatchNorm +
@@ -651,7 +651,8 @@ class SO3OutBlockRTWithMaskSep(nn.Module):
 class _SubsetBNAct(torch.autograd.Function):
     """leaky_relu(BatchNorm2d(y + bias)) with the statistics of every cloud's member points alone -- what B separate
     batch-1 calls on the gathered subsets compute -- as two passes over y forward (masked statistics, apply) and two
-    backward (reduce, apply): csrc/bn_act.hip, the eap_bn_act_cloud_* entries.  Every point is normalised; the head's
+    backward (reduce, apply): csrc/bn_act.hip, the eap_bn_act_cloud_* entries (flat over points x anchors: any anchor count that is a
+    multiple of 4; run up to 256, the 240 of a `use_2d` map included).  Every point is normalised; the head's
     later masked poolings drop the non-members.  The running statistics receive the B momentum updates in cloud
     order, as the loop would apply them."""
 
@@ -688,7 +689,7 @@ class _SubsetBNAct(torch.autograd.Function):
 
 
 def _subset_batchnorm_act_torch(y, bias, mask, bn, slope):
-    """_SubsetBNAct as device torch ops, for anchor counts the 16-byte kernels do not take (see _anchor_rows_vectorise)."""
+    """_SubsetBNAct as device torch ops, for anchor counts the 16-byte kernels are not run at (kanchor = 1, 3, more than 256)."""
     b, c, p, na = y.shape
     if bias is not None:
         y = y + bias.view(1, c, 1, 1)
@@ -713,7 +714,7 @@ def _subset_batchnorm_act(y, bias, mask, bn, slope):
             bn.num_batches_tracked.add_(y.shape[0])
     if bn.momentum is None:
         raise NotImplementedError('pose_head_over_subsets: cumulative-average BatchNorm (momentum=None) is not batched')
-    if not _anchor_rows_vectorise(y.shape[3]):
+    if not (_anchor_rows_vectorise(y.shape[3]) or _anchor_rows_wide(y.shape[3])):
         return _subset_batchnorm_act_torch(y, bias, mask, bn, slope)
     return _SubsetBNAct.apply(y, bias, mask, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps, slope)
 
@@ -861,14 +862,16 @@ def pose_head_over_slot_groups(heads, feats, xyz, labels, anchors, use_offset=Tr
 # with the rotated coordinates, the 1x1 `embed`), so with point weights w_p of sum 1
 #     mean_p embed([h_p ; A^T x_p]) = W_f (mean_p h_p) + W_x A^T (mean_p x_p) + bias
 # and the only work left on the [B,c,N,A] map is BatchNorm2d + ReLU + the weighted point mean, one fused pass (csrc/heads.hip,
-# the eap_bn_act_cloud_mean_* entries): neither the activated map, the (c+3)-channel concatenation nor the embed output exists.
+# the eap_bn_act_cloud_mean_* entries; past 64 anchors csrc/heads_wide.hip, eap_bn_act_cloud_mean_wide_*): neither the activated map,
+# the (c+3)-channel concatenation nor the embed output exists.
 
 class _NormActPointMean(torch.autograd.Function):
     """out[b,c,a] = inv_den[b] sum_p w[b,p] leaky(BatchNorm2d(y + bias))[b,c,p,a]: y [B,C,P,A] the raw contraction output, w [B,P] point
     weights and inv_den [B] (data).  stat_mask [B,P] (0/1): training statistics per cloud over its members, as _SubsetBNAct takes them
     (B momentum updates of the running statistics in cloud order, in closed form); None: the statistics of the whole batch, as
     nn.BatchNorm2d takes them.  The conv bias rides in the mean (gradient exactly zero in training mode).  Saved for the backward:
-    y and [B,C] vectors; the backward is a reduction pass and an apply pass over y."""
+    y and [B,C] vectors; the backward is a reduction pass and an apply pass over y.  Up to 64 anchors the eap_bn_act_cloud_mean_* entries
+    of csrc/heads.hip, 68 to 256 (the 240 of a `use_2d` map) their _wide twins of csrc/heads_wide.hip."""
 
     @staticmethod
     def forward(ctx, y, bias, w, inv_den, stat_mask, weight, beta, running_mean, running_var, training, momentum, eps, slope):
@@ -887,7 +890,8 @@ class _NormActPointMean(torch.autograd.Function):
             sums = (s1, s2, pivot, cnt)
         fold = norm_fold.fold(sums, weight.expand(b, c), beta, running_mean, running_var, training, momentum, eps, bias)   # (gamma per cloud: scale, shift [b, c])
         scale, shift, mean, invstd = (t.expand(b, c).float().contiguous() for t in fold[:4])
-        out = _hip.bn_act_cloud_mean_fwd(y, scale, shift, w, inv_den, slope)
+        fwd = _hip.bn_act_cloud_mean_wide_fwd if _anchor_rows_wide(na) else _hip.bn_act_cloud_mean_fwd
+        out = fwd(y, scale, shift, w, inv_den, slope)
         ctx.save_for_backward(y, scale, shift, mean, invstd, w, inv_den, stat_mask)
         ctx.training, ctx.slope, ctx.has_bias = training, slope, bias is not None
         return out
@@ -897,34 +901,45 @@ class _NormActPointMean(torch.autograd.Function):
         y, scale, shift, mean, invstd, w, inv_den, stat_mask = ctx.saved_tensors
         b, c, p, na = y.shape
         g = L._aligned16(g)
-        sg, sgx = _hip.bn_act_cloud_mean_bwd_reduce(g, y, scale, shift, mean, invstd, w, inv_den, ctx.slope)     # [b, c] float64
+        wide = _anchor_rows_wide(na)
+        reduce_, apply_ = ((_hip.bn_act_cloud_mean_wide_bwd_reduce, _hip.bn_act_cloud_mean_wide_bwd_apply) if wide else
+                           (_hip.bn_act_cloud_mean_bwd_reduce, _hip.bn_act_cloud_mean_bwd_apply))
+        sg, sgx = reduce_(g, y, scale, shift, mean, invstd, w, inv_den, ctx.slope)     # [b, c] float64
         g_y = None
         if ctx.needs_input_grad[0]:
             cnt = float(b * p * na)                                                     # whole batch: the sums of all clouds
             if ctx.training and stat_mask is not None:
                 cnt = (stat_mask.sum(1, dtype=torch.float64) * na).view(b, 1)
             k2, k3 = norm_fold.backward_coefficients(scale, sg, sgx, cnt, ctx.training)
-            g_y = _hip.bn_act_cloud_mean_bwd_apply(g, y, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, ctx.slope)
+            g_y = apply_(g, y, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, ctx.slope)
         g_bias = norm_fold.pre_bias_grad(sg, scale, ctx.training) if ctx.has_bias else None
         return g_y, g_bias, None, None, None, sgx.sum(0).float(), sg.sum(0).float(), None, None, None, None, None, None
 
 
+def _norm_act_point_mean_torch(y, bias, w, inv_den, stat_mask, bn, slope=0.0):
+    """_norm_act_point_mean as device tensor ops, for anchor counts neither set of kernels takes (kanchor = 1, 3, more than 256); w and
+    inv_den float32"""
+    b, c = y.shape[:2]
+    if stat_mask is not None:
+        if bn.training:
+            bn.num_batches_tracked.add_(b)
+        z = _subset_batchnorm_act_torch(y, bias, stat_mask, bn, slope)
+    else:
+        z = bn(y + bias.view(1, c, 1, 1) if bias is not None else y)
+        z = F.leaky_relu(z, slope) if slope else F.relu(z)
+    return torch.einsum('bcpa,bp->bca', z, w) * inv_den.view(b, 1, 1)
+
+
 def _norm_act_point_mean(y, bias, w, inv_den, stat_mask, bn, slope=0.0):
     """inv_den sum_p w act(bn(y + bias)) -> [B,c,A]; y [B,c,P,A] raw contraction output, w [B,P], inv_den [B], stat_mask [B,P] or None
-    (see _NormActPointMean); anchor counts the 16-byte kernels do not take run the same expressions as device tensor ops."""
+    (see _NormActPointMean: up to 64 anchors csrc/heads.hip, 68 to 256 csrc/heads_wide.hip); anchor counts neither takes run the same
+    expressions as device tensor ops."""
     if bn.momentum is None or not bn.track_running_stats:
         raise NotImplementedError('InvOutBlockOursWithMask: BatchNorm with running statistics and a momentum only')
     b, c = y.shape[:2]
     w, inv_den = w.to(torch.float32).contiguous(), inv_den.to(torch.float32).contiguous()
-    if not _anchor_rows_vectorise(y.shape[3]):
-        if stat_mask is not None:
-            if bn.training:
-                bn.num_batches_tracked.add_(b)
-            z = _subset_batchnorm_act_torch(y, bias, stat_mask, bn, slope)
-        else:
-            z = bn(y + bias.view(1, c, 1, 1) if bias is not None else y)
-            z = F.leaky_relu(z, slope) if slope else F.relu(z)
-        return torch.einsum('bcpa,bp->bca', z, w) * inv_den.view(b, 1, 1)
+    if not (_anchor_rows_vectorise(y.shape[3]) or _anchor_rows_wide(y.shape[3])):
+        return _norm_act_point_mean_torch(y, bias, w, inv_den, stat_mask, bn, slope)
     if bn.training:
         with torch.no_grad():
             bn.num_batches_tracked.add_(b if stat_mask is not None else 1)

@@ -966,6 +966,24 @@ int eap_bn_act_cloud_mean_bwd_reduce_f32(int b, int c, int n, int na, float slop
 int eap_bn_act_cloud_mean_bwd_apply_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
                                         const float *shift, const float *mean, const float *invstd, const float *k2, const float *k3,
                                         const float *w, const float *inv_den, const float *stat_mask, float *gx, eap_stream_t stream);
+/* The same three entries and their parts query for wide anchor rows (csrc/heads_wide.hip): na % 4 == 0, 4 <= na <= 256 -- InvOutBlockOursWithMask
+ * on the 240-anchor map of a `use_2d` backbone (SPConvNets/utils/base_so3conv.py:L1076-1107; PointnetSO3ConvOurs keeps tot_anchors [240,3,3] for
+ * it, L1173-1176, L1196).  Parameter lists and definitions are those of the entries without _wide above.  One wavefront owns a point's anchor
+ * row (lane = 16-byte quad); a wave takes every 4th point, 4 rows in flight into 4 accumulators (fp32 chains of ceil(n / 16) terms), folded as
+ * a tree, over the 4 waves in wave order (forward) or over the wave by 6 shuffle steps (reduction: eap_bn_act_cloud_mean_wide_parts(n) = 4
+ * partials per (cloud, channel), one per wave).  No atomics, bit-identical run to run; the activated map and its gradient are never written.
+ * Refused before any device call (hipErrorInvalidValue, the condition in eap_last_error()): n <= 0, other anchor counts ("multiple of 4, at
+ * most 256"), a null pointer other than stat_mask, x / out / g / gx off a 16-byte boundary, sizes beyond the launch limits.  b <= 0 or c <= 0
+ * returns 0 without touching a pointer. */
+int eap_bn_act_cloud_mean_wide_fwd_f32(int b, int c, int n, int na, float slope, const float *x, const float *scale, const float *shift,
+                                       const float *w, const float *inv_den, float *out, eap_stream_t stream);
+int eap_bn_act_cloud_mean_wide_parts(int n);
+int eap_bn_act_cloud_mean_wide_bwd_reduce_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
+                                              const float *shift, const float *mean, const float *invstd, const float *w, const float *inv_den,
+                                              float *pg, float *pgx, eap_stream_t stream);
+int eap_bn_act_cloud_mean_wide_bwd_apply_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
+                                             const float *shift, const float *mean, const float *invstd, const float *k2, const float *k3,
+                                             const float *w, const float *inv_den, const float *stat_mask, float *gx, eap_stream_t stream);
 
 /* ---- SlotAttention's per-point passes (SPConvNets/utils/slot_attention_spec_v2.py:L132-193; csrc/slot_attention.hip) -------- */
 /* The per-slot LayerNorm (L149), to_k / to_v (L153-154) and the einsums (L167, L175) are linear in z[n,:] = (x[:,n] - mean[n]) * rstd[n], the same
