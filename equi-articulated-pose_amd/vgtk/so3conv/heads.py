@@ -7,6 +7,7 @@ and 3), mirroring the reference classes so a maintainer can swap the import:
   InvPPOutBlock2DOurs      SPConvNets/utils/base_so3conv.py:L921-1008, the same head over the 60 x 4 anchors of a `use_2d` map: the
                            attention pooling over all 240 is one HIP pass (csrc/heads_wide.hip)
   orbit_selection          ...pn_38_multi_stage.py:L1381-1399: distance -> arg-min orbit per slot
+  global_orbit_selection   ...pn_38_multi_stage.py:L444-461: the global alignment's distances -> arg-min orbit per cloud
   slot_masked_mean         the masked per-slot point averages of SO3OutBlockRTWithMaskSep
                            (SPConvNets/models/model_utils.py:L470-484, L549-552) for ALL slots in one pass
   rotation_from_angle_axis model_utils.py angle -> R (Rodrigues), batched
@@ -213,6 +214,19 @@ def orbit_selection(minn_dist_ori_to_recon, minn_dist_recon_to_ori, slot_single_
         dist, orbit = torch.min(d.sum(1), dim=-1)
         return dist, orbit.unsqueeze(-1).repeat(1, d.shape[1]).contiguous()
     return torch.min(d, dim=-1)
+
+
+def global_orbit_selection(chamfer_recon_to_ori, chamfer_ori_to_recon, glb_single_cd=0):
+    """...pn_38_multi_stage.py:L444-461 on the [B,A] distances of extensions.chamfer_dist.global_orbit_distances:
+    -> (minn_glb_chamfer [B], glb_orbit [B], glb_recon_ori_dist, glb_ori_to_recon_dist), the last two the scalars the model keeps as
+    attributes of those names."""
+    glb_chamfer = chamfer_ori_to_recon if glb_single_cd == 1 else chamfer_recon_to_ori + chamfer_ori_to_recon
+    minn_glb_chamfer, glb_orbit = torch.min(glb_chamfer, dim=-1)
+    pick = glb_orbit.unsqueeze(-1)
+    minn_recon_to_ori = torch.gather(chamfer_recon_to_ori, 1, pick).squeeze(-1)
+    minn_ori_to_recon = torch.gather(chamfer_ori_to_recon, 1, pick).squeeze(-1)
+    glb_recon_ori_dist = (torch.sqrt(minn_recon_to_ori) + torch.sqrt(minn_ori_to_recon)).mean() * 0.5
+    return minn_glb_chamfer, glb_orbit, glb_recon_ori_dist, torch.sqrt(minn_ori_to_recon).mean()
 
 
 def orbit_slot_distances(minn_dist_ori_to_recon_all_pts, minn_dist_ori_to_recon, hard_one_hot_labels, attn_ori):

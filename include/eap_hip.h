@@ -772,6 +772,37 @@ int eap_chamfer_bwd_ordered_f64(int b, int n, int m, const double *xyz1, const d
                                 const int32_t *idx1, const int32_t *idx2, const double *g1, const double *g2,
                                 double *gxyz1, double *gxyz2, eap_stream_t stream);
 
+/* The reconstruction distances over the orbit (SPConvNets/models/unsup_seg_so3_pose_conv_pn_38_multi_stage.py:L1341-1361 per slot with
+ * its membership mask, L429-440 for the global alignment without one) as a shared-target search: g = b*s groups (s slots per cloud, the
+ * cloud of group i is i / s) of a candidate clouds of m points, recon [g,a,m,3], all compared with the group's ONE input cloud, ori
+ * [g/s,3,n] planar; member uint8 [g,n] flags the points of the group's slot, NULL = every point is in (the masked outputs are then not
+ * written and may be NULL).  Squared distances as eap_chamfer_fwd_*: (dx*dx + dy*dy) + dz*dz, one rounding per operation, first
+ * minimum wins.
+ *   r2o_all [g,a,m], r2o_all_idx int32 [g,a,m]   min over the n points and its index
+ *   r2o_in  [g,a,m], r2o_in_idx  int32 [g,a,m]   the same over the flagged points; (99999, -1) where the group has none
+ *   o2r_all [g,a,n], o2r_idx     int32 [g,a,n]   min over the m points of candidate cloud (g,a) and its index
+ *   o2r_in  [g,a,n]                              member ? o2r_all : 99999
+ * a, m, n, s >= 1, s divides g, every tensor below 2^31 elements; g <= 0 returns at once. */
+int eap_orbit_chamfer_fwd_f32(int g, int s, int a, int m, int n, const float *recon, const float *ori, const uint8_t *member,
+                              float *r2o_all, int32_t *r2o_all_idx, float *r2o_in, int32_t *r2o_in_idx, float *o2r_all,
+                              int32_t *o2r_idx, float *o2r_in, eap_stream_t stream);
+int eap_orbit_chamfer_fwd_f64(int g, int s, int a, int m, int n, const double *recon, const double *ori, const uint8_t *member,
+                              double *r2o_all, int32_t *r2o_all_idx, double *r2o_in, int32_t *r2o_in_idx, double *o2r_all,
+                              int32_t *o2r_idx, double *o2r_in, eap_stream_t stream);
+/* The gradient of those maps with respect to recon (...pn_38_multi_stage.py:L1341-1361, L429-440: what autograd sends through the
+ * reference's min / mean), a gather with a fixed summation order: no atomics, bit-identical run to run, grecon [g,a,m,3] written once.
+ *   grecon[g,a,j] = ((0 + own_all) + own_in) + sum over i ascending with o2r_idx[g,a,i] == j of
+ *                   (2 * (g_o2r_all[g,a,i] + member[g,i] * g_o2r_in[g,a,i])) * (recon[g,a,j] - ori[i])
+ *   own_x = (2 * g_r2o_x[g,a,j]) * (recon[g,a,j] - ori[r2o_x_idx[g,a,j]])
+ * An index outside its range (the -1 of an empty slot) contributes nothing and is not dereferenced.  member NULL: the masked index
+ * and gradients are not read and may be NULL.  The input cloud gets no gradient from this entry. */
+int eap_orbit_chamfer_bwd_f32(int g, int s, int a, int m, int n, const float *recon, const float *ori, const uint8_t *member,
+                              const int32_t *r2o_all_idx, const int32_t *r2o_in_idx, const int32_t *o2r_idx, const float *g_r2o_all,
+                              const float *g_r2o_in, const float *g_o2r_all, const float *g_o2r_in, float *grecon, eap_stream_t stream);
+int eap_orbit_chamfer_bwd_f64(int g, int s, int a, int m, int n, const double *recon, const double *ori, const uint8_t *member,
+                              const int32_t *r2o_all_idx, const int32_t *r2o_in_idx, const int32_t *o2r_idx, const double *g_r2o_all,
+                              const double *g_r2o_in, const double *g_o2r_all, const double *g_o2r_in, double *grecon, eap_stream_t stream);
+
 /* ---- block-layer epilogue: BatchNorm2d (batch statistics) + leaky_relu ------------------------- */
 /* SPConvNets/utils/base_so3poseconv.py:L214-221 (`feat = self.norm(x.feats); feat = self.relu(feat)`),
  * SURVEY.md 8(f) row 1.  x, y, gy, gx: [b, c, n] (n = P*A, a multiple of 4), contiguous.
