@@ -15,9 +15,10 @@ namespace {
 constexpr int ROWS = 4;  // (c,p) rows per block = waves per block
 
 __device__ __forceinline__ void accumulate(float &acc, const float &v) { acc += v; }
+__device__ __forceinline__ void accumulate(double &acc, const double &v) { acc += v; }
 __device__ __forceinline__ void accumulate(float4 &acc, const float4 &v) { acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w; }
 
-// V: what a lane moves per anchor (float, or the float4 of an anchor's four residuals)
+// V: what a lane moves per anchor (float, the float4 of an anchor's four residuals, or a double: the float64 regime)
 template <typename V>
 __global__ __launch_bounds__(64 * ROWS) void so3_intra_group_fwd_kernel(
     long long rows, int c, int p, int na, int t, const V *__restrict__ feats,
@@ -122,6 +123,29 @@ extern "C" int eap_so3_intra_group_bwd_f32(int b, int c, int p, int na, int t, c
     if (t <= 0)
         return eap::hip_fail(hipMemsetAsync(gfeats, 0, sizeof(float) * rows * na, eap::S(stream)), "so3_intra_group_bwd memset");
     return group_bwd<float>(rows, c, p, na, t, gout, intra_idx, gfeats, eap::S(stream), "so3_intra_group_bwd");
+}
+
+// the float64 pair (the same kernels at V = double; the launch helpers carry the pointers untyped)
+extern "C" int eap_so3_intra_group_fwd_f64(int b, int c, int p, int na, int t, const double *feats, const int32_t *intra_idx, double *out,
+                                           eap_stream_t stream) {
+    const long long rows = (long long)b * c * p;
+    if (rows <= 0 || t <= 0 || na <= 0) return 0;
+    if (na > 64) return eap::bad_arg("so3_intra_group_fwd_f64: at most 64 anchors");
+    eap::set_kernel("so3_intra_group_fwd_kernel<double>");
+    return group_fwd<double>(rows, c, p, na, t, reinterpret_cast<const float *>(feats), intra_idx, reinterpret_cast<float *>(out), eap::S(stream),
+                             "so3_intra_group_fwd_f64");
+}
+
+extern "C" int eap_so3_intra_group_bwd_f64(int b, int c, int p, int na, int t, const double *gout, const int32_t *intra_idx, double *gfeats,
+                                           eap_stream_t stream) {
+    const long long rows = (long long)b * c * p;
+    if (rows <= 0 || na <= 0) return 0;
+    if (na > 64) return eap::bad_arg("so3_intra_group_bwd_f64: at most 64 anchors");
+    if (t <= 0)
+        return eap::hip_fail(hipMemsetAsync(gfeats, 0, sizeof(double) * rows * na, eap::S(stream)), "so3_intra_group_bwd_f64 memset");
+    eap::set_kernel("so3_intra_group_bwd_kernel<double>");
+    return group_bwd<double>(rows, c, p, na, t, reinterpret_cast<const float *>(gout), intra_idx, reinterpret_cast<float *>(gfeats), eap::S(stream),
+                             "so3_intra_group_bwd_f64");
 }
 
 // intra_so3conv_grouping_2D (so3conv/functional.py:L2606-2627): out[b,c,t,p,a,r] = feats[b,c,p,intra_idx[a,t],r]

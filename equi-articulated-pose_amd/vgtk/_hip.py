@@ -321,16 +321,16 @@ def gemm_reduce(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ld
 # (row pitch, item stride, storage offset), transposed or not.  The numbers of gemm / gemm_reduce / gemm_epilogue are read off the
 # views and checked against each other and against the views' storage before anything is launched.
 
-def operand(t, name='operand'):
-    """A float32 matrix view -> (trans, ld, stride, batch, rows, cols): what a GEMM entry is told about the memory behind it.  rows, cols
+def operand(t, name='operand', dtype=torch.float32):
+    """A float32 (dtype: float64 for the float64 regime) matrix view -> (trans, ld, stride, batch, rows, cols): what a GEMM entry is told about the memory behind it.  rows, cols
     are the view's last two sizes; a 2-D view is one matrix shared by the batch (batch 1, stride 0), a 3-D view has batch = size(0) and
     stride = stride(0).  trans = 0: the columns are contiguous (stride(-1) == 1) and ld = stride(-2) as torch reports it; trans = 1: the rows
     are (stride(-2) == 1, the .transpose(-1, -2) of a row-major matrix) and ld = stride(-1).  A dimension of size 1 can make both readings
     possible: trans = 0 wins.  Raises RuntimeError for another dtype or rank, when neither of the two strides is 1, and when the elements
     addressed -- (batch - 1) * stride + (outer - 1) * ld + inner from the first -- do not fit the view's storage."""
     shape, strides = t.shape, t.stride()
-    if t.dtype != torch.float32 or len(shape) not in (2, 3):
-        raise RuntimeError(f'{name}: a float32 view [rows, cols] or [batch, rows, cols], not {t.dtype} {tuple(shape)}')
+    if t.dtype != dtype or len(shape) not in (2, 3):
+        raise RuntimeError(f'{name}: a {str(dtype)[6:]} view [rows, cols] or [batch, rows, cols], not {t.dtype} {tuple(shape)}')
     rows, cols = shape[-2], shape[-1]
     if strides[-1] == 1:
         trans, ld, outer, inner = 0, strides[-2], rows, cols
@@ -340,19 +340,21 @@ def operand(t, name='operand'):
         raise RuntimeError(f'{name}: neither the rows nor the columns are contiguous (strides {strides})')
     batch, stride = (shape[0], strides[0]) if len(shape) == 3 else (1, 0)
     extent = (batch - 1) * stride + (outer - 1) * ld + inner
-    if 4 * (t.storage_offset() + extent) > t.untyped_storage().nbytes():
+    if t.element_size() * (t.storage_offset() + extent) > t.untyped_storage().nbytes():
         raise RuntimeError(f'{name}: {tuple(shape)} with strides {strides} at offset {t.storage_offset()} addresses {extent} elements, '
-                           f'its storage holds {t.untyped_storage().nbytes() // 4}')
+                           f'its storage holds {t.untyped_storage().nbytes() // t.element_size()}')
     return trans, ld, stride, batch, rows, cols
 
 
 def _product(A, B, out, reduce=False):
     """The numbers of out_z = A_z B_z (reduce: out = sum_z A_z B_z, out 2-D) from the three views, after the checks of `operand` and: the
     inner sizes, the outer sizes and the batch counts agree, out is row-major and its rows and items do not overlap.
+    The three views are float32, or ALL float64 (the float64 regime, csrc/so3_f64.hip): a mixed set is refused, naming the offender.
     -> (transA, transB, M, N, K, lda, strideA, ldb, strideB, ldc, strideC, batch)"""
-    ta, lda, sa, ba, M, K = operand(A, 'A')
-    tb, ldb, sb, batch, Kb, N = operand(B, 'B')
-    tc, ldc, sc, bc, Mc, Nc = operand(out, 'out')
+    dtype = torch.float64 if all(t.dtype == torch.float64 for t in (A, B, out)) else torch.float32
+    ta, lda, sa, ba, M, K = operand(A, 'A', dtype)
+    tb, ldb, sb, batch, Kb, N = operand(B, 'B', dtype)
+    tc, ldc, sc, bc, Mc, Nc = operand(out, 'out', dtype)
     if B.dim() != 3 or out.dim() != 3 - reduce:
         raise RuntimeError(f'B is a stack of matrices, out {"one matrix" if reduce else "a stack"}: got B {tuple(B.shape)}, out {tuple(out.shape)}')
     if K != Kb or (M, N) != (Mc, Nc) or (A.dim() == 3 and ba != batch) or bc != (1 if reduce else batch):
@@ -391,14 +393,25 @@ def _matmul_split_k(M, N, K, A, lda, B, ldb, sb, out, ldc, sc, batch, b_bound):
 def matmul(A, B, out, b_bound=None):
     """out_z = A_z B_z: `gemm` with its numbers taken from the views (b_bound: see gemm)."""
     ta, tb, M, N, K, lda, sa, ldb, sb, ldc, sc, batch = _product(A, B, out)
+    if out.dtype == torch.float64:       # the float64 regime: one kernel for every form (csrc/so3_f64.hip)
+        call('eap_gemm_f64', out, int(ta), int(tb), M, N, K, A, lda, sa, B, ldb, sb, out, ldc, sc, batch,
+             tag={'flops': 2.0 * M * N * K * batch, 'shape': ('gemm_f64', int(ta), int(tb), M, N, K, batch)})
+        return
     if not ta and not tb and (sa == 0 or batch == 1) and _matmul_split_k(M, N, K, A, lda, B, ldb, sb, out, ldc, sc, batch, b_bound):
         return
     gemm(ta, tb, M, N, K, A, lda, sa, B, ldb, sb, out, ldc, sc, batch, b_bound=b_bound)
 
 
-def matmul_reduce(A, B, out):
-    """out [M, N] = sum_z A_z B_z: `gemm_reduce` with its numbers taken from the views."""
+def matmul_reduce(A, B, out, accumulate=False):
+    """out [M, N] = sum_z A_z B_z: `gemm_reduce` with its numbers taken from the views.  float64 views: every item's product from zero,
+    added in item order; accumulate (float64 only): onto what out holds -- the slabs of one batch give the bits of one call."""
     ta, tb, M, N, K, lda, sa, ldb, sb, ldc, _, batch = _product(A, B, out, reduce=True)
+    if out.dtype == torch.float64:
+        call('eap_gemm_f64_reduce', out, int(ta), int(tb), M, N, K, A, lda, sa, B, ldb, sb, out, ldc, batch, int(bool(accumulate)),
+             tag={'flops': 2.0 * M * N * K * batch, 'shape': ('gemm_f64_reduce', int(ta), int(tb), M, N, K, batch)})
+        return
+    if accumulate:
+        raise RuntimeError('matmul_reduce: accumulate is the float64 regime\'s (float32 products reduce through a workspace)')
     gemm_reduce(ta, tb, M, N, K, A, lda, sa, B, ldb, sb, out, ldc, batch)
 
 
@@ -406,7 +419,7 @@ def matmul_reduce_takes_split(A, B, out):
     """Would matmul_reduce(A, B, out) run on the split-bf16 kernel?  Asks what gemm_reduce asks before it takes that kernel: besides the
     kernel's own predicate (all gemm_reduce_takes_split asked), that the product is 'nt' and that out is 16-byte aligned."""
     ta, tb, M, N, K, lda, sa, ldb, sb, ldc, _, _ = _product(A, B, out, reduce=True)
-    return bool(SPLIT_BF16_CONTRACTION and not ta and tb and out.data_ptr() % 16 == 0 and
+    return bool(out.dtype == torch.float32 and SPLIT_BF16_CONTRACTION and not ta and tb and out.data_ptr() % 16 == 0 and
                 abi.eap_gemm_bf16x3_reduce_f32_supported(M, N, K, A, lda, sa, B, ldb, sb, ldc))
 
 
@@ -415,6 +428,8 @@ def matmul_epilogue(A, B, out, scale, shift, slope, residual=None, b_bound=None)
     out's shape (trailing dimensions may be split or merged) whose elements sit at out's pitch and item stride: contiguous where out is, else
     with out's strides.  -> False when the split kernel does not take the operands (nothing launched)."""
     ta, tb, M, N, K, lda, sa, ldb, sb, ldc, sc, batch = _product(A, B, out)
+    if out.dtype != torch.float32:
+        raise RuntimeError('matmul_epilogue: the folded epilogue is float32 only, float64 products have none')
     if ta or (sa != 0 and batch != 1):
         raise RuntimeError(f'A must be one row-major matrix shared by the batch, not {tuple(A.shape)} with strides {tuple(A.stride())}')
     if residual is not None:
@@ -442,6 +457,103 @@ def so3_inter_weights(gx, rk, sigma):
     w = torch.empty(b, p, na, ks, nn, dtype=torch.float32, device=gx.device)
     call('eap_so3_inter_weights_f32', w, b, p, nn, na, ks, sigma, gx, rk, w)
     return w
+
+
+# ---- the float64 regime of the SO(3) conv layers (csrc/so3_f64.hip) -----------------------------------------
+
+def _all_f64(op, **tensors):
+    """every floating tensor of a float64 call is a float64 DEVICE tensor, else RuntimeError naming the offender"""
+    for name, t in tensors.items():
+        if t is not None and t.dtype != torch.float64:
+            raise RuntimeError(f'{op}: {name} is {t.dtype} in a float64 call (every tensor of a call has one width)')
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f'{op}: {name} must be a device tensor (the float64 regime has no CPU path either)')
+
+
+def so3_prep_f64(q_xyz, s_xyz, idx, q_pose, s_pose, anchors, identity_anchor):
+    """-> g float64 [b,p,nn,3], r int32 [b,p,nn], nonident int32 [b] (include/eap_hip.h)"""
+    _all_f64('so3_prep_f64', q_xyz=q_xyz, s_xyz=s_xyz, q_pose=q_pose, s_pose=s_pose, anchors=anchors)
+    check_input(q_xyz, s_xyz, idx, q_pose, s_pose, anchors)
+    b, _, p = q_xyz.shape
+    n = s_xyz.shape[2]
+    nn = idx.shape[2]
+    g = torch.empty(b, p, nn, 3, dtype=torch.float64, device=q_xyz.device)
+    r = torch.empty(b, p, nn, dtype=torch.int32, device=q_xyz.device)
+    nonident = torch.empty(b, dtype=torch.int32, device=q_xyz.device)
+    call('eap_so3_prep_f64', g, b, p, n, nn, anchors.shape[0], q_xyz, s_xyz, idx, q_pose, s_pose, anchors, int(identity_anchor), g, r, nonident)
+    return g, r, nonident
+
+
+def so3_inter_weights_f64(g, rk, sigma):
+    _all_f64('so3_inter_weights_f64', g=g, rk=rk)
+    check_input(g, rk)
+    b, p, nn, _ = g.shape
+    na, ks, _ = rk.shape
+    w = torch.empty(b, p, na, ks, nn, dtype=torch.float64, device=g.device)
+    call('eap_so3_inter_weights_f64', w, b, p, nn, na, ks, _f64_bits(sigma), g, rk, w)
+    return w
+
+
+def so3_inter_group_fwd_f64(feats, idx, g, r, rk, mult, sigma):
+    """-> X float64 [b,c,ks,p,na]"""
+    _all_f64('so3_inter_group_fwd_f64', feats=feats, g=g, rk=rk)
+    check_input(feats, idx, g, r, rk, mult)
+    b, c, n, na = feats.shape
+    p, nn = idx.shape[1], idx.shape[2]
+    ks = rk.shape[1]
+    if rk.shape[0] != na or tuple(g.shape) != (b, p, nn, 3) or tuple(r.shape) != (b, p, nn):
+        raise RuntimeError('so3_inter_group_fwd_f64: feats [b,c,n,na], idx [b,p,nn], g [b,p,nn,3], r [b,p,nn], rk [na,ks,3] do not agree')
+    out = torch.empty(b, c, ks, p, na, dtype=torch.float64, device=feats.device)
+    call('eap_so3_inter_group_fwd_f64', out, b, c, p, n, nn, na, ks, _f64_bits(sigma), feats, idx, g, r, rk, mult, out,
+         tag={'flops': 2.0 * b * c * ks * p * nn * na, 'shape': ('group_fwd_f64', b, c, p, nn, na, ks)})
+    return out
+
+
+def inv_lists_entries(idx, rows, off):
+    """the entry numbers p * nn + n of every referenced row of idx [b,p,nn], ascending, at [off, off + cnt) -> int32 [b, p*nn]"""
+    check_input(idx, rows, off)
+    b, p, nn = idx.shape
+    ent = torch.empty(b, p * nn, dtype=torch.int32, device=idx.device)
+    call('eap_inv_lists_entries', idx, b, p, rows.shape[1], nn, idx, rows, off, ent)
+    return ent
+
+
+def so3_inter_group_bwd_f64(gout, lists, g, r, rk, multinv, sigma, n, nn):
+    """gout [b,c,ks,p,na], lists = (rows, off, cnt, ent) -> gfeats float64 [b,c,n,na]; no float atomics, one order"""
+    _all_f64('so3_inter_group_bwd_f64', gout=gout, g=g, rk=rk)
+    rows, off, cnt, ent = lists
+    check_input(gout, rows, off, cnt, ent, g, r, rk, multinv)
+    b, c, ks, p, na = gout.shape
+    if tuple(rows.shape) != (b, n) or tuple(ent.shape) != (b, p * nn) or tuple(g.shape) != (b, p, nn, 3) or tuple(rk.shape) != (na, ks, 3):
+        raise RuntimeError('so3_inter_group_bwd_f64: gout [b,c,ks,p,na], rows [b,n], ent [b,p*nn], g [b,p,nn,3], rk [na,ks,3] do not agree')
+    gfeats = torch.empty(b, c, n, na, dtype=torch.float64, device=gout.device)
+    call('eap_so3_inter_group_bwd_f64', gfeats, b, c, p, n, nn, na, ks, _f64_bits(sigma), gout, rows, off, cnt, ent, g, r, rk, multinv, gfeats,
+         tag={'flops': 2.0 * b * c * ks * p * nn * na, 'shape': ('group_bwd_f64', b, c, p, nn, na, ks)})
+    return gfeats
+
+
+def so3_intra_group_fwd_f64(feats, intra_idx):
+    _all_f64('so3_intra_group_fwd_f64', feats=feats)
+    check_input(feats, intra_idx)
+    b, c, p, na = feats.shape
+    t = intra_idx.shape[1]
+    if intra_idx.shape[0] != na:
+        raise RuntimeError(f'so3_intra_group_fwd_f64: {na} anchors, an index table of {intra_idx.shape[0]} rows')
+    out = torch.empty(b, c, t, p, na, dtype=torch.float64, device=feats.device)
+    call('eap_so3_intra_group_fwd_f64', out, b, c, p, na, t, feats, intra_idx, out)
+    return out
+
+
+def so3_intra_group_bwd_f64(gout, intra_idx):
+    _all_f64('so3_intra_group_bwd_f64', gout=gout)
+    check_input(gout, intra_idx)
+    b, c, t, p, na = gout.shape
+    if tuple(intra_idx.shape) != (na, t):
+        raise RuntimeError(f'so3_intra_group_bwd_f64: gout {tuple(gout.shape)}, an index table {tuple(intra_idx.shape)}')
+    gfeats = torch.empty(b, c, p, na, dtype=torch.float64, device=gout.device)
+    call('eap_so3_intra_group_bwd_f64', gfeats, b, c, p, na, t, gout, intra_idx, gfeats)
+    return gfeats
 
 
 def so3_anchor_perm(gx, mult):

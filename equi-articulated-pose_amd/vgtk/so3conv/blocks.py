@@ -73,6 +73,8 @@ class BatchNormLeakyReLU(nn.BatchNorm2d):
         scale / shift (no statistics pass): a single read + write of the tensor."""
         if not x.is_cuda:
             raise RuntimeError('BatchNormLeakyReLU: tensor must be a CUDA(HIP) tensor (no CPU fallback)')
+        if x.dtype == torch.float64:
+            raise RuntimeError('BatchNormLeakyReLU: float32 only -- the float64 regime covers the conv layers, not the norms')
         if self.training:
             self.num_batches_tracked.add_(1)
         return _BNAct.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.training,
@@ -141,6 +143,8 @@ class InstanceNormLeakyReLU(nn.Module):
     def forward(self, x):
         if not x.is_cuda:
             raise RuntimeError('InstanceNormLeakyReLU: tensor must be a CUDA(HIP) tensor (no CPU fallback)')
+        if x.dtype == torch.float64:
+            raise RuntimeError('InstanceNormLeakyReLU: float32 only -- the float64 regime covers the conv layers, not the norms')
         b, c = x.shape[0], x.shape[1]
         ones = torch.ones(b * c, dtype=torch.float32, device=x.device)
         y = _BNAct.apply(x.contiguous().view(1, b * c, *x.shape[2:]), ones, torch.zeros_like(ones), None, None, True,

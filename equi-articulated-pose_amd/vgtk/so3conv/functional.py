@@ -11,7 +11,8 @@ Differences a caller can observe (all documented in DESIGN.md):
     reference always builds (12 GB at B=8, P=4096).  Callers in SPConvNets only hand it back to
     the next conv, which ignores it for stride 1 (functional.py:L1025ff recomputes everything).
   * gradients flow to `feats` and `W` (what the reference trains); xyz / pose are treated as data.
-  * float32 device tensors only -- there is no CPU path.
+  * device tensors only -- there is no CPU path.  float32 everywhere; float64 (every tensor of the call) for the plain inter and
+    intra convs, the contraction and the grouping API: "the float64 regime" below, its own kernels (csrc/so3_f64.hip).
 """
 import math
 import os
@@ -154,6 +155,20 @@ def get_occupancy_features(pc, n_anchor, use_center=False):
     return features
 
 
+def _call_dtype(op, **tensors):
+    """float32 or float64: the ONE width of a call's floating tensors (None entries are skipped).  RuntimeError naming the first tensor
+    that is neither, or that differs from the first one given."""
+    items = [(name, t) for name, t in tensors.items() if t is not None]
+    first_name, first = items[0]
+    if first.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f'{op}: {first_name} is {first.dtype}: float32 tensors, or float64 ones throughout')
+    for name, t in items[1:]:
+        if t.dtype != first.dtype:
+            raise RuntimeError(f'{op}: {name} is {t.dtype} but {first_name} is {first.dtype}: every tensor of a call has one width '
+                               f'(float32, or float64 throughout)')
+    return first.dtype
+
+
 # ------------------------------------------------------------------------------------------------
 # per-(anchor set, kernel set, device) tables
 # ------------------------------------------------------------------------------------------------
@@ -291,8 +306,9 @@ def rotated_kernels(anchors, kernels):
 class InterWeights:
     """Lazy stand-in for the reference's inter_w [b,p,na,ks,nn] (functional.py:L2508-2549)."""
 
-    def __init__(self, gx, rk, sigma):
-        self.gx, self.rk, self.sigma = gx, rk, float(sigma)
+    def __init__(self, gx, rk, sigma, r=None):
+        # (float64 regime: gx is g float64 [b,p,nn,3] and r int32 [b,p,nn] the nearest-anchor index beside it)
+        self.gx, self.rk, self.sigma, self.r = gx, rk, float(sigma), r
 
     @property
     def shape(self):
@@ -303,6 +319,8 @@ class InterWeights:
         return self.shape if dim is None else self.shape[dim]
 
     def materialize(self):
+        if self.gx.dtype == torch.float64:
+            return _hip.so3_inter_weights_f64(self.gx, self.rk, self.sigma)
         return _hip.so3_inter_weights(self.gx, self.rk, self.sigma)
 
 
@@ -320,6 +338,8 @@ def inter_so3conv_grouping_anchor(grouped_xyz, anchors, kernels, sigma, interpol
     if interpolate != 'linear':
         raise NotImplementedError('kernel function %s is not implemented!' % interpolate)
     _hip.check_input(grouped_xyz)
+    if _call_dtype('inter_so3conv_grouping_anchor', grouped_xyz=grouped_xyz, anchors=anchors, kernels=kernels) == torch.float64:
+        return _hip.so3_inter_weights_f64(grouped_xyz.permute(0, 2, 3, 1).contiguous(), rotated_kernels(anchors, kernels), float(sigma))
     return _hip.so3_inter_weights(_as_gx(grouped_xyz), rotated_kernels(anchors, kernels), float(sigma))
 
 
@@ -1613,15 +1633,18 @@ class _IntraConv(torch.autograd.Function):
 
 def intra_so3conv(feats, W, intra_idx):
     """feats [b,c,p,na], W [o, c*T], intra_idx [na,T] -> [b,o,p,na]; what IntraSO3Conv.forward runs."""
-    if feats.dtype != torch.float32 or not feats.is_cuda:
-        raise RuntimeError('intra_so3conv: float32 device tensors only')
+    dtype = _call_dtype('intra_so3conv', feats=feats, W=W)
+    if not feats.is_cuda:
+        raise RuntimeError('intra_so3conv: device tensors only')
+    if dtype == torch.float64:
+        return _IntraConvF64.apply(feats, W, intra_idx.to(torch.int32).contiguous())
     return _IntraConv.apply(feats, W, intra_idx.to(torch.int32).contiguous())
 
 
 def intra_so3conv2d(feats, W, intra_idx):
     """feats [b,c,p,na*4], W [o, c*T], intra_idx [na,T] -> [b,o,p,na*4], the residual innermost; what IntraSO3Conv2D.forward runs."""
     if feats.dtype != torch.float32 or not feats.is_cuda:
-        raise RuntimeError('intra_so3conv2d: float32 device tensors only')
+        raise RuntimeError('intra_so3conv2d: float32 device tensors only (the float64 regime does not cover the 2-D variant)')
     if feats.shape[3] != 4 * intra_idx.shape[0]:
         raise RuntimeError(f'intra_so3conv2d: an anchor axis of {feats.shape[3]} entries is not {intra_idx.shape[0]} anchors x 4 residuals')
     return _IntraConv.apply(feats, W, intra_idx.to(torch.int32).contiguous())
@@ -1669,14 +1692,242 @@ class _NarrowContract(torch.autograd.Function):
 
 def so3_contract(W, x, epilogue=None):
     """W [O, C*K], x [b, C*K, P*A] -> [b, O, P*A] (epilogue: a FoldedEpilogue the product may apply, inference only)."""
+    dtype = _call_dtype('so3_contract', x=x, W=W)
+    if dtype == torch.float64 and epilogue is not None:
+        raise RuntimeError('so3_contract: a folded epilogue is float32 only, a float64 contraction takes none')
     _hip.check_input(x)
-    if x.dtype != torch.float32 or W.dtype != torch.float32:
-        raise RuntimeError('so3_contract: float32 only')
     if not W.is_cuda:
         raise RuntimeError('so3_contract: W must be a device tensor')
+    if dtype == torch.float64:
+        return _ContractF64.apply(W, x)
     if epilogue is None and W.shape[0] <= 4 and _hip.abi.eap_narrow_contract_supported(x.shape[0], W.shape[0], x.shape[1], x.shape[2]):
         return _NarrowContract.apply(W, x)
     return _Contract.apply(W, x, epilogue)
+
+
+# ------------------------------------------------------------------------------------------------
+# the float64 regime (csrc/so3_f64.hip): chosen by the dtype of the tensors, one plain kernel per step
+# ------------------------------------------------------------------------------------------------
+# The reference's Python path is dtype-generic; a model after .double() runs L1025-1261 in float64 with ONE quirk this regime keeps: the
+# neighbour coordinates pass through float32 (group_nd -> gather_points_forward returns float32 for any input, gathering_cuda.cpp:L38-39),
+# so g = R_rel (float(x_n) - x_p), the subtraction and everything after it in float64.  For inputs that are float32 numbers widened (a
+# float64 run as the checker of a float32 one) that is a no-op.
+# The grouped intermediate X [b,c,ks,p,na] is 8 b c ks p na bytes (6 GB per cloud at c = 128, p = 4096): clouds are processed in slabs
+# that keep it under F64_X_BYTES_MAX (at least one cloud), X is recomputed in the backward, never saved.  Every cloud's output and feature
+# gradient depend on that cloud alone, and dW adds every cloud's product in index order (eap_gemm_f64_reduce): the results do not
+# depend on the slab size, bit for bit.
+F64_X_BYTES_MAX = 4 << 30
+
+
+def _f64_slabs(b, bytes_per_cloud):
+    """[(b0, b1), ...]: the clouds in slabs whose intermediate stays under F64_X_BYTES_MAX (one cloud where a single one exceeds it)"""
+    step = max(1, int(F64_X_BYTES_MAX // max(int(bytes_per_cloud), 1)))
+    return [(b0, min(b, b0 + step)) for b0 in range(0, b, step)]
+
+
+class _F64Args:
+    """The inputs of the float64 inter nodes that carry no gradient: idx int32 [b,p,nn], g float64 [b,p,nn,3], r int32 [b,p,nn], rk
+    float64 [na,ks,3], mult uint8 [na,na] and its row-wise inverse (None: no anchor permutation), sigma."""
+
+    def __init__(self, idx, g, r, rk, mult, multinv, sigma):
+        self.idx, self.g, self.r, self.rk, self.mult, self.multinv, self.sigma = idx, g, r, rk, mult, multinv, float(sigma)
+        self.lists = None
+
+    def inverse_lists(self, n):
+        """(rows, off, cnt, ent) of the whole batch (csrc/inv_lists.hip, index only; csrc/so3_f64.hip the entries), built once"""
+        if self.lists is None:
+            if n > INV_LISTS_MAX_ROWS:
+                raise NotImplementedError(f'float64 backward of the inter conv: at most {INV_LISTS_MAX_ROWS} support points per cloud '
+                                          f'(the inverse neighbour lists are sorted in LDS), got {n}')
+            rows, off, cnt, _ = _hip.inv_lists_rows(self.idx, n)
+            self.lists = (rows, off, cnt, _hip.inv_lists_entries(self.idx, rows, off))
+        return self.lists
+
+    def group(self, feats, b0, b1):
+        return _hip.so3_inter_group_fwd_f64(feats[b0:b1], self.idx[b0:b1], self.g[b0:b1], self.r[b0:b1], self.rk, self.mult, self.sigma)
+
+    def group_transposed(self, gx, n, b0, b1):
+        lists = tuple(t[b0:b1] for t in self.inverse_lists(n))
+        return _hip.so3_inter_group_bwd_f64(gx, lists, self.g[b0:b1], self.r[b0:b1], self.rk, self.multinv, self.sigma, n, self.idx.shape[2])
+
+
+def _neighbourhood_f64(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose):
+    """_neighbourhood in float64: the existing float64 ball query (float radius, as the reference's signature), the tables in the module's
+    dtype, eap_so3_prep_f64 -> _F64Args.  An anchor set that is not a group (kanchor 20 / 40) is taken where the float32 path continues
+    without permutation (no pose, identity poses, one rotation per cloud); really permuted it has no float64 kernel."""
+    q_xyz = xyz if q_xyz is None else q_xyz
+    _call_dtype('so3conv', xyz=xyz, q_xyz=q_xyz, anchors=anchors, kernels=kernels, pose=pose, q_pose=q_pose)
+    if not (anchors.is_cuda and kernels.is_cuda):
+        raise RuntimeError('so3conv: anchors and kernels must be device tensors')
+    ball_idx = cuda_nn.ball_query(q_xyz.contiguous(), xyz.contiguous(), radius, n_neighbor)
+    rk = rotated_kernels(anchors, kernels)
+    mult = multinv = rot = q_rot = None
+    ident = 0
+    if pose is not None:
+        rot = pose.contiguous()
+        q_rot = rot if q_pose is None else q_pose.contiguous()
+        if rot.shape[-2:] != (4, 4) or not rot.is_cuda:
+            raise RuntimeError('so3conv: pose must be a float64 device tensor [b,p,4,4] in a float64 call')
+        if permute:
+            mult, ident = _group_tables(anchors)
+            if mult is None:
+                if _anchor_map(ball_idx, q_rot.float(), rot.float(), anchors.float()) is not None:
+                    raise NotImplementedError('anchor permutation with per-point poses over an anchor set that is not a group (kanchor 20 / 40) '
+                                              'has no float64 kernel: float32, or poses that leave the anchors in place')
+                ident = 0
+            else:
+                multinv = _group_tables_inverse(mult)
+    g, r, _ = _hip.so3_prep_f64(q_xyz.contiguous(), xyz.contiguous(), ball_idx, q_rot, rot, anchors.contiguous(), ident)
+    return _F64Args(ball_idx, g, r, rk, mult, multinv, sigma)
+
+
+def _log_f64(forward, c, o, n):
+    """the FORWARD_LOG / BACKWARD_LOG entry of a float64 inter conv"""
+    if forward and FORWARD_LOG is not None:
+        FORWARD_LOG.append({'channels': (c, o), 'dense': False, 'parts': None, 'regime': 'float64'})
+    if not forward and BACKWARD_LOG is not None:
+        BACKWARD_LOG.append({'channels': (c, o), 'support_rows': n, 'referenced_rows_max': 0, 'regime': 'float64'})
+
+
+class _InterGroupF64(torch.autograd.Function):
+    """_InterGroup in float64: new_feats[b,c,k,p,a] = sum_n feats[b,c,idx_n,perm_n(a)] w(p,a,k,n) and its transpose without atomics."""
+
+    @staticmethod
+    def forward(ctx, feats, args):
+        feats = feats.contiguous()
+        ctx.conv_args, ctx.n = args, feats.shape[2]
+        return args.group(feats, 0, feats.shape[0])
+
+    @staticmethod
+    def backward(ctx, gout):
+        return ctx.conv_args.group_transposed(gout.contiguous(), ctx.n, 0, gout.shape[0]), None
+
+
+class _InterConvF64(torch.autograd.Function):
+    """The inter conv in float64, one node: grouping -> Y = W X; backward dX = W^T gY -> the grouping's transpose, dW = sum_z gY_z X_z^T
+    with X regrouped (never saved), a slab of clouds at a time (F64_X_BYTES_MAX)."""
+
+    @staticmethod
+    def forward(ctx, feats, W_param, args):
+        feats, W = feats.contiguous(), W_param.contiguous()
+        b, c, n, na = feats.shape
+        p, ks, o = args.idx.shape[1], args.rk.shape[1], W.shape[0]
+        if W.shape[1] != c * ks:
+            raise RuntimeError(f'so3conv: W {tuple(W.shape)} for {c} channels x {ks} kernel points')
+        _log_f64(True, c, o, n)
+        y = torch.empty(b, o, p, na, dtype=torch.float64, device=feats.device)
+        for b0, b1 in _f64_slabs(b, 8 * c * ks * p * na):
+            x = args.group(feats, b0, b1)
+            _hip.matmul(W, x.view(b1 - b0, c * ks, p * na), y[b0:b1].view(b1 - b0, o, p * na))
+            del x
+        ctx.conv_args = args
+        ctx.save_for_backward(feats, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        feats, W = ctx.saved_tensors
+        args = ctx.conv_args
+        gy = gy.contiguous()
+        b, c, n, na = feats.shape
+        p, ks, o = args.idx.shape[1], args.rk.shape[1], W.shape[0]
+        need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        _log_f64(False, c, o, n)
+        gF = torch.empty_like(feats) if need_f else None
+        gW = torch.empty_like(W) if need_w else None
+        for b0, b1 in _f64_slabs(b, 8 * c * ks * p * na):
+            gys = gy[b0:b1].view(b1 - b0, o, p * na)
+            if need_f:
+                gx = torch.empty(b1 - b0, c * ks, p * na, dtype=torch.float64, device=gy.device)
+                _hip.matmul(W.t(), gys, gx)
+                gF[b0:b1] = args.group_transposed(gx.view(b1 - b0, c, ks, p, na), n, b0, b1)
+                del gx
+            if need_w:
+                x = args.group(feats, b0, b1)
+                _hip.matmul_reduce(gys, x.view(b1 - b0, c * ks, p * na).transpose(1, 2), gW, accumulate=b0 > 0)
+                del x
+        return gF, gW, None
+
+
+class _IntraGroupF64(torch.autograd.Function):
+    """_IntraGroup in float64 (csrc/so3_intra.hip at 8 bytes per element)."""
+
+    @staticmethod
+    def forward(ctx, feats, intra_idx32):
+        ctx.save_for_backward(intra_idx32)
+        return _hip.so3_intra_group_fwd_f64(feats.contiguous(), intra_idx32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        intra_idx32, = ctx.saved_tensors
+        return _hip.so3_intra_group_bwd_f64(gout.contiguous(), intra_idx32), None
+
+
+class _IntraConvF64(torch.autograd.Function):
+    """The intra conv in float64, one node: the 12-tap gather G -> Y = W G; backward dG = W^T gY -> the gather's transpose, dW = sum_z gY_z
+    G_z^T with G regathered, a slab of clouds at a time (F64_X_BYTES_MAX)."""
+
+    @staticmethod
+    def forward(ctx, feats, W, idx32):
+        feats, W = feats.contiguous(), W.contiguous()
+        b, c, p, na = feats.shape
+        o, t = W.shape[0], idx32.shape[1]
+        if W.shape[1] != c * t:
+            raise RuntimeError(f'intra_so3conv: W {tuple(W.shape)} for {c} channels x {t} taps')
+        y = torch.empty(b, o, p, na, dtype=torch.float64, device=feats.device)
+        for b0, b1 in _f64_slabs(b, 8 * c * t * p * na):
+            g = _hip.so3_intra_group_fwd_f64(feats[b0:b1], idx32)
+            _hip.matmul(W, g.view(b1 - b0, c * t, p * na), y[b0:b1].view(b1 - b0, o, p * na))
+            del g
+        ctx.save_for_backward(feats, W, idx32)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        feats, W, idx32 = ctx.saved_tensors
+        gy = gy.contiguous()
+        b, c, p, na = feats.shape
+        o, t = W.shape[0], idx32.shape[1]
+        need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gF = torch.empty_like(feats) if need_f else None
+        gW = torch.empty_like(W) if need_w else None
+        for b0, b1 in _f64_slabs(b, 8 * c * t * p * na):
+            gys = gy[b0:b1].view(b1 - b0, o, p * na)
+            if need_f:
+                gg = torch.empty(b1 - b0, c * t, p * na, dtype=torch.float64, device=gy.device)
+                _hip.matmul(W.t(), gys, gg)
+                gF[b0:b1] = _hip.so3_intra_group_bwd_f64(gg.view(b1 - b0, c, t, p, na), idx32)
+                del gg
+            if need_w:
+                g = _hip.so3_intra_group_fwd_f64(feats[b0:b1], idx32)
+                _hip.matmul_reduce(gys, g.view(b1 - b0, c * t, p * na).transpose(1, 2), gW, accumulate=b0 > 0)
+                del g
+        return gF, gW, None
+
+
+class _ContractF64(torch.autograd.Function):
+    """_Contract in float64: y[b,o,pa] = W[o,ck] x[b,ck,pa] on v_mfma_f64_16x16x4_f64 (BasicSO3Conv, modules.py:L48-55)."""
+
+    @staticmethod
+    def forward(ctx, W, x):
+        W, x = W.contiguous(), x.contiguous()
+        y = torch.empty(x.shape[0], W.shape[0], x.shape[2], dtype=torch.float64, device=x.device)
+        _hip.matmul(W, x, y)
+        ctx.save_for_backward(W, x)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        W, x = ctx.saved_tensors
+        gy = gy.contiguous()
+        gW = gx = None
+        if ctx.needs_input_grad[1]:
+            gx = torch.empty_like(x)
+            _hip.matmul(W.t(), gy, gx)
+        if ctx.needs_input_grad[0]:
+            gW = torch.empty_like(W)
+            _hip.matmul_reduce(gy, x.transpose(1, 2), gW)
+        return gW, gx
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1688,16 +1939,21 @@ def _strided_centres(xyz, pose, stride, lazy_sample):
     -> sample_idx int32 [b,p2], sample_xyz [b,3,p2], sampled_pose [b,p2,4,4] or None."""
     n_sample = math.ceil(xyz.shape[2] / stride)
     sample_idx, sample_xyz = pctk.furthest_sample(xyz, n_sample, lazy_sample)
+    # (group_nd returns float32 for any input, as the reference's: a float64 cloud gets its centres back in float64 -- float32 numbers widened)
+    sample_xyz = sample_xyz.to(xyz.dtype)
     sampled_pose = None if pose is None else batched_index_select(pose, 1, sample_idx.long()).contiguous()
     return sample_idx, sample_xyz.contiguous(), sampled_pose
 
 
-def _check_inputs(xyz, feats, W=None, on_device=True):
-    if feats.dtype != torch.float32 or xyz.dtype != torch.float32 or (W is not None and W.dtype != torch.float32):
-        raise RuntimeError('so3conv: float32 only')
+def _check_inputs(xyz, feats, W=None, on_device=True, float32_only=None):
+    """-> the call's dtype (_call_dtype).  float32_only: the name of a variant the float64 regime does not cover -- float64 is refused"""
+    dtype = _call_dtype('so3conv', feats=feats, xyz=xyz, W=W)
+    if dtype == torch.float64 and float32_only is not None:
+        raise RuntimeError(f'{float32_only}: float32 only -- the float64 regime covers the plain inter and intra convs, not this variant')
     _hip.check_input(xyz)
     if on_device and not (feats.is_cuda and (W is None or W.is_cuda)):
         raise RuntimeError('so3conv: feats must be a device tensor' if W is None else 'so3conv: feats and W must be device tensors')
+    return dtype
 
 
 def _anchor_map(idx, q_rot, rot, anchors):
@@ -1743,7 +1999,11 @@ def _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permu
 
 
 def _inter_group(xyz, pose, feats, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz=None, q_pose=None):
-    _check_inputs(xyz, feats)
+    if _check_inputs(xyz, feats) == torch.float64:
+        a = _neighbourhood_f64(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose)
+        new_feats = _InterGroupF64.apply(feats, a)
+        inter_w = InterWeights(a.g, a.rk, sigma, a.r)
+        return a.idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), new_feats
     a = _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose)
     new_feats = _InterGroup.apply(feats, a.idx, a.gx, a.rk, a.mult, a.sigma, a.ident, a.nonident, a.amap)
     inter_w = InterWeights(a.gx, a.rk, sigma)
@@ -1755,7 +2015,13 @@ def inter_so3conv_fused(xyz, pose, feats, W, n_neighbor, anchors, kernels, radiu
     """ball query + prep + fused (grouping . contraction) -> (ball_idx, InterWeights, y [b,o,p,a]).
     What InterSO3PoseConv / InterSO3Conv.forward run; q_xyz / q_pose = the sampled centres of a strided conv
     (default: every point is a centre).  epilogue: a FoldedEpilogue the contraction may apply (inference only)."""
-    _check_inputs(xyz, feats, W)
+    if _check_inputs(xyz, feats, W) == torch.float64:
+        if epilogue is not None:
+            raise RuntimeError('so3conv: conv_norm_act epilogues (FoldedEpilogue, TrainEpilogue) are float32 only, a float64 conv takes none')
+        a = _neighbourhood_f64(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose)
+        y = _InterConvF64.apply(feats, W, a)
+        inter_w = InterWeights(a.g, a.rk, sigma, a.r)
+        return a.idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), y
     a = _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose, epilogue)
     bn_w = bn_b = None
     if isinstance(epilogue, TrainEpilogue):
@@ -1776,7 +2042,7 @@ def inter_so3conv_fused_art_mode(xyz, pose, feats, W, seg_labels, n_neighbor, an
         raise RuntimeError('use_art_mode: xyz must be [b, n_states, 3, p]')
     if seg_labels is None:
         raise RuntimeError('use_art_mode: the per-point state labels `seg` are required')
-    _check_inputs(xyz, feats, W, on_device=False)
+    _check_inputs(xyz, feats, W, on_device=False, float32_only='use_art_mode')
     b, ns, _, p = xyz.shape
     flat = xyz.reshape(b * ns, 3, p).contiguous()
     idx_all = cuda_nn.ball_query(flat, flat, radius, n_neighbor)                                     # [b*ns, p, nn]
@@ -1856,7 +2122,7 @@ def _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, p
     asserts that the materialised weights were asked for).  FORCE_GENERAL_2D selects that tensor form at any size, a slab of
     SLOW_2D_CHUNK query points at a time: the comparator the tests hold the kernels against, with residual_rotation_index as the tensor
     statement of the index."""
-    _check_inputs(xyz, feats)
+    _check_inputs(xyz, feats, float32_only='use_2d')
     b, c, p, na4 = feats.shape
     na = anchors.shape[0]
     if na4 != 4 * na:
@@ -1924,7 +2190,7 @@ def _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, p
 def inter_so3conv_fused_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, permute):
     """What InterSO3PoseConv(use_2d=True).forward runs for stride 1 -> (InterWeights, y [b,o,p,na*4])."""
     if W.dtype != torch.float32 or not W.is_cuda:
-        raise RuntimeError('so3conv: W must be a float32 device tensor')
+        raise RuntimeError('use_2d: W must be a float32 device tensor (float32 only: the float64 regime does not cover this variant)')
     _, w, y = _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, permute, contract=True)
     return (w.materialize() if MATERIALIZE_INTER_W else w), y
 
@@ -1968,7 +2234,9 @@ def inter_so3conv_grouping(xyz, feats, stride, n_neighbor, anchors, kernels, rad
                                                      radius * radius_expansion, sigma, False, q_xyz=new_xyz)
         return inter_idx, inter_w, new_xyz, new_feats, sample_idx
     # cached neighbourhood from an earlier layer (functional.py:L195-201)
-    if isinstance(inter_w, InterWeights):
+    if isinstance(inter_w, InterWeights) and _call_dtype('inter_so3conv_grouping', feats=feats, inter_w=inter_w.gx) == torch.float64:
+        new_feats = _InterGroupF64.apply(feats, _F64Args(inter_idx, inter_w.gx, inter_w.r, inter_w.rk, None, None, inter_w.sigma))
+    elif isinstance(inter_w, InterWeights):
         new_feats = _InterGroup.apply(feats, inter_idx, inter_w.gx, inter_w.rk, None, inter_w.sigma, 0, None)
     else:
         new_feats = inter_so3conv_feat_grouping(inter_idx, inter_w, zpconv.add_shadow_feature(feats))
@@ -1998,8 +2266,10 @@ def inter_so3poseconv_grouping_strided(xyz, pose, feats, stride, n_neighbor, anc
 
 def intra_so3conv_grouping(intra_idx, feature):
     """intra_idx [na,pnn], feature [nb,c,np,na] -> [nb,c,pnn,np,na] (functional.py:L2553-2602)."""
-    if feature.dtype != torch.float32 or not feature.is_cuda:
-        raise RuntimeError('intra_so3conv_grouping: float32 device tensors only')
+    if not feature.is_cuda:
+        raise RuntimeError('intra_so3conv_grouping: device tensors only')
+    if _call_dtype('intra_so3conv_grouping', feature=feature) == torch.float64:
+        return _IntraGroupF64.apply(feature, intra_idx.to(torch.int32).contiguous())
     return _IntraGroup.apply(feature, intra_idx.to(torch.int32).contiguous())
 
 

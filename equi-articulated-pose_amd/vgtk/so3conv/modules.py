@@ -163,7 +163,10 @@ class IntraSO3Conv(nn.Module):
 
     def forward(self, x):
         feats = x.feats
-        if feats.is_cuda and feats.dtype == torch.float32 and feats.shape[3] % 4 == 0 and feats.shape[3] <= 64:
+        if feats.is_cuda and feats.dtype == torch.float64:
+            # the float64 regime: gather + contraction as one node, a slab of clouds at a time (L._IntraConvF64)
+            out = L.intra_so3conv(feats, self.basic_conv.W, self.intra_idx)
+        elif feats.is_cuda and feats.dtype == torch.float32 and feats.shape[3] % 4 == 0 and feats.shape[3] <= 64:
             # implicit GEMM in both directions: the 12-tap gather is folded into the contraction's operand load, the
             # [B,C,12,P,A] tensor of the reference (48 GB at C = 512) is never written (L._IntraConv)
             out = L.intra_so3conv(feats, self.basic_conv.W, self.intra_idx)
@@ -178,6 +181,8 @@ class IntraSO3Conv2D(IntraSO3Conv):
 
     def forward(self, x):
         feats = x.feats
+        if feats.dtype == torch.float64 or self.basic_conv.W.dtype == torch.float64:
+            raise RuntimeError('IntraSO3Conv2D: float32 only -- the float64 regime covers IntraSO3Conv (60 anchors), not the 2-D variant')
         if feats.is_cuda and feats.dtype == torch.float32 and feats.shape[3] == 4 * self.intra_idx.shape[0]:
             # implicit GEMM in both directions, an anchor's four residuals gathered as one 16-byte quad: the [B,C,12,P,240] tensor
             # (193 GB at C = 512, B = 8, P = 4096) is never written (L._IntraConv on the quad kernels)

@@ -1069,6 +1069,58 @@ int eap_pointnet_max_bwd_data_f32(int b, int c, int o, int n, int na, const floa
 int eap_pointnet_max_bwd_weight_f32(int b, int c, int o, int n, int na, const float *g, const int32_t *arg, const float *feats, const float *xyz,
                                     const float *centre, const float *anchors, float *dwp, eap_stream_t stream);
 
+/* ---- the SO(3) conv layers in float64 (csrc/so3_f64.hip, csrc/so3_intra.hip) ------------------------------------------------ */
+/* The reference's Python path is dtype-generic: InterSO3PoseConv(...).double() runs so3conv/functional.py:L1025-1261 in float64.  These
+ * entries are that regime, chosen by the dtype of the tensors (vgtk.so3conv.functional, _InterConvF64 / _IntraConvF64 / _ContractF64).
+ * float64 scalars (sigma) travel as their bit patterns (`*_bits`).  Every entry checks its sizes against the launch limits BEFORE it
+ * touches a pointer (at most 64 anchors, 32 kernel points, 65535 clouds, p * nn < 2^31: hipErrorInvalidValue, the reason in
+ * eap_last_error()); b <= 0 returns 0 without a launch.
+ *
+ * so3_prep_f64: so3conv/functional.py:L1061-1078 and the nearest-anchor half of L1199-1204, twin of eap_so3_prep_f32.
+ * q_xyz [b,3,p], s_xyz [b,3,n], idx int32 [b,p,nn], poses [b,.,4,4] or both NULL, anchors [na,3,3]
+ *  -> g double [b,p,nn,3] = R_rel (float(x_n) - x_p): the neighbour's coordinates pass through float32 as the reference's group_nd
+ *     returns them (gathering_cuda.cpp:L38-39), the subtraction and everything after it in float64; the shadow point sits at 1e4;
+ *     r int32 [b,p,nn] = argmax_g tr(R_rel A_g), first maximum (identity_anchor without poses); nonident int32 [b] (optional). */
+int eap_so3_prep_f64(int b, int p, int n, int nn, int na, const double *q_xyz, const double *s_xyz, const int32_t *idx,
+                     const double *q_pose, const double *s_pose, const double *anchors, int identity_anchor, double *g, int32_t *r,
+                     int32_t *nonident, eap_stream_t stream);
+/* so3_inter_weights_f64: inter_so3conv_grouping_anchor, so3conv/functional.py:L2508-2549, twin of eap_so3_inter_weights_f32.
+ * g [b,p,nn,3], rk [na,ks,3] -> w [b,p,na,ks,nn] = relu(1 - |g - rk|^2 / sigma) in the operation order of the torch expression. */
+int eap_so3_inter_weights_f64(int b, int p, int nn, int na, int ks, int64_t sigma_bits, const double *g, const double *rk, double *w,
+                              eap_stream_t stream);
+/* so3_inter_group_fwd_f64: so3conv/functional.py:L1221-1261, twin of eap_so3_inter_group_fwd_f32.
+ * feats [b,c,n,na], mult uint8 [na,na] or NULL -> out [b,c,ks,p,na] = sum_n feats[b,c,idx_n,mult[r_n][a]] w(p,a,k,n); the weights are
+ * evaluated in registers; an index outside [0, n) (the shadow row) contributes nothing. */
+int eap_so3_inter_group_fwd_f64(int b, int c, int p, int n, int nn, int na, int ks, int64_t sigma_bits, const double *feats,
+                                const int32_t *idx, const double *g, const int32_t *r, const double *rk, const uint8_t *mult, double *out,
+                                eap_stream_t stream);
+/* inv_lists_entries: the second half of the inverse neighbour lists of eap_inv_lists_rows, index only: for every referenced row slot
+ * the entry numbers p * nn + n that name it, ascending, at ent[b, off .. off + cnt) -- ent int32 [b, p*nn].  Any p * nn; n <= 16384. */
+int eap_inv_lists_entries(int b, int p, int n, int nn, const int32_t *idx, const int32_t *rows, const int32_t *off, int32_t *ent,
+                          eap_stream_t stream);
+/* so3_inter_group_bwd_f64: the autograd of so3conv/functional.py:L1221-1261 w.r.t. feats, twin of eap_so3_inter_group_bwd_f32.
+ * gout [b,c,ks,p,na]; rows, off, cnt int32 [b,n] (eap_inv_lists_rows), ent (eap_inv_lists_entries); multinv uint8 [na,na] = the
+ * row-wise inverse of mult, or NULL -> gfeats [b,c,n,na] (fully written).  One workgroup per referenced row and 16 channels sums the
+ * row's entries in entry order, each entry over k in index order: no floating-point atomics, bit-identical run to run. */
+int eap_so3_inter_group_bwd_f64(int b, int c, int p, int n, int nn, int na, int ks, int64_t sigma_bits, const double *gout,
+                                const int32_t *rows, const int32_t *off, const int32_t *cnt, const int32_t *ent, const double *g,
+                                const int32_t *r, const double *rk, const uint8_t *multinv, double *gfeats, eap_stream_t stream);
+/* so3_intra_group_{fwd,bwd}_f64: intra_so3conv_grouping, so3conv/functional.py:L2553-2602, and its transpose -- twins of
+ * eap_so3_intra_group_fwd_f32 / eap_so3_intra_group_bwd_f32 (the same kernels at 8 bytes per element). */
+int eap_so3_intra_group_fwd_f64(int b, int c, int p, int na, int t, const double *feats, const int32_t *intra_idx, double *out,
+                                eap_stream_t stream);
+int eap_so3_intra_group_bwd_f64(int b, int c, int p, int na, int t, const double *gout, const int32_t *intra_idx, double *gfeats,
+                                eap_stream_t stream);
+/* BasicSO3Conv.forward (so3conv/modules.py:L48-55) and its autograd in float64 on v_mfma_f64_16x16x4_f64: conventions and operand
+ * contract of eap_gemm_f32 (leading dimensions, batch strides, any 8-byte aligned base; rows, columns and k past an operand are
+ * selected as zero, nothing outside [M, N] of C is written).  eap_gemm_f64_reduce: C[M,N] = (C if accumulate else 0) + P_0 + P_1 + ...
+ * with P_z = op(A_z) op(B_z) accumulated from zero and added in item order -- a batch cut into slabs (accumulate = 1 from the second
+ * on) gives the bits of one call; no workspace. */
+int eap_gemm_f64(int transA, int transB, int M, int N, int K, const double *A, int64_t lda, int64_t strideA, const double *B,
+                 int64_t ldb, int64_t strideB, double *C, int64_t ldc, int64_t strideC, int batch, eap_stream_t stream);
+int eap_gemm_f64_reduce(int transA, int transB, int M, int N, int K, const double *A, int64_t lda, int64_t strideA, const double *B,
+                        int64_t ldb, int64_t strideB, double *C, int64_t ldc, int batch, int accumulate, eap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
