@@ -324,6 +324,11 @@ class InterWeights:
         return _hip.so3_inter_weights(self.gx, self.rk, self.sigma)
 
 
+def _inter_w(handle):
+    """what a conv returns as inter_w: the lazy handle, or the tensor where MATERIALIZE_INTER_W asks for it"""
+    return handle.materialize() if MATERIALIZE_INTER_W else handle
+
+
 def _as_gx(grouped_xyz):
     """[b,3,p,nn] -> float4 [b,p,nn,4] with r = 0."""
     b, _, p, nn = grouped_xyz.shape
@@ -346,64 +351,21 @@ def inter_so3conv_grouping_anchor(grouped_xyz, anchors, kernels, sigma, interpol
 # ------------------------------------------------------------------------------------------------
 # autograd ops
 # ------------------------------------------------------------------------------------------------
-class _InterGroup(torch.autograd.Function):
-    """new_feats[b,c,k,p,a] = sum_n feats[b,c,idx_n,perm_n(a)] w(p,a,k,n)  (functional.py:L1221-1261)."""
+class _Group(torch.autograd.Function):
+    """X = grouping.group(feats) as a node of its own (the functional grouping API); grouping: one of the pairs below (_ListGrouping,
+    _MapGrouping, _IntraGrouping, _F64Args).  The backward is the pair's transpose.
+    inter: new_feats[b,c,k,p,a] = sum_n feats[b,c,idx_n,perm_n(a)] w(p,a,k,n)  (functional.py:L1221-1261);
+    intra: out[b,c,t,p,a] = feats[b,c,p,intra_idx[a,t]]  (functional.py:L2553-2602, L2606-2627 for the (na, 4) anchor axis)."""
 
     @staticmethod
-    def forward(ctx, feats, idx, gx, rk, mult, sigma, ident=0, nonident=None, amap=None, shift=None):
-        # (amap: the per-entry anchor map of a set that is not a group, see _anchor_map -- perm_n(a) = amap[b,p,n,a], no table;
-        # shift: the per-entry residual index of the `use_2d` variant, see _conv_2d -- feats [b,c,n,na*4], perm_n(a, z) = (a, shift_z))
+    def forward(ctx, feats, grouping):
         feats = feats.contiguous()
-        ctx.ident = ident
-        ctx.save_for_backward(idx, gx, rk, mult if mult is not None else torch.empty(0), amap, shift)
-        ctx.has_mult = mult is not None
-        ctx.sigma = sigma
-        ctx.n = feats.shape[2]
-        if shift is not None:
-            return _hip.so3_inter_group_fwd_res(feats, idx, gx, rk, shift, sigma)
-        if amap is not None:
-            return _hip.so3_inter_group_fwd_map(feats, idx, gx, rk, amap, sigma)
-        return _hip.so3_inter_group_fwd(feats, idx, gx, rk, mult, sigma, nonident)
+        ctx.grouping, ctx.n = grouping, feats.shape[2]
+        return grouping.group(feats, 0, feats.shape[0])
 
     @staticmethod
     def backward(ctx, gout):
-        idx, gx, rk, mult, amap, shift = ctx.saved_tensors
-        if shift is not None:
-            g = _hip.so3_inter_group_bwd_res(gout.contiguous(), idx, gx, rk, shift, ctx.sigma, ctx.n)
-        elif amap is not None:
-            g = _hip.so3_inter_group_bwd_map(gout.contiguous(), idx, gx, rk, amap, ctx.sigma, ctx.n)
-        else:
-            g = _hip.so3_inter_group_bwd(gout.contiguous(), idx, gx, rk, mult if ctx.has_mult else None,
-                                         ctx.sigma, ctx.n, ctx.ident)
-        return g, None, None, None, None, None, None, None, None, None
-
-
-class _IntraGroup(torch.autograd.Function):
-    """out[b,c,t,p,a] = feats[b,c,p,intra_idx[a,t]]  (functional.py:L2553-2602)."""
-
-    @staticmethod
-    def forward(ctx, feats, intra_idx32):
-        ctx.save_for_backward(intra_idx32)
-        return _hip.so3_intra_group_fwd(feats.contiguous(), intra_idx32)
-
-    @staticmethod
-    def backward(ctx, gout):
-        intra_idx32, = ctx.saved_tensors
-        return _hip.so3_intra_group_bwd(gout.contiguous(), intra_idx32), None
-
-
-class _IntraGroup2D(torch.autograd.Function):
-    """out[b,c,t,p,(a,r)] = feats[b,c,p,(intra_idx[a,t],r)]  (functional.py:L2606-2627): one kernel each way."""
-
-    @staticmethod
-    def forward(ctx, feats, intra_idx32):
-        ctx.save_for_backward(intra_idx32)
-        return _hip.so3_intra_group2d_fwd(feats.contiguous(), intra_idx32)
-
-    @staticmethod
-    def backward(ctx, gout):
-        intra_idx32, = ctx.saved_tensors
-        return _hip.so3_intra_group2d_bwd(gout.contiguous(), intra_idx32), None
+        return ctx.grouping.group_transposed(gout.contiguous(), ctx.n, 0, gout.shape[0]), None
 
 
 class _Contract(torch.autograd.Function):
@@ -1096,92 +1058,180 @@ def _forward_dense(feats, W, plan, p, train_ep, folded):
     return y, (None if train_ep is None else train_ep.saved + (float(train_ep.norm.negative_slope), bool(train_ep.norm.sync)))
 
 
+# ---- group and contract: the textbook regimes -----------------------------------------------------------------------------------------
+# Five regimes are a grouping into the intermediate X, the contraction Y = W X, and the textbook backward dW = sum_b dY_b X_b^T, dX = W^T dY
+# through the grouping's transpose: the list kernels when the backward is 'textbook dX', the 'anchor map' and the 'residual map' (float32:
+# X is scratch, X_CHUNK_CLOUDS clouds at a time, or kept whole for the backward's dW), the float64 inter and intra convs (slabs under
+# F64_X_BYTES_MAX, X never kept).  A regime is its grouping pair; _group_contract and _backward_textbook are the skeleton around any pair.
+
+class _Grouping:
+    """A grouping and its transpose over the clouds [b0, b1) of a batch, the tensors that carry no gradient held as attributes:
+        group(feats, b0, b1)             -> X [b1-b0, c, mid, p, a] (nominal shape: `layout` says what the memory behind it is)
+        group_transposed(gx, n, b0, b1)  -> [b1-b0, c, n, a] from gx [b1-b0, c, mid, p, a] (reference layout)
+    mid = kernel points or taps; layout = 0 / 1 / 2: reference / blocked / transposed (X_LAYOUT); log: the float64 node around the pair
+    writes a FORWARD_LOG / BACKWARD_LOG entry; what: how a refusal names the conv and its middle axis."""
+    layout, log, what = 0, False, ('so3conv', 'kernel points')
+
+    def points(self, feats):
+        """p of X for these features"""
+        return self.idx.shape[1]
+
+
+class _ListGrouping(_Grouping):
+    """The list kernels (csrc/so3_inter.hip, csrc/so3_inter_lists2.hip) over an _InterConvArgs: the anchor axis unpermuted or permuted
+    through the group's table `mult`.  store_order: the transposed X with its columns in the order the kernel's lanes hold them -- scratch
+    for a contraction with W's columns permuted to match (_forward_lists), never what a backward regroups."""
+
+    def __init__(self, a, layout=0):
+        self.a, self.idx, self.mid, self.layout, self.store_order = a, a.idx, a.rk.shape[1], layout, False
+        self.coset = _coset_tables(a.mult, a.ident) if (a.mult is not None and a.nonident is not None and layout == 2) else None
+
+    def group(self, feats, b0, b1):
+        a = self.a
+        return _hip.so3_inter_group_fwd(feats[b0:b1], a.idx[b0:b1], a.gx[b0:b1], a.rk, a.mult, a.sigma,
+                                        None if a.nonident is None else a.nonident[b0:b1], blocked=self.layout, coset=self.coset,
+                                        store_order=self.store_order)
+
+    def group_transposed(self, gx, n, b0, b1):
+        a = self.a
+        return _hip.so3_inter_group_bwd(gx, a.idx[b0:b1], a.gx[b0:b1], a.rk, a.mult, a.sigma, n, a.ident)
+
+
+class _MapGrouping(_Grouping):
+    """The per-entry maps of an _InterConvArgs, reference layout, the transpose accumulated without float atomics: `amap` uint8 [b,p,nn,na]
+    of an anchor set that is not a group (_anchor_map; csrc/so3_inter_map.hip: many-to-one in the support row AND the anchor), or `shift`
+    uint8 [b,p,nn], the residual index of the `use_2d` variant (_conv_2d; csrc/so3_inter_res.hip: feats [b,c,n,na*4], all four residual
+    planes at once, many-to-one in the support row and, on ties, in the residual plane)."""
+
+    def __init__(self, a):
+        self.a, self.idx, self.mid = a, a.idx, a.rk.shape[1]
+        if a.shift is None:
+            self.regime, self.table, self.fwd, self.bwd = 'anchor map', a.amap, _hip.so3_inter_group_fwd_map, _hip.so3_inter_group_bwd_map
+        else:
+            self.regime, self.table, self.fwd, self.bwd = 'residual map', a.shift, _hip.so3_inter_group_fwd_res, _hip.so3_inter_group_bwd_res
+
+    def group(self, feats, b0, b1):
+        a = self.a
+        return self.fwd(feats[b0:b1], a.idx[b0:b1], a.gx[b0:b1], a.rk, self.table[b0:b1], a.sigma)
+
+    def group_transposed(self, gx, n, b0, b1):
+        a = self.a
+        return self.bwd(gx, a.idx[b0:b1], a.gx[b0:b1], a.rk, self.table[b0:b1], a.sigma, n)
+
+
+def _inter_grouping(a, layout=0):
+    """the float32 pair of an _InterConvArgs: through its per-entry map where it carries one, else the list kernels"""
+    return _MapGrouping(a) if (a.amap is not None or a.shift is not None) else _ListGrouping(a, layout)
+
+
+class _IntraGrouping(_Grouping):
+    """The 12-tap gather of the intra convs, out[b,c,t,p,a] = feats[b,c,p,idx32[a,t]], and its transpose: kind 'f32' (csrc/so3_intra.hip),
+    '2d' (the (na, 4) anchor axis, an anchor's residuals moved as one quad) or 'f64'."""
+    what = ('intra_so3conv', 'taps')
+    KERNELS = {'f32': ('so3_intra_group_fwd', 'so3_intra_group_bwd'), '2d': ('so3_intra_group2d_fwd', 'so3_intra_group2d_bwd'),
+               'f64': ('so3_intra_group_fwd_f64', 'so3_intra_group_bwd_f64')}
+
+    def __init__(self, intra_idx, kind):
+        self.idx32, self.mid = intra_idx.to(torch.int32).contiguous(), intra_idx.shape[1]
+        self.fwd, self.bwd = (getattr(_hip, name) for name in self.KERNELS[kind])
+
+    def points(self, feats):
+        return feats.shape[2]
+
+    def group(self, feats, b0, b1):
+        return self.fwd(feats[b0:b1], self.idx32)
+
+    def group_transposed(self, gx, n, b0, b1):
+        return self.bwd(gx, self.idx32)
+
+
+def _slabs(b, step):
+    """[(b0, b1), ...]: b clouds, `step` at a time"""
+    return [(b0, min(b, b0 + step)) for b0 in range(0, b, step)]
+
+
+def _f32_slabs(b, keep):
+    """X_CHUNK_CLOUDS clouds at a time; a kept X is one slab of all clouds"""
+    return _slabs(b, max(1, b if keep else X_CHUNK_CLOUDS))
+
+
+def _empty_output(grouping, feats, W):
+    """y [b,o,p,a] of the conv of feats [b,c,n,a] around `grouping`"""
+    return torch.empty(feats.shape[0], W.shape[0], grouping.points(feats), feats.shape[3], dtype=feats.dtype, device=feats.device)
+
+
+def _group_contract(grouping, feats, W, y, slabs, keep, contract):
+    """The forward of every regime: per slab (b0, b1) the grouping into X, then contract(W, X, y[b0:b1] as [b1-b0, o, p*a], b0).
+    -> X when `keep` (the backward's dW = dY X^T wants it; `slabs` is one slab of all clouds then), else None: X is scratch, one slab at a
+    time."""
+    x = None
+    for b0, b1 in slabs:
+        x = grouping.group(feats, b0, b1)
+        contract(W, x, y[b0:b1].view(b1 - b0, y.shape[1], -1), b0)
+        x = x if keep else None
+    return x
+
+
+def _backward_textbook(grouping, gy, W, feats, x, need_f, need_w, slabs):
+    """The backward of every regime: per slab dW += dY X^T, then dX = W^T dY followed by the grouping's transpose -> (gF, gW).
+    x = the forward's intermediate of the whole batch, or None (not kept): regrouped slab by slab, for dW only.
+    float32: `slabs` is the whole batch -- the products reduce through a workspace, dX from W^T written out (a few MB: the product is then
+    'nn' with a shared A operand, which the split-operand kernels take; with the transposition left to the GEMM it ran on the fp32 matrix
+    pipe: 15.6 of the 61.6 ms step at 16 x 512 points).  float64: any slabs, dW accumulated in cloud order, dX from the view of W."""
+    b, c, n, _ = feats.shape
+    (o, ck), p, a = W.shape, gy.shape[2], gy.shape[3]
+    pa, layout = p * a, grouping.layout
+    gF = gW = None
+    for b0, b1 in slabs:
+        nb = b1 - b0
+        gys = gy[b0:b1].view(nb, o, pa)
+        if need_w:
+            xs = x if x is not None else grouping.group(feats, b0, b1)      # wrong guess (or the first step): one more run of the grouping
+            gW = torch.empty_like(W) if gW is None else gW
+            # (measured and dropped: every cloud's dY_b X^T_b on the split-operand 'nn' kernel instead of the batch-reducing fp32 kernel --
+            # 512 x 3072 outputs over K = 30720 are 48 workgroups without a split of K: 15.5 -> 48 ms at 16 x 512 points)
+            if layout == 2:     # X^T [pa, ck]: dW = dY X^T is a plain row-major product
+                _hip.matmul_reduce(gys, xs.view(nb, pa, ck), gW, accumulate=b0 > 0)
+            elif layout == 1:   # blocked by 4: a storage without strides to read the numbers from -- the positional call
+                _hip.gemm_reduce(0, 1, o, ck, pa, gys, pa, o * pa, xs, pa, ck * pa, gW, ck, nb, b_blocked=True)
+            else:
+                _hip.matmul_reduce(gys, xs.view(nb, ck, pa).transpose(1, 2), gW, accumulate=b0 > 0)
+            xs = None                                                        # (released before W^T dY is allocated)
+        if need_f:
+            gx = torch.empty(nb, ck, pa, dtype=gy.dtype, device=gy.device)   # W^T gy
+            _hip.matmul(W.t() if gy.dtype == torch.float64 else W.t().contiguous(), gys, gx)
+            g = grouping.group_transposed(gx.view(nb, c, grouping.mid, p, a), n, b0, b1)
+            del gx
+            if nb == b:
+                gF = g
+            else:
+                gF = torch.empty_like(feats) if gF is None else gF
+                gF[b0:b1] = g
+            del g                                                            # (not held beside the next slab's X)
+    return gF, gW
+
+
 def _forward_lists(feats, W, args, layout, keep, folded, head, fill):
     """The forward on the list kernels: grouping into the intermediate X (layout 0 / 1 / 2: reference / blocked / transposed, see X_LAYOUT),
     then the contraction -> (y [b,o,p,a], x): x = the intermediate when it is kept for a textbook backward (keep), else None -- X is then
     scratch, X_CHUNK_CLOUDS clouds at a time.  fill: the second half of head's lists is still to be made."""
-    idx, gx, rk, mult, sigma, nonident = args.idx, args.gx, args.rk, args.mult, args.sigma, args.nonident
     b, c, n, na = feats.shape
-    p, ks, o = idx.shape[1], rk.shape[1], W.shape[0]
+    ks, mult = args.rk.shape[1], args.mult
     if fill:
-        head.fill(idx, gx, n)                          # (the probe postponed it; a dense backward does not need the entries)
-    y = torch.empty(b, o, p, na, dtype=torch.float32, device=feats.device)
-    coset = _coset_tables(mult, args.ident) if (mult is not None and nonident is not None and layout == 2) else None
-    x_bound = _grouped_bound(feats, idx) if layout == 2 else None          # [b, p] words
-    step = max(1, b if keep else X_CHUNK_CLOUDS)          # (a kept X is one slab of all clouds)
+        head.fill(args.idx, args.gx, n)                # (the probe postponed it; a dense backward does not need the entries)
+    grouping = _ListGrouping(args, layout)
+    y = _empty_output(grouping, feats, W)
+    x_bound = _grouped_bound(feats, args.idx) if layout == 2 else None          # [b, p] words
     # where X is scratch between the grouping and the contraction its columns may be in the order the grouping kernel's
     # lanes hold them (1 KB store runs, csrc/so3_inter_lists2.hip LAYOUT 4) with W's columns permuted to match
     tp = (not keep and STORE_ORDER_COLUMNS and layout == 2 and _hip.so3_group_fwd_tp_takes(c, na, ks)
-          and (mult is None or (coset is not None and _hip.so3_group_perm_lists2_takes(c, na, ks, n))))
+          and (mult is None or (grouping.coset is not None and _hip.so3_group_perm_lists2_takes(c, na, ks, n))))
+    grouping.store_order = tp
     Wc = W.index_select(1, _hip.so3_group_fwd_tp_columns(c, ks, W.device)) if tp else W
-    x = None
-    for b0 in range(0, b, step):
-        b1 = min(b, b0 + step)
-        x = _hip.so3_inter_group_fwd(feats[b0:b1], idx[b0:b1], gx[b0:b1], rk, mult, sigma,
-                                     None if nonident is None else nonident[b0:b1], blocked=layout, coset=coset, store_order=tp)   # [b,c,k,p,a] (nominal shape)
-        _contract_into(Wc, x, y[b0:b1].view(b1 - b0, o, p * na), layout, folded, b0,
-                       x_bound=None if x_bound is None else (x_bound[b0:b1], na, 1.0))
-        x = x if keep else None
-    return y, x
 
-
-def _forward_map(feats, W, args, keep, folded):
-    """The forward of the 'anchor map' regime (anchor sets that are not a group, really permuted): grouping through the per-entry map
-    (csrc/so3_inter_map.hip) into the reference layout, then the contraction -> (y [b,o,p,a], x): x = the intermediate when it is kept for
-    the backward's dW = dY X^T (keep), else None -- X_CHUNK_CLOUDS clouds at a time then."""
-    idx, gx, rk, amap = args.idx, args.gx, args.rk, args.amap
-    b, na = feats.shape[0], feats.shape[3]
-    p, o = idx.shape[1], W.shape[0]
-    y = torch.empty(b, o, p, na, dtype=torch.float32, device=feats.device)
-    step = max(1, b if keep else X_CHUNK_CLOUDS)
-    x = None
-    for b0 in range(0, b, step):
-        b1 = min(b, b0 + step)
-        x = _hip.so3_inter_group_fwd_map(feats[b0:b1], idx[b0:b1], gx[b0:b1], rk, amap[b0:b1], args.sigma)      # [b,c,k,p,a]
-        _contract_into(W, x, y[b0:b1].view(b1 - b0, o, p * na), 0, folded, b0)
-        x = x if keep else None
-    return y, x
-
-
-def _forward_res(feats, W, args, keep, folded):
-    """The forward of the 'residual map' regime (the `use_2d` variant with really permuted residual indices): grouping through the per-entry
-    byte (csrc/so3_inter_res.hip) into the reference layout -- all four residual planes at once -- then the contraction -> (y [b,o,p,na*4], x):
-    x = the intermediate when it is kept for the backward's dW = dY X^T (keep), else None -- X_CHUNK_CLOUDS clouds at a time then."""
-    idx, gx, rk, shift = args.idx, args.gx, args.rk, args.shift
-    b, na4 = feats.shape[0], feats.shape[3]
-    p, o = idx.shape[1], W.shape[0]
-    y = torch.empty(b, o, p, na4, dtype=torch.float32, device=feats.device)
-    step = max(1, b if keep else X_CHUNK_CLOUDS)
-    x = None
-    for b0 in range(0, b, step):
-        b1 = min(b, b0 + step)
-        x = _hip.so3_inter_group_fwd_res(feats[b0:b1], idx[b0:b1], gx[b0:b1], rk, shift[b0:b1], args.sigma)      # [b,c,k,p,a*4]
-        _contract_into(W, x, y[b0:b1].view(b1 - b0, o, p * na4), 0, folded, b0)
-        x = x if keep else None
-    return y, x
-
-
-def _backward_res(gy, W, feats, x, args, need_f, need_w):
-    """The backward of the 'residual map' regime: the textbook dW = dY X^T and dX = W^T dY on the GEMMs of _backward_textbook, then the
-    transposed grouping through the residual index (csrc/so3_inter_res.hip: many-to-one in the support row and, on ties, in the residual
-    plane; accumulated without float atomics) -> (gF, gW)"""
-    b, c, n, na4 = feats.shape
-    idx, gx, rk, shift = args.idx, args.gx, args.rk, args.shift
-    p, ks = idx.shape[1], rk.shape[1]
-    o, ck, pa = W.shape[0], c * ks, p * na4
-    gF = gW = None
-    if need_w:
-        if x is None:
-            x = _hip.so3_inter_group_fwd_res(feats, idx, gx, rk, shift, args.sigma)
-        gW = torch.empty_like(W)          # sum_b gy_b x_b^T
-        _hip.matmul_reduce(gy.view(b, o, pa), x.view(b, ck, pa).transpose(1, 2), gW)
-        x = None
-    if need_f:
-        gx_ = torch.empty(b, ck, pa, dtype=torch.float32, device=gy.device)      # W^T gy
-        Wt = W.t().contiguous()
-        _hip.matmul(Wt, gy.view(b, o, pa), gx_)
-        gF = _hip.so3_inter_group_bwd_res(gx_.view(b, c, ks, p, na4), idx, gx, rk, shift, args.sigma, n)
-    return gF, gW
+    def contract(Wc, x, ys, b0):
+        _contract_into(Wc, x, ys, layout, folded, b0, x_bound=None if x_bound is None else (x_bound[b0:b0 + x.shape[0]], na, 1.0))
+    return y, _group_contract(grouping, feats, Wc, y, _f32_slabs(b, keep), keep, contract)
 
 
 # ---- regime 'narrow input': C*K <= 32 contraction indices, no input gradient, training-mode norm in the node (csrc/narrow_conv.hip) ----
@@ -1395,61 +1445,10 @@ def _backward_lists(gy, W, feats, idx, gx, rk, mult, args, head, rcap, any_nonid
     return gF, gW
 
 
-def _backward_textbook(gy, W, feats, x, idx, gx, rk, mult, nonident, args, layout, need_f, need_w):
-    """dW = dY X^T, dX = W^T dY followed by the transposed grouping; x = the forward's intermediate or None (not kept) -> (gF, gW)"""
-    b, c, n, na = feats.shape
-    p, ks = idx.shape[1], rk.shape[1]
-    o, ck, pa = W.shape[0], c * ks, p * na
-    gF = gW = None
-    if x is None:                                     # wrong guess (or the first step): one more run of the grouping kernel
-        x = _hip.so3_inter_group_fwd(feats, idx, gx, rk, mult, args.sigma, nonident, blocked=layout,
-                                     coset=_coset_tables(mult, args.ident) if (mult is not None and layout == 2) else None)
-    if need_w:
-        gW = torch.empty_like(W)          # sum_b gy_b x_b^T
-        # (measured and dropped: every cloud's dY_b X^T_b on the split-operand 'nn' kernel instead of the batch-reducing fp32 kernel --
-        # 512 x 3072 outputs over K = 30720 are 48 workgroups without a split of K: 15.5 -> 48 ms at 16 x 512 points)
-        if layout == 2:     # X^T [pa, ck]: dW = dY X^T is a plain row-major product
-            _hip.matmul_reduce(gy.view(b, o, pa), x.view(b, pa, ck), gW)
-        elif layout == 1:   # blocked by 4: a storage without strides to read the numbers from -- the positional call
-            _hip.gemm_reduce(0, 1, o, ck, pa, gy, pa, o * pa, x, pa, ck * pa, gW, ck, b, b_blocked=True)
-        else:
-            _hip.matmul_reduce(gy.view(b, o, pa), x.view(b, ck, pa).transpose(1, 2), gW)
-    if need_f:
-        gx_ = torch.empty_like(x.view(b, ck, pa))      # W^T gy
-        # (W^T written out -- a few MB: the product is then 'nn' with a shared A operand, which the split-operand kernels take;
-        # with the transposition left to the GEMM it ran on the fp32 matrix pipe: 15.6 of the 61.6 ms step at 16 x 512 points)
-        Wt = W.t().contiguous()
-        _hip.matmul(Wt, gy.view(b, o, pa), gx_)
-        gF = _hip.so3_inter_group_bwd(gx_.view(b, c, ks, p, na), idx, gx, rk, mult, args.sigma, n, args.ident)
-    return gF, gW
-
-
-def _backward_map(gy, W, feats, x, args, need_f, need_w):
-    """The backward of the 'anchor map' regime: the textbook dW = dY X^T and dX = W^T dY on the GEMMs of _backward_textbook, then the
-    transposed grouping through the map (csrc/so3_inter_map.hip: many-to-one in the support row AND the anchor, accumulated without
-    float atomics) -> (gF, gW)"""
-    b, c, n, na = feats.shape
-    idx, gx, rk, amap = args.idx, args.gx, args.rk, args.amap
-    p, ks = idx.shape[1], rk.shape[1]
-    o, ck, pa = W.shape[0], c * ks, p * na
-    gF = gW = None
-    if need_w:
-        if x is None:
-            x = _hip.so3_inter_group_fwd_map(feats, idx, gx, rk, amap, args.sigma)
-        gW = torch.empty_like(W)          # sum_b gy_b x_b^T
-        _hip.matmul_reduce(gy.view(b, o, pa), x.view(b, ck, pa).transpose(1, 2), gW)
-    if need_f:
-        gx_ = torch.empty(b, ck, pa, dtype=torch.float32, device=gy.device)      # W^T gy
-        Wt = W.t().contiguous()
-        _hip.matmul(Wt, gy.view(b, o, pa), gx_)
-        gF = _hip.so3_inter_group_bwd_map(gx_.view(b, c, ks, p, na), idx, gx, rk, amap, args.sigma, n)
-    return gF, gW
-
-
 class _InterConv(torch.autograd.Function):
     """Fused inter conv  y = W . group(feats)  (functional.py:L1221-1261 + modules.py:L48-55)
     with the re-associated feature gradient (csrc/so3_inter_inv.hip).  forward and backward decide the regime and dispatch to the
-    _forward_* / _backward_* functions above."""
+    _forward_* / _backward_* functions above; the regimes that group and contract hand their pair to _group_contract / _backward_textbook."""
 
     DIFFERENTIABLE = 4      # feats, W, bn_weight, bn_bias come first: needs_input_grad is indexed by these positions only
 
@@ -1476,10 +1475,13 @@ class _InterConv(torch.autograd.Function):
         if args.amap is not None or args.shift is not None:
             # an anchor set that is not a group, really permuted ('anchor map'), or the 60 x 4 anchor axis of the `use_2d` variant with really
             # permuted residual indices ('residual map', feats [b,c,n,na*4]): a per-entry map has no inverse-list or dense form
-            regime, fwd = ('anchor map', _forward_map) if args.shift is None else ('residual map', _forward_res)
+            # (X in the reference layout, kept only for the backward's dW = dY X^T)
+            grouping, keep = _MapGrouping(args), bool(needs_grad and ctx.needs_input_grad[1])
             if FORWARD_LOG is not None:
-                FORWARD_LOG.append({'channels': (c, o), 'dense': False, 'parts': None, 'regime': regime})
-            y, x = fwd(feats, W, args, needs_grad and ctx.needs_input_grad[1], folded)
+                FORWARD_LOG.append({'channels': (c, o), 'dense': False, 'parts': None, 'regime': grouping.regime})
+            y = _empty_output(grouping, feats, W)
+            x = _group_contract(grouping, feats, W, y, _f32_slabs(feats.shape[0], keep), keep,
+                                lambda W, x, ys, b0: _contract_into(W, x, ys, 0, folded, b0))
             ctx.bn, ctx.conv_args, ctx.head, ctx.layout, ctx.plan = None, args, None, 0, None
             ctx.W_param = weakref.ref(W_param)
             ctx.save_for_backward(W, x, idx, args.gx, rk, None, nonident, feats, None)
@@ -1538,10 +1540,11 @@ class _InterConv(torch.autograd.Function):
             gF = None
             gW, g_bn_w, g_bn_b = _backward_narrow(gy, W, x, ctx.bn, need_w)
         elif args.amap is not None or args.shift is not None:
-            regime, bwd = ('anchor map', _backward_map) if args.shift is None else ('residual map', _backward_res)
+            grouping = _MapGrouping(args)
             if BACKWARD_LOG is not None:
-                BACKWARD_LOG.append({'channels': (feats.shape[1], W.shape[0]), 'support_rows': n, 'referenced_rows_max': 0, 'regime': regime})
-            gF, gW = bwd(gy, W, feats, x, args, need_f, need_w)
+                BACKWARD_LOG.append({'channels': (feats.shape[1], W.shape[0]), 'support_rows': n, 'referenced_rows_max': 0,
+                                     'regime': grouping.regime})
+            gF, gW = _backward_textbook(grouping, gy, W, feats, x, need_f, need_w, [(0, feats.shape[0])])
         elif plan is not None and plan.parts is not None:
             gF, gW = _backward_dense_parts(gy, W, feats, head, plan.geo(), need_f, need_w)
         elif plan is not None:
@@ -1562,7 +1565,7 @@ class _InterConv(torch.autograd.Function):
             if head is not None:
                 gF, gW = _backward_lists(gy, W, feats, idx, gx, rk, mult, args, head, rcap, any_nonident, need_f, need_w)
             else:
-                gF, gW = _backward_textbook(gy, W, feats, x, idx, gx, rk, mult, nonident, args, ctx.layout, need_f, need_w)
+                gF, gW = _backward_textbook(_ListGrouping(args, ctx.layout), gy, W, feats, x, need_f, need_w, [(0, feats.shape[0])])
         return (gF, gW, g_bn_w, g_bn_b) + (None,) * (len(ctx.needs_input_grad) - _InterConv.DIFFERENTIABLE)
 
 
@@ -1637,7 +1640,7 @@ def intra_so3conv(feats, W, intra_idx):
     if not feats.is_cuda:
         raise RuntimeError('intra_so3conv: device tensors only')
     if dtype == torch.float64:
-        return _IntraConvF64.apply(feats, W, intra_idx.to(torch.int32).contiguous())
+        return _GroupContractF64.apply(feats, W, _IntraGrouping(intra_idx, 'f64'))
     return _IntraConv.apply(feats, W, intra_idx.to(torch.int32).contiguous())
 
 
@@ -1721,17 +1724,17 @@ F64_X_BYTES_MAX = 4 << 30
 
 def _f64_slabs(b, bytes_per_cloud):
     """[(b0, b1), ...]: the clouds in slabs whose intermediate stays under F64_X_BYTES_MAX (one cloud where a single one exceeds it)"""
-    step = max(1, int(F64_X_BYTES_MAX // max(int(bytes_per_cloud), 1)))
-    return [(b0, min(b, b0 + step)) for b0 in range(0, b, step)]
+    return _slabs(b, max(1, int(F64_X_BYTES_MAX // max(int(bytes_per_cloud), 1))))
 
 
-class _F64Args:
-    """The inputs of the float64 inter nodes that carry no gradient: idx int32 [b,p,nn], g float64 [b,p,nn,3], r int32 [b,p,nn], rk
+class _F64Args(_Grouping):
+    """The grouping pair of the float64 inter conv (csrc/so3_f64.hip; the transpose over inverse neighbour lists, no atomics), made of the
+    inputs that carry no gradient: idx int32 [b,p,nn], g float64 [b,p,nn,3], r int32 [b,p,nn], rk
     float64 [na,ks,3], mult uint8 [na,na] and its row-wise inverse (None: no anchor permutation), sigma."""
 
     def __init__(self, idx, g, r, rk, mult, multinv, sigma):
         self.idx, self.g, self.r, self.rk, self.mult, self.multinv, self.sigma = idx, g, r, rk, mult, multinv, float(sigma)
-        self.lists = None
+        self.lists, self.mid, self.log = None, rk.shape[1], True
 
     def inverse_lists(self, n):
         """(rows, off, cnt, ent) of the whole batch (csrc/inv_lists.hip, index only; csrc/so3_f64.hip the entries), built once"""
@@ -1766,8 +1769,7 @@ def _neighbourhood_f64(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, p
     if pose is not None:
         rot = pose.contiguous()
         q_rot = rot if q_pose is None else q_pose.contiguous()
-        if rot.shape[-2:] != (4, 4) or not rot.is_cuda:
-            raise RuntimeError('so3conv: pose must be a float64 device tensor [b,p,4,4] in a float64 call')
+        _check_pose(rot, torch.float64)
         if permute:
             mult, ident = _group_tables(anchors)
             if mult is None:
@@ -1789,119 +1791,32 @@ def _log_f64(forward, c, o, n):
         BACKWARD_LOG.append({'channels': (c, o), 'support_rows': n, 'referenced_rows_max': 0, 'regime': 'float64'})
 
 
-class _InterGroupF64(torch.autograd.Function):
-    """_InterGroup in float64: new_feats[b,c,k,p,a] = sum_n feats[b,c,idx_n,perm_n(a)] w(p,a,k,n) and its transpose without atomics."""
+class _GroupContractF64(torch.autograd.Function):
+    """The inter and intra convs in float64, one node around a pair (_F64Args, _IntraGrouping): grouping -> Y = W X; backward dW = sum_z
+    gY_z X_z^T with X regrouped (never saved), dX = W^T gY -> the grouping's transpose, a slab of clouds at a time (F64_X_BYTES_MAX)."""
 
     @staticmethod
-    def forward(ctx, feats, args):
-        feats = feats.contiguous()
-        ctx.conv_args, ctx.n = args, feats.shape[2]
-        return args.group(feats, 0, feats.shape[0])
-
-    @staticmethod
-    def backward(ctx, gout):
-        return ctx.conv_args.group_transposed(gout.contiguous(), ctx.n, 0, gout.shape[0]), None
-
-
-class _InterConvF64(torch.autograd.Function):
-    """The inter conv in float64, one node: grouping -> Y = W X; backward dX = W^T gY -> the grouping's transpose, dW = sum_z gY_z X_z^T
-    with X regrouped (never saved), a slab of clouds at a time (F64_X_BYTES_MAX)."""
-
-    @staticmethod
-    def forward(ctx, feats, W_param, args):
+    def forward(ctx, feats, W_param, grouping):
         feats, W = feats.contiguous(), W_param.contiguous()
         b, c, n, na = feats.shape
-        p, ks, o = args.idx.shape[1], args.rk.shape[1], W.shape[0]
-        if W.shape[1] != c * ks:
-            raise RuntimeError(f'so3conv: W {tuple(W.shape)} for {c} channels x {ks} kernel points')
-        _log_f64(True, c, o, n)
-        y = torch.empty(b, o, p, na, dtype=torch.float64, device=feats.device)
-        for b0, b1 in _f64_slabs(b, 8 * c * ks * p * na):
-            x = args.group(feats, b0, b1)
-            _hip.matmul(W, x.view(b1 - b0, c * ks, p * na), y[b0:b1].view(b1 - b0, o, p * na))
-            del x
-        ctx.conv_args = args
+        if W.shape[1] != c * grouping.mid:
+            raise RuntimeError(f'{grouping.what[0]}: W {tuple(W.shape)} for {c} channels x {grouping.mid} {grouping.what[1]}')
+        if grouping.log:
+            _log_f64(True, c, W.shape[0], n)
+        y = _empty_output(grouping, feats, W)
+        _group_contract(grouping, feats, W, y, _f64_slabs(b, 8 * W.shape[1] * y.shape[2] * na), False,
+                        lambda W, x, ys, b0: _contract_into(W, x, ys, 0))
+        ctx.grouping = grouping
         ctx.save_for_backward(feats, W)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         feats, W = ctx.saved_tensors
-        args = ctx.conv_args
-        gy = gy.contiguous()
-        b, c, n, na = feats.shape
-        p, ks, o = args.idx.shape[1], args.rk.shape[1], W.shape[0]
-        need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        _log_f64(False, c, o, n)
-        gF = torch.empty_like(feats) if need_f else None
-        gW = torch.empty_like(W) if need_w else None
-        for b0, b1 in _f64_slabs(b, 8 * c * ks * p * na):
-            gys = gy[b0:b1].view(b1 - b0, o, p * na)
-            if need_f:
-                gx = torch.empty(b1 - b0, c * ks, p * na, dtype=torch.float64, device=gy.device)
-                _hip.matmul(W.t(), gys, gx)
-                gF[b0:b1] = args.group_transposed(gx.view(b1 - b0, c, ks, p, na), n, b0, b1)
-                del gx
-            if need_w:
-                x = args.group(feats, b0, b1)
-                _hip.matmul_reduce(gys, x.view(b1 - b0, c * ks, p * na).transpose(1, 2), gW, accumulate=b0 > 0)
-                del x
-        return gF, gW, None
-
-
-class _IntraGroupF64(torch.autograd.Function):
-    """_IntraGroup in float64 (csrc/so3_intra.hip at 8 bytes per element)."""
-
-    @staticmethod
-    def forward(ctx, feats, intra_idx32):
-        ctx.save_for_backward(intra_idx32)
-        return _hip.so3_intra_group_fwd_f64(feats.contiguous(), intra_idx32)
-
-    @staticmethod
-    def backward(ctx, gout):
-        intra_idx32, = ctx.saved_tensors
-        return _hip.so3_intra_group_bwd_f64(gout.contiguous(), intra_idx32), None
-
-
-class _IntraConvF64(torch.autograd.Function):
-    """The intra conv in float64, one node: the 12-tap gather G -> Y = W G; backward dG = W^T gY -> the gather's transpose, dW = sum_z gY_z
-    G_z^T with G regathered, a slab of clouds at a time (F64_X_BYTES_MAX)."""
-
-    @staticmethod
-    def forward(ctx, feats, W, idx32):
-        feats, W = feats.contiguous(), W.contiguous()
-        b, c, p, na = feats.shape
-        o, t = W.shape[0], idx32.shape[1]
-        if W.shape[1] != c * t:
-            raise RuntimeError(f'intra_so3conv: W {tuple(W.shape)} for {c} channels x {t} taps')
-        y = torch.empty(b, o, p, na, dtype=torch.float64, device=feats.device)
-        for b0, b1 in _f64_slabs(b, 8 * c * t * p * na):
-            g = _hip.so3_intra_group_fwd_f64(feats[b0:b1], idx32)
-            _hip.matmul(W, g.view(b1 - b0, c * t, p * na), y[b0:b1].view(b1 - b0, o, p * na))
-            del g
-        ctx.save_for_backward(feats, W, idx32)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        feats, W, idx32 = ctx.saved_tensors
-        gy = gy.contiguous()
-        b, c, p, na = feats.shape
-        o, t = W.shape[0], idx32.shape[1]
-        need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gF = torch.empty_like(feats) if need_f else None
-        gW = torch.empty_like(W) if need_w else None
-        for b0, b1 in _f64_slabs(b, 8 * c * t * p * na):
-            gys = gy[b0:b1].view(b1 - b0, o, p * na)
-            if need_f:
-                gg = torch.empty(b1 - b0, c * t, p * na, dtype=torch.float64, device=gy.device)
-                _hip.matmul(W.t(), gys, gg)
-                gF[b0:b1] = _hip.so3_intra_group_bwd_f64(gg.view(b1 - b0, c, t, p, na), idx32)
-                del gg
-            if need_w:
-                g = _hip.so3_intra_group_fwd_f64(feats[b0:b1], idx32)
-                _hip.matmul_reduce(gys, g.view(b1 - b0, c * t, p * na).transpose(1, 2), gW, accumulate=b0 > 0)
-                del g
+        if ctx.grouping.log:
+            _log_f64(False, feats.shape[1], W.shape[0], feats.shape[2])
+        slabs = _f64_slabs(feats.shape[0], 8 * W.shape[1] * gy.shape[2] * gy.shape[3])
+        gF, gW = _backward_textbook(ctx.grouping, gy.contiguous(), W, feats, None, ctx.needs_input_grad[0], ctx.needs_input_grad[1], slabs)
         return gF, gW, None
 
 
@@ -1956,6 +1871,15 @@ def _check_inputs(xyz, feats, W=None, on_device=True, float32_only=None):
     return dtype
 
 
+def _check_pose(rot, dtype=torch.float32):
+    """pose [b,p,4,4] of the call's width (a float64 call: on the device; its width was checked with the other tensors, _call_dtype)"""
+    if dtype == torch.float64:
+        if rot.shape[-2:] != (4, 4) or not rot.is_cuda:
+            raise RuntimeError('so3conv: pose must be a float64 device tensor [b,p,4,4] in a float64 call')
+    elif rot.shape[-2:] != (4, 4) or rot.dtype != torch.float32:
+        raise RuntimeError('so3conv: pose must be float32 [b,p,4,4]')
+
+
 def _anchor_map(idx, q_rot, rot, anchors):
     """The anchor index of a conv that permutes by poses over an anchor set that is NOT a group (kanchor 20 / 40: subsets of the
     icosahedral rotations, L2641-2649).  There the reference's argmax_j tr(R_rel^T A_a A_j^T) (L1199-1204) depends on the actual R_rel --
@@ -1989,8 +1913,7 @@ def _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permu
     if pose is not None:
         rot = pose.contiguous()
         q_rot = rot if q_pose is None else q_pose.contiguous()
-        if rot.shape[-2:] != (4, 4) or rot.dtype != torch.float32:
-            raise RuntimeError('so3conv: pose must be float32 [b,p,4,4]')
+        _check_pose(rot)
         if permute:
             mult, ident, amap = _permutation_tables(anchors, ball_idx, q_rot, rot)
     gx, nonident = _hip.so3_prep(q_xyz, xyz, ball_idx, q_rot, rot, anchors.contiguous(), ident)
@@ -2001,13 +1924,9 @@ def _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permu
 def _inter_group(xyz, pose, feats, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz=None, q_pose=None):
     if _check_inputs(xyz, feats) == torch.float64:
         a = _neighbourhood_f64(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose)
-        new_feats = _InterGroupF64.apply(feats, a)
-        inter_w = InterWeights(a.g, a.rk, sigma, a.r)
-        return a.idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), new_feats
+        return a.idx, _inter_w(InterWeights(a.g, a.rk, sigma, a.r)), _Group.apply(feats, a)
     a = _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose)
-    new_feats = _InterGroup.apply(feats, a.idx, a.gx, a.rk, a.mult, a.sigma, a.ident, a.nonident, a.amap)
-    inter_w = InterWeights(a.gx, a.rk, sigma)
-    return a.idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), new_feats
+    return a.idx, _inter_w(InterWeights(a.gx, a.rk, sigma)), _Group.apply(feats, _inter_grouping(a))
 
 
 def inter_so3conv_fused(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz=None, q_pose=None,
@@ -2019,16 +1938,12 @@ def inter_so3conv_fused(xyz, pose, feats, W, n_neighbor, anchors, kernels, radiu
         if epilogue is not None:
             raise RuntimeError('so3conv: conv_norm_act epilogues (FoldedEpilogue, TrainEpilogue) are float32 only, a float64 conv takes none')
         a = _neighbourhood_f64(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose)
-        y = _InterConvF64.apply(feats, W, a)
-        inter_w = InterWeights(a.g, a.rk, sigma, a.r)
-        return a.idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), y
+        return a.idx, _inter_w(InterWeights(a.g, a.rk, sigma, a.r)), _GroupContractF64.apply(feats, W, a)
     a = _neighbourhood(xyz, pose, n_neighbor, anchors, kernels, radius, sigma, permute, q_xyz, q_pose, epilogue)
     bn_w = bn_b = None
     if isinstance(epilogue, TrainEpilogue):
         bn_w, bn_b = epilogue.norm.weight, epilogue.norm.bias
-    y = _InterConv.apply(feats, W, bn_w, bn_b, a)
-    inter_w = InterWeights(a.gx, a.rk, sigma)
-    return a.idx, (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), y
+    return a.idx, _inter_w(InterWeights(a.gx, a.rk, sigma)), _InterConv.apply(feats, W, bn_w, bn_b, a)
 
 
 def inter_so3conv_fused_art_mode(xyz, pose, feats, W, seg_labels, n_neighbor, anchors, kernels, radius, sigma, permute):
@@ -2056,8 +1971,7 @@ def inter_so3conv_fused_art_mode(xyz, pose, feats, W, seg_labels, n_neighbor, an
     ident = 0
     if pose is not None and permute:
         rot = pose.contiguous()
-        if rot.shape[-2:] != (4, 4) or rot.dtype != torch.float32:
-            raise RuntimeError('so3conv: pose must be float32 [b,p,4,4]')
+        _check_pose(rot)
         mult, ident, amap = _permutation_tables(anchors, ball_idx, rot, rot)
         # the nearest anchor of every pair's relative rotation (4th word of gx) and the per-cloud "not all identity" flag; the
         # rotated offsets this call also produces are not used in this mode
@@ -2065,8 +1979,7 @@ def inter_so3conv_fused_art_mode(xyz, pose, feats, W, seg_labels, n_neighbor, an
         g_rot, nonident = _hip.so3_prep(first, first, ball_idx, rot, rot, anchors.contiguous(), ident)
         gx = torch.cat([gx[..., :3], g_rot[..., 3:]], dim=-1).contiguous()
     y = _InterConv.apply(feats, W, None, None, _InterConvArgs(ball_idx, gx, rk, mult, sigma, ident, nonident, anchors, amap=amap))
-    inter_w = InterWeights(gx, rk, sigma)
-    return (inter_w.materialize() if MATERIALIZE_INTER_W else inter_w), y
+    return _inter_w(InterWeights(gx, rk, sigma)), y
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2115,7 +2028,7 @@ def _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, p
     With a really permuted residual index (one rotation per rigid part, one per point) -- the 'residual map' regime: the index as one
     byte per entry (eap_so3_residual_index_f32; one host read of its per-cloud flags, as _anchor_map), the grouping through it for all
     240 anchors at once and its transpose without float atomics (csrc/so3_inter_res.hip), ONE autograd node (_InterConv for the module,
-    _InterGroup for the functional grouping API).
+    _Group for the functional grouping API).
 
     KERNEL_2D_MIN_POINTS: a cloud of at most one slab (p <= SLOW_2D_CHUNK) keeps the reference's expression in device tensor ops -- there
     it materialises everything exactly once, a few MB, and it is the form the 40-point reference-made fixture pins (the fixture's test
@@ -2138,18 +2051,15 @@ def _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, p
                 shift = None
         else:
             rot = pose.contiguous()
-            if rot.shape[-2:] != (4, 4) or rot.dtype != torch.float32:
-                raise RuntimeError('so3conv: pose must be float32 [b,p,4,4]')
+            _check_pose(rot)
             packed, nontrivial = _hip.so3_residual_index(ball_idx, rot, rot, res)
             if int(nontrivial.max()) == 0:            # (one host read) unpermuted: the four fused convolutions below
                 packed = None
     if packed is not None:
         rk = rotated_kernels(tot.view(na4, 3, 3), kernels)                                           # [na*4,ks,3]
         gx, _ = _hip.so3_prep(xyz, xyz, ball_idx, rot, rot, anchors.contiguous(), 0)                  # rotated offsets (L1859-1862)
-        if contract:
-            y = _InterConv.apply(feats, W, None, None, _InterConvArgs(ball_idx, gx, rk, None, sigma, 0, shift=packed))
-        else:
-            y = _InterGroup.apply(feats, ball_idx, gx, rk, None, float(sigma), 0, None, None, packed)
+        a = _InterConvArgs(ball_idx, gx, rk, None, sigma, 0, shift=packed)
+        y = _InterConv.apply(feats, W, None, None, a) if contract else _Group.apply(feats, _MapGrouping(a))
         return ball_idx, InterWeights(gx, rk, sigma), y
     f5 = feats.contiguous().view(b, c, p, na, 4)
     if shift is None:
@@ -2192,7 +2102,7 @@ def inter_so3conv_fused_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, ra
     if W.dtype != torch.float32 or not W.is_cuda:
         raise RuntimeError('use_2d: W must be a float32 device tensor (float32 only: the float64 regime does not cover this variant)')
     _, w, y = _conv_2d(xyz, pose, feats, W, n_neighbor, anchors, kernels, radius, sigma, permute, contract=True)
-    return (w.materialize() if MATERIALIZE_INTER_W else w), y
+    return _inter_w(w), y
 
 
 def inter_so3poseconv_grouping_strided_2D(xyz, pose, feats, stride, n_neighbor, anchors, kernels, radius, sigma, inter_idx=None,
@@ -2206,7 +2116,7 @@ def inter_so3poseconv_grouping_strided_2D(xyz, pose, feats, stride, n_neighbor, 
     if inter_idx is None and stride > 1:
         raise NotImplementedError('use_2d with stride > 1: the reference\'s strided branch (functional.py:L1754-1810) does not match its 240-anchor features')
     _, w, new_feats = _conv_2d(xyz, pose, feats, None, n_neighbor, anchors, kernels, radius, sigma, permute_modes != 0, contract=False)
-    return inter_idx, (w.materialize() if MATERIALIZE_INTER_W else w), xyz, new_feats, None, pose
+    return inter_idx, _inter_w(w), xyz, new_feats, None, pose
 
 
 def inter_so3conv_grouping(xyz, feats, stride, n_neighbor, anchors, kernels, radius, sigma,
@@ -2235,9 +2145,9 @@ def inter_so3conv_grouping(xyz, feats, stride, n_neighbor, anchors, kernels, rad
         return inter_idx, inter_w, new_xyz, new_feats, sample_idx
     # cached neighbourhood from an earlier layer (functional.py:L195-201)
     if isinstance(inter_w, InterWeights) and _call_dtype('inter_so3conv_grouping', feats=feats, inter_w=inter_w.gx) == torch.float64:
-        new_feats = _InterGroupF64.apply(feats, _F64Args(inter_idx, inter_w.gx, inter_w.r, inter_w.rk, None, None, inter_w.sigma))
+        new_feats = _Group.apply(feats, _F64Args(inter_idx, inter_w.gx, inter_w.r, inter_w.rk, None, None, inter_w.sigma))
     elif isinstance(inter_w, InterWeights):
-        new_feats = _InterGroup.apply(feats, inter_idx, inter_w.gx, inter_w.rk, None, inter_w.sigma, 0, None)
+        new_feats = _Group.apply(feats, _ListGrouping(_InterConvArgs(inter_idx, inter_w.gx, inter_w.rk, None, inter_w.sigma, 0)))
     else:
         new_feats = inter_so3conv_feat_grouping(inter_idx, inter_w, zpconv.add_shadow_feature(feats))
     return inter_idx, inter_w, xyz, new_feats, None
@@ -2268,18 +2178,17 @@ def intra_so3conv_grouping(intra_idx, feature):
     """intra_idx [na,pnn], feature [nb,c,np,na] -> [nb,c,pnn,np,na] (functional.py:L2553-2602)."""
     if not feature.is_cuda:
         raise RuntimeError('intra_so3conv_grouping: device tensors only')
-    if _call_dtype('intra_so3conv_grouping', feature=feature) == torch.float64:
-        return _IntraGroupF64.apply(feature, intra_idx.to(torch.int32).contiguous())
-    return _IntraGroup.apply(feature, intra_idx.to(torch.int32).contiguous())
+    f64 = _call_dtype('intra_so3conv_grouping', feature=feature) == torch.float64
+    return _Group.apply(feature, _IntraGrouping(intra_idx, 'f64' if f64 else 'f32'))
 
 
 def intra_so3conv_grouping_2D(intra_idx, feature):
     """The 2-D variant (functional.py:L2606-2628): the anchor axis is (na, 4); the 12-tap gather acts on na.
-    feature [nb,c,np,na*4] -> [nb,c,pnn,np,na*4].  float32 device tensors: one kernel each way (_IntraGroup2D); anything else: the
+    feature [nb,c,np,na*4] -> [nb,c,pnn,np,na*4].  float32 device tensors: one kernel each way (_IntraGrouping '2d'); anything else: the
     reference's tensor expression (a view + one gather)."""
     nb, c_in, nq, tot_na = feature.shape
     if feature.is_cuda and feature.dtype == torch.float32:
-        return _IntraGroup2D.apply(feature, intra_idx.to(torch.int32).contiguous())
+        return _Group.apply(feature, _IntraGrouping(intra_idx, '2d'))
     f = feature.contiguous().view(nb, c_in, nq, -1, 4)
     na = f.size(-2)
     _, pnn = intra_idx.shape

@@ -164,7 +164,7 @@ class IntraSO3Conv(nn.Module):
     def forward(self, x):
         feats = x.feats
         if feats.is_cuda and feats.dtype == torch.float64:
-            # the float64 regime: gather + contraction as one node, a slab of clouds at a time (L._IntraConvF64)
+            # the float64 regime: gather + contraction as one node, a slab of clouds at a time (L._GroupContractF64 around L._IntraGrouping)
             out = L.intra_so3conv(feats, self.basic_conv.W, self.intra_idx)
         elif feats.is_cuda and feats.dtype == torch.float32 and feats.shape[3] % 4 == 0 and feats.shape[3] <= 64:
             # implicit GEMM in both directions: the 12-tap gather is folded into the contraction's operand load, the

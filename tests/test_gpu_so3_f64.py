@@ -1,5 +1,5 @@
-"""GPU: the float64 regime of the SO(3) conv layers (csrc/so3_f64.hip; vgtk.so3conv.functional _InterConvF64 / _IntraConvF64 /
-_ContractF64) against exact integer products, the reference-made fixture, the CPU oracle in float64, finite differences, itself (run to
+"""GPU: the float64 regime of the SO(3) conv layers (csrc/so3_f64.hip; vgtk.so3conv.functional _GroupContractF64 around _F64Args /
+_IntraGrouping, _ContractF64) against exact integer products, the reference-made fixture, the CPU oracle in float64, finite differences, itself (run to
 run, slab size to slab size) and as the checker of the float32 layer.
 
 Bars (tests/so3_f64_cases.py): 1e-12 of the reference's scale for outputs and gradients, 1e-13 for inter_w and for the random GEMMs (sums of
@@ -346,7 +346,7 @@ def test_gradcheck_inter_node(dev):
     import vgtk.so3conv.functional as L
     args, feats, W = small_inter_node(dev)
     assert args.mult is not None and len(torch.unique(args.r)) > 1        # the poses really permute the anchors
-    assert torch.autograd.gradcheck(lambda f, w: L._InterConvF64.apply(f, w, args), (feats, W))
+    assert torch.autograd.gradcheck(lambda f, w: L._GroupContractF64.apply(f, w, args), (feats, W))
 
 
 def test_gradcheck_intra_node(dev):
@@ -355,7 +355,7 @@ def test_gradcheck_intra_node(dev):
     feats = torch.randn(1, 2, 3, 60, generator=gen, dtype=torch.float64).to(dev).requires_grad_(True)
     W = torch.randn(3, 24, generator=gen, dtype=torch.float64).to(dev).requires_grad_(True)
     idx = torch.from_numpy(L.get_intra_idx()).to(torch.int32).to(dev).contiguous()
-    assert torch.autograd.gradcheck(lambda f, w: L._IntraConvF64.apply(f, w, idx), (feats, W))
+    assert torch.autograd.gradcheck(lambda f, w: L._GroupContractF64.apply(f, w, L._IntraGrouping(idx, 'f64')), (feats, W))
 
 
 def layer_pair(dev):

@@ -10,7 +10,9 @@ positional functions are replaced by recorders here (nothing is launched); tenso
 
 The SITES rows restate the sites' view expressions: an edit to a site does not fail its row.  Where the function of functional.py runs on
 host tensors (_contract_into, _weight_grad_from_z, _rows_grad_from_z) test_the_functions_of_the_operator_layer_make_these_calls calls it
-against the same rows; the other sites are held by the GPU suite.
+against the same rows.  _backward_textbook and _group_contract are functions of a grouping pair: with a stub pair (zero tensors, counted
+calls) they run on host tensors too -- the float32 products against the `_backward_textbook` rows, the float64 ones through a recorder in
+place of _hip.call (the `_backward_map` rows are the same function on the same views).  The other sites are held by the GPU suite.
 
 A recorded call is the full parameter list of the positional function, in its order (defaults filled in); a tensor is compared by
 its data pointer, anything else by equality (a b_bound tuple by identity)."""
@@ -251,6 +253,104 @@ def test_the_functions_of_the_operator_layer_make_these_calls(rec, monkeypatch):
     g = F._rows_grad_from_z(z, W2, c, rp, na, ldz, True, zb)
     assert g.shape == (b, c, rp, na) and len(rec.calls) == 1
     same(rec.calls[0], rows['_rows_grad_from_z'], dict(W2=W2, z=z, gFc=rec.calls[0][12], bound=zb))
+
+
+# ---- the skeleton around a grouping pair ----------------------------------------------------------------------------------------------
+
+n_sup = 5                                        # support rows per cloud
+
+
+class StubGrouping:
+    """a grouping pair whose two methods return zero tensors of the right shape and record their calls"""
+
+    def __init__(self, layout=0, dtype=torch.float32):
+        self.layout, self.mid, self.dtype = layout, ks, dtype
+        self.grouped, self.transposed, self.made = [], [], []
+
+    def group(self, feats, b0, b1):
+        self.grouped.append((b0, b1))
+        self.made.append(torch.zeros(b1 - b0, feats.shape[1], self.mid, p, na, dtype=self.dtype))
+        return self.made[-1]
+
+    def group_transposed(self, gx, n, b0, b1):
+        assert tuple(gx.shape) == (b1 - b0, c, self.mid, p, na) and gx.is_contiguous() and n == n_sup
+        self.transposed.append((b0, b1, gx.data_ptr()))
+        return torch.zeros(b1 - b0, c, n, na, dtype=self.dtype)
+
+
+def test_the_textbook_backward_of_a_pair_makes_these_calls(rec):
+    """float32, the whole batch in one slab: dW in the view expression of the layout, then dX from W^T written out; X regrouped only for dW"""
+    from vgtk.so3conv import functional as F
+    rows = {s[0]: s[2] for s in SITES}
+    gy, W, feats, x = f32(b, o, p, na), f32(o, ck), f32(b, c, n_sup, na), f32(b, c, ks, p, na)
+    for layout, row in ((2, '_backward_textbook, dW from the transposed intermediate'), (0, '_backward_textbook, dW from the row-major intermediate')):
+        del rec.calls[:]
+        stub = StubGrouping(layout)
+        gF, gW = F._backward_textbook(stub, gy, W, feats, x, True, True, [(0, b)])
+        assert [call[0] for call in rec.calls] == ['gemm_reduce', 'gemm']                 # X kept: dW first, then dX
+        same(rec.calls[0], rows[row], dict(gy=gy, x=x, gW=gW))
+        Wt, gx = rec.calls[1][6], rec.calls[1][12]
+        same(rec.calls[1], rows['_backward_textbook, dX'], dict(Wt=Wt, gy=gy, gx=gx))
+        assert Wt.data_ptr() != W.data_ptr() and tuple(Wt.shape) == (ck, o) and Wt.is_contiguous()      # W^T written out
+        assert stub.grouped == [] and stub.transposed == [(0, b, gx.data_ptr())]
+        assert tuple(gF.shape) == tuple(feats.shape) and tuple(gW.shape) == tuple(W.shape)
+    # X not kept
+    for need_f, need_w, groups, calls in ((False, True, 1, ['gemm_reduce']), (True, False, 0, ['gemm']), (True, True, 1, ['gemm_reduce', 'gemm'])):
+        del rec.calls[:]
+        stub = StubGrouping(0)
+        gF, gW = F._backward_textbook(stub, gy, W, feats, None, need_f, need_w, [(0, b)])
+        assert len(stub.grouped) == groups and len(stub.transposed) == int(need_f), (need_f, need_w, stub.grouped)
+        assert [call[0] for call in rec.calls] == calls
+        assert (gF is not None) == need_f and (gW is not None) == need_w
+        if need_w:
+            same(rec.calls[0], rows['_backward_textbook, dW from the row-major intermediate'], dict(gy=gy, x=stub.made[0], gW=gW))
+
+
+def test_the_textbook_backward_in_float64_runs_slab_by_slab(monkeypatch):
+    """float64: X regrouped per slab, dW accumulated onto the slabs before, dX from the VIEW W^T (no copy), every product over its slab's clouds"""
+    from vgtk import _hip
+    from vgtk.so3conv import functional as F
+    calls = []
+    monkeypatch.setattr(_hip, 'call', lambda name, ref, *args, tag=None: calls.append((name,) + args))
+    f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
+    nb = 3
+    gy, W, feats = f64(nb, o, p, na), f64(o, ck), f64(nb, c, n_sup, na)
+    one_cloud = 8 * ck * pa
+    for limit, want in ((one_cloud, [(0, 1), (1, 2), (2, 3)]), (1 << 62, [(0, 3)])):
+        del calls[:]
+        monkeypatch.setattr(F, 'F64_X_BYTES_MAX', limit)
+        slabs = F._f64_slabs(nb, one_cloud)
+        assert slabs == want
+        stub = StubGrouping(0, torch.float64)
+        gF, gW = F._backward_textbook(stub, gy, W, feats, None, True, True, slabs)
+        assert [call[0] for call in calls] == ['eap_gemm_f64_reduce', 'eap_gemm_f64'] * len(slabs)      # per slab: dW, then dX
+        reduces, products = calls[0::2], calls[1::2]
+        # (ta, tb, M, N, K, A, lda, sa, B, ldb, sb, out, ldc, batch, accumulate) / (..., out, ldc, sc, batch)
+        assert [r[15] for r in reduces] == [int(b0 > 0) for b0, _ in slabs]
+        assert [r[14] for r in reduces] == [b1 - b0 for b0, b1 in slabs] and [g[15] for g in products] == [b1 - b0 for b0, b1 in slabs]
+        for (b0, b1), r, g, x in zip(slabs, reduces, products, stub.made):
+            assert r[6].data_ptr() == gy[b0:b1].data_ptr() and r[9].data_ptr() == x.data_ptr() and r[12].data_ptr() == gW.data_ptr()
+            assert g[1] == 1 and g[6].data_ptr() == W.data_ptr() and g[9].data_ptr() == gy[b0:b1].data_ptr()      # A = W^T as a view of W
+        assert stub.grouped == slabs and [t[:2] for t in stub.transposed] == slabs
+        assert tuple(gF.shape) == tuple(feats.shape) and gF.dtype == torch.float64
+
+
+def test_the_forward_loop_of_a_pair_groups_and_contracts_slab_by_slab(rec, monkeypatch):
+    from vgtk.so3conv import functional as F
+    monkeypatch.setattr(F, 'X_CHUNK_CLOUDS', 2)
+    nb = 3
+    W, feats, y = f32(o, ck), f32(nb, c, n_sup, na), f32(nb, o, p, na)
+    contract = lambda W, x, ys, b0: F._contract_into(W, x, ys, 0)
+    stub = StubGrouping(0)
+    assert F._group_contract(stub, feats, W, y, F._f32_slabs(nb, False), False, contract) is None       # X is scratch
+    assert stub.grouped == [(0, 2), (2, 3)] and len(rec.calls) == 2
+    for (b0, b1), x, got in zip(stub.grouped, stub.made, rec.calls):
+        same(got, ('gemm', 0, 0, o, pa, ck, 'W', ck, 0, 'x', pa, ck * pa, 'y', pa, o * pa, b1 - b0, False, None), dict(W=W, x=x, y=y[b0:b1]))
+    del rec.calls[:]
+    stub = StubGrouping(0)
+    kept = F._group_contract(stub, feats, W, y, F._f32_slabs(nb, True), True, contract)                  # a kept X: one slab of all clouds
+    assert stub.grouped == [(0, 3)] and kept is stub.made[0] and len(rec.calls) == 1
+    same(rec.calls[0], ('gemm', 0, 0, o, pa, ck, 'W', ck, 0, 'x', pa, ck * pa, 'y', pa, o * pa, nb, False, None), dict(W=W, x=kept, y=y))
 
 
 # ---- the derivation -----------------------------------------------------------------------------------------------------------------
