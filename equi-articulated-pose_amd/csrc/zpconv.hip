@@ -171,7 +171,8 @@ int inter_zpconv_bwd_flagged(int b, int np, int nq, int na, int ks, int ann, int
 }  // namespace eap
 
 // Every entry names the regime it chose (eap_last_kernel): zpconv_fwd_rows / zpconv_fwd_scalar / zpconv_bwd_scatter / intra_zpconv here,
-// zpconv_fwd_matrix, zpconv_bwd_products and zp_hot_kernel in their own files.
+// zpconv_fwd_matrix, zpconv_bwd_products and zp_hot_kernel in their own files, as are the ordered backwards a caller asks for
+// (zpconv_bwd_ordered, intra_zpconv_bwd_ordered: csrc/native_ordered.hip).
 #define EAP_INTER(NAME, T, BWD)                                                                  \
     extern "C" int NAME(int b, int np, int nq, int na, int ks, int ann, int c, const int32_t *idx, \
                         const T *w, const T *src, T *dst, eap_stream_t stream) {                 \

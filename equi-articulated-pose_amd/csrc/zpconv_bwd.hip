@@ -214,13 +214,16 @@ extern "C" int64_t eap_inter_zpconv_bwd_workspace(int b, int np, int nq, int na,
     return BwdWorkspace(b, np, nq, na, ann, c).total;
 }
 
+extern "C" int eap_inter_zpconv_bwd_ws_takes(int np, int nq, int na, int ks, int ann, int c) {
+    return eap::inter_zpconv_bwd_matrix_supported(np, nq, na, ks, ann, c) && (ann & 3) == 0 && (long long)na * ks * ann < (1ll << 31);
+}
+
 extern "C" int eap_inter_zpconv_bwd_ws_f32(int b, int np, int nq, int na, int ks, int ann, int c, const int32_t *idx,
                                            const float *w, const float *grad, float *gfeats, void *workspace,
                                            eap_stream_t stream) {
     if (b <= 0 || np <= 0 || c <= 0) return eap_inter_zpconv_bwd_f32(b, np, nq, na, ks, ann, c, idx, w, grad, gfeats, stream);
     hipStream_t s = eap::S(stream);
-    const bool matrix = workspace != nullptr && eap::inter_zpconv_bwd_matrix_supported(np, nq, na, ks, ann, c) && (ann & 3) == 0 &&
-                        (long long)na * ks * ann < (1ll << 31) &&
+    const bool matrix = workspace != nullptr && eap_inter_zpconv_bwd_ws_takes(np, nq, na, ks, ann, c) &&
                         // 16-byte accesses: idx (int4 rows), grad (the A operand's quads), gfeats (float4 along the anchors) and the
                         // workspace; w is read 4 bytes per lane (ld_off<float>) and may sit at any 4-byte offset
                         eap::aligned16(idx, grad, gfeats, reinterpret_cast<const char *>(workspace));

@@ -14,6 +14,7 @@ import os
 import re
 import struct
 import types
+import warnings
 import weakref
 
 import torch
@@ -160,6 +161,27 @@ def suffix(t):
     if t.dtype == torch.float64:
         return 'f64'
     raise RuntimeError(f'unsupported dtype {t.dtype} (float32 / float64 only)')
+
+
+def use_ordered(ordered):
+    """The `ordered=` keyword of the backward operators that have both a scatter kernel and an ordered one: None follows
+    torch.are_deterministic_algorithms_enabled() (the rule of chamfer.backward), True / False force the choice."""
+    return torch.are_deterministic_algorithms_enabled() if ordered is None else bool(ordered)
+
+
+def no_deterministic(op, why, requested=False):
+    """torch's contract for an op that is about to run a float-atomic scatter because no ordered kernel can serve the call: under
+    torch.use_deterministic_algorithms(True) raise, under warn_only=True warn the same text and let the caller scatter, with the
+    flag off say nothing.  requested: the caller passed ordered=True itself -- then the call is refused whatever the flag says."""
+    msg = (f'{op} does not have a deterministic implementation for this call ({why}), but you set '
+           '\'torch.use_deterministic_algorithms(True)\' or asked for ordered=True. You can turn off determinism just for this '
+           'operation, or pass ordered=False to run its atomicAdd scatter.')
+    if torch.are_deterministic_algorithms_enabled():
+        if not torch.is_deterministic_algorithms_warn_only_enabled():
+            raise RuntimeError(msg)
+        warnings.warn(msg, stacklevel=3)
+    elif requested:
+        raise RuntimeError(msg)
 
 
 # ---- raw launchers used by the operator layer ---------------------------------------------------
@@ -748,6 +770,9 @@ def so3_inter_group_bwd(gout, idx, gx, rk, mult, sigma, n, identity_anchor=0):
                          device=gout.device)
         call('eap_so3_inter_group_bwd_slab_f32', gfeats, b, c, p, n, nn, na, ks, sigma, gout, idx, gx, rk, mult, int(identity_anchor), gfeats, ws)
         return gfeats
+    # (the one SO(3) site that still scatters: float atomicAdd into gfeats)
+    no_deterministic('so3_inter_group_bwd', 'FORCE_ATOMIC_BWD is set' if FORCE_ATOMIC_BWD else
+                     f'ks = {ks}, na = {na}: the atomics-free kernel takes ks <= 24 and na % 4 == 0')
     call('eap_so3_inter_group_bwd_f32', gfeats, b, c, p, n, nn, na, ks, sigma, gout, idx, gx, rk, mult, gfeats)
     return gfeats
 
@@ -863,6 +888,23 @@ def inv_lists_rows(idx, n):
     n_rows = torch.empty(b, dtype=torch.int32, device=dev)
     call('eap_inv_lists_rows', idx, b, p, n, nn, idx, counts, rows, off, cnt, n_rows)
     return rows, off, cnt, n_rows
+
+
+INV_LISTS_MAX_ROWS = 16384      # target rows per cloud the list builders take (csrc/inv_lists.hip)
+GRID_YZ_MAX = 65535             # grid.y / grid.z of a launch (eap_launch_dims_ok): clouds, channel groups, cloud x anchor pairs
+
+
+def inv_lists(idx, n):
+    """idx int32 [b,p,nn] -> (rows, off, cnt, ent): for every one of the n target rows the entry numbers p * nn + slot that name it,
+    ascending (eap_inv_lists_rows + eap_inv_lists_entries_ws, the builder whose cost does not grow with the number of rows); what the
+    ordered backward of the point gather walks."""
+    check_input(idx)
+    b, p, nn = idx.shape
+    rows, off, cnt, _ = inv_lists_rows(idx, n)
+    ent = torch.empty(b, p * nn, dtype=torch.int32, device=idx.device)
+    ws = torch.empty((int(abi.eap_inv_lists_entries_workspace(b, p, n, nn)) + 3) // 4, dtype=torch.int32, device=idx.device)
+    call('eap_inv_lists_entries_ws', idx, b, p, n, nn, idx, rows, off, ent, ws)
+    return rows, off, cnt, ent
 
 
 def inv_lists_fill(idx, gx, rows, off, rcap):

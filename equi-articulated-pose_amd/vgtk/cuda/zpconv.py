@@ -35,12 +35,17 @@ def inter_zpconv_forward(idx, w, feats):
     return out
 
 
-def inter_zpconv_backward(idx, w, grad, npoint):
-    """(idx, w, grad T [B,C,K,P,A], int npoint) -> T [B,C,npoint,A]; zpconv_cuda.cpp:L58-75."""
+def inter_zpconv_backward(idx, w, grad, npoint, ordered=None):
+    """(idx, w, grad T [B,C,K,P,A], int npoint) -> T [B,C,npoint,A]; zpconv_cuda.cpp:L58-75.
+    ordered: no float atomicAdd anywhere.  The float32 on-chip kernel and product pipeline keep the clouds they take (they sum in a
+    fixed order already); the clouds they leave, every call that gets no scratch for them and every float64 call go to
+    eap_inter_zpconv_bwd_ordered_* instead of the scatter kernel.  None: torch.are_deterministic_algorithms_enabled()."""
     _check(idx, w, grad)
     b, np_, na, ks, ann = idx.shape
     c = grad.shape[1]
     out = torch.empty(b, c, int(npoint), na, dtype=grad.dtype, device=grad.device)
+    if _hip.use_ordered(ordered) and b > 0:
+        return _backward_ordered_any(idx, w, grad, int(npoint), out, ordered is True)
     if grad.dtype == torch.float32 and b > 0:
         # 1. scatter target on chip (csrc/zpconv_bwd_hot.hip): clouds whose lists reference few support rows, whole batch
         #    in one launch, nothing but the operands moves; the per-cloud status comes back in one small read
@@ -63,6 +68,7 @@ def inter_zpconv_backward(idx, w, grad, npoint):
     return out
 
 
+ORDERED_TABLE_BYTES = 64 << 10      # LDS the ordered intra backward inverts its table in (csrc/native_ordered.hip)
 ON_CHIP_BACKWARD = True     # False: always the product pipeline of csrc/zpconv_bwd.hip (A/B runs, tests)
 
 
@@ -97,11 +103,12 @@ def _check_pending_verdicts(block=False):
                                'through torch in-place ops or pass a new tensor')
 
 
-def _backward_on_chip(idx, w, grad, out):
+def _backward_on_chip(idx, w, grad, out, remember=True):
     """-> clouds still to do (all of them when the shape is not taken).  The verdict depends on the INDEX alone (which clouds
     name a row twice / reference too many rows), so it is remembered per index tensor: a training loop that keeps its
     neighbourhood pays the status read once, and a batch the kernel cannot take at all (padded lists: small radii, sparse or
-    partial input) skips its prelude from the second call on.  Re-checked on the device every call: _check_pending_verdicts."""
+    partial input) skips its prelude from the second call on.  Re-checked on the device every call: _check_pending_verdicts.
+    remember=False: the verdict is read back and neither looked up nor stored (the table of remembered verdicts stays the default path's)."""
     _check_pending_verdicts()
     b, np_, na, ks, ann = idx.shape
     c, nq = grad.shape[1], out.shape[2]
@@ -110,7 +117,7 @@ def _backward_on_chip(idx, w, grad, out):
     if nbytes <= 0 or any(t.data_ptr() % 16 for t in (idx, grad, out)):
         return list(range(b))
     key = (_verdict_key(idx), c, nq)
-    hit = _HOT_VERDICTS.get(key)
+    hit = _HOT_VERDICTS.get(key) if remember else None
     known = hit[1] if (hit is not None and hit[0]() is idx) else None
     if known is not None and len(known) == b:
         return list(known)                                   # nothing for the on-chip kernel here (every cloud goes to the product pipeline: correct whatever the index holds)
@@ -128,6 +135,8 @@ def _backward_on_chip(idx, w, grad, out):
             _HOT_PENDING.append([ev, host, tuple(known), key])
         return list(known)
     todo = [i for i, s in enumerate(status.tolist()) if s != 0]
+    if not remember:
+        return todo
     if len(_HOT_VERDICTS) > 64:
         _HOT_VERDICTS.clear()
     import weakref
@@ -135,9 +144,80 @@ def _backward_on_chip(idx, w, grad, out):
     return todo
 
 
-def _backward_with_products(idx, w, grad, npoint, out=None):
+def _runs(items):
+    """sorted cloud numbers -> [(first, past the last)] of every run of consecutive ones"""
+    runs = []
+    for i in items:
+        if runs and runs[-1][1] == i:
+            runs[-1][1] = i + 1
+        else:
+            runs.append([i, i + 1])
+    return [tuple(r) for r in runs]
+
+
+def _backward_ordered(idx, w, grad, npoint, out, requested):
+    """csrc/native_ordered.hip: any 5-D index, either width; the clouds in slices whose scratch (twice the index) stays under
+    BWD_WORKSPACE_BYTES.  Where the lists cannot be built or the scratch cannot be had: torch's policy (_hip.no_deterministic), then
+    the scatter kernel."""
+    b, np_, na, ks, ann = idx.shape
+    c = grad.shape[1]
+    sfx = _hip.suffix(grad)
+    why = None
+    if npoint > _hip.INV_LISTS_MAX_ROWS:
+        why = f'{npoint} target rows, the inverse lists take {_hip.INV_LISTS_MAX_ROWS}'
+    elif na > _hip.GRID_YZ_MAX or c > 16 * _hip.GRID_YZ_MAX:
+        why = f'{na} anchors, {c} channels: the ordered kernel takes {_hip.GRID_YZ_MAX} anchors and {16 * _hip.GRID_YZ_MAX} channels'
+    ws = None
+    if why is None:
+        per_cloud = int(_hip.abi.eap_inter_zpconv_bwd_ordered_workspace(1, np_, npoint, na, ks, ann))
+        step = min(b, BWD_WORKSPACE_BYTES // max(per_cloud, 1), _hip.GRID_YZ_MAX // max(na, 1))
+        if step >= 1:
+            try:
+                ws = torch.empty((int(_hip.abi.eap_inter_zpconv_bwd_ordered_workspace(step, np_, npoint, na, ks, ann)) + 3) // 4,
+                                 dtype=torch.int32, device=grad.device)
+            except torch.cuda.OutOfMemoryError:
+                ws = None
+        if ws is None:
+            why = f'{per_cloud} bytes of scratch per cloud cannot be had (BWD_WORKSPACE_BYTES = {BWD_WORKSPACE_BYTES})'
+    if why is not None:
+        _hip.no_deterministic('inter_zpconv_backward', why, requested=requested)
+        _hip.call('eap_inter_zpconv_bwd_' + sfx, out, b, np_, npoint, na, ks, ann, c, idx, w, grad, out)
+        return out
+    for b0 in range(0, b, step):
+        nb = min(step, b - b0)
+        _hip.call('eap_inter_zpconv_bwd_ordered_' + sfx, out, nb, np_, npoint, na, ks, ann, c, idx[b0:b0 + nb], w[b0:b0 + nb], grad[b0:b0 + nb],
+                  out[b0:b0 + nb], ws)
+    return out
+
+
+def _backward_ordered_any(idx, w, grad, npoint, out, requested):
+    """ordered=True.  float64: the ordered kernel.  float32: per run of clouds, the atomics-free paths of the default route where
+    they serve a cloud WITHOUT their scatter fall-back -- which they do for a cloud whose index is one list per point (compared here,
+    one host read per cloud: this is the deterministic mode, not the fast one), the product pipeline on top of that only for the
+    sizes and alignments it takes and with its scratch in hand -- and the ordered kernel for the rest."""
+    b, np_, na, ks, ann = idx.shape
+    c = grad.shape[1]
+    if grad.dtype != torch.float32:
+        return _backward_ordered(idx, w, grad, npoint, out, requested)
+    shared = [bool((idx[i] == idx[i, :, :1, :1, :]).all()) for i in range(b)] if np_ * na * ks * ann > 0 else [False] * b
+    rest = [i for i in range(b) if not shared[i]]
+    for b0, b1 in _runs([i for i in range(b) if shared[i]]):
+        sl = idx[b0:b1], w[b0:b1], grad[b0:b1], out[b0:b1]
+        left = _backward_on_chip(*sl, remember=False)          # (slices are temporaries: nothing to remember a verdict by)
+        pipeline = bool(_hip.abi.eap_inter_zpconv_bwd_ws_takes(np_, npoint, na, ks, ann, c))
+        for r0, r1 in _runs(left):
+            part = [t[r0:r1] for t in sl]
+            aligned = all(t.data_ptr() % 16 == 0 for t in (part[0], part[2], part[3]))
+            if not (pipeline and aligned and _backward_with_products(part[0], part[1], part[2], npoint, part[3], scatter=False) is not None):
+                rest += range(b0 + r0, b0 + r1)
+    for b0, b1 in _runs(sorted(rest)):
+        _backward_ordered(idx[b0:b1], w[b0:b1], grad[b0:b1], npoint, out[b0:b1], requested)
+    return out
+
+
+def _backward_with_products(idx, w, grad, npoint, out=None, scatter=True):
     """csrc/zpconv_bwd.hip: products in forward order + sorted sums (any number of referenced rows), scratch-free scatter
-    kernel when no scratch can be had."""
+    kernel when no scratch can be had (scatter=False: None then, nothing launched)."""
     b, np_, na, ks, ann = idx.shape
     c = grad.shape[1]
     if out is None:
@@ -153,6 +233,8 @@ def _backward_with_products(idx, w, grad, npoint, out=None):
         except torch.cuda.OutOfMemoryError:
             ws = None
     if ws is None:
+        if not scatter:
+            return None
         _hip.call('eap_inter_zpconv_bwd_f32', out, b, np_, int(npoint), na, ks, ann, c, idx, w, grad, out)
         return out
     for b0 in range(0, b, step):
@@ -174,12 +256,23 @@ def intra_zpconv_forward(idx, w, feats):
     return out
 
 
-def intra_zpconv_backward(idx, w, grad, anchor_in):
-    """(idx, w, grad T [B,C,K,P,A_out], int anchor_in) -> T [B,C,P,anchor_in]; zpconv_cuda.cpp:L94-110."""
+def intra_zpconv_backward(idx, w, grad, anchor_in, ordered=None):
+    """(idx, w, grad T [B,C,K,P,A_out], int anchor_in) -> T [B,C,P,anchor_in]; zpconv_cuda.cpp:L94-110.
+    ordered: the sum over a, then k, then n ascending with idx[a,n] == a' (eap_intra_zpconv_bwd_ordered_*: no float atomics, the same
+    bits every run) instead of the reference's atomicAdd scatter.  None: torch.are_deterministic_algorithms_enabled()."""
     _check(idx, w, grad)
     na_out, ann = idx.shape
     ks = w.shape[1]
     b, c, _, np_, _ = grad.shape
     out = torch.empty(b, c, np_, int(anchor_in), dtype=grad.dtype, device=grad.device)
+    if _hip.use_ordered(ordered):
+        # (the conditions of intra_ordered in csrc/native_ordered.hip: target rows, lanes, the LDS table, the grid)
+        if (int(anchor_in) <= _hip.INV_LISTS_MAX_ROWS and na_out <= 64 and 4 * (int(anchor_in) + 1 + 2 * na_out * ann) <= ORDERED_TABLE_BYTES
+                and b <= _hip.GRID_YZ_MAX and c <= _hip.GRID_YZ_MAX):
+            _hip.call('eap_intra_zpconv_bwd_ordered_' + _hip.suffix(grad), out, b, np_, int(anchor_in), na_out, ks, ann, c, idx, w, grad, out)
+            return out
+        _hip.no_deterministic('intra_zpconv_backward', f'{anchor_in} input anchors, a table of {na_out} x {ann}, {b} clouds, {c} channels: the ordered kernel '
+                              f'takes {_hip.INV_LISTS_MAX_ROWS} input and 64 output anchors, {ORDERED_TABLE_BYTES} bytes of inverted table in LDS, and '
+                              f'{_hip.GRID_YZ_MAX} clouds and channels', requested=ordered is True)
     _hip.call('eap_intra_zpconv_bwd_' + _hip.suffix(grad), out, b, np_, int(anchor_in), na_out, ks, ann, c, idx, w, grad, out)
     return out

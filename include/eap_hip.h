@@ -107,11 +107,20 @@ int eap_gather_points_bwd_f32(int b, int c, int n, int m, const float *grad_out,
                               const int32_t *idx, float *grad_pts, eap_stream_t stream);
 int eap_gather_points_bwd_f64(int b, int c, int n, int m, const double *grad_out,
                               const int32_t *idx, double *grad_pts, eap_stream_t stream);
+/* gather_points_backward (gathering_cuda.cpp:L45-60) as an ordered sum: grad_pts[b,c,q] = the grad_out[b,c,j] with idx[b,j] == q
+ * added in ascending j, starting from zero.  rows, off, cnt int32 [b,n] = eap_inv_lists_rows and ent int32 [b,m] =
+ * eap_inv_lists_entries (or _ws) of idx seen as [b,m,1] (n <= 16384, their limit).  grad_pts is fully written (zeros where nothing names
+ * a row); no floating-point atomics, bit-identical run to run.  Regime name: gather_points_bwd_ordered. */
+int eap_gather_points_bwd_ordered_f32(int b, int c, int n, int m, const float *grad_out, const int32_t *rows, const int32_t *off,
+                                      const int32_t *cnt, const int32_t *ent, float *grad_pts, eap_stream_t stream);
+int eap_gather_points_bwd_ordered_f64(int b, int c, int n, int m, const double *grad_out, const int32_t *rows, const int32_t *off,
+                                      const int32_t *cnt, const int32_t *ent, double *grad_pts, eap_stream_t stream);
 
 /* ---- zpconv (vgtk/vgtk/cuda/zpconv_cuda.cpp) ---------------------------------------------- */
 
 /* Every zpconv entry names the regime that served the call (eap_last_kernel): zpconv_fwd_matrix, zpconv_fwd_rows,
- * zpconv_fwd_scalar, zp_hot_kernel, zpconv_bwd_products, zpconv_bwd_scatter, intra_zpconv.  Operands may sit at any
+ * zpconv_fwd_scalar, zp_hot_kernel, zpconv_bwd_products, zpconv_bwd_scatter, intra_zpconv, and the ordered backwards
+ * (csrc/native_ordered.hip, taken on request only) zpconv_bwd_ordered and intra_zpconv_bwd_ordered.  Operands may sit at any
  * element-aligned address: a kernel that moves 16-byte words is selected only when every operand it touches that way is
  * 16-byte aligned (rows kernel: idx, w, feats, out; matrix forward: those and the workspace; product pipeline and on-chip
  * backward: idx, grad, gfeats and the workspace -- w is read 4 bytes per lane); the scalar kernels take the rest. */
@@ -149,6 +158,23 @@ int64_t eap_inter_zpconv_bwd_workspace(int b, int np, int nq, int na, int ann, i
 int eap_inter_zpconv_bwd_ws_f32(int b, int np, int nq, int na, int ks, int ann, int c,
                                 const int32_t *idx, const float *w, const float *grad, float *gfeats,
                                 void *workspace, eap_stream_t stream);
+/* 1 when eap_inter_zpconv_bwd_ws_f32 serves these sizes with its product pipeline (given 16-byte aligned idx, grad, gfeats and
+ * workspace), 0 when it would hand the whole call to the scatter kernel.  Host only. */
+int eap_inter_zpconv_bwd_ws_takes(int np, int nq, int na, int ks, int ann, int c);
+/* inter_zpconv_backward (zpconv_cuda.cpp:L58-75, kernel .cu:L77-116) as an ordered sum, for ANY 5-D index:
+ * gfeats[b,c,q,a] = the products grad[b,c,k,p,a] * w[b,p,a,k,n] with idx[b,p,a,k,n] == q, each rounded once, added in ascending
+ * entry number (p*ks + k)*ann + n, starting from zero.  The entry copies the index with the anchor axis next to the batch
+ * ([b*na, np, ks*ann]), builds the inverse lists of those b*na "clouds" (eap_inv_lists_rows, eap_inv_lists_entries_ws) and walks
+ * them; workspace: eap_inter_zpconv_bwd_ordered_workspace BYTES (about 8*b*na*np*ks*ann, twice the index, plus the list builders'
+ * tables; 256-byte aligned) -- split the batch to bound it.  nq <= 16384, b*na <= 65535.  gfeats is fully written; no floating-point atomics, bit-identical run to run.
+ * Regime name: zpconv_bwd_ordered. */
+int64_t eap_inter_zpconv_bwd_ordered_workspace(int b, int np, int nq, int na, int ks, int ann);
+int eap_inter_zpconv_bwd_ordered_f32(int b, int np, int nq, int na, int ks, int ann, int c,
+                                     const int32_t *idx, const float *w, const float *grad, float *gfeats,
+                                     void *workspace, eap_stream_t stream);
+int eap_inter_zpconv_bwd_ordered_f64(int b, int np, int nq, int na, int ks, int ann, int c,
+                                     const int32_t *idx, const double *w, const double *grad, double *gfeats,
+                                     void *workspace, eap_stream_t stream);
 /* The same op (zpconv_cuda.cpp:L58-75) with the scatter target held in LDS -- no per-(point, neighbour) intermediate
  * (csrc/zpconv_bwd_hot.hip): for clouds whose index is one neighbour list per point AND whose lists reference at most
  * eap_inter_zpconv_bwd_hot_rows() distinct support rows (large balls under the reference's first-nsample-in-index-order
@@ -176,6 +202,18 @@ int eap_intra_zpconv_bwd_f32(int b, int np, int na_in, int na_out, int ks, int a
 int eap_intra_zpconv_bwd_f64(int b, int np, int na_in, int na_out, int ks, int ann, int c,
                              const int32_t *idx, const double *w, const double *grad,
                              double *gfeats, eap_stream_t stream);
+/* intra_zpconv_backward (zpconv_cuda.cpp:L94-110, kernel .cu:L160-195) as an ordered sum, same operands:
+ * gfeats[b,c,p,a'] = the products grad[b,c,k,p,a] * w[a,k,n] with idx[a,n] == a', each rounded once, added over a ascending, then k
+ * ascending, then n ascending, starting from zero.  The table is inverted in LDS (4*(na_in + 1 + 2*na_out*ann) bytes <= 64 KB;
+ * na_in <= 16384).  Meant for SMALL tables (the reference's are 60 x 12): every block of 32 points inverts the table again, each lane
+ * scanning all of it, with a serial prefix over na_in -- at the largest sizes admitted that prelude dominates.  gfeats is fully written; no
+ * floating-point atomics.  Regime name: intra_zpconv_bwd_ordered. */
+int eap_intra_zpconv_bwd_ordered_f32(int b, int np, int na_in, int na_out, int ks, int ann, int c,
+                                     const int32_t *idx, const float *w, const float *grad, float *gfeats,
+                                     eap_stream_t stream);
+int eap_intra_zpconv_bwd_ordered_f64(int b, int np, int na_in, int na_out, int ks, int ann, int c,
+                                     const int32_t *idx, const double *w, const double *grad,
+                                     double *gfeats, eap_stream_t stream);
 
 /* ---- SO(3) inter convolution (vgtk/vgtk/so3conv/functional.py) ---------------------------- */
 
@@ -1098,6 +1136,14 @@ int eap_so3_inter_group_fwd_f64(int b, int c, int p, int n, int nn, int na, int 
  * the entry numbers p * nn + n that name it, ascending, at ent[b, off .. off + cnt) -- ent int32 [b, p*nn].  Any p * nn; n <= 16384. */
 int eap_inv_lists_entries(int b, int p, int n, int nn, const int32_t *idx, const int32_t *rows, const int32_t *off, int32_t *ent,
                           eap_stream_t stream);
+/* inv_lists_entries_ws: what eap_inv_lists_entries writes, bit for bit, by a stable counting sort in chunks of 8192 entries
+ * (csrc/native_ordered.hip): the index is read twice whatever the number of rows, where eap_inv_lists_entries reads a cloud's entries
+ * twice per referenced row -- the builder for many short lists (the ordered backwards of the point gather and of the inter zpconv).
+ * workspace: eap_inv_lists_entries_workspace BYTES (4 * b * ceil(p*nn / 8192) * n, 256-byte rounded), 4-byte aligned.  n <= 16384,
+ * b <= 65535. */
+int64_t eap_inv_lists_entries_workspace(int b, int p, int n, int nn);
+int eap_inv_lists_entries_ws(int b, int p, int n, int nn, const int32_t *idx, const int32_t *rows, const int32_t *off, int32_t *ent,
+                             void *workspace, eap_stream_t stream);
 /* so3_inter_group_bwd_f64: the autograd of so3conv/functional.py:L1221-1261 w.r.t. feats, twin of eap_so3_inter_group_bwd_f32.
  * gout [b,c,ks,p,na]; rows, off, cnt int32 [b,n] (eap_inv_lists_rows), ent (eap_inv_lists_entries); multinv uint8 [na,na] = the
  * row-wise inverse of mult, or NULL -> gfeats [b,c,n,na] (fully written).  One workgroup per referenced row and 16 channels sums the
