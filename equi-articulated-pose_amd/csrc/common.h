@@ -45,6 +45,14 @@ static inline hipStream_t S(eap_stream_t s) { return (hipStream_t)s; }
 
 static inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
+// Row slots of a cloud with n_rows referenced rows in a batch of rp slots, in whole 16-row groups (csrc/so3_dense.hip: the dense index keeps
+// 16 row slots together): where the trimmed backward product ends, and the anchor pitch of PACKED Z -- column (a, r) of the cloud at
+// a live16 + r, its na live16 live columns one prefix of the row.  0 for a cloud without rows.
+__host__ __device__ static inline int live16(int n_rows, int rp) {
+    const int n = n_rows < rp ? n_rows : rp;
+    return n > 0 ? (n + 15) & ~15 : 0;
+}
+
 // true when every pointer is 16-byte aligned: the predicate of a kernel lists exactly the operands it touches with 16-byte
 // instructions (a contiguous tensor view may start at any 4-byte offset of its storage)
 template <typename... P>

@@ -67,6 +67,10 @@ struct Args {
     // words): absA[row of A]; absB[z][column of C / grpB] x multB >= the largest magnitude in that column of B_z (one word
     // serves grpB consecutive columns: the 60 anchors of a point)
     const unsigned *absA, *absB; float multB; int grpB; long long sAbsB;
+    // TAIL kernels only: ncols[item] = the live prefix of the item's packed axis (device words) -- BMODE 1: of its N columns (column tiles
+    // past it return before any load, the last live tile masks loads and stores); BMODE 0: of its contraction axis (the k-loop ends there,
+    // the last k-tile is zero-filled past it)
+    const int *ncols;
 };
 constexpr int TAPS = 12;                // intra_idx is [60, 12] (vgtk/so3conv/functional.py get_intra_idx)
 constexpr unsigned TBL_BYTES = 64 * TAPS * 4;
@@ -118,8 +122,10 @@ __device__ __forceinline__ void split_quad(const f32x4 &a, const f32x4 &b, u32x4
 // MI = row tiles per wave: 4 -> block tile 256 x 256; 2 -> 128 x 256 (wave tile 64 x 64) for row counts that would leave
 // half of a 256-row tile empty (the second layer's contraction: 128 output channels)
 // PL = planes per operand (3: bf16, 2: fp16 after the tensor scales -- see split_pair_h)
-template <int MI, int WN, int BMODE, bool APRE, int PL>
+// TAIL = the item's packed axis ends at ncols[item] (Args::ncols; the dense layers' gradient tail on packed Z): nothing past it is read
+template <int MI, int WN, int BMODE, bool APRE, int PL, bool TAIL = false>
 __device__ __forceinline__ void split_gemm_body(const Args &g) {
+    static_assert(!TAIL || BMODE == 0 || BMODE == 1, "the live prefix is of the columns (nn) or of the contraction axis (nt)");
     constexpr unsigned OPER_BYTES = oper_bytes(PL), STAGE_BYTES = stage_bytes(PL);
     constexpr int NT = 128 * WN, NI = 8 / WN, WM = 8 / WN, BM = 32 * MI * WM, RG = NT / 4;   // threads, column tiles per wave, waves along M, rows per block, rows per staging group
     constexpr int NPA = BM / RG, NPO = 256 / RG;                                              // staged pieces per thread: A tile, B tile
@@ -139,7 +145,21 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
     const int m0 = tm * BM, n0 = tn * BN;
     const int item = g.slabs > 1 ? z / g.slabs : z;
     const long long item_of_z = item;
-    const long long kbeg = g.slabs > 1 ? (long long)(z - item * g.slabs) * g.kslab : 0;
+    // TAIL: this item's live prefix (see Args::ncols)
+    int nlive = 0, kleft = 0;
+    if constexpr (TAIL) nlive = __builtin_amdgcn_readfirstlane(g.ncols[item]);
+    long long kbeg = g.slabs > 1 ? (long long)(z - item * g.slabs) * g.kslab : 0;
+    if constexpr (TAIL && BMODE == 0) {
+        // nt: the item's slabs share ITS live prefix in equal runs of whole k-tiles (not the K / slabs of the longest item: a short item's
+        // last slab would be short and its first one not); kleft = the live elements of this slab
+        nlive = min(max(nlive, 0), g.K);
+        long long span = g.K;
+        if (g.slabs > 1) {
+            span = (long long)((nlive + g.slabs * BK - 1) / (g.slabs * BK)) * BK;
+            kbeg = (long long)(z - item * g.slabs) * span;
+        }
+        kleft = (int)min(span, max(0ll, (long long)nlive - kbeg));
+    }
     const float *A = g.A + item * g.sA + kbeg;
     // (BMODE 1, split K: the slab's k-rows of the row-major operand; its partial goes to slab-major scratch [slab][item][M, ldc])
     const float *B = g.B + item * g.sB + (BMODE == 0 ? kbeg : BMODE == 1 ? kbeg * g.ldb : 0);
@@ -153,6 +173,30 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
+
+    // TAIL, nn: a column tile that starts at or past the live prefix returns here, before any load and any barrier (block-uniform); nt: a
+    // slab without live elements writes its zero partial
+    if constexpr (TAIL) {
+        if constexpr (BMODE == 1) {
+            nlive = min(max(nlive, 0), g.N);
+            if (n0 >= nlive) return;
+        } else {
+            if (kleft <= 0) {
+                constexpr int BM0 = 32 * MI * (8 / WN);
+                for (int e = t; e < BM0 * (BN / 4); e += 128 * WN) {
+                    const int row = m0 + e / (BN / 4), col = n0 + 4 * (e % (BN / 4));
+                    if (row < g.M && col < g.N) *reinterpret_cast<f32x4 *>(C + (long long)row * g.ldc + col) = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+                return;
+            }
+        }
+    }
+    // the operand row (nt) / column (nn) of the B tile this thread stages as piece u; TAIL, nn: never a dead column (the last live one instead)
+    auto b_line = [&](int u) __attribute__((always_inline)) {
+        int n = min(n0 + (NT / 4) * u, g.N - NT / 4) + (BMODE ? (t & 127) : (t >> 2));
+        if constexpr (TAIL && BMODE == 1) n = min(n, nlive - 1);
+        return n;
+    };
 
     // ---- staging: per k-tile thread t moves eight 16-byte pieces global -> VGPR -> (split) -> LDS: pieces 0..3 of the A
     //      tile (rows 64 u + (t >> 2), u = 0..3), 4..7 of the B tile, k-chunk t & 3.  Request address = wave-uniform base of
@@ -182,13 +226,13 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
 #pragma unroll
         for (int u = 0; u < NPA; ++u) sclA[u] = pow2_scale(__uint_as_float(g.absA[min(m0 + RG * u, g.M - RG) + rq]));
 #pragma unroll
-        for (int u = 0; u < NPO; ++u) sclB[u] = pow2_scale(__uint_as_float(absBz[(min(n0 + RG * u, g.N - RG) + rqb) / g.grpB]) * g.multB);
+        for (int u = 0; u < NPO; ++u) sclB[u] = pow2_scale(__uint_as_float(absBz[b_line(u) / g.grpB]) * g.multB);
     }
     const unsigned offA = (unsigned)((long long)rq * g.lda + 4 * c4) * 4u, offB = (unsigned)((long long)rq * g.ldb + 4 * c4) * 4u;
     unsigned colB[NPO], tapB[NPO];      // BMODE 1: byte offset of the piece's column; BMODE 2: of its point's row, and of its anchor's table row
 #pragma unroll
     for (int u = 0; u < NPO; ++u) {
-        const int n = min(n0 + RG * u, g.N - RG) + rqb;
+        const int n = b_line(u);
         if constexpr (BMODE == 2) {
             // column n = (point, anchor, residual): the residual stays with the column, the anchor picks the table row
             const int per = g.na * g.nr, pt = n / per, an = (n - pt * per) / g.nr;
@@ -209,7 +253,12 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
         for (int i = t; i < g.na * TAPS; i += NT) reinterpret_cast<int *>(smem + 3 * STAGE_BYTES)[i] = g.tbl[i] * 4 * g.nr;   // byte offsets of the anchor's nr residuals
         __syncthreads();
     }
-    const int nk = (g.slabs > 1 ? g.kslab : g.K) / BK;
+    const int nk = (TAIL && BMODE == 0) ? (kleft + BK - 1) / BK : (g.slabs > 1 ? g.kslab : g.K) / BK;
+    // TAIL, nt: the elements of a staged piece at or past the live end become zeros when the piece is parked (rem = live elements from the
+    // piece's first; the loads stay inside the operand rows: K is a whole number of k-tiles)
+    auto live4 = [&](const f32x4 &q, int rem) __attribute__((always_inline)) {
+        return (f32x4){rem > 0 ? q.x : 0.f, rem > 1 ? q.y : 0.f, rem > 2 ? q.z : 0.f, rem > 3 ? q.w : 0.f};
+    };
 
     Row16 ra0, rb0, ra1, rb1;                                           // (A pieces 0..3, B pieces 0..3) of two tiles in flight
     auto ld = [&](const float *ubase, unsigned voff) __attribute__((always_inline)) {
@@ -249,8 +298,10 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
         }
     };
     // one piece (4 k's) -> three 8-byte words, parked at its place in row 64 u + rq of the operand tile
-    auto park_piece = [&](unsigned char *oper, int u, const f32x4 &q, unsigned wr, float scl) __attribute__((always_inline)) {
+    auto park_piece = [&](unsigned char *oper, int u, const f32x4 &q_, unsigned wr, float scl, int rem) __attribute__((always_inline)) {
         unsigned h0, m0_, l0, h1, m1, l1;
+        f32x4 q = q_;
+        if constexpr (TAIL && BMODE == 0) q = live4(q_, rem);
         if constexpr (PL == 2) {
             split_pair_h(q.x * scl, q.y * scl, h0, l0);
             split_pair_h(q.z * scl, q.w * scl, h1, l1);
@@ -267,11 +318,11 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
         *reinterpret_cast<u32x2 *>(row + 2 * PLANE_BYTES) = (u32x2){l0, l1};
     };
     // half of an operand's pieces of a tile (the split rides between the products in four portions)
-    auto park_half = [&](unsigned char *oper, const Row16 &r, int half, int pieces, unsigned wr, float scl) __attribute__((always_inline)) {
-        if (half < pieces) park_piece(oper, half, half ? r.q1 : r.q0, wr, scl);
+    auto park_half = [&](unsigned char *oper, const Row16 &r, int half, int pieces, unsigned wr, float scl, int rem) __attribute__((always_inline)) {
+        if (half < pieces) park_piece(oper, half, half ? r.q1 : r.q0, wr, scl, rem);
     };
     // an A piece that arrived split: three 8-byte words straight to the planes
-    auto park_half_a = [&](unsigned char *oper, const Row16 &r, int half, unsigned wr) __attribute__((always_inline)) {
+    auto park_half_a = [&](unsigned char *oper, const Row16 &r, int half, unsigned wr, int rem) __attribute__((always_inline)) {
         if constexpr (APRE) {
             if (half < NPA) {
                 const f32x4 &q = half ? r.q1 : r.q0;
@@ -282,17 +333,19 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
                 if constexpr (PL == 3) *reinterpret_cast<u32x2 *>(row + 2 * PLANE_BYTES) = l;
             }
         } else {
-            park_half(oper, r, half, NPA, wr, sclA[half]);
+            park_half(oper, r, half, NPA, wr, sclA[half], rem);
         }
     };
-    auto park = [&](unsigned char *oper, const Row16 &r, int pieces, unsigned wr) __attribute__((always_inline)) {      // (B tiles)
-        park_half(oper, r, 0, pieces, wr, sclB[0]);
-        park_half(oper, r, 1, pieces, wr, sclB[1]);
+    auto park = [&](unsigned char *oper, const Row16 &r, int pieces, unsigned wr, int rem) __attribute__((always_inline)) {      // (B tiles)
+        park_half(oper, r, 0, pieces, wr, sclB[0], rem);
+        park_half(oper, r, 1, pieces, wr, sclB[1], rem);
     };
-    auto park_a = [&](unsigned char *oper, const Row16 &r, unsigned wr) __attribute__((always_inline)) {
-        park_half_a(oper, r, 0, wr);
-        park_half_a(oper, r, 1, wr);
+    auto park_a = [&](unsigned char *oper, const Row16 &r, unsigned wr, int rem) __attribute__((always_inline)) {
+        park_half_a(oper, r, 0, wr, rem);
+        park_half_a(oper, r, 1, wr, rem);
     };
+    // rem of the pieces of k-tile kt (TAIL, nt; unused otherwise)
+    auto rem_of = [&](int kt) __attribute__((always_inline)) { return kleft - (kt * BK + 4 * c4); };
 
     // ---- fragments: lane (row li of a 32-row tile, k-half lh) reads 16 bytes = 8 bf16 ------------------------------
     // row r of the wave's A rows = 128 wm + 32 i + li: bits 2 and 3 of r are those of li
@@ -333,6 +386,7 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
                 for (int j = 0; j < NI; ++j) acc[i][j] = mm(fa[i], fb[j], zc);
         };
 #define SB() __builtin_amdgcn_sched_barrier(0)
+        const int rem2 = rem_of(kt + 2);            // (sa, sb) hold tile kt + 2
         if constexpr (PL == 2) {
             // three products per tile: ah bl, ah bh, al bh (ah, bl arrive from the previous tile; the last product needs
             // neither, so the next tile's pair is read straight into them).  The split of tile kt + 2 rides in three portions.
@@ -340,18 +394,18 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
             frag(st, rdB, 0, bh);
             SB();
             if constexpr (decltype(first)::value) product0(ah, bl); else product(ah, bl);
-            park_a(s2, sa, wr_off);
+            park_a(s2, sa, wr_off, rem2);
             SB();
             frag(st, rdA, 1, al);
             SB();
             product(ah, bh);
-            park_half(s2 + OPER_BYTES, sb, 0, NPO, wr_offB, sclB[0]);
+            park_half(s2 + OPER_BYTES, sb, 0, NPO, wr_offB, sclB[0], rem2);
             SB();
             frag(s1, rdA, 0, ah);                // the next tile's pair (its stage was certified a tile ago)
             frag(s1, rdB, 1, bl);
             SB();
             product(al, bh);
-            park_half(s2 + OPER_BYTES, sb, 1, NPO, wr_offB, sclB[1]);
+            park_half(s2 + OPER_BYTES, sb, 1, NPO, wr_offB, sclB[1], rem2);
             load_tile(min(kt + 4, nk - 1), sa, sb);
             SB();
             __syncthreads();
@@ -364,22 +418,22 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
         frag(st, rdB, 1, bm);
         SB();
         if constexpr (decltype(first)::value) product0(ah, bl); else product(ah, bl);
-        park_half_a(s2, sa, 0, wr_off);
+        park_half_a(s2, sa, 0, wr_off, rem2);
         SB();
         frag(st, rdA, 1, am);
         SB();
         product(ah, bm);
-        park_half_a(s2, sa, 1, wr_off);
+        park_half_a(s2, sa, 1, wr_off, rem2);
         SB();
         frag(st, rdB, 0, bh);
         SB();
         product(am, bm);
-        park_half(s2 + OPER_BYTES, sb, 0, NPO, wr_offB, sclB[0]);
+        park_half(s2 + OPER_BYTES, sb, 0, NPO, wr_offB, sclB[0], rem2);
         SB();
         frag(st, rdA, 2, al);
         SB();
         product(am, bh);
-        park_half(s2 + OPER_BYTES, sb, 1, NPO, wr_offB, sclB[1]);
+        park_half(s2 + OPER_BYTES, sb, 1, NPO, wr_offB, sclB[1], rem2);
         SB();
         // branch-free on purpose (accumulators that cross a control-flow join get copied): past the last tiles the
         // staged registers are re-split into a stage nobody reads, the loads repeat the last tile, the fragment reads hit
@@ -403,11 +457,11 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
     // ---- prologue --------------------------------------------------------------------------------------------------
     load_tile(0, ra0, rb0);
     load_tile(min(1, nk - 1), ra1, rb1);
-    park_a(smem, ra0, wr_off);
-    park(smem + OPER_BYTES, rb0, NPO, wr_offB);
+    park_a(smem, ra0, wr_off, rem_of(0));
+    park(smem + OPER_BYTES, rb0, NPO, wr_offB, rem_of(0));
     load_tile(min(2, nk - 1), ra0, rb0);
-    park_a(smem + STAGE_BYTES, ra1, wr_off);
-    park(smem + STAGE_BYTES + OPER_BYTES, rb1, NPO, wr_offB);
+    park_a(smem + STAGE_BYTES, ra1, wr_off, rem_of(1));
+    park(smem + STAGE_BYTES + OPER_BYTES, rb1, NPO, wr_offB, rem_of(1));
     load_tile(min(3, nk - 1), ra1, rb1);
     __syncthreads();
     frag(smem, rdA, 0, ah);
@@ -435,11 +489,12 @@ __device__ __forceinline__ void split_gemm_body(const Args &g) {
         for (int j = 0; j < NI; ++j) {
             const int col = n0 + 32 * NI * wn + 32 * j + li;
             float unsB = 1.0f;         // PL = 2: the scales come off again, in two factors (their product can leave the normal range)
-            if constexpr (PL == 2) unsB = 1.0f / pow2_scale(__uint_as_float(absBz[min(col, g.N - 1) / g.grpB]) * g.multB);
+            const int ncol = (TAIL && BMODE == 1) ? nlive : g.N;        // the columns this item writes
+            if constexpr (PL == 2) unsB = 1.0f / pow2_scale(__uint_as_float(absBz[min(col, ncol - 1) / g.grpB]) * g.multB);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + 32 * MI * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (row < g.M && col < g.N) {
+                if (row < g.M && col < ncol) {
                     float v = acc[i][j][r];
                     if constexpr (PL == 2) v = (v * (1.0f / pow2_scale(__uint_as_float(g.absA[row])))) * unsB;
                     if (g.ep_scale != nullptr) {                      // kernel-uniform
@@ -459,6 +514,12 @@ __global__ __launch_bounds__(128 * WN, WN / 2) void gemm_bf16x3_kernel(Args g) {
 // two fp16 planes per operand, three products per k-tile (see split_pair_h for what that costs in accuracy)
 template <int MI, int WN, int BMODE, bool APRE>
 __global__ __launch_bounds__(128 * WN, WN / 2) void gemm_f16x2_kernel(Args g) { split_gemm_body<MI, WN, BMODE, APRE, 2>(g); }
+
+// the same two bodies on a packed axis that ends at ncols[item] (TAIL)
+template <int MI, int WN, int BMODE, bool APRE>
+__global__ __launch_bounds__(128 * WN, WN / 2) void gemm_bf16x3_tail_kernel(Args g) { split_gemm_body<MI, WN, BMODE, APRE, 3, true>(g); }
+template <int MI, int WN, int BMODE, bool APRE>
+__global__ __launch_bounds__(128 * WN, WN / 2) void gemm_f16x2_tail_kernel(Args g) { split_gemm_body<MI, WN, BMODE, APRE, 2, true>(g); }
 
 }  // namespace
 
@@ -558,12 +619,12 @@ void keep_pool_memory() {
     (void)hipGetLastError();
 }
 
-template <int BMODE, int PL = 3>
+template <int BMODE, int PL = 3, bool TAIL = false>
 int launch_split(Args &g, long long batch, hipStream_t stream, const char *who) {
     // pays from a few thousand k-tiles per workgroup column upwards (+2.7 % on the deepest layer's contraction; on the 1-2 ms
     // pointwise contractions the extra launch and the allocation cost more than the saved vector work:
     // tools/split_modes_timing.py); the test switch value 2 forces it for every shape
-    bool pre = g.sA == 0 && (g.slabs <= 1 || BMODE == 1) && (g_presplit == 2 || (g_presplit == 1 && g.K >= 1024));
+    bool pre = !(TAIL && PL == 3) && g.sA == 0 && (g.slabs <= 1 || BMODE == 1) && (g_presplit == 2 || (g_presplit == 1 && g.K >= 1024));
     void *scratch = nullptr;
     if (pre) {
         const long long pieces = (long long)g.M * (g.K / 4);
@@ -594,6 +655,19 @@ int launch_split(Args &g, long long batch, hipStream_t stream, const char *who) 
     g.tiles_n = (g.N + BN - 1) / BN;
     const size_t shmem = shmem_bytes(PL) + (BMODE == 2 ? TBL_BYTES : 0);
     void (*kern)(Args);
+    if constexpr (TAIL) {
+        // the two products of the dense layers' gradient tail on packed Z: dF = W2 Z (two planes, nn) and dW = sum_b Fc_b Z_b^T (three planes, nt)
+        static_assert((PL == 2 && BMODE == 1) || (PL == 3 && BMODE == 0), "the tail kernels: two-plane nn, three-plane nt");
+        if constexpr (PL == 2) {
+            if (pre) kern = tall ? gemm_f16x2_tail_kernel<4, WAVES_N, 1, true> : gemm_f16x2_tail_kernel<2, WAVES_N, 1, true>;
+            else kern = tall ? gemm_f16x2_tail_kernel<4, WAVES_N, 1, false> : gemm_f16x2_tail_kernel<2, WAVES_N, 1, false>;
+            eap::set_kernel(tall ? "gemm_f16x2_tail_kernel<4, 4, nn>" : "gemm_f16x2_tail_kernel<2, 4, nn>");
+        } else {
+            kern = tall ? gemm_bf16x3_tail_kernel<4, WAVES_N, 0, false> : gemm_bf16x3_tail_kernel<2, WAVES_N, 0, false>;      // (batch-reduce form: nothing pre-split)
+            eap::set_kernel(tall ? "gemm_bf16x3_tail_kernel<4, 4>" : "gemm_bf16x3_tail_kernel<2, 4>");
+        }
+        return eap::run_kernel(who, kern, (long long)g.tiles_m * g.tiles_n, batch, 1, dim3(128 * WAVES_N), shmem, stream, g);
+    }
     if constexpr (PL == 2) {
         if (pre) kern = tall ? gemm_f16x2_kernel<4, WAVES_N, BMODE, true> : gemm_f16x2_kernel<2, WAVES_N, BMODE, true>;
         else kern = tall ? gemm_f16x2_kernel<4, WAVES_N, BMODE, false> : gemm_f16x2_kernel<2, WAVES_N, BMODE, false>;
@@ -915,6 +989,32 @@ extern "C" int eap_gemm_bf16x3_reduce_f32(int M, int N, int K, const float *A, i
                            batch * slabs, reinterpret_cast<const f32x4 *>(workspace), C, N, (long long)ldc);
 }
 
+// eap_gemm_bf16x3_reduce_f32 over a PACKED contraction axis: item z contracts over its first ncols[z] elements only (device words; clamped
+// to 0 .. K) -- nothing past them is read in A_z or B_z, a last partial k-tile is zero-filled, an item or slab without live elements adds
+// zeros.  Slab count and workspace (eap_gemm_bf16x3_reduce_workspace) as the entry above; an item's slabs share ITS live prefix in equal
+// runs of whole k-tiles, summed in slab order.
+extern "C" int eap_gemm_bf16x3_reduce_tail_f32(int M, int N, int K, const float *A, int64_t lda, int64_t strideA, const float *B, int64_t ldb,
+                                               int64_t strideB, float *C, int64_t ldc, int batch, const int32_t *ncols, float *workspace,
+                                               eap_stream_t stream) {
+    if (M <= 0 || N <= 0 || batch <= 0) return eap::bad_arg("gemm_bf16x3_reduce_tail_f32: M, N and batch must be positive");
+    if (!A || !B || !C || !ncols || !workspace) return eap::bad_arg("gemm_bf16x3_reduce_tail_f32: A, B, C, ncols and the workspace are required");
+    if (!eap_gemm_bf16x3_reduce_f32_supported(M, N, K, A, lda, strideA, B, ldb, strideB, ldc) || !eap::aligned16(C, workspace))
+        return eap::bad_arg("gemm_bf16x3_reduce_tail_f32: unsupported operands (ask eap_gemm_bf16x3_reduce_f32_supported)");
+    const int slabs = reduce_slabs(M, N, K, batch);
+    if ((long long)batch * slabs > 65535) return eap::bad_arg("gemm_bf16x3_reduce_tail_f32: batch x slabs exceeds 65535");
+    Args g{};
+    g.M = M; g.N = N; g.K = K;
+    g.A = A; g.lda = lda; g.sA = strideA;
+    g.B = B; g.ldb = ldb; g.sB = strideB;
+    g.C = workspace; g.ldc = N; g.sC = (long long)M * N;
+    g.slabs = slabs; g.kslab = K / slabs;
+    g.ncols = ncols;
+    if (int e = launch_split<0, 3, true>(g, (long long)batch * slabs, eap::S(stream), "gemm_bf16x3_reduce_tail_f32")) return e;
+    const long long mn4 = (long long)M * N / 4;
+    return eap::run_kernel("gemm_bf16x3_reduce_tail_f32 (sum of the partials)", split_reduce_kernel, eap::cdiv(mn4, 256), 1, 1, dim3(256), 0, eap::S(stream), mn4,
+                           batch * slabs, reinterpret_cast<const f32x4 *>(workspace), C, N, (long long)ldc);
+}
+
 // ---- split-K form of the two-plane 'nn' product: C_z[M,N] = A[M,K] B_z[K,N] with ONE row tile (M = 128) and a long contraction -----
 // The feature gradient of the dense layers (dF = W2 Z: M = 128, K = o ks up to 12288, N = the padded row axis) has 34 x 8 = 272
 // workgroups of 768 k-tiles each on 256 CUs with one workgroup per CU: a second round of 16 workgroups while 240 CUs idle.  Here the
@@ -1007,4 +1107,59 @@ extern "C" int eap_gemm_f16x2_splitk_f32(int M, int N, int K, const float *A, in
     const long long mn4 = (long long)batch * M * N / 4;
     return eap::run_kernel("gemm_f16x2_splitk_f32 (sum of the slabs)", split_reduce_kernel, eap::cdiv(mn4, 256), 1, 1, dim3(256), 0, eap::S(stream), mn4, slabs,
                            reinterpret_cast<const f32x4 *>(workspace), C, N, (long long)ldc);
+}
+
+namespace {
+
+// split_reduce_kernel over the rows of a batch whose item z has ncols[z] live columns: the partials hold nothing past them, C keeps what it held
+__global__ __launch_bounds__(256) void split_reduce_tail_kernel(long long mn4, int parts, const f32x4 *__restrict__ ws, float *__restrict__ C, int M, int N,
+                                                                long long ldc, const int *__restrict__ ncols) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= mn4) return;
+    const long long e = i * 4, row = e / N, col = e - row * N;
+    if (col >= ncols[row / M]) return;
+    f32x4 acc = ws[i];
+    for (int z = 1; z < parts; ++z) acc += ws[(long long)z * mn4 + i];
+    *reinterpret_cast<f32x4 *>(C + row * ldc + col) = acc;
+}
+
+}  // namespace
+
+// eap_gemm_f16x2_splitk_f32 over PACKED columns: item z has ncols[z] live columns (device words, multiples of 4; clamped to 0 .. N) -- a
+// column tile that starts at or past them returns before any load, the last live tile masks its loads and stores, and the sum of the
+// slabs stops there: nothing past ncols[z] is read in B_z or abs_b, nothing past it is written in C_z.  The live columns get the bits
+// of eap_gemm_f16x2_splitk_f32 on the same operands and slab count (columns are independent).
+extern "C" int eap_gemm_f16x2_splitk_tail_f32(int M, int N, int K, const float *A, int64_t lda, const float *B, int64_t ldb, int64_t strideB,
+                                              float *C, int64_t ldc, int64_t strideC, int batch, const int32_t *abs_a, const int32_t *abs_b, int grp_b,
+                                              float mult_b, int slabs, float *workspace, int64_t workspace_floats, const int32_t *ncols,
+                                              eap_stream_t stream) {
+    if (M <= 0 || N <= 0 || batch <= 0) return eap::bad_arg("gemm_f16x2_splitk_tail_f32: M, N and batch must be positive");
+    if (!A || !B || !C || !ncols) return eap::bad_arg("gemm_f16x2_splitk_tail_f32: A, B, C and ncols are required");
+    if (!abs_a || !abs_b || !(mult_b > 0.f) || grp_b <= 0 || (N % grp_b) != 0)
+        return eap::bad_arg("gemm_f16x2_splitk_tail_f32: the operand magnitudes are required (eap_absmax_rows_f32 / _colgroups_f32), column groups dividing N");
+    if (M != 128 || !eap_gemm_bf16x3_nn_f32_supported(M, N, K, A, lda, B, ldb, strideB))
+        return eap::bad_arg("gemm_f16x2_splitk_tail_f32: one 128-row tile of operands eap_gemm_bf16x3_nn_f32_supported takes");
+    if (slabs == 0) slabs = eap_gemm_f16x2_splitk_slabs(M, N, K, batch, 0);
+    if (!splitk_slabs_ok(K, slabs))
+        return eap::bad_arg("gemm_f16x2_splitk_tail_f32: the slab count must divide the K / 16 k-tiles into slabs of at least 16 (at most 64 slabs)");
+    if ((long long)batch * slabs > 65535) return eap::bad_arg("gemm_f16x2_splitk_tail_f32: batch x slabs exceeds 65535");
+    Args g{};
+    g.M = M; g.N = N; g.K = K;
+    g.A = A; g.lda = lda;
+    g.B = B; g.ldb = ldb; g.sB = strideB;
+    g.C = C; g.ldc = ldc; g.sC = strideC;
+    g.absA = reinterpret_cast<const unsigned *>(abs_a); g.absB = reinterpret_cast<const unsigned *>(abs_b); g.multB = mult_b;
+    g.grpB = grp_b; g.sAbsB = N / grp_b;
+    g.ncols = ncols;
+    if (slabs == 1) return launch_split<1, 2, true>(g, batch, eap::S(stream), "gemm_f16x2_splitk_tail_f32");
+    if (strideC != (int64_t)M * ldc || (ldc & 3) || ldc < N || !eap::aligned16(C, workspace))
+        return eap::bad_arg("gemm_f16x2_splitk_tail_f32: more than one slab needs strideC = M ldc, ldc a multiple of 4, C and the workspace 16-byte aligned");
+    if (!workspace || workspace_floats < eap_gemm_f16x2_splitk_workspace(M, N, batch, slabs))
+        return eap::bad_arg("gemm_f16x2_splitk_tail_f32: the workspace is too small (ask eap_gemm_f16x2_splitk_workspace)");
+    g.C = workspace; g.ldc = N; g.sC = (long long)M * N;
+    g.slabs = slabs; g.kslab = K / slabs;
+    if (int e = launch_split<1, 2, true>(g, (long long)batch * slabs, eap::S(stream), "gemm_f16x2_splitk_tail_f32")) return e;
+    const long long mn4 = (long long)batch * M * N / 4;
+    return eap::run_kernel("gemm_f16x2_splitk_tail_f32 (sum of the slabs)", split_reduce_tail_kernel, eap::cdiv(mn4, 256), 1, 1, dim3(256), 0, eap::S(stream), mn4,
+                           slabs, reinterpret_cast<const f32x4 *>(workspace), C, M, N, (long long)ldc, reinterpret_cast<const int *>(ncols));
 }

@@ -190,6 +190,52 @@ __global__ __launch_bounds__(256) void rows_scatter_kernel(int c, int n, int na4
     if (q >= 0) dst[(((size_t)bi * c + ci) * n + q) * na4 + a] = src[(((size_t)bi * c + ci) * rcap + r) * na4 + a];
 }
 
+// The same two movements on the PACKED anchor-major axis of the dense layers' gradient tail: element (a, r) of cloud bi at a live16 + r,
+// live16 = eap::live16(n_rows[bi], rp).  A block moves 64 row slots x na anchors of one (cloud, channel) through an LDS tile, so both sides run
+// in whole runs: 4 na bytes of a feature row, 256 bytes of a packed anchor (rows of na + 1 floats, na <= 64: conflict-free both ways).
+// gather: src [b,c,n,na] -> dst [b,c,ld] (slots whose row is negative or not below n_rows: zeros; nothing written past na live16)
+constexpr int PACKED_SLOTS = 64, PACKED_MAX_NA = 64;
+__global__ __launch_bounds__(256) void rows_gather_packed_kernel(int c, int n, int na, int rp, int rld, long long ld, const int32_t *__restrict__ rows,
+                                                                 const int32_t *__restrict__ n_rows, const float *__restrict__ src, float *__restrict__ dst) {
+    __shared__ float tile[PACKED_SLOTS][PACKED_MAX_NA + 1];
+    const int bi = blockIdx.z, ci = blockIdx.y, r0 = blockIdx.x * PACKED_SLOTS, t = threadIdx.x;
+    const int live = eap::live16(n_rows[bi], rp), nr = min(n_rows[bi], live);      // (more rows than slots: the first rp)
+    if (r0 >= live) return;                                  // (block-uniform, before the barrier)
+    const float *s = src + ((size_t)bi * c + ci) * n * na;
+    for (int i = t; i < PACKED_SLOTS * na; i += 256) {
+        const int rr = i / na, a = i - rr * na, r = r0 + rr;
+        const int q = r < nr ? rows[(size_t)bi * rld + r] : -1;
+        tile[rr][a] = (q >= 0 && q < n) ? s[(size_t)q * na + a] : 0.f;
+    }
+    __syncthreads();
+    float *d = dst + ((size_t)bi * c + ci) * ld;
+    for (int i = t; i < PACKED_SLOTS * na; i += 256) {
+        const int a = i / PACKED_SLOTS, rr = i - a * PACKED_SLOTS, r = r0 + rr;
+        if (r < live) d[(size_t)a * live + r] = tile[rr][a];
+    }
+}
+
+// scatter: src [b,c_ld,ld] (the first c of c_ld rows per cloud) -> dst [b,c,n,na] (zeroed by the caller); nothing read past na live16
+__global__ __launch_bounds__(256) void rows_scatter_packed_kernel(int c, int c_ld, int n, int na, int rp, int rld, long long ld, const int32_t *__restrict__ rows,
+                                                                  const int32_t *__restrict__ n_rows, const float *__restrict__ src, float *__restrict__ dst) {
+    __shared__ float tile[PACKED_SLOTS][PACKED_MAX_NA + 1];
+    const int bi = blockIdx.z, ci = blockIdx.y, r0 = blockIdx.x * PACKED_SLOTS, t = threadIdx.x;
+    const int live = eap::live16(n_rows[bi], rp), nr = min(n_rows[bi], live);      // (more rows than slots: the first rp)
+    if (r0 >= live) return;                                  // (block-uniform, before the barrier)
+    const float *s = src + ((size_t)bi * c_ld + ci) * ld;
+    for (int i = t; i < PACKED_SLOTS * na; i += 256) {
+        const int a = i / PACKED_SLOTS, rr = i - a * PACKED_SLOTS, r = r0 + rr;
+        if (r < live) tile[rr][a] = s[(size_t)a * live + r];
+    }
+    __syncthreads();
+    float *d = dst + ((size_t)bi * c + ci) * n * na;
+    for (int i = t; i < PACKED_SLOTS * na; i += 256) {
+        const int rr = i / na, a = i - rr * na, r = r0 + rr;
+        const int q = r < nr ? rows[(size_t)bi * rld + r] : -1;          // (r < nr <= live: the slot was loaded above)
+        if (q >= 0 && q < n) d[(size_t)q * na + a] = tile[rr][a];
+    }
+}
+
 }  // namespace
 
 extern "C" int eap_inv_lists_rows(int b, int p, int n, int nn, const int32_t *idx, int32_t *counts, int32_t *rows,
@@ -236,4 +282,31 @@ extern "C" int eap_rows_scatter_f32(int b, int c, int n, int na, int rcap, int r
     if (e || rcap <= 0) return e;
     return eap::run_kernel("rows_scatter", rows_scatter_kernel, eap::cdiv((long long)rcap * (na / 4), 256), c, b, dim3(256), 0, s, c, n, na / 4, rcap, rows_ld, rows,
                            reinterpret_cast<const float4 *>(src), reinterpret_cast<float4 *>(dst));
+}
+
+// The referenced feature rows as the PACKED anchor-major operand of the dense layers' weight gradient: src [b,c,n,na] -> dst [b,c,ld] with
+// element (a, r) of cloud i at a live16[i] + r, live16[i] = eap_so3_dense_live16(n_rows[i], rp) (the layout eap_so3_dense_product_packed_f32
+// gives Z); slots r >= n_rows[i] of the last 16-row group hold zeros, nothing is written past na live16[i].  ld >= na rp.
+extern "C" int eap_rows_gather_packed_f32(int b, int c, int n, int na, int rp, int rows_ld, int64_t ld, const int32_t *rows, const int32_t *n_rows,
+                                          const float *src, float *dst, eap_stream_t stream) {
+    if (!rows || !n_rows || !src || !dst) return eap::bad_arg("rows_gather_packed: null pointer");
+    if (b <= 0 || c <= 0 || n <= 0 || na <= 0 || rp <= 0) return eap::bad_arg("rows_gather_packed: every size must be positive");
+    if (na > PACKED_MAX_NA || rp % 16 != 0 || rows_ld < rp || ld < (int64_t)na * rp)
+        return eap::bad_arg("rows_gather_packed: na <= 64, rp a multiple of 16, the row stride of rows >= rp, ld >= na * rp");
+    return eap::run_kernel("rows_gather_packed", rows_gather_packed_kernel, eap::cdiv(rp, PACKED_SLOTS), c, b, dim3(256), 0, eap::S(stream), c, n, na, rp,
+                           rows_ld, (long long)ld, rows, n_rows, src, dst);
+}
+
+// Its counterpart for the feature gradient: src [b,c_ld,ld] packed as above (the first c of every cloud's c_ld rows are read, and only
+// their live columns) -> dst [b,c,n,na], zero except the rows named by `rows`.
+extern "C" int eap_rows_scatter_packed_f32(int b, int c, int c_ld, int n, int na, int rp, int rows_ld, int64_t ld, const int32_t *rows,
+                                           const int32_t *n_rows, const float *src, float *dst, eap_stream_t stream) {
+    if (!rows || !n_rows || !src || !dst) return eap::bad_arg("rows_scatter_packed: null pointer");
+    if (b <= 0 || c <= 0 || n <= 0 || na <= 0 || rp <= 0) return eap::bad_arg("rows_scatter_packed: every size must be positive");
+    if (na > PACKED_MAX_NA || rp % 16 != 0 || rows_ld < rp || ld < (int64_t)na * rp || c_ld < c)
+        return eap::bad_arg("rows_scatter_packed: na <= 64, rp a multiple of 16, the row stride of rows >= rp, ld >= na * rp, c_ld >= c");
+    hipStream_t s = eap::S(stream);
+    if (int e = eap::hip_fail(hipMemsetAsync(dst, 0, sizeof(float) * (size_t)b * c * n * na, s), "rows_scatter_packed memset")) return e;
+    return eap::run_kernel("rows_scatter_packed", rows_scatter_packed_kernel, eap::cdiv(rp, PACKED_SLOTS), c, b, dim3(256), 0, s, c, c_ld, n, na, rp, rows_ld,
+                           (long long)ld, rows, n_rows, src, dst);
 }

@@ -140,6 +140,30 @@ __global__ __launch_bounds__(256) void dense_zbound_kernel(int b, int na, int rp
     words[(long)cloud * ldw + w] = v;
 }
 
+// the same words for PACKED Z (eap_so3_dense_product_packed_f32): column (a, r) of a cloud at a live16 + r, live16 = eap::live16(n_rows, rp) -- a
+// multiple of 16, so a word's four columns stay with one anchor; the words past the cloud's na live16 columns are zero; ncols[cloud] = na live16
+__global__ __launch_bounds__(256) void dense_zbound_packed_kernel(int b, int na, int rp, int p, int ldw, long cnt_stride, const float *__restrict__ colmax,
+                                                                  const int32_t *__restrict__ cnt, const int32_t *__restrict__ n_rows,
+                                                                  float *__restrict__ words, int32_t *__restrict__ ncols) {
+    const int w = blockIdx.x * blockDim.x + threadIdx.x, cloud = blockIdx.y;
+    if (w >= ldw) return;
+    const int live = n_rows[cloud], pitch = eap::live16(live, rp);
+    if (w == 0) ncols[cloud] = na * pitch;
+    float v = 0.f;
+    if (w < na * pitch / 4) {
+        const int a = 4 * w / pitch, r0 = 4 * w - a * pitch;
+        const float m = colmax[(long)cloud * na + a];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int c = r0 + j < live ? cnt[cloud * cnt_stride + r0 + j] : 0;
+            c = c < 0 ? 0 : (c > p ? p : c);
+            const float t = m * (float)c;
+            v = j == 0 ? t : nan_max(v, t);
+        }
+    }
+    words[(long)cloud * ldw + w] = v;
+}
+
 // ---- 4. the bound of the forward's stored operand: max_{c,r} |F| x (max_k sum_c |W| x 1.0001) ---------------------------------
 // first launch: blocks [0, b c) take one (cloud, channel) slab of F [rp, na] each -> fpart [b, c, na]; blocks [b c, b c + o) one output channel
 // of W3 each -> wsum [o] (the row sums in float64, rounded once: within half an ulp of the exact sum).  4 x na threads: a thread keeps its anchor.
@@ -270,6 +294,18 @@ extern "C" int eap_so3_dense_zbound_f32(int b, int na, int rp, int p, int ldz, i
         return eap::bad_arg("so3_dense_zbound: rp and ldz multiples of 4, ldz >= na * rp, the row stride of cnt >= rp");
     return eap::run_kernel("so3_dense_zbound", dense_zbound_kernel, eap::cdiv(ldz / 4, 256), b, 1, dim3(256), 0, eap::S(stream), b, na, rp, p, ldz / 4,
                            (long)cnt_stride, colmax, cnt, n_rows, words);
+}
+
+// eap_so3_dense_zbound_f32 for packed Z: the word of columns 4 w .. 4 w + 3 of cloud i bounds (a, r0 .. r0 + 3) with a = 4 w / live16[i],
+// r0 = 4 w % live16[i]; also writes ncols int32 [b] = na live16[i], the live prefix the two tail products take
+extern "C" int eap_so3_dense_zbound_packed_f32(int b, int na, int rp, int p, int ldz, int64_t cnt_stride, const float *colmax, const int32_t *cnt,
+                                               const int32_t *n_rows, float *words, int32_t *ncols, eap_stream_t stream) {
+    if (!colmax || !cnt || !n_rows || !words || !ncols) return eap::bad_arg("so3_dense_zbound_packed: null pointer");
+    if (b <= 0 || na <= 0 || rp <= 0 || p <= 0 || ldz <= 0) return eap::bad_arg("so3_dense_zbound_packed: b, na, rp, p and ldz must be positive");
+    if (rp % 16 != 0 || ldz % 4 != 0 || (long long)na * rp > ldz || cnt_stride < rp)
+        return eap::bad_arg("so3_dense_zbound_packed: rp a multiple of 16, ldz a multiple of 4, ldz >= na * rp, the row stride of cnt >= rp");
+    return eap::run_kernel("so3_dense_zbound_packed", dense_zbound_packed_kernel, eap::cdiv(ldz / 4, 256), b, 1, dim3(256), 0, eap::S(stream), b, na, rp, p, ldz / 4,
+                           (long)cnt_stride, colmax, cnt, n_rows, words, ncols);
 }
 
 extern "C" int eap_so3_dense_gplanes_bound_f32(int b, int o, int c, int na, int ks, int rp, const float *W3, const float *fc4, float *fpart,

@@ -823,6 +823,7 @@ struct KcArgs {
                                           // 2: the k axis is cut at the cloud's prefix (forward), 0: not cut
     float *C; long long cB, cA, ldm; int rp; long long kstride;     // element (row, n) of (b, a) at C[b cB + a cA + row ldm + (n / rp) kstride + n % rp]
     int row_slots;                        // row slots of the dense index range (the launcher's rp; `rp` above is the output's column split)
+    int packed;                           // trim 1 only: the anchor pitch of cloud b is its own ceil16(min(n_rows[b], row_slots)) instead of cA (packed Z)
     const int32_t *steps;                 // (may be null) [b][blocks_n][KS + 1]: count, then the k-steps this column block runs (dense_steps_kernel)
 };
 
@@ -1087,7 +1088,8 @@ __global__ __launch_bounds__(256, MI == 4 ? 2 : 1) void kc_gemm_kernel(KcArgs g)
     if (t < 32 * MI) isc[t] = 1.0f / g.scale[(size_t)z * (32 * g.MT) + 32 * MI * bm + t];
     __syncthreads();
     if (!active) return;
-    float *Cz = g.C + b * g.cB + a * g.cA + (long long)(32 * MI * bm) * g.ldm;
+    // (packed: column (a, r) of cloud b at a live16[b] + r, live16 = used / ks -- the cloud's live columns are one prefix of the row)
+    float *Cz = g.C + b * g.cB + a * (g.packed ? (long long)(used / g.ks) : g.cA) + (long long)(32 * MI * bm) * g.ldm;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = 64 * wt + 32 * j + li;
@@ -1314,15 +1316,17 @@ extern "C" int eap_so3_dense_gplanes_f32(int b, int o, int c, int na, int ks, in
                            eap::S(stream), o, na, ks, rp, rch, kb_total, W3, Ft, n_rows, bound, scale, reinterpret_cast<u32x4 *>(planes));
 }
 
-// steps (may be null): the k-step lists of eap_so3_dense_steps for this direction -- column blocks run their listed k-steps only
-extern "C" int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int na, int ks, int rp, int64_t ldz, float sigma, const int32_t *n_rows,
-                                               const void *planes, const float *scale, const float *pt, const float *kr, const uint64_t *mask,
-                                               const int32_t *steps, float *out, eap_stream_t stream) {
+namespace {
+
+// the product behind the three entries below; packed (dir 0, n_rows given): Z's anchor pitch per cloud is ceil16(min(n_rows[b], rp)), the
+// slots past it do not exist in the row (nothing zeroed, nothing written there)
+int dense_product(int dir, int packed, int b, int o, int p, int na, int ks, int rp, int64_t ldz, float sigma, const int32_t *n_rows, const void *planes,
+                  const float *scale, const float *pt, const float *kr, const uint64_t *mask, const int32_t *steps, float *out, eap_stream_t stream) {
     if (b <= 0) return 0;
     if (!eap_so3_dense_supported(p, na, ks, rp, o)) return eap::bad_arg("so3_dense_product: shape not taken (eap_so3_dense_supported)");
     const int p_pad = ceil_to(p, KC_BK), kd_pad = ceil_to(ks * rp, KC_BK);
     KcArgs g;
-    g.MT = o / 32; g.na = na; g.zcount = b * na; g.row_slots = rp;
+    g.MT = o / 32; g.na = na; g.zcount = b * na; g.row_slots = rp; g.packed = packed;
     g.N = dir ? p : ks * rp;
     g.KS = (dir ? kd_pad : p) / KC_BK;
     const bool wide = (o % 256) == 0;     // 256-row blocks; else 128-row blocks (half the matrix work per generated weight, two workgroups per CU)
@@ -1348,12 +1352,33 @@ extern "C" int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int
     g.neg_inv_sigma = -1.0f / sigma;
     g.n_rows = n_rows; g.ks = ks; g.trim = dir ? 2 : 1;       // (columns / k axis are dense indices either way; without n_rows every slot counts)
     if (n_rows == nullptr) g.trim = dir ? 0 : 3;
-    if (dir == 0 && n_rows != nullptr) {
+    if (dir == 0 && n_rows != nullptr && !packed) {
         if (int e = eap::run_kernel("so3_dense zero tail", dense_zero_tail_kernel, (long long)o * ks, b, 1, dim3(256), 0, eap::S(stream), o * ks, na, rp, (long long)ldz, n_rows, out))
             return e;
     }
     return wide ? kc_launch<8>(g, eap::S(stream)) : kc_launch<4>(g, eap::S(stream));
 }
+
+}  // namespace
+
+// steps (may be null): the k-step lists of eap_so3_dense_steps for this direction -- column blocks run their listed k-steps only
+extern "C" int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int na, int ks, int rp, int64_t ldz, float sigma, const int32_t *n_rows,
+                                               const void *planes, const float *scale, const float *pt, const float *kr, const uint64_t *mask,
+                                               const int32_t *steps, float *out, eap_stream_t stream) {
+    return dense_product(dir, 0, b, o, p, na, ks, rp, ldz, sigma, n_rows, planes, scale, pt, kr, mask, steps, out, stream);
+}
+
+// The backward product (dir 0) with PACKED rows of Z: cloud b's column (a, r) at a live16[b] + r, live16[b] = eap_so3_dense_live16(n_rows[b], rp),
+// so its na live16[b] live columns are one prefix of every (o, k) row (pitch ldz as above) and NOTHING behind the prefix is written or
+// zeroed: the consumers end at the prefix (eap_gemm_f16x2_splitk_tail_f32, eap_gemm_bf16x3_reduce_tail_f32).  n_rows is required.
+extern "C" int eap_so3_dense_product_packed_f32(int b, int o, int p, int na, int ks, int rp, int64_t ldz, float sigma, const int32_t *n_rows,
+                                                const void *planes, const float *scale, const float *pt, const float *kr, const uint64_t *mask,
+                                                const int32_t *steps, float *out, eap_stream_t stream) {
+    if (n_rows == nullptr) return eap::bad_arg("so3_dense_product_packed: n_rows is required (the packing is per cloud)");
+    return dense_product(0, 1, b, o, p, na, ks, rp, ldz, sigma, n_rows, planes, scale, pt, kr, mask, steps, out, stream);
+}
+
+extern "C" int eap_so3_dense_live16(int n_rows, int rp) { return eap::live16(n_rows, rp); }
 
 extern "C" int eap_so3_dense_product_f32(int dir, int b, int o, int p, int na, int ks, int rp, int64_t ldz, float sigma, const int32_t *n_rows,
                                          const void *planes, const float *scale, const float *pt, const float *kr, const uint64_t *mask, float *out, eap_stream_t stream) {

@@ -1140,20 +1140,29 @@ def _dense_executed_flops(geo, o, p, direction):
     return 6.0 * o * p * geo.na * geo.ks * rows
 
 
-def _dense_product(direction, geo, b, o, p, ld, scale, planes, out, flops):
+def _dense_product(direction, geo, b, o, p, ld, scale, planes, out, flops, packed=False):
     """One launch of the product kernel over p columns with the stored operand (scale, planes): direction 0 -> Z [b,o,ks,ld] (the backward;
-    row pitch ld), 1 -> Yt [b,na,o,p] (the forward; ld 0).  flops: what the launch stands for algorithmically (bench.py).  -> out"""
+    row pitch ld), 1 -> Yt [b,na,o,p] (the forward; ld 0).  flops: what the launch stands for algorithmically (bench.py).  packed (direction
+    0): every cloud's columns at its own anchor pitch (eap_so3_dense_product_packed_f32: no zero fill behind them).  -> out"""
+    tag = {'flops': flops, 'executed_f16_flops': _dense_executed_flops(geo, o, p, direction), 'shape': ('so3_dense', direction, b, o, p, geo.na, geo.ks, geo.rp)}
+    if packed:
+        if direction != 0 or geo.n_rows is None:
+            raise RuntimeError('_dense_product: packed rows are the backward product\'s, with the clouds\' row counts')
+        call('eap_so3_dense_product_packed_f32', out, b, o, p, geo.na, geo.ks, geo.rp, ld, geo.sigma, geo.n_rows, planes, scale, geo.pt, geo.kr,
+             geo.mask(0), geo.steps(0), out, tag=tag)
+        return out
     call('eap_so3_dense_product_steps_f32', out, direction, b, o, p, geo.na, geo.ks, geo.rp, ld, geo.sigma, geo.n_rows, planes, scale, geo.pt, geo.kr,
-         geo.mask(direction), geo.steps(direction), out, tag={'flops': flops, 'executed_f16_flops': _dense_executed_flops(geo, o, p, direction),
-         'shape': ('so3_dense', direction, b, o, p, geo.na, geo.ks, geo.rp)})
+         geo.mask(direction), geo.steps(direction), out, tag=tag)
     return out
 
 
-def so3_dense_bwd(gy, geo, ldz=None, colmap=None, rowmax=False):
+def so3_dense_bwd(gy, geo, ldz=None, colmap=None, rowmax=False, packed=False):
     """gy [b,o,p,na] -> Z [b,o,ks,ldz] whose rows hold [na,rp] (the inverse-list kernel's Z with the anchor axis in front of the row
     axis); ldz >= na*rp (default: equal) pads the rows for the GEMMs that follow -- the padding is NOT written.
     colmap int32 [b,p']: the product runs over the columns colmap[b, :] of gy (the query points of one rigid part: geo is that part's);
-    rowmax: row maxima of gy somebody already took from the hint (None: none available; default: ask the hint)."""
+    rowmax: row maxima of gy somebody already took from the hint (None: none available; default: ask the hint).
+    packed: cloud i's column (a, r) at a * live16[i] + r instead of a * rp + r (dense_live16), nothing zeroed or written behind its na * live16[i]
+    live columns."""
     b, o, p, na = gy.shape
     ldz = na * geo.rp if ldz is None else int(ldz)
     colmap = geo.columns(colmap)                                  # (the geometry's own point order: occupancy-sorted)
@@ -1161,7 +1170,7 @@ def so3_dense_bwd(gy, geo, ldz=None, colmap=None, rowmax=False):
     if colmap is not None:
         p = colmap.shape[1]
     z = torch.empty(b, o, geo.ks, ldz, dtype=torch.float32, device=gy.device)
-    return _dense_product(0, geo, b, o, p, ldz, scale, planes, z, 2.0 * b * o * p * na * geo.ks * geo.nn)
+    return _dense_product(0, geo, b, o, p, ldz, scale, planes, z, 2.0 * b * o * p * na * geo.ks * geo.nn, packed=packed)
 
 
 def so3_dense_gplanes(fc4, W3, geo):
@@ -1248,6 +1257,106 @@ def so3_dense_zbound(colmax, cnt, n_rows, rp, p, ldz):
     words = torch.empty(b, ldz // 4, dtype=torch.float32, device=colmax.device)
     call('eap_so3_dense_zbound_f32', colmax, b, na, int(rp), int(p), int(ldz), cnt.stride(0), colmax, cnt, n_rows, words)
     return words
+
+
+# ---- the gradient tail on PACKED Z (vgtk/so3conv/functional.py _backward_dense) ----------------------------------------------------------
+# The trimmed backward product ends at every cloud's own live16 = ceil16(min(n_rows, rp)) row slots.  Packed, column (a, r) of a cloud sits at
+# a * live16 + r, so its na * live16 live columns are one prefix of the row and the two GEMMs behind the product end there: no zero fill, no
+# product over dead columns.  Nothing of this path reads a column past the prefix (the buffers are torch.empty).
+
+def dense_live16(n_rows, rp):
+    """row slots of a cloud with n_rows referenced rows in a batch of rp: whole 16-row groups (the library's own arithmetic)"""
+    return int(abi.eap_so3_dense_live16(int(n_rows), int(rp)))
+
+
+def dense_packed_column(a, r, n_rows, rp):
+    """the column of (anchor a, row slot r) in a packed row of a cloud with n_rows referenced rows"""
+    return int(a) * dense_live16(n_rows, rp) + int(r)
+
+
+def dense_tail_packed_takes(c, oks, ra, ldz):
+    """Do both tail products of a layer with c input channels, Z rows of ra = na * rp columns at pitch ldz and oks = o * ks rows run on the
+    packed kernels?  dF = W2 Z on the two-plane 'nn' kernel with one 128-row tile, dW = sum_b Fc_b Z_b^T on the three-plane reduce kernel
+    (freshly allocated operands: 16-byte aligned)."""
+    return bool(SPLIT_BF16_CONTRACTION and SPLIT_PLANES == 2 and c == 128 and oks % 4 == 0 and ldz % 4 == 0 and
+                abi.eap_gemm_bf16x3_nn_f32_supported(c, ldz, oks, None, oks, None, ldz, oks * ldz) and
+                abi.eap_gemm_bf16x3_reduce_f32_supported(c, oks, ra, None, ldz, c * ldz, None, ldz, oks * ldz, oks))
+
+
+def so3_dense_zbound_packed(colmax, cnt, n_rows, rp, p, ldz):
+    """so3_dense_zbound for packed Z -> (words float32 [b, ldz / 4], ncols int32 [b] = na * live16 per cloud)"""
+    b, na = colmax.shape
+    if cnt.dtype != torch.int32 or n_rows.dtype != torch.int32 or cnt.stride(1) != 1 or not n_rows.is_contiguous():
+        raise RuntimeError('so3_dense_zbound_packed: cnt and n_rows must be int32, the rows of cnt contiguous')
+    words = torch.empty(b, ldz // 4, dtype=torch.float32, device=colmax.device)
+    ncols = torch.empty(b, dtype=torch.int32, device=colmax.device)
+    call('eap_so3_dense_zbound_packed_f32', colmax, b, na, int(rp), int(p), int(ldz), cnt.stride(0), colmax, cnt, n_rows, words, ncols)
+    return words, ncols
+
+
+def _packed_rows_args(rows, n_rows, who):
+    if rows.dtype != torch.int32 or n_rows.dtype != torch.int32 or rows.stride(1) != 1 or not n_rows.is_contiguous():
+        raise RuntimeError(f'{who}: rows and n_rows must be int32, the rows of `rows` contiguous')
+
+
+def rows_gather_packed(src, rows, n_rows, rp, ld):
+    """src [b,c,n,na] -> [b,c,ld]: the referenced rows anchor-major and packed, element (a, r) of cloud i at a * live16[i] + r (zeros in the
+    slots past n_rows[i] of the last 16-row group; nothing written past na * live16[i])"""
+    b, c, n, na = src.shape
+    check_input(src)
+    _packed_rows_args(rows, n_rows, 'rows_gather_packed')
+    dst = torch.empty(b, c, int(ld), dtype=torch.float32, device=src.device)
+    call('eap_rows_gather_packed_f32', src, b, c, n, na, int(rp), rows.stride(0), int(ld), rows, n_rows, src, dst)
+    return dst
+
+
+def rows_scatter_packed(src, c, rows, n_rows, rp, n, na):
+    """src [b,c_ld,ld] packed as above (its first c rows per cloud) -> [b,c,n,na], zero except the rows named by `rows`"""
+    b, c_ld, ld = src.shape
+    check_input(src)
+    _packed_rows_args(rows, n_rows, 'rows_scatter_packed')
+    dst = torch.empty(b, c, n, na, dtype=torch.float32, device=src.device)
+    call('eap_rows_scatter_packed_f32', src, b, int(c), c_ld, int(n), int(na), int(rp), rows.stride(0), ld, rows, n_rows, src, dst)
+    return dst
+
+
+def matmul_tail_takes(A, B, out, b_bound):
+    """Would matmul_tail run?  The two-plane 'nn' kernel with one 128-row tile, a bound on B's columns, A shared by the batch."""
+    ta, tb, M, N, K, lda, sa, ldb, sb, ldc, sc, batch = _product(A, B, out)
+    return bool(out.dtype == torch.float32 and SPLIT_BF16_CONTRACTION and SPLIT_PLANES == 2 and b_bound is not None and not ta and not tb and sa == 0 and
+                M == 128 and sc == M * ldc and ldc % 4 == 0 and out.data_ptr() % 16 == 0 and _pieces_ok(A, K, lda) and
+                abi.eap_gemm_bf16x3_nn_f32_supported(M, N, K, A, lda, B, ldb, sb))
+
+
+def matmul_tail(A, B, out, ncols, b_bound):
+    """out_z[:, :ncols[z]] = A (B_z[:, :ncols[z]]) on the two-plane kernel (eap_gemm_f16x2_splitk_tail_f32; the slab count of `matmul` on the same
+    shapes, so the live columns get matmul's bits); the columns past ncols[z] are neither read nor written.  A missing qualification is an
+    error (ask matmul_tail_takes)."""
+    if not matmul_tail_takes(A, B, out, b_bound):
+        raise RuntimeError('matmul_tail: the operands do not qualify for the two-plane tail kernel (matmul_tail_takes)')
+    ta, tb, M, N, K, lda, sa, ldb, sb, ldc, sc, batch = _product(A, B, out)
+    slabs = int(abi.eap_gemm_f16x2_splitk_slabs(M, N, K, batch, 0)) if (SPLIT_K_ONE_ROW_TILE and K >= 16 * 64) else 1
+    abs_a = absmax_rows(A, 1, M, K, lda, 0)
+    floats = int(abi.eap_gemm_f16x2_splitk_workspace(M, N, batch, slabs))
+    work = torch.empty(max(floats, 4), dtype=torch.float32, device=out.device)
+    tag = {'flops': 2.0 * M * N * K * batch, 'shape': ('gemm_tail', 0, 0, M, N, K, batch)}
+    call('eap_gemm_f16x2_splitk_tail_f32', out, M, N, K, A, lda, B, ldb, sb, out, ldc, sc, batch, abs_a, b_bound[0], int(b_bound[1]), float(b_bound[2]),
+         slabs, work, floats, ncols, tag=tag)
+
+
+def matmul_reduce_tail_takes(A, B, out):
+    """Would matmul_reduce_tail run?  What matmul_reduce_takes_split asks."""
+    return matmul_reduce_takes_split(A, B, out)
+
+
+def matmul_reduce_tail(A, B, out, ncols):
+    """out = sum_z A_z[:, :ncols[z]] B_z[:ncols[z], :] on the three-plane kernel (eap_gemm_bf16x3_reduce_tail_f32): nothing past ncols[z] is read."""
+    if not matmul_reduce_tail_takes(A, B, out):
+        raise RuntimeError('matmul_reduce_tail: the operands do not qualify for the split kernel (matmul_reduce_tail_takes)')
+    ta, tb, M, N, K, lda, sa, ldb, sb, ldc, _, batch = _product(A, B, out, reduce=True)
+    ws = torch.empty(max(int(abi.eap_gemm_bf16x3_reduce_workspace(M, N, K, batch)), 4), dtype=torch.float32, device=out.device)
+    tag = {'flops': 2.0 * M * N * K * batch, 'shape': ('gemm_reduce_tail', 0, 1, M, N, K, batch)}
+    call('eap_gemm_bf16x3_reduce_tail_f32', out, M, N, K, A, lda, sa, B, ldb, sb, out, ldc, batch, ncols, ws, tag=tag)
 
 
 def so3_dense_gplanes_bound(W3, fc4, ks):
@@ -1354,10 +1463,10 @@ def bn_act_bwd_reduce_fromy(gy, y, beta, inv_gamma, slope, partials=False):
     return pg.sum(1, dtype=torch.float64), pgx.sum(1, dtype=torch.float64), gmax.view(torch.float32), xmax.view(torch.float32)
 
 
-def so3_dense_bwd_bn(gy, yact, geo, ldz, coef, rowbound, slope):
+def so3_dense_bwd_bn(gy, yact, geo, ldz, coef, rowbound, slope, packed=False):
     """so3_dense_bwd for the gradient BEHIND a training-mode BatchNorm + leaky_relu, formed while it is split into the product's planes
     (eap_so3_dense_split_bn_f32): gy = dL/dy', yact = y' [b,o,p,na], coef float32 [5,o] = k1, k2, k3, beta, 1/gamma, rowbound float32 [b,o,na] >=
-    max |gx| of every row.  -> Z as so3_dense_bwd."""
+    max |gx| of every row.  -> Z as so3_dense_bwd; packed: with every cloud's columns (a, r) at a * live16 + r (see dense_live16), nothing zeroed."""
     b, o, p, na = gy.shape
     ldz = na * geo.rp if ldz is None else int(ldz)
     colmap = geo.columns(None)
@@ -1366,7 +1475,7 @@ def so3_dense_bwd_bn(gy, yact, geo, ldz, coef, rowbound, slope):
     planes = torch.empty(b * na * o * ((l + 31) // 32 * 32), dtype=torch.int32, device=gy.device)
     call('eap_so3_dense_split_bn_f32', gy, b, o, l, p, na, rowbound.view(torch.int32), colmap, gy, yact, coef, slope, scale, planes)
     z = torch.empty(b, o, geo.ks, ldz, dtype=torch.float32, device=gy.device)
-    return _dense_product(0, geo, b, o, l, ldz, scale, planes, z, 2.0 * b * o * l * na * geo.ks * geo.nn)
+    return _dense_product(0, geo, b, o, l, ldz, scale, planes, z, 2.0 * b * o * l * na * geo.ks * geo.nn, packed=packed)
 
 
 def _partials(x, b, c, n):

@@ -1324,6 +1324,38 @@ def _weight_grad_rows(z, fc4, o, ks, ldz, anchor_major, reorder=None):
 # two small GEMMs over the referenced rows only -- no dX = W^T dY, no scatter, and the
 # [O x P*A] x [P*A x C*K] weight-gradient GEMM shrinks by P / (referenced rows).
 
+# The tail on PACKED Z (vgtk/_hip.py "the gradient tail on PACKED Z"): the product writes cloud i's column (a, r) at a * live16[i] + r, so the
+# live columns are one prefix of the row; dF, dW, the bound words, the gathered feature rows and the row scatter all end at that prefix.  No
+# zero fill of the dead slots, no product over them, no transposed copy of the gathered rows.  Taken by the identity-pose node with its norm
+# inside, where both GEMMs are on the split kernels (128-channel inputs: the 64-channel layer's dW runs on the fp32 pipe, which has no
+# per-cloud end of the contraction -- it keeps the zero-filled layout).  False: the zero-filled layout everywhere.
+DENSE_TAIL_PACKED = True
+
+
+def _dense_tail_packed_takes(W, feats, head, geo, c, pad_c, ldz, need_f, need_w):
+    na, o, ks, rp = feats.shape[3], W.shape[0], geo.ks, geo.rp
+    if not (need_f and need_w and pad_c == c and c % 128 == 0 and rp % 16 == 0 and ldz == _hip.dense_pitch(na * rp) and geo.n_rows is not None
+            and head.n_rows is geo.n_rows and feats.is_cuda):
+        return False
+    return _hip.dense_tail_packed_takes(c, o * ks, na * rp, ldz)
+
+
+def _dense_tail_packed(z, W, feats, head, geo, colmax, p, ldz, need_f, need_w):
+    """dF and dW from packed Z [b,o,ks,ldz] -> (gF, gW)"""
+    b, c, n, na = feats.shape
+    o, ks, rp = W.shape[0], geo.ks, geo.rp
+    ra = na * rp
+    words, ncols = _hip.so3_dense_zbound_packed(colmax, head.cnt, head.n_rows, rp, p, ldz)
+    zm = z.view(b, o * ks, ldz)
+    gFc = torch.empty(b, c, ldz, dtype=torch.float32, device=z.device)
+    _hip.matmul_tail(_weight_operand(W, c, ks), zm, gFc, ncols, (words.view(torch.int32), 4, 1.0))
+    gF = _hip.rows_scatter_packed(gFc, c, head.rows, head.n_rows, rp, n, na)
+    fc = _hip.rows_gather_packed(feats, head.rows, head.n_rows, rp, ldz)             # [b,c,ldz]
+    dt = torch.empty(c, o * ks, dtype=torch.float32, device=z.device)
+    _hip.matmul_reduce_tail(fc[..., :ra], zm[..., :ra].transpose(1, 2), dt, ncols)
+    return gF, dt.view(c, o, ks).permute(1, 0, 2).reshape(o, c * ks).contiguous()
+
+
 def _backward_dense(gy, W, feats, head, geo, bn, yact, need_f, need_w):
     """Z by the dense product (bn: through the node's BatchNorm + leaky_relu first, yact = the node's output) -> (gF, gW, g_bn_w, g_bn_b)"""
     b, c, n, na = feats.shape
@@ -1353,6 +1385,9 @@ def _backward_dense(gy, W, feats, head, geo, bn, yact, need_f, need_w):
             k2, k3 = norm_fold.backward_coefficients(k1, sg, sgx, count, True, sync)
             coef = torch.stack([k1, k2, k3, beta, inv_gamma]).contiguous()      # [5, o]
             bound = (k1.abs()[None, :, None] * gmax + k2.abs()[None, :, None] + k3.abs()[None, :, None] * xmax).contiguous()
+        if DENSE_TAIL_PACKED and native and _dense_tail_packed_takes(W, feats, head, geo, c, pad_c, ldz, need_f, need_w):
+            z = _hip.so3_dense_bwd_bn(gy, yact, geo, ldz, coef, bound, slope, packed=True)
+            return (*_dense_tail_packed(z, W, feats, head, geo, colmax, p, ldz, need_f, need_w), g_bn_w, g_bn_b)
         z = _hip.so3_dense_bwd_bn(gy, yact, geo, ldz, coef, bound, slope)
         if ldz % 4 == 0 and rp % 4 == 0 and native:
             # (the same bound as below in one launch: eap_so3_dense_zbound_f32)

@@ -441,6 +441,14 @@ int eap_rows_gather_f32(int b, int c, int n, int na, int rcap, int rows_ld, cons
                         const float *src, float *dst, eap_stream_t stream);
 int eap_rows_scatter_f32(int b, int c, int n, int na, int rcap, int rows_ld, const int32_t *rows,
                          const float *src, float *dst, eap_stream_t stream);
+/* The two movements above on the PACKED anchor-major axis of the dense layers' gradient tail (eap_so3_dense_product_packed_f32): element (a, r) of
+ * cloud i at a live16[i] + r, live16[i] = eap_so3_dense_live16(n_rows[i], rp).  gather: src [b,c,n,na] -> dst [b,c,ld] (slots r >= n_rows[i] of the
+ * last 16-row group: zeros; nothing written past na live16[i]); scatter: src [b,c_ld,ld] (the first c of each cloud's c_ld rows, live columns only)
+ * -> dst [b,c,n,na], zero except the named rows.  na <= 64, rp % 16 == 0, ld >= na rp. */
+int eap_rows_gather_packed_f32(int b, int c, int n, int na, int rp, int rows_ld, int64_t ld, const int32_t *rows, const int32_t *n_rows,
+                               const float *src, float *dst, eap_stream_t stream);
+int eap_rows_scatter_packed_f32(int b, int c, int c_ld, int n, int na, int rp, int rows_ld, int64_t ld, const int32_t *rows,
+                                const int32_t *n_rows, const float *src, float *dst, eap_stream_t stream);
 
 /* ---- the fused inter conv re-associated over its referenced rows as a dense product (csrc/so3_dense.hip) ----
  * Replaces, for clouds WITHOUT pose rotations whose neighbour lists name few support rows, the grouping einsum +
@@ -539,6 +547,14 @@ int eap_so3_dense_steps(int b, int p, int ks, int rp, int dir, int skip, const i
 int eap_so3_dense_product_steps_f32(int dir, int b, int o, int p, int na, int ks, int rp, int64_t ldz, float sigma, const int32_t *n_rows,
                                     const void *planes, const float *scale, const float *pt, const float *kr, const uint64_t *mask,
                                     const int32_t *steps, float *out, eap_stream_t stream);
+/* the backward product (dir 0) with PACKED rows of Z: column (a, r) of cloud i at a live16[i] + r, live16[i] = eap_so3_dense_live16(n_rows[i], rp)
+ * = ceil16(min(n_rows[i], rp)) -- the cloud's na live16[i] live columns are one prefix of every (o, k) row (pitch ldz >= na rp as above); nothing
+ * behind the prefix is written or zeroed.  n_rows is required.  Consumers: eap_gemm_f16x2_splitk_tail_f32, eap_gemm_bf16x3_reduce_tail_f32. */
+int eap_so3_dense_product_packed_f32(int b, int o, int p, int na, int ks, int rp, int64_t ldz, float sigma, const int32_t *n_rows,
+                                     const void *planes, const float *scale, const float *pt, const float *kr, const uint64_t *mask,
+                                     const int32_t *steps, float *out, eap_stream_t stream);
+/* host arithmetic: the row slots of a cloud with n_rows referenced rows in a batch of rp slots, in whole 16-row groups (0 without rows) */
+int eap_so3_dense_live16(int n_rows, int rp);
 /* Clouds that reference up to 1024 support rows: 64 groups of 16 rows, 32 membership words per point, a 64-bit group key.
  *   eap_so3_dense_max_rows          the largest rp any entry takes (1024)
  *   eap_so3_dense_member_wide       eap_so3_dense_member with memb uint32 [b,p,32] (bit i of word w of point p = m[p, 32 w + i]); rp <= 1024;
@@ -642,6 +658,12 @@ int eap_gemm_bf16x3_reduce_f32_supported(int M, int N, int K, const float *A, in
 int64_t eap_gemm_bf16x3_reduce_workspace(int M, int N, int K, int batch);
 int eap_gemm_bf16x3_reduce_f32(int M, int N, int K, const float *A, int64_t lda, int64_t strideA, const float *B, int64_t ldb,
                                int64_t strideB, float *C, int64_t ldc, int batch, float *workspace, eap_stream_t stream);
+/* the same over a PACKED contraction axis: item z contracts over its first ncols[z] elements (int32 device words, clamped to 0 .. K); nothing
+ * past them is read in A_z or B_z, a last partial k-tile is zero-filled, an item or k-slab without live elements adds zeros.  Slab count and
+ * workspace as eap_gemm_bf16x3_reduce_f32; an item's slabs share ITS live prefix in equal runs of whole k-tiles. */
+int eap_gemm_bf16x3_reduce_tail_f32(int M, int N, int K, const float *A, int64_t lda, int64_t strideA, const float *B, int64_t ldb,
+                                    int64_t strideB, float *C, int64_t ldc, int batch, const int32_t *ncols, float *workspace,
+                                    eap_stream_t stream);
 /* eap_so3_intra_conv_f32 on the split kernel (nt = 12; o, p*na multiples of 128; c*nt a multiple of 16) */
 int eap_so3_intra_conv_bf16x3_f32_supported(int b, int o, int c, int p, int na, int nt);
 int eap_so3_intra_conv_bf16x3_f32(int b, int o, int c, int p, int na, int nt, const float *W, const float *feats,
@@ -692,6 +714,13 @@ int64_t eap_gemm_f16x2_splitk_workspace(int M, int N, int batch, int slabs);
 int eap_gemm_f16x2_splitk_f32(int M, int N, int K, const float *A, int64_t lda, const float *B, int64_t ldb, int64_t strideB,
                               float *C, int64_t ldc, int64_t strideC, int batch, const int32_t *abs_a, const int32_t *abs_b, int grp_b,
                               float mult_b, int slabs, float *workspace, int64_t workspace_floats, eap_stream_t stream);
+/* the same over PACKED columns: item z has ncols[z] live columns (int32 device words, multiples of 4, clamped to 0 .. N).  A column tile that
+ * starts at or past them returns before any load, the last live tile masks its loads and stores, the sum of the slabs stops there: nothing
+ * past ncols[z] is read in B_z or abs_b or written in C_z.  The live columns get the bits of eap_gemm_f16x2_splitk_f32. */
+int eap_gemm_f16x2_splitk_tail_f32(int M, int N, int K, const float *A, int64_t lda, const float *B, int64_t ldb, int64_t strideB,
+                                   float *C, int64_t ldc, int64_t strideC, int batch, const int32_t *abs_a, const int32_t *abs_b, int grp_b,
+                                   float mult_b, int slabs, float *workspace, int64_t workspace_floats, const int32_t *ncols,
+                                   eap_stream_t stream);
 int eap_so3_intra_conv_f16x2_f32(int b, int o, int c, int p, int na, int nt, const float *W, const float *feats,
                                  const int32_t *intra_idx, float *out, const int32_t *abs_w, const int32_t *abs_f, eap_stream_t stream);
 
@@ -958,6 +987,10 @@ int eap_norm_fold_bwd_f32(int o, int parts, int b, int na, int64_t count, const 
  * colmax[b,a] * clamp(cnt[b,r], 0, p) (cnt int32, rows cnt_stride apart; 0 for r >= n_rows[b]), zero from na rp / 4 on.  rp % 4 == 0, ldz % 4 == 0. */
 int eap_so3_dense_zbound_f32(int b, int na, int rp, int p, int ldz, int64_t cnt_stride, const float *colmax, const int32_t *cnt,
                              const int32_t *n_rows, float *words, eap_stream_t stream);
+/* the same words for packed Z: word w of cloud i bounds columns 4 w .. 4 w + 3 = (a, r0 .. r0 + 3), a = 4 w / live16[i], r0 = 4 w % live16[i]; zero from
+ * na live16[i] / 4 on.  Also writes ncols int32 [b] = na live16[i], the live prefix the tail products take.  rp % 16 == 0, ldz % 4 == 0. */
+int eap_so3_dense_zbound_packed_f32(int b, int na, int rp, int p, int ldz, int64_t cnt_stride, const float *colmax, const int32_t *cnt,
+                                    const int32_t *n_rows, float *words, int32_t *ncols, eap_stream_t stream);
 /* replaces the reductions in front of eap_so3_dense_gplanes_f32: bound float [b,na,o] = max_{c,r} |fc4[b,c,r,a]| x (max_k sum_c |W3[(o,k),c]| x 1.0001)
  * from W3 [o ks, c] and fc4 [b,c,rp,na]; fpart float [b,c,na] and wsum float [o] are scratch (written).  na <= 128.  Two launches. */
 int eap_so3_dense_gplanes_bound_f32(int b, int o, int c, int na, int ks, int rp, const float *W3, const float *fc4, float *fpart, float *wsum,
