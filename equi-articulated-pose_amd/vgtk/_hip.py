@@ -1663,58 +1663,37 @@ def bn_act_cloud_bwd_apply(gy, x, b, c, n, na, scale, shift, mean, invstd, k2, k
     return gx
 
 
-# the same layer with the weighted point mean behind it (csrc/heads.hip, the eap_bn_act_cloud_mean_* entries): x [b,c,p,na] the raw
-# contraction output, w [b,p] point weights, inv_den [b]; the activated map and its gradient are never written
+# the same layer with the weighted point mean behind it (csrc/heads.hip): x [b,c,p,na] the raw contraction output, w [b,p] point
+# weights, inv_den [b]; the activated map and its gradient are never written.  Anchor rows of at most 64 floats take the
+# eap_bn_act_cloud_mean_* entries (16 lanes per row), longer ones of at most 256 (the 240 of a `use_2d` map) their _wide twins (a
+# wavefront per row)
+
+def _cloud_mean_entries(na):
+    return 'eap_bn_act_cloud_mean_wide' if na > 64 else 'eap_bn_act_cloud_mean'
+
 
 def bn_act_cloud_mean_fwd(x, scale, shift, w, inv_den, slope):
     """-> [b, c, na] = inv_den sum_p w leaky(x scale + shift)"""
     b, c, p, na = x.shape
     out = torch.empty(b, c, na, dtype=torch.float32, device=x.device)
-    call('eap_bn_act_cloud_mean_fwd_f32', x, b, c, p, na, slope, x, scale, shift, w, inv_den, out)
+    call(_cloud_mean_entries(na) + '_fwd_f32', x, b, c, p, na, slope, x, scale, shift, w, inv_den, out)
     return out
 
 
 def bn_act_cloud_mean_bwd_reduce(g, x, scale, shift, mean, invstd, w, inv_den, slope):
     """-> sum(gg), sum(gg xhat) per (cloud, channel), float64 [b, c]"""
     b, c, p, na = x.shape
-    parts = int(abi.eap_bn_act_cloud_mean_parts(p))
+    parts = int(getattr(abi, _cloud_mean_entries(na) + '_parts')(p))
     pg = torch.empty(b, c, parts, dtype=torch.float32, device=x.device)
     pgx = torch.empty_like(pg)
-    call('eap_bn_act_cloud_mean_bwd_reduce_f32', x, b, c, p, na, slope, g, x, scale, shift, mean, invstd, w, inv_den, pg, pgx)
+    call(_cloud_mean_entries(na) + '_bwd_reduce_f32', x, b, c, p, na, slope, g, x, scale, shift, mean, invstd, w, inv_den, pg, pgx)
     return pg.sum(2, dtype=torch.float64), pgx.sum(2, dtype=torch.float64)
 
 
 def bn_act_cloud_mean_bwd_apply(g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, slope):
     b, c, p, na = x.shape
     gx = torch.empty_like(x)
-    call('eap_bn_act_cloud_mean_bwd_apply_f32', x, b, c, p, na, slope, g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, gx)
-    return gx
-
-
-# the same three for anchor rows of up to 256 floats, the 240 of a `use_2d` map (csrc/heads_wide.hip, the eap_bn_act_cloud_mean_wide_* entries)
-
-def bn_act_cloud_mean_wide_fwd(x, scale, shift, w, inv_den, slope):
-    """-> [b, c, na] = inv_den sum_p w leaky(x scale + shift)"""
-    b, c, p, na = x.shape
-    out = torch.empty(b, c, na, dtype=torch.float32, device=x.device)
-    call('eap_bn_act_cloud_mean_wide_fwd_f32', x, b, c, p, na, slope, x, scale, shift, w, inv_den, out)
-    return out
-
-
-def bn_act_cloud_mean_wide_bwd_reduce(g, x, scale, shift, mean, invstd, w, inv_den, slope):
-    """-> sum(gg), sum(gg xhat) per (cloud, channel), float64 [b, c]"""
-    b, c, p, na = x.shape
-    parts = int(abi.eap_bn_act_cloud_mean_wide_parts(p))
-    pg = torch.empty(b, c, parts, dtype=torch.float32, device=x.device)
-    pgx = torch.empty_like(pg)
-    call('eap_bn_act_cloud_mean_wide_bwd_reduce_f32', x, b, c, p, na, slope, g, x, scale, shift, mean, invstd, w, inv_den, pg, pgx)
-    return pg.sum(2, dtype=torch.float64), pgx.sum(2, dtype=torch.float64)
-
-
-def bn_act_cloud_mean_wide_bwd_apply(g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, slope):
-    b, c, p, na = x.shape
-    gx = torch.empty_like(x)
-    call('eap_bn_act_cloud_mean_wide_bwd_apply_f32', x, b, c, p, na, slope, g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, gx)
+    call(_cloud_mean_entries(na) + '_bwd_apply_f32', x, b, c, p, na, slope, g, x, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, gx)
     return gx
 
 

@@ -5,7 +5,7 @@ and 3), mirroring the reference classes so a maintainer can swap the import:
                            names `linear.i`, `norm.i`, `attention_layer`, same outputs); the attention pooling
                            over the 60 anchors runs in one HIP pass (csrc/heads.hip)
   InvPPOutBlock2DOurs      SPConvNets/utils/base_so3conv.py:L921-1008, the same head over the 60 x 4 anchors of a `use_2d` map: the
-                           attention pooling over all 240 is one HIP pass (csrc/heads_wide.hip)
+                           attention pooling over all 240 is one HIP pass (csrc/heads.hip, 64 lanes per row)
   orbit_selection          ...pn_38_multi_stage.py:L1381-1399: distance -> arg-min orbit per slot
   global_orbit_selection   ...pn_38_multi_stage.py:L444-461: the global alignment's distances -> arg-min orbit per cloud
   slot_masked_mean         the masked per-slot point averages of SO3OutBlockRTWithMaskSep
@@ -20,7 +20,7 @@ and 3), mirroring the reference classes so a maintainer can swap the import:
   pose_head_over_subsets   the model's per-cloud loop around that head (...pn_38_multi_stage.py:L706-830) as one call per slot
   InvOutBlockOursWithMask  SPConvNets/utils/base_so3conv.py:L1013-1150 with its PointnetSO3ConvOurs (L1153-1205), the per-slot
                            shape-code head: the last unary layer's BatchNorm + ReLU and the point mean are one HIP pass
-                           (csrc/heads.hip; on the 240 anchors of a `use_2d` map csrc/heads_wide.hip), the embed layer runs on the means
+                           (csrc/heads.hip, at 60 anchors and at the 240 of a `use_2d` map), the embed layer runs on the means
   inv_head_over_subsets, inv_heads_over_slot_groups   the model's per-cloud / per-slot loops around that head, batched
 
 Every 1x1 convolution over the [B,C,N,A] map (InvPPOutBlockOurs' included) is the path's contraction, every BatchNorm +
@@ -36,6 +36,12 @@ from .blocks import _BNAct
 
 
 
+def _head_entries(na):
+    """The entry family of csrc/heads.hip for anchor rows of na floats: '_wide' (a wavefront per row) past the 64 anchors the entries
+    without a suffix (16 lanes per row) take.  A node picks it in forward and calls the backward of the same family."""
+    return '_wide' if _anchor_rows_wide(na) else ''
+
+
 class _AnchorAttnPool(torch.autograd.Function):
     """out[b,c,n] = sum_a x[b,c,n,a] softmax_a(logits[b,n,a] * T)  (base_so3conv.py:L905-912)."""
 
@@ -45,7 +51,8 @@ class _AnchorAttnPool(torch.autograd.Function):
         b, c, n, na = x.shape
         out = torch.empty(b, c, n, dtype=torch.float32, device=x.device)
         conf = torch.empty(b, n, na, dtype=torch.float32, device=x.device)
-        _hip.call('eap_anchor_attn_pool_fwd_f32', x, b, c, n, na, temperature, x, logits, out, conf)
+        ctx.family = _head_entries(na)
+        _hip.call(f'eap_anchor_attn_pool{ctx.family}_fwd_f32', x, b, c, n, na, temperature, x, logits, out, conf)
         ctx.save_for_backward(x, logits)
         ctx.temperature = temperature
         ctx.mark_non_differentiable(conf)
@@ -58,34 +65,7 @@ class _AnchorAttnPool(torch.autograd.Function):
         dx = torch.empty_like(x)
         dl = torch.empty_like(logits)
         g = g.contiguous()            # bound to a local: the buffer must outlive the enqueue
-        _hip.call('eap_anchor_attn_pool_bwd_f32', x, b, c, n, na, ctx.temperature, x, logits, g, dx, dl)
-        return dx, dl, None
-
-
-class _AnchorAttnPoolWide(torch.autograd.Function):
-    """_AnchorAttnPool for anchor rows of 68 to 256 floats (the 240 anchors of a `use_2d` map): one wavefront per point
-    (csrc/heads_wide.hip)."""
-
-    @staticmethod
-    def forward(ctx, x, logits, temperature):
-        x, logits = L._aligned16(x), L._aligned16(logits)           # 16-byte loads along the anchor axis
-        b, c, n, na = x.shape
-        out = torch.empty(b, c, n, dtype=torch.float32, device=x.device)
-        conf = torch.empty(b, n, na, dtype=torch.float32, device=x.device)
-        _hip.call('eap_anchor_attn_pool_wide_fwd_f32', x, b, c, n, na, temperature, x, logits, out, conf)
-        ctx.save_for_backward(x, logits)
-        ctx.temperature = temperature
-        ctx.mark_non_differentiable(conf)
-        return out, conf
-
-    @staticmethod
-    def backward(ctx, g, _gconf):
-        x, logits = ctx.saved_tensors
-        b, c, n, na = x.shape
-        dx = torch.empty_like(x)
-        dl = torch.empty_like(logits)
-        g = g.contiguous()            # bound to a local: the buffer must outlive the enqueue
-        _hip.call('eap_anchor_attn_pool_wide_bwd_f32', x, b, c, n, na, ctx.temperature, x, logits, g, dx, dl)
+        _hip.call(f'eap_anchor_attn_pool{ctx.family}_bwd_f32', x, b, c, n, na, ctx.temperature, x, logits, g, dx, dl)
         return dx, dl, None
 
 
@@ -99,18 +79,15 @@ def anchor_attention_pool(x, logits, temperature):
     The fused pass hands the confidence out as data; when the logits carry a gradient the returned confidence is the
     (small, [b,n,a]) torch softmax instead, so a caller that feeds it to a loss (the reference's `orbit_attn == 1`
     concatenation, ...pn_38_multi_stage.py:L612-613) gets the gradient the reference's softmax gives.
-    Up to 64 anchors: csrc/heads.hip (_anchor_rows_vectorise); 68 to 256, the 240 of a `use_2d` map: csrc/heads_wide.hip
-    (_anchor_rows_wide).  Anchor counts neither takes (kanchor = 1, 3, more than 256) run the same two expressions as device torch ops."""
+    One node over csrc/heads.hip: up to 64 anchors its entries without a suffix (_anchor_rows_vectorise); 68 to 256, the 240 of a `use_2d`
+    map, the _wide ones (_anchor_rows_wide).  Anchor counts neither takes (kanchor = 1, 3, more than 256) run the same two expressions as device torch ops."""
     if x.dtype != torch.float32 or not x.is_cuda:
         raise RuntimeError('anchor_attention_pool: float32 device tensors only')
     if logits.dim() == 4:
         logits = logits.squeeze(1)
-    if _anchor_rows_wide(x.shape[3]):
-        out, conf = _AnchorAttnPoolWide.apply(x, logits, float(temperature))
-    elif not _anchor_rows_vectorise(x.shape[3]):
+    if not (_anchor_rows_vectorise(x.shape[3]) or _anchor_rows_wide(x.shape[3])):
         return _anchor_attention_pool_torch(x, logits, temperature)
-    else:
-        out, conf = _AnchorAttnPool.apply(x, logits, float(temperature))
+    out, conf = _AnchorAttnPool.apply(x, logits, float(temperature))
     if logits.requires_grad and torch.is_grad_enabled():
         conf = torch.softmax(logits * float(temperature), dim=-1)
     return out, conf
@@ -201,7 +178,7 @@ class InvPPOutBlock2DOurs(nn.Module):
             quad = planes[..., self.sel_mode, :].contiguous()       # [b,c,n,4]: one quad of every row
             return anchor_attention_pool(quad, _conv1x1(self.attention_layer, quad), self.temperature)[0]
         if self.pooling_method.startswith('attention'):
-            out_feat = _conv1x1(self.attention_layer, x_out)        # [b,1,n,na*4]: softmax over all of them (csrc/heads_wide.hip)
+            out_feat = _conv1x1(self.attention_layer, x_out)        # [b,1,n,na*4]: softmax over all of them (csrc/heads.hip, the _wide entries)
             return anchor_attention_pool(x_out, out_feat, self.temperature)
         raise NotImplementedError(f"Pooling mode {self.pooling_method} is not implemented!")
 
@@ -255,7 +232,7 @@ def _anchor_rows_vectorise(na):
 
 
 def _anchor_rows_wide(na):
-    """The wide twins of the three oldest head kernels (csrc/heads_wide.hip) give a point's anchor row a whole wavefront, one 16-byte
+    """The _wide entries of the head kernels (csrc/heads.hip compiled for 64 lanes per row) give a point's anchor row a whole wavefront, one 16-byte
     word per lane: anchor counts that are a multiple of 4 past the 64 of _anchor_rows_vectorise, at most 256 -- the 60 x 4 = 240 anchors
     of a `use_2d` feature map."""
     return na % 4 == 0 and 64 < na <= 256
@@ -269,7 +246,8 @@ class _SlotMaskedMean(torch.autograd.Function):
         ns = mask.shape[1]
         inv_den = (1.0 / mask.sum(-1).clamp(min=1e-8)).contiguous()
         out = torch.empty(b, ns, c, na, dtype=torch.float32, device=x.device)
-        _hip.call('eap_slot_masked_mean_fwd_f32', x, b, ns, c, n, na, x, mask, inv_den, out)
+        ctx.family = _head_entries(na)
+        _hip.call(f'eap_slot_masked_mean{ctx.family}_fwd_f32', x, b, ns, c, n, na, x, mask, inv_den, out)
         ctx.save_for_backward(mask, inv_den)
         ctx.dims = (b, c, n, na, ns)
         return out
@@ -280,7 +258,7 @@ class _SlotMaskedMean(torch.autograd.Function):
         b, c, n, na, ns = ctx.dims
         dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
         g = L._aligned16(g)           # bound to a local: the buffer must outlive the enqueue
-        _hip.call('eap_slot_masked_mean_bwd_f32', g, b, ns, c, n, na, g, mask, inv_den, dx)
+        _hip.call(f'eap_slot_masked_mean{ctx.family}_bwd_f32', g, b, ns, c, n, na, g, mask, inv_den, dx)
         return dx, None
 
 
@@ -293,7 +271,8 @@ class _MaskedMax(torch.autograd.Function):
         b, c, n, na = x.shape
         out = torch.empty(b, c, na, dtype=torch.float32, device=x.device)
         arg = torch.empty(b, c, na, dtype=torch.int32, device=x.device)
-        _hip.call('eap_masked_max_fwd_f32', x, b, c, n, na, x, mask, out, arg)
+        ctx.family = _head_entries(na)
+        _hip.call(f'eap_masked_max{ctx.family}_fwd_f32', x, b, c, n, na, x, mask, out, arg)
         ctx.save_for_backward(arg, mask)
         ctx.dims = (b, c, n, na)
         return out
@@ -304,56 +283,7 @@ class _MaskedMax(torch.autograd.Function):
         b, c, n, na = ctx.dims
         g = L._aligned16(g)
         dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
-        _hip.call('eap_masked_max_bwd_f32', g, b, c, n, na, g, arg, mask, dx)
-        return dx, None
-
-
-class _SlotMaskedMeanWide(torch.autograd.Function):
-    """_SlotMaskedMean for anchor rows of 68 to 256 floats (csrc/heads_wide.hip)."""
-
-    @staticmethod
-    def forward(ctx, x, mask):
-        x, mask = L._aligned16(x), mask.contiguous()                 # 16-byte loads along the anchor axis
-        b, c, n, na = x.shape
-        ns = mask.shape[1]
-        inv_den = (1.0 / mask.sum(-1).clamp(min=1e-8)).contiguous()
-        out = torch.empty(b, ns, c, na, dtype=torch.float32, device=x.device)
-        _hip.call('eap_slot_masked_mean_wide_fwd_f32', x, b, ns, c, n, na, x, mask, inv_den, out)
-        ctx.save_for_backward(mask, inv_den)
-        ctx.dims = (b, c, n, na, ns)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        mask, inv_den = ctx.saved_tensors
-        b, c, n, na, ns = ctx.dims
-        dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
-        g = L._aligned16(g)           # bound to a local: the buffer must outlive the enqueue
-        _hip.call('eap_slot_masked_mean_wide_bwd_f32', g, b, ns, c, n, na, g, mask, inv_den, dx)
-        return dx, None
-
-
-class _MaskedMaxWide(torch.autograd.Function):
-    """_MaskedMax for anchor rows of 68 to 256 floats (csrc/heads_wide.hip)."""
-
-    @staticmethod
-    def forward(ctx, x, mask):
-        x, mask = L._aligned16(x), mask.contiguous()                 # 16-byte loads along the anchor axis
-        b, c, n, na = x.shape
-        out = torch.empty(b, c, na, dtype=torch.float32, device=x.device)
-        arg = torch.empty(b, c, na, dtype=torch.int32, device=x.device)
-        _hip.call('eap_masked_max_wide_fwd_f32', x, b, c, n, na, x, mask, out, arg)
-        ctx.save_for_backward(arg, mask)
-        ctx.dims = (b, c, n, na)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        arg, mask = ctx.saved_tensors
-        b, c, n, na = ctx.dims
-        g = L._aligned16(g)
-        dx = torch.empty(b, c, n, na, dtype=torch.float32, device=g.device)
-        _hip.call('eap_masked_max_wide_bwd_f32', g, b, c, n, na, g, arg, mask, dx)
+        _hip.call(f'eap_masked_max{ctx.family}_bwd_f32', g, b, c, n, na, g, arg, mask, dx)
         return dx, None
 
 
@@ -368,12 +298,10 @@ def _slot_masked_mean_torch(x, mask):
 
 def masked_max(x, mask):
     """x [b,c,n,a], mask [b,n] (0/1, treated as data) -> [b,c,a] = (x * mask[:, None, :, None]).max(2)[0]: the pose heads' 'max'
-    pooling over a point subset without the masked copy of x (up to 64 anchors csrc/heads.hip, 68 to 256 csrc/heads_wide.hip)."""
+    pooling over a point subset without the masked copy of x (csrc/heads.hip: up to 64 anchors the entries without a suffix, 68 to 256 the _wide ones)."""
     if x.dtype != torch.float32 or not x.is_cuda:
         raise RuntimeError('masked_max: float32 device tensors only')
-    if _anchor_rows_wide(x.shape[3]):
-        return _MaskedMaxWide.apply(x, mask.to(torch.float32))
-    if not _anchor_rows_vectorise(x.shape[3]):
+    if not (_anchor_rows_vectorise(x.shape[3]) or _anchor_rows_wide(x.shape[3])):
         return _masked_max_torch(x, mask)
     return _MaskedMax.apply(x, mask.to(torch.float32))
 
@@ -382,15 +310,13 @@ def slot_masked_mean(x, mask):
     """x [b,c,n,a], mask [b,s,n] (hard or soft slot weights, treated as data) ->
     [b,s,c,a] = sum_n mask x / clamp(sum_n mask, 1e-8): the masked point averages the pose head takes slot by slot
     (model_utils.py:L470-484 `x_out * mask` then `.mean(2)`-style pooling, L549-552 for the translations), for all
-    slots (at most 8) in one pass over x (up to 64 anchors csrc/heads.hip, 68 to 256 csrc/heads_wide.hip)."""
+    slots (at most 8) in one pass over x (csrc/heads.hip: up to 64 anchors the entries without a suffix, 68 to 256 the _wide ones)."""
     if x.dtype != torch.float32 or not x.is_cuda:
         raise RuntimeError('slot_masked_mean: float32 device tensors only')
     if mask.requires_grad:
         raise RuntimeError('slot_masked_mean: the slot weights are treated as data (no gradient reaches them); detach the mask or '
                            'use torch ops for a differentiable soft mask')
-    if mask.shape[1] <= 8 and _anchor_rows_wide(x.shape[3]):
-        return _SlotMaskedMeanWide.apply(x, mask.to(torch.float32))
-    if not _anchor_rows_vectorise(x.shape[3]) or mask.shape[1] > 8:
+    if not (_anchor_rows_vectorise(x.shape[3]) or _anchor_rows_wide(x.shape[3])) or mask.shape[1] > 8:
         return _slot_masked_mean_torch(x, mask)
     return _SlotMaskedMean.apply(x, mask.to(torch.float32))
 
@@ -876,7 +802,7 @@ def pose_head_over_slot_groups(heads, feats, xyz, labels, anchors, use_offset=Tr
 # with the rotated coordinates, the 1x1 `embed`), so with point weights w_p of sum 1
 #     mean_p embed([h_p ; A^T x_p]) = W_f (mean_p h_p) + W_x A^T (mean_p x_p) + bias
 # and the only work left on the [B,c,N,A] map is BatchNorm2d + ReLU + the weighted point mean, one fused pass (csrc/heads.hip,
-# the eap_bn_act_cloud_mean_* entries; past 64 anchors csrc/heads_wide.hip, eap_bn_act_cloud_mean_wide_*): neither the activated map,
+# the eap_bn_act_cloud_mean_* entries; past 64 anchors eap_bn_act_cloud_mean_wide_*): neither the activated map,
 # the (c+3)-channel concatenation nor the embed output exists.
 
 class _NormActPointMean(torch.autograd.Function):
@@ -885,7 +811,7 @@ class _NormActPointMean(torch.autograd.Function):
     (B momentum updates of the running statistics in cloud order, in closed form); None: the statistics of the whole batch, as
     nn.BatchNorm2d takes them.  The conv bias rides in the mean (gradient exactly zero in training mode).  Saved for the backward:
     y and [B,C] vectors; the backward is a reduction pass and an apply pass over y.  Up to 64 anchors the eap_bn_act_cloud_mean_* entries
-    of csrc/heads.hip, 68 to 256 (the 240 of a `use_2d` map) their _wide twins of csrc/heads_wide.hip."""
+    of csrc/heads.hip, 68 to 256 (the 240 of a `use_2d` map) their _wide twins; the wrappers of vgtk/_hip.py choose by the anchor count."""
 
     @staticmethod
     def forward(ctx, y, bias, w, inv_den, stat_mask, weight, beta, running_mean, running_var, training, momentum, eps, slope):
@@ -904,8 +830,7 @@ class _NormActPointMean(torch.autograd.Function):
             sums = (s1, s2, pivot, cnt)
         fold = norm_fold.fold(sums, weight.expand(b, c), beta, running_mean, running_var, training, momentum, eps, bias)   # (gamma per cloud: scale, shift [b, c])
         scale, shift, mean, invstd = (t.expand(b, c).float().contiguous() for t in fold[:4])
-        fwd = _hip.bn_act_cloud_mean_wide_fwd if _anchor_rows_wide(na) else _hip.bn_act_cloud_mean_fwd
-        out = fwd(y, scale, shift, w, inv_den, slope)
+        out = _hip.bn_act_cloud_mean_fwd(y, scale, shift, w, inv_den, slope)
         ctx.save_for_backward(y, scale, shift, mean, invstd, w, inv_den, stat_mask)
         ctx.training, ctx.slope, ctx.has_bias = training, slope, bias is not None
         return out
@@ -915,17 +840,14 @@ class _NormActPointMean(torch.autograd.Function):
         y, scale, shift, mean, invstd, w, inv_den, stat_mask = ctx.saved_tensors
         b, c, p, na = y.shape
         g = L._aligned16(g)
-        wide = _anchor_rows_wide(na)
-        reduce_, apply_ = ((_hip.bn_act_cloud_mean_wide_bwd_reduce, _hip.bn_act_cloud_mean_wide_bwd_apply) if wide else
-                           (_hip.bn_act_cloud_mean_bwd_reduce, _hip.bn_act_cloud_mean_bwd_apply))
-        sg, sgx = reduce_(g, y, scale, shift, mean, invstd, w, inv_den, ctx.slope)     # [b, c] float64
+        sg, sgx = _hip.bn_act_cloud_mean_bwd_reduce(g, y, scale, shift, mean, invstd, w, inv_den, ctx.slope)     # [b, c] float64
         g_y = None
         if ctx.needs_input_grad[0]:
             cnt = float(b * p * na)                                                     # whole batch: the sums of all clouds
             if ctx.training and stat_mask is not None:
                 cnt = (stat_mask.sum(1, dtype=torch.float64) * na).view(b, 1)
             k2, k3 = norm_fold.backward_coefficients(scale, sg, sgx, cnt, ctx.training)
-            g_y = apply_(g, y, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, ctx.slope)
+            g_y = _hip.bn_act_cloud_mean_bwd_apply(g, y, scale, shift, mean, invstd, k2, k3, w, inv_den, stat_mask, ctx.slope)
         g_bias = norm_fold.pre_bias_grad(sg, scale, ctx.training) if ctx.has_bias else None
         return g_y, g_bias, None, None, None, sgx.sum(0).float(), sg.sum(0).float(), None, None, None, None, None, None
 
@@ -946,7 +868,7 @@ def _norm_act_point_mean_torch(y, bias, w, inv_den, stat_mask, bn, slope=0.0):
 
 def _norm_act_point_mean(y, bias, w, inv_den, stat_mask, bn, slope=0.0):
     """inv_den sum_p w act(bn(y + bias)) -> [B,c,A]; y [B,c,P,A] raw contraction output, w [B,P], inv_den [B], stat_mask [B,P] or None
-    (see _NormActPointMean: up to 64 anchors csrc/heads.hip, 68 to 256 csrc/heads_wide.hip); anchor counts neither takes run the same
+    (see _NormActPointMean: csrc/heads.hip up to 256 anchors); anchor counts its kernels do not take run the same
     expressions as device tensor ops."""
     if bn.momentum is None or not bn.track_running_stats:
         raise NotImplementedError('InvOutBlockOursWithMask: BatchNorm with running statistics and a momentum only')

@@ -1028,7 +1028,7 @@ int eap_masked_max_fwd_f32(int b, int c, int n, int na, const float *x, const fl
                            eap_stream_t stream);
 int eap_masked_max_bwd_f32(int b, int c, int n, int na, const float *g, const int32_t *arg, const float *mask, float *dx,
                            eap_stream_t stream);
-/* The same three pairs for wide anchor rows (csrc/heads_wide.hip): na % 4 == 0, 4 <= na <= 256 -- the 60 x 4 = 240 anchors of a `use_2d`
+/* The same three pairs for wide anchor rows (the same kernels of csrc/heads.hip compiled with 64 lanes per row instead of 16): na % 4 == 0, 4 <= na <= 256 -- the 60 x 4 = 240 anchors of a `use_2d`
  * feature map.  Parameter lists, definitions, NaN / -inf / tie rules and alignment demands are those of the entries without _wide above;
  * one wavefront owns a point's anchor row (lane = 16-byte quad), the anchor reductions are 6 shuffle steps, the point sums of the slot
  * mean are chains of ceil(n / 4) fused multiply-adds folded over 4 waves in a fixed order.  No atomics, bit-identical run to run.  Other
@@ -1068,7 +1068,7 @@ int eap_bn_act_cloud_mean_bwd_reduce_f32(int b, int c, int n, int na, float slop
 int eap_bn_act_cloud_mean_bwd_apply_f32(int b, int c, int n, int na, float slope, const float *g, const float *x, const float *scale,
                                         const float *shift, const float *mean, const float *invstd, const float *k2, const float *k3,
                                         const float *w, const float *inv_den, const float *stat_mask, float *gx, eap_stream_t stream);
-/* The same three entries and their parts query for wide anchor rows (csrc/heads_wide.hip): na % 4 == 0, 4 <= na <= 256 -- InvOutBlockOursWithMask
+/* The same three entries and their parts query for wide anchor rows (the same kernels of csrc/heads.hip compiled with 64 lanes per row instead of 16): na % 4 == 0, 4 <= na <= 256 -- InvOutBlockOursWithMask
  * on the 240-anchor map of a `use_2d` backbone (SPConvNets/utils/base_so3conv.py:L1076-1107; PointnetSO3ConvOurs keeps tot_anchors [240,3,3] for
  * it, L1173-1176, L1196).  Parameter lists and definitions are those of the entries without _wide above.  One wavefront owns a point's anchor
  * row (lane = 16-byte quad); a wave takes every 4th point, 4 rows in flight into 4 accumulators (fp32 chains of ceil(n / 16) terms), folded as

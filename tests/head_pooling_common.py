@@ -120,7 +120,7 @@ def _fma(a, b, acc):
 
 
 def _butterfly16(v):
-    """group16_sum: v += shfl_xor(v, 8), 4, 2, 1 over the last axis (16 lanes); every lane ends with the same float32 value"""
+    """row_sum<16>: v += shfl_xor(v, 8), 4, 2, 1 over the last axis (16 lanes); every lane ends with the same float32 value"""
     lanes = np.arange(16)
     for step in (8, 4, 2, 1):
         v = v + v[..., lanes ^ step]

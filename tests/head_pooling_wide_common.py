@@ -1,5 +1,5 @@
 """Shared by tests/test_head_pooling_wide_host.py (CPU) and tests/test_gpu_head_pooling_wide.py (GPU): the wide twins of the three oldest
-kernel pairs (csrc/heads_wide.hip: one wavefront per point, anchor rows of up to 256 floats) as numpy.  The float32 inputs and the float64
+kernel pairs (csrc/heads.hip at Q = 64: one wavefront per point, anchor rows of up to 256 floats) as numpy.  The float32 inputs and the float64
 expressions are those of tests/head_pooling_common.py (same generators, same families); the per-element bounds are counted from the NEW
 kernels, and the float32 emulations follow the new kernels' summation order.
 
@@ -35,7 +35,7 @@ SUM_ADDS = 3 + 6                                # a sum over the anchors of a po
 
 def attn_reference(t, exp_rel=None):
     """float64 out [B,c,n], conf [B,n,na], dx [B,c,n,na], dlogits [B,n,na] and a bound for every element: {name: (ref, bound)}; the
-    derivation is head_pooling_common.attn_reference's with the counts of anchor_attn_pool_wide_kernel:
+    derivation is head_pooling_common.attn_reference's with the counts of anchor_attn_pool_kernel<64, BWD>:
 
     conf_i = e_i / S: the argument terms d_i = u (|T l_i| + |z_i|) + exp_rel + |z_i| u are unchanged (the same statements); S carries the
     conf-weighted mean of the d_j and SUM_ADDS = 9 adds (3 in a lane, 6 shuffle steps), then 1 / S and e_i * (1 / S): 11 u.
@@ -76,7 +76,7 @@ def attn_reference(t, exp_rel=None):
 
 
 def _butterfly64(v):
-    """wave_sum: v += shfl_xor(v, 32), 16, 8, 4, 2, 1 over the last axis (64 lanes); every lane ends with the same float32 value"""
+    """row_sum<64>: v += shfl_xor(v, 32), 16, 8, 4, 2, 1 over the last axis (64 lanes); every lane ends with the same float32 value"""
     lanes = np.arange(64)
     for step in (32, 16, 8, 4, 2, 1):
         v = v + v[..., lanes ^ step]
@@ -91,7 +91,7 @@ def _quads(a, na):
 
 
 def attn_emulate(t, logits=None):
-    """anchor_attn_pool_wide_kernel<false / true> in float32, operation by operation (products and sums rounded one by one where the
+    """anchor_attn_pool_kernel<64, false / true> in float32, operation by operation (products and sums rounded one by one where the
     compiler may fuse them: the longest path); the exponential is the correctly rounded one.  -> out, conf, dx, dlogits"""
     x, l, g, T = t['x'], t['logits'] if logits is None else logits, t['g'], f32(t['T'])
     b, c, n, na = x.shape
@@ -114,9 +114,9 @@ def attn_emulate(t, logits=None):
 # ---- slot-masked point mean --------------------------------------------------------------------------------------------------------------
 
 def slot_reference(t):
-    """forward out[b,s,c,a] = inv_den[b,s] sum_p m[b,s,p] x[b,c,p,a] (slot_mean_wide_fwd_kernel): a lane's chain over the points w, w + 4, ...
+    """forward out[b,s,c,a] = inv_den[b,s] sum_p m[b,s,p] x[b,c,p,a] (slot_mean_fwd_kernel<64, NS>): a lane's chain over the points w, w + 4, ...
     is ceil(n / 4) fused multiply-adds, the fold of the 4 waves' partials through LDS 4 adds, the product with inv_den 1:
-    k = ceil(n / 4) + 4 + 1.  backward dx[b,c,p,a] = sum_s m[b,s,p] (g[b,s,c,a] inv_den[b,s]) (slot_mean_wide_bwd_kernel): the product
+    k = ceil(n / 4) + 4 + 1.  backward dx[b,c,p,a] = sum_s m[b,s,p] (g[b,s,c,a] inv_den[b,s]) (slot_mean_bwd_kernel<64, NS>): the product
     g inv_den is rounded once, then a chain of ns fused multiply-adds: k = 1 + ns."""
     x, m, d, g = (t[k].astype(f64) for k in ('x', 'mask', 'inv_den', 'g'))
     n, ns = x.shape[2], m.shape[1]
@@ -143,7 +143,7 @@ def _chains(a, axis):
 
 
 def slot_emulate(t, mask=None, inv_den=None, n_points=None):
-    """slot_mean_wide_fwd_kernel / slot_mean_wide_bwd_kernel in float32 in the kernels' order: wave chains over w, w + 4, ..., the 4 partials
+    """slot_mean_fwd_kernel<64, NS> / slot_mean_bwd_kernel<64, NS> in float32 in the kernels' order: wave chains over w, w + 4, ..., the 4 partials
     in wave order, the product with inv_den.  n_points: the forward stops there (a mutation)."""
     x, g = t['x'], t['g']
     m = t['mask'] if mask is None else mask
@@ -170,7 +170,7 @@ def slot_emulate(t, mask=None, inv_den=None, n_points=None):
 # ---- masked point max ----------------------------------------------------------------------------------------------------------------------
 
 def max_emulate(t, mask=None, n_points=None, higher_on_tie=False):
-    """masked_max_wide_fwd_kernel / masked_max_wide_bwd_kernel in float32 in the kernels' order: a wave's ascending chain w, w + 4, ... keeps the
+    """masked_max_fwd_kernel<64> / masked_max_bwd_kernel<64> in float32 in the kernels' order: a wave's ascending chain w, w + 4, ... keeps the
     first of equals and the first NaN, the 4 chains are folded in wave order (larger, or equal at a lower point; a NaN beats a number, the
     lower NaN another).  n_points, higher_on_tie: mutations."""
     x, g = t['x'], t['g']

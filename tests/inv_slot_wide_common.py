@@ -1,5 +1,5 @@
 """Shared by tests/test_inv_slot_head_wide_host.py and tests/test_gpu_inv_slot_head_wide.py: the grid, the float64 references and bounds and
-a float32 emulation of the wide fused BatchNorm + leaky_relu + point-mean kernels (csrc/heads_wide.hip, eap_bn_act_cloud_mean_wide_*), and
+a float32 emulation of the wide fused BatchNorm + leaky_relu + point-mean kernels (csrc/heads.hip at Q = 64, eap_bn_act_cloud_mean_wide_*), and
 tests/golden/inv_slot_head_2d.npz (tests/golden/make_golden_inv_slot_2d.py) unpacked for the package's class.
 
 The cases are those of tests/test_gpu_inv_slot_head.py (_kernel_case: the same generators, the same float32 coefficients widened, the same

@@ -1,4 +1,4 @@
-"""GPU: the wide twins of the three oldest head kernels (csrc/heads_wide.hip: eap_anchor_attn_pool_wide_*, eap_slot_masked_mean_wide_*,
+"""GPU: the wide twins of the three oldest head kernels (csrc/heads.hip at Q = 64: eap_anchor_attn_pool_wide_*, eap_slot_masked_mean_wide_*,
 eap_masked_max_wide_*) at every anchor and point edge of their mapping (one wavefront per point: 15 quads where the narrow kernels also run,
 17 quads just past them, 60 at the use_2d count, one idle lane at 252 and none at 256; blocks of 4 points, chains of 1 to 5 wave iterations;
 1 to 8 slots), every output element against float64 under its own bound (tests/head_pooling_wide_common.py; tests/test_head_pooling_wide_host.py

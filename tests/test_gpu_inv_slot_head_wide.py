@@ -1,5 +1,5 @@
 """GPU: the per-cloud BatchNorm and the fused BatchNorm + leaky_relu + point mean on the 240-anchor map of a `use_2d` backbone:
-the eap_bn_act_cloud_mean_wide_* entries (csrc/heads_wide.hip) against float64 under bounds counted from their mapping
+the eap_bn_act_cloud_mean_wide_* entries (csrc/heads.hip at Q = 64) against float64 under bounds counted from their mapping
 (tests/inv_slot_wide_common.py) and against their narrow twins at 60 anchors; vgtk.so3conv.heads._NormActPointMean and _subset_batchnorm_act
 at 240 anchors against the unfused composition and float64; InvOutBlockOursWithMask against the fixture the reference class produced on a
 240-anchor map (tests/golden/inv_slot_head_2d.npz); pose_head_over_subsets and the per-slot forms against the loops they replace; and the

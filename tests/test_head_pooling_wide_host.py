@@ -1,4 +1,4 @@
-"""CPU: the wide twins of the three oldest head kernels (csrc/heads_wide.hip: anchor rows of up to 256 floats, one wavefront per point) and
+"""CPU: the wide twins of the three oldest head kernels (csrc/heads.hip at Q = 64: anchor rows of up to 256 floats, one wavefront per point) and
 InvPPOutBlock2DOurs as far as they go without a device: the six C-ABI entries on calls that return before they launch (arity, empty batch,
 anchor and slot counts, 16-byte alignment), the predicate and the fallbacks of the wrappers past the kernels' domain, the per-element bounds
 that tests/test_gpu_head_pooling_wide.py holds the kernels to (tests/head_pooling_wide_common.py): a float32 emulation of each kernel in

@@ -46,6 +46,28 @@ def test_an_anchor_count_the_16_byte_rows_do_not_take_is_refused(hip, na):
         assert name[len('eap_'):-len('_f32')] in msg and 'multiple of 4, at most 64' in msg, msg
 
 
+POINTERS = {'eap_bn_act_cloud_mean_fwd_f32': ('x', 'scale', 'shift', 'w', 'inv_den', 'out'),
+            'eap_bn_act_cloud_mean_bwd_reduce_f32': ('g', 'x', 'scale', 'shift', 'mean', 'invstd', 'w', 'inv_den', 'pg', 'pgx'),
+            'eap_bn_act_cloud_mean_bwd_apply_f32': ('g', 'x', 'scale', 'shift', 'mean', 'invstd', 'k2', 'k3', 'w', 'inv_den', 'stat_mask', 'gx')}
+
+
+def test_a_null_required_pointer_is_refused(hip):
+    """as by the _wide twins (tests/test_inv_slot_head_wide_host.py): every pointer but stat_mask, one at a time, the others non-null and
+    16-byte aligned (addresses, not memory: nothing may be launched); a null stat_mask alone is no refusal (the entry then goes on to the
+    alignment rule, which an operand at 0x...4 fails)"""
+    for name, ptrs in POINTERS.items():
+        base = {p: 0x10000 * (i + 1) for i, p in enumerate(ptrs)}
+        call = lambda given: getattr(hip.abi, name)(3, 8, 40, 60, 0.0, *(given[p] for p in ptrs), None)
+        for p in ptrs:
+            if p == 'stat_mask':
+                assert call(dict(base, stat_mask=None, gx=base['gx'] + 4)) == INVALID_VALUE
+                assert 'must be 16-byte aligned' in hip.abi.eap_last_error().decode()
+                continue
+            assert call(dict(base, **{p: None})) == INVALID_VALUE, (name, p)
+            msg = hip.abi.eap_last_error().decode()
+            assert name[len('eap_'):-len('_f32')] in msg and 'a required pointer is null' in msg, (name, p, msg)
+
+
 def test_the_backward_reduction_leaves_one_partial_per_wave_and_point_group(hip):
     """csrc/heads.hip bn_act_mean_bwd_reduce_kernel: a block of 4 waves, 4 point groups of 16 lanes each, one partial per group"""
     for n in (1, 33, 700, 4096):

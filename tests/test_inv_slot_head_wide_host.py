@@ -1,4 +1,4 @@
-"""CPU: the wide twins of the fused BatchNorm + leaky_relu + point-mean entries (csrc/heads_wide.hip, eap_bn_act_cloud_mean_wide_*: anchor
+"""CPU: the wide twins of the fused BatchNorm + leaky_relu + point-mean entries (csrc/heads.hip at Q = 64, eap_bn_act_cloud_mean_wide_*: anchor
 rows of up to 256 floats, the 240 of a `use_2d` map; SPConvNets/utils/base_so3conv.py:L1076-1107) as far as they go without a device: the four
 C-ABI entries on calls that return before they launch (arity, empty batch, point and anchor counts, null and misaligned operands), the routing
 of vgtk.so3conv.heads._norm_act_point_mean and _subset_batchnorm_act by anchor count with the library stubbed, and the bounds
@@ -109,7 +109,7 @@ def test_sizes_beyond_the_launch_limits_are_refused(hip):
 
 
 def test_the_backward_reduction_leaves_one_partial_per_wave(hip):
-    """csrc/heads_wide.hip bn_act_mean_wide_bwd_reduce_kernel: a block of 4 waves, each summed by the shuffle tree to one partial -- the count
+    """csrc/heads.hip at Q = 64 bn_act_mean_bwd_reduce_kernel<64>: a block of 4 waves, each summed by the shuffle tree to one partial -- the count
     the emulation of tests/inv_slot_wide_common.py adds in float64"""
     for n in (1, 3, 33, 700, 4096):
         assert hip.abi.eap_bn_act_cloud_mean_wide_parts(n) == W.WAVES == 4
@@ -180,28 +180,27 @@ def test_wide_anchor_counts_reach_the_library(first_call, na):
 
 @pytest.mark.parametrize('na', [60, 68, 240, 256])
 def test_the_node_picks_its_entries_by_anchor_count(monkeypatch, na):
-    """_NormActPointMean's forward and backward with the three wrappers of each family replaced by stand-ins of the right shapes: 60 anchors
-    call the narrow three, 68 to 256 the wide three, and nothing else of the library is needed in eval mode"""
+    """_NormActPointMean's forward and backward through the three wrappers of vgtk/_hip.py (bn_act_cloud_mean_fwd / _bwd_reduce / _bwd_apply,
+    which choose the family) with _hip.call replaced by a recorder that zeroes the outputs: 60 anchors call the three narrow entries, 68 to
+    256 the three wide ones, the partials have the family's count, and nothing else of the library is needed in eval mode"""
     import vgtk.so3conv.heads as H
     from vgtk import _hip
     seen = []
 
-    def stand_in(name, make):
-        def f(*a):
-            seen.append(name)
-            return make(*a)
-        monkeypatch.setattr(_hip, name, f)
-    for fam in ('bn_act_cloud_mean', 'bn_act_cloud_mean_wide'):
-        stand_in(fam + '_fwd', lambda x, *a: torch.zeros(x.shape[0], x.shape[1], x.shape[3]))
-        stand_in(fam + '_bwd_reduce', lambda g, x, *a: (torch.zeros(x.shape[:2], dtype=torch.float64), torch.zeros(x.shape[:2], dtype=torch.float64)))
-        stand_in(fam + '_bwd_apply', lambda g, x, *a: torch.zeros_like(x))
+    def record(name, ref, *a, **k):
+        seen.append((name, a))
+        for out in a[-2 if name.endswith('_bwd_reduce_f32') else -1:]:        # pg and pgx; out; gx
+            out.zero_()
+    monkeypatch.setattr(_hip, 'call', record)
     monkeypatch.setattr(H.L, '_aligned16', lambda t: t.contiguous())
     y, bias, mask, bn = _node_inputs(na, training=False)
     y.requires_grad_(True)
     out = H._norm_act_point_mean(y, bias, mask, 1.0 / mask.sum(1), mask, bn, 0.0)
     out.sum().backward()
-    fam = 'bn_act_cloud_mean_wide' if na > 64 else 'bn_act_cloud_mean'
-    assert seen == [fam + '_fwd', fam + '_bwd_reduce', fam + '_bwd_apply'], seen
+    fam = 'eap_bn_act_cloud_mean_wide' if na > 64 else 'eap_bn_act_cloud_mean'
+    assert [name for name, _ in seen] == [fam + '_fwd_f32', fam + '_bwd_reduce_f32', fam + '_bwd_apply_f32'], seen
+    assert seen[1][1][-2].shape == seen[1][1][-1].shape == (y.shape[0], y.shape[1], W.WAVES if na > 64 else 16)
+    assert float(y.grad.abs().max()) == 0.0
 
 
 def test_60_anchors_still_reach_the_narrow_entries(first_call):

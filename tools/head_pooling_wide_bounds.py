@@ -1,5 +1,5 @@
 """tools/head_pooling_wide_bounds.py -- what tests/head_pooling_wide_common.py's measured constants come from, and the worst error / bound of
-every wide head kernel (csrc/heads_wide.hip) over the grid of tests/test_gpu_head_pooling_wide.py.  Needs the device.
+every wide head kernel (csrc/heads.hip at Q = 64) over the grid of tests/test_gpu_head_pooling_wide.py.  Needs the device.
     python tools/head_pooling_wide_bounds.py [--out profiles/head_pooling_wide_bounds.txt]"""
 import argparse
 import os
@@ -97,7 +97,7 @@ for na in W.NA_GRID:
                              and W.same_values(dx.cpu().numpy(), ref['dx']))
 
 lines = [
-    'Wide head pooling kernels (csrc/heads_wide.hip: eap_anchor_attn_pool_wide_*, eap_slot_masked_mean_wide_*, eap_masked_max_wide_*) against',
+    'Wide head pooling kernels (csrc/heads.hip at Q = 64: eap_anchor_attn_pool_wide_*, eap_slot_masked_mean_wide_*, eap_masked_max_wide_*) against',
     "float64 on an MI355X: what tests/head_pooling_wide_common.py's constants were measured from, and the worst error / bound per kernel.",
     f'Written by tools/head_pooling_wide_bounds.py.  Grid: b = {W.B}, c in {list(W.C_GRID)}, na in {list(W.NA_GRID)}, n in {list(W.N_GRID)}, slot mean also ns in {list(W.NS_GRID)}.',
     '',

@@ -1,5 +1,5 @@
 """tools/head_pooling_wide_time.py -- the three head poolings on a `use_2d` feature map, x [4, 256, 2048, 240] (2.01 GB): the wide kernels
-(csrc/heads_wide.hip, through vgtk.so3conv.anchor_attention_pool / masked_max / slot_masked_mean) against the torch expressions the wrappers
+(csrc/heads.hip at Q = 64, through vgtk.so3conv.anchor_attention_pool / masked_max / slot_masked_mean) against the torch expressions the wrappers
 ran at 240 anchors before the kernels existed (the fallback functions of vgtk/so3conv/heads.py themselves).  Forward and forward + backward,
 3 repeats after a warm-up, device events; the peak memory above the inputs; the achieved GB/s of every kernel on its algorithmic bytes.
     python tools/head_pooling_wide_time.py [--out profiles/head_pooling_wide.txt] [--shape 4 256 2048 240] [--slots 8 1]"""
@@ -87,7 +87,7 @@ def kernel_times(run, inputs):
 
 fmt = lambda v: f'{sorted(v)[len(v) // 2]:8.2f} ms ({min(v):.2f} - {max(v):.2f})'
 lines = [f'Head poolings on a use_2d map, x [{b}, {c}, {n}, {na}] float32 ({GB:.2f} GB), {torch.cuda.get_device_name(0)}; tools/head_pooling_wide_time.py.',
-         f'kernel: csrc/heads_wide.hip through the wrappers of vgtk.so3conv; torch: the expressions the wrappers ran at {na} anchors without the',
+         f'kernel: csrc/heads.hip at Q = 64 through the wrappers of vgtk.so3conv; torch: the expressions the wrappers ran at {na} anchors without the',
          f'kernels (vgtk/so3conv/heads.py: _anchor_attention_pool_torch, _masked_max_torch, _slot_masked_mean_torch).  Median (min - max) of {REPEATS} repeats after',
          'a warm-up, device events around the whole call; peak = the most device memory in use above the inputs during forward + backward.', '']
 for name, (kern, ref, inputs, gb_f, gb_b) in OPS.items():

@@ -8,9 +8,9 @@ profiles/head_pooling_wide.txt).
 
 Two groups, every form of a group in the same process, ALTERNATING over ROUNDS rounds of STEPS steps after WARMUP steps each, timed with device
 events, statistics pass included; forward alone and forward + backward (gradient to y, gamma, beta, bias):
-  norm + point mean   fused     vgtk/so3conv/heads.py _norm_act_point_mean over csrc/heads_wide.hip eap_bn_act_cloud_mean_wide_*
+  norm + point mean   fused     vgtk/so3conv/heads.py _norm_act_point_mean over csrc/heads.hip at Q = 64 eap_bn_act_cloud_mean_wide_*
                       torch     _norm_act_point_mean_torch, the expression that ran at 240 anchors before the wide kernels
-                      composed  _subset_batchnorm_act (csrc/bn_act.hip eap_bn_act_cloud_*) + slot_masked_mean (csrc/heads_wide.hip)
+                      composed  _subset_batchnorm_act (csrc/bn_act.hip eap_bn_act_cloud_*) + slot_masked_mean (csrc/heads.hip at Q = 64)
   per-cloud norm      kernels   _subset_batchnorm_act
                       torch     _subset_batchnorm_act_torch
 Per form: median and range over the rounds, and the peak of torch.cuda.max_memory_allocated above what is allocated before a forward + backward
